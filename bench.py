@@ -17,10 +17,10 @@ top_diff to the forward.  `--path fused` (one launch for both, mms_simcross_forw
 is a labelled variant for hosts that do know top_diff up front.
 
 Protocol (SURVEY.md 8d, tools/caffe.cpp:318-385): inputs resident in HBM; W untimed warm-up steps;
-then the K-step region is timed REPEATS (5) times, each repeat bracketed by barrier +
-torch.cuda.synchronize() on both sides and by two HIP events on the launch stream; ONE clock -- the
-events, max over ranks -- gives `value`, `ms_per_step` and `roofline`; the MEDIAN repeat is
-reported (all repeats are in `config.repeats_ms_per_step`).  Steps walk a ring of RING distinct
+then, after one untimed rehearsal region (256 steps of the same walk, same protocol), ONE region of exactly K
+steps is timed (`--repeats R` times R regions of K steps and reports the median), bracketed by barrier +
+torch.cuda.synchronize() on both sides and by two HIP events on the launch stream; ONE clock -- the events, max over
+ranks -- gives `value`, `ms_per_step` and `roofline` (every region is in `config.repeats_ms_per_step`).  Steps walk a ring of RING distinct
 batches (RING x 19.7 MB > 1 GiB >> 256 MiB of Infinity Cache) continuing where the warm-up stopped,
 and the caches are flushed (a 512 MiB fill) before the warm-up, so every timed step reads its q and
 a from HBM ("cold"); `--warm` re-uses one batch instead.  Between each repeat's opening fence and its
@@ -37,7 +37,15 @@ the ranks, gather per step); `--workload cfg5` (`--f16-distance ordered|tree`) /
 the two BASELINE configurations that are multi-GPU by definition.  `python bench.py --gpus N` typed as is starts its own
 N rank processes (launch_ranks); the torchrun form works too.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line (keys: tests/test_bench_contract.py) with `roofline`.  A plain run does only what
+that line needs: set-up, warm-up, the timed steps, `--dump-outputs DIR` if given, the line.  `--full` adds the side
+measurements, each taking runs of its own: `cpu_baseline`, `variants` (other paths, residencies and BASELINE
+configurations), `roofline.per_kernel_cold` / `launch_floor` / `long_region`, and at N > 1
+`config.per_step_gather_variant` / `strong_split_variant`.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed -- the arrays a caller of the
+timed path receives -- as DIR/<name>.npy (float32, or float64 for integers); inputs come from fixed seeds, so two
+builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -56,7 +64,10 @@ B_BWD = S * (2 * N_PAIRS * 2 * DIM + 2 * N_PAIRS)      # 19,693,568
 B_UNFUSED = B_FWD + B_BWD                              # 29,540,352  (7,212 B/pair)
 B_FUSED = S * (2 * N_PAIRS * 2 * DIM + 2 * N_PAIRS)    # q,a read once; dq,da written once; dT in, T out
 HBM_PEAK_GBS = 8000.0                                  # MI355X_MICROARCH.md: 8.0 TB/s spec
-REPEATS = 5
+REPEATS = 1                                            # timed steps = --steps exactly, unless --repeats asks for more
+DUMP_LIMIT_BYTES = 64 << 20                            # --dump-outputs: all arrays together
+DUMP_SAMPLE_ROWS = 4096                                # rows kept of a per-pair output too large to write whole
+REHEARSAL_STEPS = 256                                  # untimed region ahead of the timed one (run(): why)
 
 
 def parse():
@@ -90,13 +101,43 @@ def parse():
                         "bit-identical to the fp32 CPU code on the fp16-rounded inputs; 'tree' = fixed-shape tree sum, "
                         "within ~1e-6 relative of it -- SURVEY 8(d) asks 1e-3 of this configuration (the reference has "
                         "no fp16), so both are contract-compliant; the line reports both accountings either way")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-variants", action="store_true")
-    p.add_argument("--cpu-seconds", type=float, default=10.0)
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (cpu_baseline, variants, per-kernel / launch-floor / "
+                        "long-region roofline figures, the N > 1 per-step-gather and strong-split variants)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    p.add_argument("--no-variants", action="store_true", help="with --full: leave out the GPU side measurements")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: cpu_baseline's time budget")
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                    help="nccl = RCCL over xGMI (default). gloo = rehearsal of the N>1 control flow "
                         "on a box with fewer GPUs than ranks (scores staged through the host)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        p.error("--steps and --repeats must be >= 1, --warmup >= 0")
+    return args
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: each array of `arrays` (name -> numpy array) as out_dir/<name>.npy, float32 (float64 for
+    float64 and integer arrays); refuses to write more than DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    conv = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 or v.dtype.kind in "iub"
+                                    else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+def sample_rows(n):
+    """Fixed, seeded, sorted row sample of an n-row output (all rows when n <= DUMP_SAMPLE_ROWS)."""
+    import numpy as np
+    if n <= DUMP_SAMPLE_ROWS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(1701).choice(n, DUMP_SAMPLE_ROWS, replace=False))
 
 
 class Batches:
@@ -480,17 +521,22 @@ def run(args):
     use_graph = not eager
     reg = Region(torch, step, ring, G, buckets, use_graph, raw_step)
 
-    # eager pass over every code path (instantiates kernels), then the graphs of the warm-up and of
+    # eager pass over every code path (instantiates kernels), then the graphs of the warm-up, of the rehearsal and of
     # every timed repeat -- all captured before anything is timed
     reg.body(0, min(G, ring), 0)
     torch.cuda.synchronize()
     warm_chunks = reg.chunks(0, Wm)
-    rep_chunks = [reg.chunks(Wm + r * K, K) for r in range(args.repeats)]
+    # one UNTIMED rehearsal region of REHEARSAL_STEPS steps of the walk, run under the timing protocol before the timed
+    # region: a process's first regions run slower (8.6, then 8.1 -> 7.95 us per step in 20-step regions; not the events,
+    # the fences, the lead-in graphs or the score buckets), which the median of five regions used to leave out
+    rehearsal = reg.chunks(Wm, REHEARSAL_STEPS)
+    start = Wm + REHEARSAL_STEPS
+    rep_chunks = [reg.chunks(start + r * K, K) for r in range(args.repeats)]
     # untimed lead-in of each repeat: the Gp steps of the walk that PRECEDE the region's first step
     Gp = max(1, min(G, 32, args.lead_in)) if args.lead_in > 0 else 0
     pad_reps = (args.lead_in + Gp - 1) // Gp if Gp else 0
-    pad_chunks = [reg.chunks((Wm + r * K - Gp) % ring + ring, Gp) if Gp else [] for r in range(args.repeats)]
-    reg.capture([warm_chunks] + rep_chunks)
+    pad_chunks = [reg.chunks((start + r * K - Gp) % ring + ring, Gp) if Gp else [] for r in range(args.repeats)]
+    reg.capture([warm_chunks, rehearsal] + rep_chunks)
     for r in range(args.repeats):
         reg.capture_fixed(pad_chunks[r], 0)
 
@@ -529,8 +575,21 @@ def run(args):
         for _ in range(pad_reps):
             reg.run_fixed(pad_chunks[r], 0)       # no gather: nothing reads these scores, and every gather
                                                   # of an earlier region finished before the fence
+    time_regions(torch, dist, world, main, 1, lambda r: reg.run(rehearsal, before, after), pad=lead_in if Gp else None)
     ev_ms, wall_ms = time_regions(torch, dist, world, main, args.repeats, one, pad=lead_in if Gp else None)
     t_ms = median(ev_ms)
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step: the last step of the last chunk, which wrote row cnt-1 of the bucket it ran on
+        i0, cnt = rep_chunks[-1][-1]
+        bi, sl = (reg.nchunk - 1) & 1, (i0 + cnt - 1) % ring
+        host = lambda t: t.detach().cpu().numpy()
+        arrays = {"top": host(buckets[bi][cnt - 1]), "dq": host(bt.dq[sl]), "da": host(bt.da[sl])}
+        if args.path == "triplet":
+            arrays.update(sneg=host(bt.sneg[sl]), loss=host(bt.loss[sl]), dan=host(bt.dan[sl]))
+        if world > 1:                                  # what every rank receives: the gathered scores of that step
+            arrays["top_gathered"] = host(gathered[bi].view(world, G, N_PAIRS)[:, cnt - 1])
+        write_outputs(args.dump_outputs, arrays)
 
     out = None
     if rank == 0:
@@ -596,10 +655,10 @@ def run(args):
         dist.barrier()
 
     # N > 1: the same walk with the scores all-gathered after EVERY step (no bucketing), for the record
-    if world > 1 and not args.no_variants:
+    if world > 1 and args.full and not args.no_variants:
         K2 = min(K, 256)
         reg1 = Region(torch, step, ring, 1, buckets, use_graph, raw_step)
-        first = Wm + args.repeats * K
+        first = start + args.repeats * K
         ch = [reg1.chunks(first + r * K2, K2) for r in range(3)]
         reg1.capture(ch)
 
@@ -616,7 +675,7 @@ def run(args):
     # N > 1, the north-star's split: ONE 4096-pair batch divided over the ranks (strong scaling), each rank runs the
     # Forward and Backward launches on its contiguous 4096/N pairs and the per-pair scores are all-gathered after
     # every step -- latency-bound by construction (SURVEY 8e "scaling caveat"), reported next to the weak line
-    if world > 1 and not args.no_variants:
+    if world > 1 and args.full and not args.no_variants:
         from mms_answer_selection_amd import sharded
         lo, hi = sharded.shard_range(N_PAIRS, rank, world)
         ns = hi - lo
@@ -661,15 +720,16 @@ def run(args):
 
     # a SHORT region (the driver's --steps 20) carries a fixed cost of two event packets and one graph boundary
     # (about 9 us: 0.4 us per step at K = 20, nothing at K = 4096); for the record, the same walk over 2048 steps
-    if rank == 0 and world == 1 and K < 1024 and "roofline" in out:
+    if args.full and rank == 0 and world == 1 and K < 1024 and "roofline" in out:
         K3 = 2048
-        first = Wm + args.repeats * K
+        first = start + args.repeats * K
         G3 = max(1, min(args.group, K3))
         reg3 = Region(torch, step, ring, G3, [torch.empty(G3, N_PAIRS, 1, 1, 1, device="cuda") for _ in range(2)],
                       use_graph, raw_step)
         ch3 = [reg3.chunks(first + r * K3, K3) for r in range(3)]
         reg3.capture(ch3)
-        ev3, _ = time_regions(torch, dist, world, main, 3, lambda r: reg3.run(ch3[r]), pad=lead_in if Gp else None)
+        ev3, _ = time_regions(torch, dist, world, main, 3, lambda r: reg3.run(ch3[r]),
+                              pad=(lambda r: lead_in(r % args.repeats)) if Gp else None)
         us3 = median(ev3) * 1e3 / K3
         out["roofline"]["long_region"] = {
             "steps": K3, "us_per_step": us3, "frac": B_UNFUSED / (us3 * 1e-6) / 1e9 / HBM_PEAK_GBS,
@@ -677,7 +737,7 @@ def run(args):
                     "the two event packets and the graph boundary of a region are amortised" % K3}
 
     # side measurements on rank 0 at N=1 only (not part of the timed region above)
-    if rank == 0 and world == 1 and not args.no_variants:
+    if args.full and rank == 0 and world == 1 and not args.no_variants:
         if "roofline" in out:
             out["roofline"].update(per_kernel_roofline(torch, capi))
             fl = out["roofline"]["launch_floor"]["us_per_empty_launch"] * launches_per_step + \
@@ -689,7 +749,7 @@ def run(args):
                 "GBps_above_launch_floor": B_UNFUSED / (above * 1e-6) / 1e9,
                 "frac_ceiling_if_data_were_free": B_UNFUSED / (fl * 1e-6) / 1e9 / HBM_PEAK_GBS})
         out["variants"] = variants(torch, capi, args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -824,8 +884,20 @@ def run_cfg5(args, torch, dist, capi, world, rank):
         if world > 1:
             main.wait_event(free[0])
             main.wait_event(free[1])
+    time_regions(torch, dist, world, main, 1, lambda r: [step() for _ in range(REHEARSAL_STEPS)])   # untimed rehearsal, as in run()
     ev_ms, wall_ms = time_regions(torch, dist, world, main, args.repeats, one)
     t_ms = median(ev_ms)
+    if args.dump_outputs and rank == 0:
+        # the last timed step; dq, da (n x 1024 each) as a fixed sample of DUMP_SAMPLE_ROWS pairs
+        last = cnt[0] - 1
+        bi, s = last & 1, last % ring
+        rows = torch.from_numpy(sample_rows(n)).cuda()
+        host = lambda t: t.detach().float().cpu().numpy()
+        arrays = {"top": host(tops[bi]), "dq_sampled": host(dq[s][rows]), "da_sampled": host(da[s][rows]),
+                  "sample_rows": rows.cpu().numpy()}
+        if world > 1:
+            arrays["top_gathered"] = host(full[bi])
+        write_outputs(args.dump_outputs, arrays)
     if rank == 0:
         b_unfused = 2 * (3 * NT * 2 * D) + 4 * 3 * NT                 # SURVEY 8(d), s = 2, whole batch
         b_moved = 2 * (2 * NT * 2 * D) + 4 * 2 * NT                   # the fused launch: q, a read once; dq, da written once
@@ -925,7 +997,12 @@ def run_cfg4(args, torch, dist, capi, world, rank):
     for _ in range(Wm):
         step()
     main = torch.cuda.current_stream()
+    time_regions(torch, dist, world, main, 1, lambda r: [step() for _ in range(REHEARSAL_STEPS)])   # untimed rehearsal, as in run()
     ev_ms, wall_ms = time_regions(torch, dist, world, main, args.repeats, lambda r: [step() for _ in range(K)])
+    if args.dump_outputs and rank == 0:
+        host = lambda t: t.detach().cpu().numpy()
+        write_outputs(args.dump_outputs, {"top": host(top), "scores": host(prob[:, 1]), "map_mrr": host(res),
+                                          "eff": host(eff)})
     # device-resident steps: HIP events on the launch stream are the clock (the gloo rehearsal stages the gather
     # through the host, so there the host wall is)
     device_only = world == 1 or args.backend == "nccl"

@@ -1,5 +1,5 @@
 """The driver's bench contract: `python bench.py` prints exactly one JSON line with the
-agreed keys (metric/value/unit/..., plus `roofline` and `cpu_baseline`)."""
+agreed keys (metric/value/unit/..., plus `roofline`; `cpu_baseline` with `--full`)."""
 import json
 import os
 import subprocess
@@ -16,7 +16,7 @@ REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "96", "--warmup", "16",
-                          "--no-variants", "--cpu-seconds", "0.5"],
+                          "--full", "--no-variants", "--cpu-seconds", "0.5"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -35,6 +35,53 @@ def test_bench_prints_one_contract_line():
     assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["unit"] == "pairs/s" and c["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the headline only and exactly --steps steps are timed; --dump-outputs writes
+    the last timed step's scores and gradients, bit for bit the same in a second run with the same arguments."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "64", "--warmup", "8",
+                              "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for k in REQUIRED:
+            assert k in d, k
+        assert d["steps"] == 64 and d["warmup"] == 8 and len(d["config"]["repeats_ms_per_step"]) == 1
+        assert "cpu_baseline" not in d and "variants" not in d
+        assert not {"long_region", "per_kernel_cold", "launch_floor"} & set(d["roofline"])
+        dumps.append({f: np.load(str(tmp_path / run / f)) for f in sorted(os.listdir(str(tmp_path / run)))})
+    a, b = dumps
+    assert sorted(a) == ["da.npy", "dq.npy", "top.npy"]
+    assert a["top.npy"].shape == (4096, 1, 1, 1) and a["dq.npy"].shape == a["da.npy"].shape == (4096, 1, 300)
+    for f in a:
+        assert a[f].dtype == np.float32 and np.isfinite(a[f]).all(), f
+        assert (a[f].view(np.uint32) == b[f].view(np.uint32)).all(), f
+
+
+def test_bench_dump_writer_converts_and_caps(tmp_path):
+    """write_outputs: float32 for float arrays (halves included), float64 for integers, nothing past 64 MB;
+    sample_rows: a fixed sorted sample."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.write_outputs(str(tmp_path / "d"), {"h": np.ones(3, np.float16), "i": np.arange(3, dtype=np.int32)})
+    assert np.load(str(tmp_path / "d" / "h.npy")).dtype == np.float32
+    assert np.load(str(tmp_path / "d" / "i.npy")).dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "e"), {"x": np.zeros((bench.DUMP_LIMIT_BYTES // 4) + 1, np.float32)})
+    assert not (tmp_path / "e").exists()
+    rows = bench.sample_rows(65536)
+    assert len(rows) == bench.DUMP_SAMPLE_ROWS and (np.diff(rows) > 0).all() and (rows == bench.sample_rows(65536)).all()
+    assert (bench.sample_rows(10) == np.arange(10)).all()
 
 
 def test_bench_refuses_without_gpu_or_falls_loudly():
@@ -100,7 +147,7 @@ def test_bench_two_ranks_as_typed():
     (rehearsal of the N > 1 control flow), one JSON line comes back through the parent."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                          "--steps", "4", "--warmup", "1", "--no-cpu-baseline"],
+                          "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
