@@ -413,6 +413,12 @@ int mms_triplet_simmatrix_step_f32(int N, int K1, int K2, float margin, float lo
  * libstdc++'s std::sort does for a bucket of at most 16 items, its stable insertion sort:
  * MAP / MRR over candidate groups that small match a libstdc++ build of the reference bit
  * for bit even when tied scores carry different labels).
+ * Labels and group ids are taken as int(x), as the reference stores them: labels are not
+ * limited to {0, 1} (MAP counts a bucket with a label 1 and any label != 1, MRR one with a
+ * label 1 and a label 0; 0.7 -> 0, 1.9 -> 1), and -0.5 / 0.5 are both group 0.
+ * -0.0 and +0.0 are EQUAL scores, as under the reference's `lhs.first > rhs.first`.
+ * NaN scores: the reference's comparator is then no strict weak order and its result is
+ * undefined; so is the result here.
  * ------------------------------------------------------------------------- */
 
 /* Order of EQUAL scores that carry different labels (MAP / MRR / AUC; per calling thread).
@@ -434,7 +440,7 @@ int mms_get_rank_tie_mode(void);
 /* Replaces MAPLayer<float>::Forward_cpu (src/caffe/layers/map_layer.cpp:41-100) and
  * MRRLayer<float>::Forward_cpu (src/caffe/layers/mrr_layer.cpp:38-79).
  * prob (n, fixed_axis+1): the score of item i is prob[i*(fixed_axis+1)+fixed_axis];
- * label (n) in {0,1}; group (n): items are bucketed by int(group[i]).
+ * label (n), taken as int(label[i]); group (n): items are bucketed by int(group[i]).
  * map_out / mrr_out / effective_out (device scalars) may each be NULL. */
 int mms_rank_map_mrr_f32(int n, int fixed_axis, const float* prob, const float* label,
                          const float* group, float* map_out, float* mrr_out,

@@ -19,7 +19,8 @@
 // radix sort is stable (original index ascending).  Results can differ from a
 // particular libstdc++ only when equal scores carry different labels IN A BUCKET OF MORE THAN 16 ITEMS: up to
 // 16, std::sort is libstdc++'s insertion sort, which is stable -- the same order as here
-// (tests/test_gpu_ranking.py, tools/soak_ranking_embed.py).
+// (tests/test_gpu_ranking.py, tests/test_gpu_ranking_edges.py, tools/soak_ranking_embed.py).  -0.0 and +0.0 are
+// equal scores there, and one key here (desc_bits).
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -34,8 +35,11 @@ static thread_local int t_rank_ties = MMS_RANK_TIES_INPUT_ORDER;
 int rank_tie_mode() { return t_rank_ties; }
 void set_rank_tie_mode(int m) { t_rank_ties = m; }
 
+// -0.0 and +0.0 are one key: the reference's `lhs.first > rhs.first` holds them equal (map_layer.cpp:33-38), so they
+// keep input order in the stable sorts and are seen as a tie by rank_ties_detect_kernel
 __device__ __forceinline__ unsigned desc_bits(float s) {
   unsigned u = __float_as_uint(s);
+  if (u == 0x80000000u) u = 0u;                      // -0.0 -> +0.0
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // ascending total order
   return ~u;                                         // descending
 }
@@ -391,7 +395,7 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
   __shared__ unsigned long long xk[kRankMid];          // the second exchange buffer (cross-wave passes)
   __shared__ unsigned xv[kRankMid];
   __shared__ float ap[MODE == 0 ? kRankMid : 1];
-  __shared__ int rk[MODE == 0 ? kRankMid : 1];
+  __shared__ int rk[MODE == 0 ? kRankMid + 1 : 1];     // + 1: as `hd` it holds B + 1 <= 2049 bucket bounds
   __shared__ int fl[MODE == 0 ? kRankMid : 1];
   __shared__ float slab[MODE == 0 ? kRankMid : 1];
   const int t = threadIdx.x;
@@ -572,13 +576,18 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
       }
     }
     __syncthreads();
-    // one thread per bucket: the ordered sum of its terms (x + 0.0f == x: the non-positive items add nothing), its
-    // flags and its two quotients.  The bucket's extent is known, so the loads run ahead of the adds.
-    float b_ap = 0.f;
-    double b_inv = 0.0;
-    int b_fl = 0;
-    if (t < B) {
-      const int head = hd[t], end = hd[t + 1];
+    // one thread per bucket (buckets t, t + 1024, ...: B reaches n = 2048): the ordered sum of its terms
+    // (x + 0.0f == x: the non-positive items add nothing), its flags and its two quotients, stored for the fold.  The
+    // bucket's extent is known, so the loads run ahead of the adds.  The walks read hd / term / slab / xv only; the
+    // fold's arrays alias keys / xk / fl, which nothing reads between the barrier above and the one below.
+    float* bap = reinterpret_cast<float*>(keys);     // (the sorted keys are not needed any more)
+    double* binv = reinterpret_cast<double*>(xk);
+    int* bfl = fl;
+    for (int bk = t; bk < B; bk += 1024) {
+      float b_ap = 0.f;
+      double b_inv = 0.0;
+      int b_fl = 0;
+      const int head = hd[bk], end = hd[bk + 1];
       float apv = 0.f;
       int not_one = 0, zero = 0, first = -1;
       for (int p = head; p < end; p += 8) {
@@ -598,16 +607,13 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
       const int map_rank = (int)xv[end - 1] - (head ? (int)xv[head - 1] : 0);
       if (map_rank >= 1 && not_one) { b_fl |= 1; b_ap = apv / map_rank; }                 // map_layer.cpp:92-94
       if (first >= 0 && zero) { b_fl |= 2; b_inv = 1.0 / (first + 1); }                   // mrr_layer.cpp:75
+      bap[bk] = b_ap; binv[bk] = b_inv; bfl[bk] = b_fl;
     }
 #ifdef MMS_RANK_STAMPS
     st3 = __builtin_amdgcn_s_memrealtime();
 #endif
-    // the fold over the buckets in sorted (ascending group) order: running sums only, one wave, 64 buckets per step
-    float* bap = reinterpret_cast<float*>(keys);     // (the sorted keys are not needed any more)
-    double* binv = reinterpret_cast<double*>(xk);
-    int* bfl = fl;
-    if (t < B) { bap[t] = b_ap; binv[t] = b_inv; bfl[t] = b_fl; }
     __syncthreads();
+    // the fold over the buckets in sorted (ascending group) order: running sums only, one wave, 64 buckets per step
     if (t < 64) {
       float map_ = 0.f, mrr = 0.f;
       int eff_map = 0, eff_mrr = 0;
