@@ -36,7 +36,6 @@ HIPCC_FLAGS = [
 ]
 # pairrank.hip: the arrival atomics of the fused step are issued by ONE lane and their return values are consumed
 # after the gradient stores; the atomic optimizer's wave scan + readfirstlane would pull the wait to the issue.
-HIPCC_FLAGS += os.environ.get("MMS_HIPCC_EXTRA", "").split()   # dev builds (-DMMS_STAMPS, -DMMS_ABLATE=.., ...)
 EXTRA_FLAGS = {"pairrank.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
 
 

@@ -28,32 +28,6 @@
 
 namespace mms {
 
-// Dev-only phase stamps (tools/gemmstamp.hip builds this file with -DMMS_GEMM_STAMPS): thread 0 of
-// every workgroup of the fast kernel records s_memtime at its phase boundaries, plus where it ran.
-#ifdef MMS_GEMM_STAMPS
-__device__ unsigned long long* mms_gemm_stamp_buf = nullptr;
-#define MMS_GSTAMP(k)                                                                          \
-  do {                                                                                         \
-    if (mms_gemm_stamp_buf && threadIdx.x == 0)                                                \
-      mms_gemm_stamp_buf[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#define MMS_GSTAMP_REAL(k)                                                                     \
-  do {                                                                                         \
-    if (mms_gemm_stamp_buf && threadIdx.x == 0)                                                \
-      mms_gemm_stamp_buf[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#define MMS_GSTAMP_WHERE()                                                                     \
-  do {                                                                                         \
-    if (mms_gemm_stamp_buf && threadIdx.x == 0)                                                \
-      mms_gemm_stamp_buf[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + 7] = \
-          ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492); \
-  } while (0)
-#else
-#define MMS_GSTAMP(k) do {} while (0)
-#define MMS_GSTAMP_WHERE() do {} while (0)
-#define MMS_GSTAMP_REAL(k) do {} while (0)
-#endif
-
 typedef float v16f __attribute__((ext_vector_type(16)));
 
 struct GemmArgs {
@@ -333,7 +307,6 @@ __device__ __forceinline__ void gemm32_fast_tile(const GemmArgs& g, int bx, int 
     load(kbeg);
     store(0);
     __syncthreads();
-    MMS_GSTAMP(1);
     int cur = 0;
     for (int k0 = kbeg; k0 < kend; k0 += FK, cur ^= 1) {
       const bool more = k0 + FK < kend;
@@ -356,7 +329,6 @@ __device__ __forceinline__ void gemm32_fast_tile(const GemmArgs& g, int bx, int 
     }
   }
 
-  MMS_GSTAMP(2);
   const float* rs = g.rowscale ? g.rowscale + b0 * g.rs_b0 : nullptr;
   const float* ad = g.addend ? g.addend + b1 * g.ad_b1 : nullptr;
   const int gj = j0 + wn * 32 + r;
@@ -390,11 +362,6 @@ __device__ __forceinline__ void gemm32_fast_tile(const GemmArgs& g, int bx, int 
     else if (g.stream_c) __builtin_nontemporal_store(v, c);
     else *c = v;
   }
-#ifdef MMS_GEMM_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  MMS_GSTAMP(3);
-  MMS_GSTAMP_REAL(5);
 }
 
 
@@ -407,9 +374,6 @@ __global__ __launch_bounds__(256) void gemm32_fast_kernel(GemmArgs g) {
   // Remap so that CONSECUTIVE logical tiles land on one XCD: the column tiles of one row panel
   // (they re-read the same A rows), and -- for a split-K product -- all tiles of one k-chunk (each
   // re-reads the chunk's A and B slabs; dealt over 8 L2s those slabs came from HBM 6 times over).
-  MMS_GSTAMP(0);
-  MMS_GSTAMP_REAL(4);
-  MMS_GSTAMP_WHERE();
   int bx = blockIdx.x, by = blockIdx.y, z = blockIdx.z;
   {
     const int plane = gridDim.x * gridDim.y, total = plane * gridDim.z;

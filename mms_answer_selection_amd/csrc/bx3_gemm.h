@@ -179,16 +179,6 @@ __global__ __launch_bounds__(256) void bx3_split_b_kernel(const Bx3SplitArgs a) 
   bx3_split_b_body(a, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
-#ifdef MMS_BX3_STAMPS     // dev-only (tools/bx3bench.hip): per-workgroup wall-clock (100 MHz) / shader-clock stamps of wave 0
-__device__ unsigned long long* bx3_stamp_buf = nullptr;
-#define BX3_STAMP(k, v)                                                                        \
-  do {                                                                                         \
-    if (bx3_stamp_buf && threadIdx.x == 0) bx3_stamp_buf[(size_t)blockIdx.x * 16 + (k)] = (v); \
-  } while (0)
-#else
-#define BX3_STAMP(k, v) do {} while (0)
-#endif
-
 // LDS-DMA with a scalar base and a 32-bit per-lane offset: no VALU per request (the loaders share their SIMD's vector
 // issue with a compute wave; per-lane 64-bit addresses cost it some 130 VALU per k-step)
 __device__ __forceinline__ void bx3_dma16s(const void* sbase, unsigned voff, unsigned lds_byte) {
@@ -208,14 +198,6 @@ __device__ __forceinline__ void bx3_wait_vm() { asm volatile("s_waitcnt vmcnt(%0
 // the loader's loop: PER DMAs per k-step, issued by issue(step)
 template <int PER, int NS, class Issue, class Side, class SideOps>
 __device__ __forceinline__ void bx3_loader_loop(int ksteps, Issue&& issue, Side&& side, SideOps&& side_ops) {
-#if defined(MMS_BX3_ABLATE) && MMS_BX3_ABLATE == 4       // MMS_BX3_ABLATE / MMS_BX3TN_ABLATE: dev-only timing ablations (tools/bx3bench.hip)
-  __builtin_amdgcn_s_barrier();
-  return;
-#endif
-#if defined(MMS_BX3_ABLATE) && (MMS_BX3_ABLATE == 1 || MMS_BX3_ABLATE == 3)
-  for (int j = 0; j <= ksteps; ++j) __builtin_amdgcn_s_barrier();
-  return;
-#endif
   for (int s = 0; s < NS - 1 && s < ksteps; ++s) issue(s);
   for (int j = 0; j <= ksteps; ++j) {
     // barrier j: steps j and j+1 have landed; issued so far: up to step j + NS - 2
@@ -334,7 +316,6 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
   const int row0 = panel * G::ROWS;
   if (row0 >= p.M) return;                                // grid rounded up to a multiple of 16 (whole workgroups only)
   const int ksteps = bx3_ksteps(p.K);
-  BX3_STAMP(0, __builtin_amdgcn_s_memrealtime());
   const unsigned lds0 = (unsigned)(uintptr_t)bx3_lds;     // LDS byte address of the ring
 
   bx3_f16 acc[NTW];
@@ -473,13 +454,6 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
     };
     __builtin_amdgcn_s_barrier();                    // barrier 0: steps 0 and 1 have landed
     asm volatile("" ::: "memory");
-    BX3_STAMP(1, __builtin_amdgcn_s_memrealtime());
-    BX3_STAMP(4, __builtin_amdgcn_s_memtime());
-#if defined(MMS_BX3_ABLATE) && (MMS_BX3_ABLATE == 2 || MMS_BX3_ABLATE == 3)
-    for (int s = 0; s < ksteps; ++s) __builtin_amdgcn_s_barrier();
-    if (false)
-#endif
-    {
     pg_v4f r0 = {0.f, 0.f, 0.f, 0.f}, r1 = {0.f, 0.f, 0.f, 0.f};
     read_a(0, r0, r1);
     Bx3Frag a = split_a(r0, r1);
@@ -528,18 +502,13 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
       a = an;
       slot = nslot;
       asm volatile("" ::: "memory");
-#if !defined(MMS_BX3_ABLATE) || MMS_BX3_ABLATE != 4
       __builtin_amdgcn_s_barrier();                  // barrier s + 1: this step's slot is free; steps s + 1, s + 2 have landed
-#endif
       asm volatile("" ::: "memory");
-    }
     }
   }
 
   // ---------------------------------- epilogue ----------------------------------
   // (the loop's last barrier: every ring read is done and every DMA has landed)
-  BX3_STAMP(2, __builtin_amdgcn_s_memrealtime());
-  BX3_STAMP(5, __builtin_amdgcn_s_memtime());
   // Accumulators through LDS (the ring is free: the loop's last barrier), then all eight waves write 16-byte row
   // segments.  Register i of a 32x32 tile holds row 8 (i / 4) + 4 (lane / 32) + i % 4 at column lane % 32.
   float* stage = reinterpret_cast<float*>(bx3_lds);
@@ -611,7 +580,6 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
       }
     }
   }
-  BX3_STAMP(3, __builtin_amdgcn_s_memrealtime());
 }
 
 inline bool bx3_eligible(const Bx3Args& p) {
@@ -768,9 +736,6 @@ __global__ __launch_bounds__(512, 1) void bx3_tn_kernel(const Bx3TnArgs p) {
     const float* const ksp = p.kscale;                        // null: no scale
     auto fetch = [&](auto stage, int s) {
       constexpr int R = decltype(stage)::value;
-#if defined(MMS_BX3TN_ABLATE) && MMS_BX3TN_ABLATE == 3
-      return;
-#endif
       const int nb = __builtin_amdgcn_readfirstlane(n0 + 32 * s);   // wave-uniform by construction; said so, the row bases are scalar
       if (nb + 32 <= nend) {
         // a whole step: one 64-bit address per tile, then row to row by one add -- the splitters share the vector pipe
@@ -813,9 +778,6 @@ __global__ __launch_bounds__(512, 1) void bx3_tn_kernel(const Bx3TnArgs p) {
     };
     auto emit = [&](auto stage, int buf) {
       constexpr int R = decltype(stage)::value;
-#if defined(MMS_BX3TN_ABLATE) && MMS_BX3TN_ABLATE == 1
-      return;
-#endif
 #pragma unroll
       for (int u = 0; u < 5; ++u) {
         const bool isb = ((w + 4 * u) >> 1) >= 5;           // wave-uniform
@@ -862,9 +824,6 @@ __global__ __launch_bounds__(512, 1) void bx3_tn_kernel(const Bx3TnArgs p) {
   for (int s = 0; s < steps; ++s) {
     __syncthreads();
     const bx3_u4* img = reinterpret_cast<const bx3_u4*>(tn_lds + (s & 1) * BX3TN_BUF) + lane;
-#if defined(MMS_BX3TN_ABLATE) && MMS_BX3TN_ABLATE == 2
-    continue;
-#endif
     bx3_h8 ah[5], am[5], al[5];
 #pragma unroll
     for (int a = 0; a < 5; ++a) {

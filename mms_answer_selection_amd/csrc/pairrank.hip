@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256) void triplet_wave_kernel(
   }
   const float Tmine = 1.0f / (1.0f + sqrtf(dist));
   const float Tp = __shfl(Tmine, 0, 64), Tn = __shfl(Tmine, 32, 64);
-  asm volatile("" : "+v"(yy));   // in a register before the stores below (see triplet32_kernel)
+  asm volatile("" : "+v"(yy));   // in a register before the stores below, or its wait becomes vmcnt(0) behind them (see euclid_pair32_kernel)
   if (lane == 0) { s_pos[row] = Tp; s_neg[row] = Tn; }
 
   // PairRankLoss on (Tp, Tn, y): every lane computes the same scalars
@@ -350,202 +350,20 @@ __global__ __launch_bounds__(256) void triplet_wave_kernel(
   }
 }
 
-// Width-specialised variant (D = 100 / 200 / 300), the triplet counterpart of
-// euclid_pair32_kernel (simcross_elementwise.hip): D4C known at compile time, all 64 lanes
-// hold float4s lane, lane+64 of q, a+ and a-; the window centres of the positive branch are
-// reduced INTO lanes 0-31 and those of the negative branch into lanes 32-63 with one
-// v_permlane32_swap + a half-wave DPP sum each; the chain is straight-line packed adds fed
-// by LDS reads issued before the reductions; the stitch is the DPP OR-reduction; eight
-// waves per workgroup, no early exit, N first for the kernarg preload, streaming stores.
-// EXACT as in euclid_pair32_kernel (include/mms.h: mms_set_euclid_backward_mode).
-template <int D4C, bool EXACT, int WPB, bool INL>
-__global__ __launch_bounds__(64 * WPB) void triplet32_kernel(
-    int N, float margin, float s0, float s1, const float* __restrict__ q,
-    const float* __restrict__ ap, const float* __restrict__ an, const float* __restrict__ y,
-    float* __restrict__ s_pos, float* __restrict__ s_neg, float* __restrict__ partials,
-    float* __restrict__ dq, float* __restrict__ dap, float* __restrict__ dan, int hinge_ge,
-    unsigned long long* __restrict__ ticket, float* __restrict__ loss, double fx_scale) {
-  constexpr int NIT = (D4C + 63) / 64;
-  constexpr int LASTN = D4C - 64 * (NIT - 1);
-  constexpr int H4 = (D4C + 2) / 3, ST4 = 3 * H4;
-  __shared__ float4 lds4[WPB * 2 * ST4];
-  __shared__ unsigned long long wg_arrivals;       // INL: [60..63] waves arrived, [52..59] poisoned waves, [0..51] sum
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (INL) {
-    // zeroed before anything is in flight: a raw barrier here waits for nothing but the eight wave starts
-    if (threadIdx.x == 0) wg_arrivals = 0;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  }
-  const int want = blockIdx.x * WPB + wave;
-  const bool have = want < N;
-  const int row = have ? want : N - 1;           // a wave past the end recomputes the last triplet, stores nothing
-  const size_t base4 = (size_t)row * D4C;
-  const float4* q4 = reinterpret_cast<const float4*>(q) + base4;
-  const float4* p4 = reinterpret_cast<const float4*>(ap) + base4;
-  const float4* m4 = reinterpret_cast<const float4*>(an) + base4;
-  const bool last_ok = (LASTN >= 64) || (lane < LASTN);
-  float4* sqp = lds4 + (size_t)wave * 2 * ST4;
-  float4* sqn = sqp + ST4;
-
-  float yy = y[row];
-  float4 x[NIT], u[NIT], v[NIT], dp[NIT], dn[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = (it < NIT - 1 || last_ok) ? lane + 64 * it : 0;
-    x[it] = q4[i]; u[it] = p4[i]; v[it] = m4[i];
-  }
-  float pp1 = 0.f, pp2 = 0.f, pn1 = 0.f, pn2 = 0.f;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const bool valid = (it < NIT - 1) || last_ok;
-    const int i = lane + 64 * it;
-    dp[it].x = x[it].x - u[it].x; dp[it].y = x[it].y - u[it].y;
-    dp[it].z = x[it].z - u[it].z; dp[it].w = x[it].w - u[it].w;
-    dn[it].x = x[it].x - v[it].x; dn[it].y = x[it].y - v[it].y;
-    dn[it].z = x[it].z - v[it].z; dn[it].w = x[it].w - v[it].w;
-    float4 a, b;
-    a.x = dp[it].x * dp[it].x; a.y = dp[it].y * dp[it].y;
-    a.z = dp[it].z * dp[it].z; a.w = dp[it].w * dp[it].w;
-    b.x = dn[it].x * dn[it].x; b.y = dn[it].y * dn[it].y;
-    b.z = dn[it].z * dn[it].z; b.w = dn[it].w * dn[it].w;
-    if (valid) { sqp[i] = a; sqn[i] = b; }
-    const float a4 = valid ? (a.x + a.y) + (a.z + a.w) : 0.f;
-    const float b4 = valid ? (b.x + b.y) + (b.z + b.w) : 0.f;
-    if (64 * it + 63 < H4) { pp1 += a4; pn1 += b4; }
-    else if (64 * it < H4) { pp1 += (i < H4) ? a4 : 0.f; pn1 += (i < H4) ? b4 : 0.f; }
-    if (64 * it + 63 < 2 * H4) { pp2 += a4; pn2 += b4; }
-    else if (64 * it < 2 * H4) { pp2 += (i < 2 * H4) ? a4 : 0.f; pn2 += (i < 2 * H4) ? b4 : 0.f; }
-  }
-  if (ST4 > D4C && lane < 2 * (ST4 - D4C))
-    sqp[(lane / (ST4 - D4C)) * ST4 + D4C + (lane % (ST4 - D4C))] = make_float4(0.f, 0.f, 0.f, 0.f);
-  wave_lds_sync();
-  const int br = lane >> 5, j = lane & 31;       // branch handled by this half-wave
-  SpecSegment<H4> sg;
-  sg.load((br ? sqn : sqp) + spec_seg32(j) * H4);
-  // positive totals into lanes 0-31, negative totals into lanes 32-63
-  const float p1 = half_wave_sum(swap_halves_add(pp1, pn1));
-  const float p2 = half_wave_sum(swap_halves_add(pp2, pn2));
-  __builtin_amdgcn_s_setprio(3);
-  const float2v start = spec_start32(p1, p2, j);
-  const float2v end = sg.chain(start);
-  bool hit;
-  float dist = spec_resolve_halves(start, end, j, &hit);
-  if (!hit) {
-    MMS_COUNT_MISS();
-    dist = chain_sum_lds(br ? sqn : sqp, ST4, 0.0f);
-  }
-  __builtin_amdgcn_s_setprio(0);
-  const float Tmine = 1.0f / (1.0f + sqrtf(dist));
-  const float Tp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tmine), 0));
-  const float Tn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tmine), 32));
-  asm volatile("" : "+v"(yy));   // in a register before the stores below, or its wait becomes vmcnt(0) behind them (see euclid_pair32_kernel)
-  if (lane == 0 && have) { s_pos[row] = Tp; s_neg[row] = Tn; }
-
-  // PairRankLoss on (Tp, Tn, y): every lane computes the same scalars
-  const PairTerm pt = pair_term(Tp, Tn, yy, margin);
-  float ga, gb;
-  pair_grad(yy, pt.ordered, pt.similar, s0, s1, ga, gb, hinge_ge != 0);
-  // ---- loss scalar ------------------------------------------------------------------------------------------
-  // INL: ONE launch.  The terms are added as integers (units of 2^-S), so the sum does not depend on the order
-  // of arrival, and the arrival count travels in the same 64-bit word as the sum: an atomic's return value
-  // tells its issuer both that it was the last and what the others brought, with no store whose visibility
-  // would have to be waited for first.  Three hops: waves -> workgroup word in LDS -> one word per
-  // kTicketGroup workgroups -> top word; the wave that completes the top word writes the loss.  All of it is
-  // issued BEFORE this wave's gradient stores (one wave per workgroup waits one round trip for its group word,
-  // one per group issues the top atomic and reads its return after its stores), so the round trips run under
-  // the launch's store drain instead of behind it (the first in-launch form -- write-through term stores,
-  // arrival tickets, then a 16 KB read of the terms by the last workgroup -- had four dependent round trips
-  // behind the terms and measured 12.6 us against 11.3 for a second launch).
-  // A term outside [0, 2^kFxTermBits) (labels or a margin in the hundreds, a NaN input) poisons the words it
-  // passes through and the loss comes out NaN; the two-launch mode has no such limit (include/mms.h).
-  bool top_wait = false;
-  unsigned long long top_old = 0, top_pay = 0;
-  if (INL) {
-    if (lane == 0) {
-      const float t = have ? pt.term : 0.f;
-      const bool ok = t >= 0.f && t < (float)(1 << kFxTermBits);
-      const unsigned long long fx = ok ? (unsigned long long)((double)t * fx_scale) : 0ull;
-      const unsigned long long pay = (1ull << 60) | (ok ? 0ull : kFxOne) | fx;
-      const unsigned long long old = __hip_atomic_fetch_add(&wg_arrivals, pay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if ((old >> 60) == (unsigned long long)(WPB - 1)) {            // this wave completes the workgroup
-        const unsigned long long wg = old + pay;
-        const unsigned grp = blockIdx.x / kTicketGroup;
-        const unsigned gsize = min((unsigned)kTicketGroup, gridDim.x - (unsigned)kTicketGroup * grp);
-        const unsigned long long gpay = kFxOne | (wg & kFxSumMask);
-        if ((wg >> kFxSumBits) & 0xffull)
-          __hip_atomic_fetch_or(ticket + grp, kFxPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long gold = __hip_atomic_fetch_add(ticket + grp, gpay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (((gold >> kFxSumBits) & 0x7ffull) == (unsigned long long)(gsize - 1)) {   // ... and its group
-          const unsigned long long g = gold + gpay;
-          __hip_atomic_store(ticket + grp, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the slot's next launch
-          top_pay = kFxOne | (g & kFxSumMask);
-          if (g & kFxPoison) __hip_atomic_fetch_or(ticket + kTicketTop, kFxPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          top_old = __hip_atomic_fetch_add(ticket + kTicketTop, top_pay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          top_wait = true;                                            // consumed after this wave's stores
-        }
-      }
-    }
-  } else {
-    // the term leaves as a plain store: a second, one-workgroup launch sums all N of them
-    if (lane == 0 && have) partials[row] = pt.term;
-  }
-
-  float4* dq4 = reinterpret_cast<float4*>(dq) + base4;
-  float4* dp4 = reinterpret_cast<float4*>(dap) + base4;
-  float4* dn4 = reinterpret_cast<float4*>(dan) + base4;
-  float4 tp[NIT], tn[NIT];
-  if (EXACT) {
-    const EuclidCoef k0 = euclid_coef(Tp, ga), k1 = euclid_coef(Tn, gb);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) { tp[it] = euclid_tt4(k0, dp[it]); tn[it] = euclid_tt4(k1, dn[it]); }
-  } else {
-    const float c0 = ga * Tp * Tp * Tp, c1 = gb * Tn * Tn * Tn;
-    const float r0 = (float)rcp_newton((double)(Tp - 1.0f) + 1e-9);
-    const float r1 = (float)rcp_newton((double)(Tn - 1.0f) + 1e-9);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      tp[it].x = (c0 * dp[it].x) * r0; tp[it].y = (c0 * dp[it].y) * r0;
-      tp[it].z = (c0 * dp[it].z) * r0; tp[it].w = (c0 * dp[it].w) * r0;
-      tn[it].x = (c1 * dn[it].x) * r1; tn[it].y = (c1 * dn[it].y) * r1;
-      tn[it].z = (c1 * dn[it].z) * r1; tn[it].w = (c1 * dn[it].w) * r1;
-    }
-  }
-  if (have) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      if (!((it < NIT - 1) || last_ok)) break;
-      const int i = lane + 64 * it;
-      float4 oq, op, on;
-      oq.x = (0.f + tp[it].x) + (0.f + tn[it].x); oq.y = (0.f + tp[it].y) + (0.f + tn[it].y);
-      oq.z = (0.f + tp[it].z) + (0.f + tn[it].z); oq.w = (0.f + tp[it].w) + (0.f + tn[it].w);
-      op.x = 0.f + (-tp[it].x); op.y = 0.f + (-tp[it].y); op.z = 0.f + (-tp[it].z); op.w = 0.f + (-tp[it].w);
-      on.x = 0.f + (-tn[it].x); on.y = 0.f + (-tn[it].y); on.z = 0.f + (-tn[it].z); on.w = 0.f + (-tn[it].w);
-      stream_store(dq4 + i, oq);
-      stream_store(dp4 + i, op);
-      stream_store(dn4 + i, on);
-    }
-  }
-
-  if (!INL) return;
-  if (top_wait) {                                  // lane 0 of one wave per kTicketGroup workgroups
-    const unsigned ngrp = (gridDim.x + kTicketGroup - 1) / kTicketGroup;
-    if (((top_old >> kFxSumBits) & 0x7ffull) == (unsigned long long)(ngrp - 1)) {
-      const unsigned long long all = top_old + top_pay;
-      __hip_atomic_store(ticket + kTicketTop, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float sum = (float)((double)(all & kFxSumMask) / fx_scale);
-      *loss = (all & kFxPoison) ? __builtin_nanf("") : sum / (float)N;                       // pair_rank_loss_layer.cpp:49
-    }
-  }
-}
-
-// ---- the same step with TWO triplets per wave --------------------------------------------------------------
+// Width-specialised step (D = 100 / 200 / 300), the triplet counterpart of euclid_pair32_kernel
+// (simcross_elementwise.hip): D4C known at compile time, eight waves per workgroup, no early exit, N first
+// for the kernarg preload, streaming stores.  EXACT as in euclid_pair32_kernel (include/mms.h:
+// mms_set_euclid_backward_mode).
 // A wave owns triplets 2w and 2w+1: their rows of q, a+ and a- are ONE dense run of 2*D4C float4 per array
 // (lane l holds float4s l, l+64, l+128 of the run, whatever triplet they fall in), all requested up front.
-// The two triplets then go through the chain phase one after the other -- pass 0, pass 1, each exactly the
-// half-wave scheme of triplet32_kernel on images in LDS -- and a pass stores its own triplet's gradients as
+// The two triplets then go through the chain phase one after the other -- pass 0, pass 1.  In a pass lanes
+// 0-31 walk the image of the positive branch in LDS and lanes 32-63 that of the negative branch: the window
+// centres by a half-wave DPP sum, the chain straight-line packed adds fed by LDS reads issued before the
+// reductions, the stitch the DPP OR-reduction.  A pass stores its own triplet's gradients as
 // soon as its scores are known: pass 1's LDS round trip and packed-add chains run while pass 0's stores drain,
 // instead of every wave of the launch chaining and then every wave storing.  Half as many waves to dispatch,
-// and a CU has half as many chains in its LDS return path at a time.  Same arithmetic, same bits.
+// and a CU has half as many chains in its LDS return path at a time than with one triplet per wave (10.0
+// against 10.4 us per step at 4096x300).  Same arithmetic, same bits.
 template <int D4C, bool EXACT, int WPB, bool INL>
 __global__ __launch_bounds__(64 * WPB) void triplet32x2_kernel(
     int N, float margin, float s0, float s1, const float* __restrict__ q,
@@ -614,6 +432,19 @@ __global__ __launch_bounds__(64 * WPB) void triplet32x2_kernel(
   float4* dq4 = reinterpret_cast<float4*>(dq);
   float4* dp4 = reinterpret_cast<float4*>(dap);
   float4* dn4 = reinterpret_cast<float4*>(dan);
+  // ---- loss scalar ------------------------------------------------------------------------------------------
+  // INL: ONE launch.  The terms are added as integers (units of 2^-S), so the sum does not depend on the order
+  // of arrival, and the arrival count travels in the same 64-bit word as the sum: an atomic's return value
+  // tells its issuer both that it was the last and what the others brought, with no store whose visibility
+  // would have to be waited for first.  Three hops: waves -> workgroup word in LDS -> one word per
+  // kTicketGroup workgroups -> top word; the wave that completes the top word writes the loss.  All of it is
+  // issued BEFORE this wave's gradient stores (one wave per workgroup waits one round trip for its group word,
+  // one per group issues the top atomic and reads its return after its stores), so the round trips run under
+  // the launch's store drain instead of behind it (the first in-launch form -- write-through term stores,
+  // arrival tickets, then a 16 KB read of the terms by the last workgroup -- had four dependent round trips
+  // behind the terms and measured 12.6 us against 11.3 for a second launch).
+  // A term outside [0, 2^kFxTermBits) (labels or a margin in the hundreds, a NaN input) poisons the words it
+  // passes through and the loss comes out NaN; the two-launch mode has no such limit (include/mms.h).
   // In-launch loss: both passes first, then the arrival atomics, then ALL gradient stores, so that the atomics
   // enter the memory queues ahead of the wave's 7 KB of stores.  Measured (rocprofv3): the launch takes 9.6 us
   // with the in-launch sum against 7.6 us without, wherever the atomics are issued -- two DEPENDENT device-scope
@@ -682,7 +513,6 @@ __global__ __launch_bounds__(64 * WPB) void triplet32x2_kernel(
     bool hit;
     float dist = spec_resolve_halves(start, end, j, &hit);
     if (!hit) {
-      MMS_COUNT_MISS();
       dist = chain_sum_lds(im, ST4, 0.0f);
     }
     __builtin_amdgcn_s_setprio(0);
@@ -703,7 +533,7 @@ __global__ __launch_bounds__(64 * WPB) void triplet32x2_kernel(
       const bool ok = tm >= 0.f && tm < (float)(1 << kFxTermBits);
       fx_sum += ok ? (unsigned long long)((double)tm * fx_scale) : 0ull;
       fx_bad += ok ? 0ull : 1ull;
-      if (t == 1 && lane == 0) {                   // the wave's two terms arrive together (see triplet32_kernel)
+      if (t == 1 && lane == 0) {                   // the wave's two terms arrive together ("loss scalar" above)
         const unsigned long long pay = (1ull << 60) | (fx_bad ? kFxOne : 0ull) | fx_sum;
         const unsigned long long old = __hip_atomic_fetch_add(&wg_arrivals, pay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if ((old >> 60) == (unsigned long long)(WPB - 1)) {
@@ -844,21 +674,12 @@ int triplet_euclid_step(int N, int D, float margin, float loss_weight, const flo
   if (v && (D == 300 || D == 200 || D == 100)) {
     constexpr int WPB = 8;
     nparts = N;
-    // dev switch for A/B timing (tools/triplet_probe.py): MMS_TRIPLET_TPW = 1 | 2 triplets per wave
-    static const int tpw = [] { const char* e = std::getenv("MMS_TRIPLET_TPW"); return e && std::atoi(e) == 1 ? 1 : 2; }();
-    const unsigned grid = (unsigned)((N + WPB * tpw - 1) / (WPB * tpw));
+    const unsigned grid = (unsigned)((N + WPB * 2 - 1) / (WPB * 2));   // two triplets per wave
     const bool exact = euclid_backward_mode() == MMS_EUCLID_BWD_REFERENCE;
 #define MMS_T32_GO(d4, ex, inl)                                                                        \
-  do {                                                                                                     \
-    if (tpw == 2)                                                                                          \
-      hipLaunchKernelGGL((triplet32x2_kernel<d4, ex, WPB, inl>), dim3(grid), dim3(64 * WPB), 0, s, N,      \
-                         margin, s0, s1, q, ap, an, y, s_pos, s_neg, partials, dq, dap, dan, hge, tk,      \
-                         loss, fx_scale);                                                                  \
-    else                                                                                                   \
-      hipLaunchKernelGGL((triplet32_kernel<d4, ex, WPB, inl>), dim3(grid), dim3(64 * WPB), 0, s, N,        \
-                         margin, s0, s1, q, ap, an, y, s_pos, s_neg, partials, dq, dap, dan, hge, tk,      \
-                         loss, fx_scale);                                                                  \
-  } while (0)
+  hipLaunchKernelGGL((triplet32x2_kernel<d4, ex, WPB, inl>), dim3(grid), dim3(64 * WPB), 0, s, N,          \
+                     margin, s0, s1, q, ap, an, y, s_pos, s_neg, partials, dq, dap, dan, hge, tk,          \
+                     loss, fx_scale)
 #define MMS_T32(d4)                                                       \
   case 4 * d4:                                                            \
     if (exact) { if (tk) MMS_T32_GO(d4, true, true); else MMS_T32_GO(d4, true, false); }     \

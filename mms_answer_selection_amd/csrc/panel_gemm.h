@@ -113,19 +113,6 @@ __device__ __forceinline__ void pg_dma4(const float* gsrc, unsigned lds_byte) {
                : "=&s"(keep) : "v"(gsrc), "s"(lds_byte) : "memory");
 }
 
-#ifdef MMS_PG_STAMPS      // dev-only (tools/panelbench.hip): per-workgroup shader-clock / wall-clock stamps around the main loop
-__device__ unsigned long long* pg_stamp_buf = nullptr;
-#define PG_STAMP(k)                                                                                   \
-  do {                                                                                                \
-    if (pg_stamp_buf && threadIdx.x == 0) {                                                           \
-      pg_stamp_buf[(size_t)blockIdx.x * 8 + 2 * (k)] = __builtin_amdgcn_s_memtime();                  \
-      pg_stamp_buf[(size_t)blockIdx.x * 8 + 2 * (k) + 1] = __builtin_amdgcn_s_memrealtime();          \
-    }                                                                                                 \
-  } while (0)
-#else
-#define PG_STAMP(k) do {} while (0)
-#endif
-
 // f(integral_constant<int, I>) for I = 0 .. N-1: the hand-issued tile needs its operand index as a compile-time
 // constant (instruction immediates); a `#pragma unroll` loop only promises that if the unroller agrees
 template <int I, int N, typename F>
@@ -264,9 +251,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // read -> wait -> two MFMAs; all reads first, then all MFMAs, idles the matrix pipe while the reads issue.)
   pg_v4f av[2];
   float bv[2][NT];
-#ifdef MMS_PG_STAMPS
-  unsigned long long pg_wait_lgkm = 0, pg_wait_bar = 0;
-#endif
   auto read_a = [&](pg_v4f (&dst)[2], int stage) {
     const float* At = lds + stage * STAGE_F + G::B_F;
 #pragma unroll
@@ -301,16 +285,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // operands beside step 7.
   auto full_tile = [&](auto bar_tag, auto pre_tag, int stage, int nstage) {
     constexpr bool BAR = decltype(bar_tag)::value, PRE = decltype(pre_tag)::value;
-#if defined(MMS_PG_ABLATE) && MMS_PG_ABLATE >= 2      // dev-only timing ablation: MFMAs alone, operands from registers
-#pragma unroll
-    for (int st = 0; st < 8; ++st) {
-      if (st == 7 && BAR) asm volatile("s_barrier" ::: "memory");
-#pragma unroll
-      for (int tt = 0; tt < NT; ++tt)
-        acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[st >> 2][st & 3], av[(st >> 2) ^ 1][st & 3], acc[tt], 0, 0, 0);
-    }
-    return;
-#endif
 #pragma unroll
     for (int st = 0; st < 7; ++st) {
       read_b(bv[(st + 1) & 1], stage, st + 1);
@@ -319,16 +293,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[st >> 2][st & 3], bv[st & 1][tt], acc[tt], 0, 0, 0);
       interleave();
     }
-#ifdef MMS_PG_STAMPS
-    const unsigned long long tb0 = __builtin_amdgcn_s_memtime();
-    if (BAR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const unsigned long long tb1 = __builtin_amdgcn_s_memtime();
-    if (BAR) asm volatile("s_barrier" ::: "memory");
-    const unsigned long long tb2 = __builtin_amdgcn_s_memtime();
-    pg_wait_lgkm += tb1 - tb0; pg_wait_bar += tb2 - tb1;
-#else
     if (BAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");        // B_{T+1}
-#endif
     pg_v4f an[2];
     if (PRE) {
       read_a(an, nstage);
@@ -381,9 +346,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // landed" (LDS operations return in order), and __builtin_amdgcn_sched_barrier pins the order read, wait, MFMA.
   // The microbenchmark's loop of exactly this shape runs at 32.1 cycles per MFMA, 34.6 with the ring, the barrier and
   // the loaders' DMAs beside it.  Operand n = NT st + tt of a tile lives in slot n mod 2 NT.
-#ifndef MMS_PG_HAND
-#define MMS_PG_HAND 1
-#endif
   float bb[2 * NT];
   pg_v4f an[2];                                       // A_KC: the next tile's fragments as read
   float araw[8], sraw[8];                             // !A_KC: the next tile's A values and their k scales as read
@@ -564,43 +526,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       issue_next(0);
       issue_next(1);
     }
-#ifdef MMS_PG_STAMPS
-    unsigned long long ld_wait = 0, ld_bar = 0, ld_issue = 0;
-#endif
     const int SP = ntiles >= 8 ? 2 : 1;               // side-job passes: requested in iteration SP rr, stored one later
     int s_loaded = 0, s_stored = 0;
     for (int T = 0; T < ntiles; ++T) {
-#ifdef MMS_PG_STAMPS
-      const unsigned long long l0 = __builtin_amdgcn_s_memtime();
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPT) : "memory");
-      const unsigned long long l1 = __builtin_amdgcn_s_memtime();
-      asm volatile("s_barrier" ::: "memory");
-      const unsigned long long l2 = __builtin_amdgcn_s_memtime();
-      if (T > 0) { ld_wait += l1 - l0; ld_bar += l2 - l1; }
-#else
       asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NPT) : "memory");       // B_T
-#endif
       if (p.side_in) {
         // round 3: one row pass every SPth iteration instead of the first four -- 256 workgroups streaming their
         // 2 x 77 KB at the same moment, in front of their own first tiles, cost the launch 3-4 us
         if (s_stored < s_loaded && T >= SP * s_stored + 1) { side_pin(); side_store(s_stored); ++s_stored; }
         if (s_loaded < 4 && s_loaded == s_stored && T >= SP * s_loaded) { side_load(s_loaded); ++s_loaded; }
       }
-#if defined(MMS_PG_ABLATE) && MMS_PG_ABLATE >= 1      // dev-only timing ablation (tools/panelbench.hip): no loads after the prologue
-      if (false)
-#endif
       issue_next((T + 2) % 3);
-#ifdef MMS_PG_STAMPS
-      if (T > 0) ld_issue += __builtin_amdgcn_s_memtime() - l2;
-#endif
     }
-#ifdef MMS_PG_STAMPS
-    if (pg_stamp_buf && threadIdx.x == 256) {
-      pg_stamp_buf[(size_t)(gridDim.x + blockIdx.x) * 8 + 0] = ld_wait;
-      pg_stamp_buf[(size_t)(gridDim.x + blockIdx.x) * 8 + 1] = ld_bar;
-      pg_stamp_buf[(size_t)(gridDim.x + blockIdx.x) * 8 + 2] = ld_issue;
-    }
-#endif
     if (p.side_in) {                                  // what the loop was too short for
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       side_pin();
@@ -615,14 +552,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   } else {
     // Barriers: B_0 here, B_{T+1} inside tile T (full tiles: in front of step 7; a partial tile: behind it).
     int T = 0;
-    PG_STAMP(0);
     if (ntiles > 0) asm volatile("s_barrier" ::: "memory");                              // B_0
-#if MMS_PG_HAND && !defined(MMS_PG_ABLATE)
-    // Same-box A/B (gpurun_out/r3/ab_hand.txt, three alternations): the hand-issued tile is worth 2.4 us on the
+    // Same-box A/B (profiles/r03_ab_hand_tile.txt, three alternations): the hand-issued tile is worth 2.4 us on the
     // split-K dW product (38.7 -> 36.3 us), nothing on Q.W (40.1 / 40.4) and COSTS 1.8 us where the loaders carry
     // the da side job (36.6 -> 38.4) -- the launch is then power-bound: the shader clock falls from 2.18 to 2.10 GHz
-    // as the stream tightens (stamps).  So it serves the !A_KC product only; MMS_PG_HAND=2 forces it everywhere.
-    if (p.nseg == 1 && (!A_KC || MMS_PG_HAND >= 2)) {
+    // as the stream tightens.  So it serves the !A_KC product only.
+    if (p.nseg == 1 && !A_KC) {
       // one segment (every product of cfg 3): all full tiles that are followed by a full tile run in ONE loop body
       if (nfull > 0) {
         hand_prime();
@@ -632,9 +567,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       if (has_tail) tail_tile(nfull % 3, kbeg + 32 * nfull);
       T = ntiles;
-    } else
-#endif
-    {
+    } else {
     bool primed = false;                               // are tile T's first operands in registers?
     for (int seg = 0; seg < p.nseg; ++seg) {
       int k0 = kbeg;
@@ -658,20 +591,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
     }
-    PG_STAMP(1);
   }
   // ---- epilogue: accumulators -> LDS (16 x LD slice per compute wave) -> 256-byte row segments ----------
   if (loader) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's DMAs (and side job) have landed
   asm volatile("s_barrier" ::: "memory");                            // B_end: ring drained, nobody reads it any more
-#if defined(MMS_PG_ABLATE) && MMS_PG_ABLATE >= 3      // dev-only: no epilogue (one store keeps the accumulators live)
-  {
-    float keep = 0.f;
-#pragma unroll
-    for (int tt = 0; tt < NT; ++tt) keep += acc[tt][0] + acc[tt][1] + acc[tt][2] + acc[tt][3];
-    if (keep == 12345.678f && p.C) p.C[t] = keep;
-    return;
-  }
-#endif
   float* Cs = lds + wave * 16 * LD;
   if (!loader) {
 #pragma unroll
@@ -761,11 +684,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         pg_v4f v = *reinterpret_cast<const pg_v4f*>(Cs + row_l * LD + 4 * c4);
         if (p.rowscale) v = rs * v;
         if (do_dot) dot += (v[0] * y4[rr][cc][0] + v[1] * y4[rr][cc][1]) + (v[2] * y4[rr][cc][2] + v[3] * y4[rr][cc][3]);
-#if defined(MMS_PG_ABLATE) && MMS_PG_ABLATE == -4    // dev-only: epilogue without its global stores
-        if (do_store && valid && v[0] == 12345.678f) {
-#else
         if (do_store && valid) {
-#endif
           pg_v4f* dst = reinterpret_cast<pg_v4f*>(Cg + (long long)grow * p.ldc + 4 * c4);
           if (p.stream_c) __builtin_nontemporal_store(v, dst);
           else *dst = v;
@@ -783,14 +702,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
   }
-#ifdef MMS_PG_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (pg_stamp_buf && threadIdx.x == 0) {
-    pg_stamp_buf[(size_t)blockIdx.x * 8 + 6] = pg_wait_lgkm;
-    pg_stamp_buf[(size_t)blockIdx.x * 8 + 7] = pg_wait_bar;
-  }
-#endif
-  PG_STAMP(2);
 }
 
 // ------------------------------------------------ host side -----------------------------------------

@@ -399,9 +399,6 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
   __shared__ int fl[MODE == 0 ? kRankMid : 1];
   __shared__ float slab[MODE == 0 ? kRankMid : 1];
   const int t = threadIdx.x;
-#ifdef MMS_RANK_STAMPS      // dev-only (tools/rank_mid_probe.py): phase times in 10-ns ticks behind the results, out0[4..]
-  unsigned long long st0 = __builtin_amdgcn_s_memrealtime(), st1 = 0, st2 = 0, st3 = 0, st4 = 0;
-#endif
   unsigned long long k[2];
   unsigned v[2];
 #pragma unroll
@@ -415,16 +412,13 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
     const bool mine_gt = km > ko || (km == ko && vm > vo);
     return (mine_gt == (lower == up)) ? false : true;   // ascending pair keeps the smaller one at the lower position
   };
-#ifdef MMS_RANK_STAMPS
-  st1 = __builtin_amdgcn_s_memrealtime();
-#endif
   // Sort = (1) each wave sorts its 128 items in registers (bitonic network of 28 passes; the partner of a lane at
   // distance 1 / 2 / 4 / 8 / 16 / 32 comes by DPP or v_permlane{16,32}_swap, no LDS), then (2) four MERGE rounds
   // 128 -> 256 -> 512 -> 1024 -> 2048: every item finds by binary search how many items of the sibling run precede it
   // ((key, index) pairs are distinct, so "precede" needs no tie rule) and is written to its merged position in the other
   // LDS buffer.  8 + 9 + 10 + 11 dependent LDS reads and four barriers instead of the 66 passes (56 of them 6
   // ds_bpermute each, 10 through LDS with a barrier) of one flat bitonic network: 19 -> 11.8 us at 1,517 items on a lone
-  // workgroup (stamps, tools/rank_mid_probe.py: the 38 search steps are bound by the LDS round trip at that clock).
+  // workgroup (profiles/r03_rank_mid_phases_merge_sort.txt: the 38 search steps are bound by the LDS round trip at that clock).
   const int lane_s = t & 63;
   auto lane_xor = [&](unsigned x, int m) -> unsigned {          // the value lane (lane ^ m) holds
     switch (m) {
@@ -514,9 +508,6 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
     for (int e = 0; e < 2; ++e) { k[e] = ck[2 * t + e]; v[e] = cv[2 * t + e]; }
   }
   __syncthreads();                                    // the last readers of `keys` / `vals` as exchange buffers are done
-#ifdef MMS_RANK_STAMPS
-  st2 = __builtin_amdgcn_s_memrealtime();
-#endif
 #pragma unroll
   for (int e = 0; e < 2; ++e) { keys[2 * t + e] = k[e]; vals[2 * t + e] = v[e]; }
   __syncthreads();
@@ -524,7 +515,7 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
     // A lone workgroup runs at a fraction of the chip's loaded clock: the per-bucket walks of rank_bucket_at (one
     // thread per bucket, a data-dependent exit and a division per item: two LDS round trips + ~40 dependent
     // instructions per iteration) took 15.8 us at 1,517 items and the one-wave fold with its double divisions 7.6 us
-    // (stamps, tools/rank_mid_probe.py).  Same expressions and the same summation orders, but everything that is not
+    // (profiles/r03_rank_mid_phases.txt).  Same expressions and the same summation orders, but everything that is not
     // a running fp sum now happens in parallel: bucket heads, lengths and positive counts by workgroup scans, every
     // positive's term map_rank / (pos + 1) and every bucket's ap / map_rank and 1.0 / (mrr_rank + 1) by its own
     // thread; what is left sequential is adds over loads whose addresses are known up front.
@@ -609,9 +600,6 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
       if (first >= 0 && zero) { b_fl |= 2; b_inv = 1.0 / (first + 1); }                   // mrr_layer.cpp:75
       bap[bk] = b_ap; binv[bk] = b_inv; bfl[bk] = b_fl;
     }
-#ifdef MMS_RANK_STAMPS
-    st3 = __builtin_amdgcn_s_memrealtime();
-#endif
     __syncthreads();
     // the fold over the buckets in sorted (ascending group) order: running sums only, one wave, 64 buckets per step
     if (t < 64) {
@@ -642,10 +630,6 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
         if (out0) *out0 = map_ / eff_map;             // NaN when no bucket counts, like the reference (:99)
         if (out1) *out1 = mrr / eff_mrr;
         if (effective) *effective = eff_map;
-#ifdef MMS_RANK_STAMPS
-        st4 = __builtin_amdgcn_s_memrealtime();
-        out0[4] = (float)(st1 - st0); out0[5] = (float)(st2 - st1); out0[6] = (float)(st3 - st2); out0[7] = (float)(st4 - st3);
-#endif
       }
     }
   } else {

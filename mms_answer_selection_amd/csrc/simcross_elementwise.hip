@@ -30,20 +30,6 @@
 
 namespace mms {
 
-// Dev-only phase stamps (tools/stampbench.hip builds this file with -DMMS_STAMPS): lane 0 of
-// every wave of the fused rows kernel records s_memtime at its phase boundaries into a
-// buffer no other code reads.  Compiled out of the product.
-#ifdef MMS_STAMPS
-__device__ unsigned long long* mms_stamp_buf = nullptr;
-#define MMS_STAMP(k)                                                                        \
-  do {                                                                                      \
-    if (mms_stamp_buf && (threadIdx.x & 63) == 0)                                           \
-      mms_stamp_buf[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define MMS_STAMP(k) do {} while (0)
-#endif
-
 // =============================== rows geometry ==============================
 
 // ---- wave-centric kernel (the fast path) ------------------------------------
@@ -80,7 +66,6 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
   const int st4 = spec_stride4(D4);
   float4* sq4 = lds4 + (size_t)wave * RW * st4;
 
-  MMS_STAMP(0);
   float4 x[NIT], y[NIT], df[NIT];
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
@@ -89,7 +74,6 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
     x[it] = q4[ii];
     y[it] = a4[ii];
   }
-  MMS_STAMP(1);
   // this lane's pair for the chain / coefficient work
   const int grp = lane / LPR, j = lane % LPR;
   const int grow = min(grp, rows - 1);           // a missing 2nd pair mirrors the 1st (results unused)
@@ -125,10 +109,6 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
       if (RW == 2) pred[RW - 1] += r1 ? c : z2;
     }
   }
-#ifdef MMS_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  MMS_STAMP(2);
   if (FWD) {
     // zero pad at the end of each image (0..2 entries)
     const int npad = st4 - D4;
@@ -140,13 +120,7 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
       if (r == grow) { my1 = p1; my2 = p2; }
     }
     wave_lds_sync();
-    MMS_STAMP(3);
-#if defined(MMS_ABLATE) && MMS_ABLATE >= 1   // dev-only timing ablation (tools/ablate.sh): no chain
-    const float dist = my2;
-#else
     const float dist = chain_sum_speculative<LPR>(sq4 + grow * st4, D4, my1, my2, j, grp * LPR);
-#endif
-    MMS_STAMP(4);
     T = 1.0f / (1.0f + sqrtf(dist));            // :106-107
     if (BWD) asm volatile("" : "+v"(g));        // in a register before the store of T (see euclid_pair32_kernel)
     if (j == 0 && grp < rows) top_out[row0 + grp] = T;
@@ -170,7 +144,6 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
       kr[r].rcp = __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
     }
   }
-  MMS_STAMP(5);
   float4* dq4 = reinterpret_cast<float4*>(dq) + base4;
   float4* da4 = reinterpret_cast<float4*>(da) + base4;
   // all NIT float4s as ONE straight-line block (their instruction chains interleave),
@@ -204,11 +177,6 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
     stream_store(dq4 + i, o0);
     stream_store(da4 + i, o1);
   }
-  MMS_STAMP(6);
-#ifdef MMS_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  MMS_STAMP(7);
 }
 
 // ---- width-specialised wave-pair kernel (the headline configuration) ----------
@@ -249,7 +217,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
   const float4* a4 = reinterpret_cast<const float4*>(a) + (size_t)row * D4C;
   const bool last_ok = (LASTN >= 32) || (j < LASTN);
 
-  MMS_STAMP(0);
   float T = 0.f;
   if (!FWD) T = top_in[row];
   float g = 0.f;
@@ -261,7 +228,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     x[it] = q4[i];
     y[it] = a4[i];
   }
-  MMS_STAMP(1);
 
   float p1 = 0.f, p2 = 0.f;
   float4* img = lds4 + (wave * 2 + grp) * ST4;
@@ -284,10 +250,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
       else if (32 * it < 2 * H4) p2 += (i < 2 * H4) ? s4 : 0.f;
     }
   }
-#ifdef MMS_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  MMS_STAMP(2);
   if (FWD) {
     if (ST4 > D4C && j < ST4 - D4C) img[D4C + j] = make_float4(0.f, 0.f, 0.f, 0.f);
     wave_lds_sync();
@@ -295,30 +257,16 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     sg.load(img + spec_seg32(j) * H4);          // in flight while the window centres are reduced
     p1 = half_wave_sum(p1);
     p2 = half_wave_sum(p2);
-    MMS_STAMP(3);
     __builtin_amdgcn_s_setprio(3);
     const float2v start = spec_start32(p1, p2, j);
-#if defined(MMS_ABLATE) && MMS_ABLATE >= 12     // dev-only timing ablations (tools/ablate.sh)
-    float dist = p2 + sg.v[0].x;
-#elif defined(MMS_ABLATE) && MMS_ABLATE == 11
-    const float2v end = sg.chain(start);
-    float dist = end.x + end.y;
-#else
     const float2v end = sg.chain(start);
     bool hit;
     float dist = spec_resolve_halves(start, end, j, &hit);
     if (!hit) {                                 // uniform per half; exact re-walk of this lane's pair
-      MMS_COUNT_MISS();
       dist = chain_sum_lds(img, ST4, 0.0f);
     }
-#endif
     __builtin_amdgcn_s_setprio(0);
-    MMS_STAMP(4);
-#if defined(MMS_ABLATE) && MMS_ABLATE >= 13
-    T = dist;
-#else
     T = 1.0f / (1.0f + sqrtf(dist));            // :106-107
-#endif
     // g is pinned as "in a register" HERE, before the store of T: left to the compiler, its first use came
     // after that store (issued under a lane mask, so the wait could not be counted) and every wave sat in
     // s_waitcnt vmcnt(0) until the store was acknowledged
@@ -358,7 +306,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
       t[it].z = (c * df[it].z) * r; t[it].w = (c * df[it].w) * r;
     }
   }
-  MMS_STAMP(5);
   if (have) {
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
@@ -371,11 +318,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     stream_store(da4 + j + 32 * it, o1);
   }
   }
-  MMS_STAMP(6);
-#ifdef MMS_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  MMS_STAMP(7);
 }
 
 // ---- the same algorithm with the global-memory side laid out by WORKGROUP, not by pair ----------
@@ -488,7 +430,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_block_kernel(
     bool hit;
     float dist = spec_resolve_halves(start, end, j, &hit);
     if (!hit) {                                 // uniform per half; exact re-walk of this lane's pair
-      MMS_COUNT_MISS();
       dist = chain_sum_lds(img, ST4, 0.0f);
     }
     __builtin_amdgcn_s_setprio(0);
@@ -561,18 +502,15 @@ void set_f16_distance_mode(int m) { t_f16_distance_mode = m; }
 // MI355X-side storage format, not a change of the layer's numerics.
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
-// RW pairs per wave (64 / RW lanes each).  At D = 1024 the ordered chain is 55 % of the kernel
-// (tools/f16abl.sh: 18.6 us with, 8.3 us without it at 8192 pairs): two pairs per wave would halve its
-// VALU issue cost per pair, but the narrower speculation windows (+-12 / +-15 ulp instead of +-25 / +-36)
-// miss too often there (see simcross_euclid_rows_f16); a miss re-walks one segment exactly, so results
-// never change, only time.
-// QUAD (RW == 1 only): the quad-shared chain of euclid_math.h (a quarter of the LDS operand traffic).
+// RW pairs per wave (64 / RW lanes each).  The ordered sum runs with RW == 2 (D <= 400: beyond that its
+// speculation windows of 32 lanes miss too often, see simcross_euclid_rows_f16, and the lane-chain kernel
+// below takes over); a miss re-walks one segment exactly, so results never change, only time.
 // TREE (RW == 1 only): the distance is the TREE sum of the squares that the ordered variants use only to centre
 // their speculation windows -- no ordered chain, 8.3 instead of 19 us at cfg 5's shard.  The reference has no
 // fp16 instantiation, so there is no reference rounding to reproduce; SURVEY 8(d) holds cfg 5 to 1e-3 relative
 // against the fp32 oracle on the fp16-rounded inputs, and this sum is within ~1e-6 of it.  Opt-in
 // (mms_set_f16_distance_mode): the default stays the ordered sum, bit-identical to the fp32 layer's.
-template <int NIT, int RW, bool BWD, bool QUAD = false, bool TREE = false>
+template <int NIT, int RW, bool BWD, bool TREE = false>
 __global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
     const _Float16* __restrict__ q, const _Float16* __restrict__ a,
     const float* __restrict__ top_diff, float* __restrict__ top_out,
@@ -588,7 +526,7 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
   const size_t base8 = (size_t)row0 * D8;
   const half8* q8 = reinterpret_cast<const half8*>(q) + base8;
   const half8* a8 = reinterpret_cast<const half8*>(a) + base8;
-  const int h4 = QUAD ? quad_h4(D4) : spec_h4(D4), st4 = 3 * h4;
+  const int h4 = spec_h4(D4), st4 = 3 * h4;
   float4* sq4 = lds4 + (size_t)wave * RW * st4;
 
   half8 x[NIT], y[NIT];
@@ -645,13 +583,8 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
     if (r == grow) { my1 = p1; my2 = p2; }
   }
   wave_lds_sync();
-#if defined(MMS_F16ABL) && MMS_F16ABL == 1     // dev-only timing ablation (tools/f16bench.hip): no chain
-  const float dist = my2;
-#else
   const float dist = TREE ? wave_sum(tree_total)
-                   : QUAD ? chain_sum_speculative_quad(sq4, h4, my1, my2, lane)
                           : chain_sum_speculative<LPR>(sq4 + grow * st4, D4, my1, my2, j, grp * LPR);
-#endif
   const float T = 1.0f / (1.0f + sqrtf(dist));
   if (BWD) asm volatile("" : "+v"(g));          // in a register before the store of T (see euclid_pair32_kernel)
   if (j == 0 && grp < rows) top_out[row0 + grp] = T;
@@ -686,18 +619,13 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
       o1[4 * hh + 0] = (_Float16)(0.f + (-t.x)); o1[4 * hh + 1] = (_Float16)(0.f + (-t.y));
       o1[4 * hh + 2] = (_Float16)(0.f + (-t.z)); o1[4 * hh + 3] = (_Float16)(0.f + (-t.w));
     }
-#if defined(MMS_F16ABL) && MMS_F16ABL == 2     // dev-only timing ablation: no stores
-    if (T == 12345.0f)
-#endif
-    {
-      stream_store_vec(dq8 + i, o0);
-      stream_store_vec(da8 + i, o1);
-    }
+    stream_store_vec(dq8 + i, o0);
+    stream_store_vec(da8 + i, o1);
   }
 }
 
-// The ORDERED distance at large D without speculation (round 3; D > 400, where the kernel above runs one pair per wave
-// and its quad-shared speculative chain is 55 % of the launch: 18.9 us at cfg 5's shard).  One wave per pair loads,
+// The ORDERED distance at large D without speculation (round 3; D > 400, where a speculative chain with one pair per
+// wave was 55 % of the launch: 20.2 us at cfg 5's shard against 13.2 here, profiles/r03_f16_lanewalk.txt).  One wave per pair loads,
 // squares and later differentiates its pair exactly as above; the squares go to LDS as the pair's image, and after one
 // workgroup barrier LANE p of wave 0 walks pair p's image front to back -- the reference's d-ascending fp32 sum
 // (sim_cross_layer.cpp:100-106) as 4 D4 dependent adds fed by D4 ds_read_b128, about 2.4 us for D = 1024 whatever the
@@ -879,29 +807,24 @@ int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const f
   const int D8 = D / 8;
   // Two pairs per wave (32 candidate lanes each) only while the narrower windows hold: at D = 1024 the
   // ordered fp32 sum of a 344-term segment strays sigma ~ 6 ulp from its tree-sum prediction, the +-12 / +-15
-  // windows of 32 lanes missed on 3.4 % of pairs (tools/f16abl.sh) and the exact re-walks ate the gain at
+  // windows of 32 lanes missed on 3.4 % of pairs and the exact re-walks ate the gain at
   // cfg 5's shard size (19.5 vs 18.6 us; 125 vs 149 us at 65536 pairs).  Same limit as the fp32 kernels.
   const int rw = D <= 400 ? 2 : 1;
   const int nit = (rw * D8 + 63) / 64;
   const unsigned grid = (unsigned)((N + 4 * rw - 1) / (4 * rw));
-  // one pair per wave: the quad-shared chain (MMS_F16_CHAIN=lanes selects the per-lane chain, for A/B timing)
-  static const bool quad_off = [] { const char* e = std::getenv("MMS_F16_CHAIN"); return e && !std::strcmp(e, "lanes"); }();   // "quad": the quad chain
-  const bool quad = rw == 1 && !quad_off;
-  static const bool chain_env = [] { return std::getenv("MMS_F16_CHAIN") != nullptr; }();
-  const bool chain_old = rw == 2 || chain_env;      // (rw == 2 is handled above this branch)
   const bool tree = f16_distance_mode() == MMS_F16_DISTANCE_TREE;
-  const size_t lds = (size_t)4 * rw * 3 * (quad ? quad_h4(2 * D8) : (2 * D8 + 2) / 3) * sizeof(float4);
+  const size_t lds = (size_t)4 * rw * 3 * ((2 * D8 + 2) / 3) * sizeof(float4);
   const _Float16* qh = static_cast<const _Float16*>(q);
   const _Float16* ah = static_cast<const _Float16*>(a);
   _Float16* dqh = static_cast<_Float16*>(dq);
   _Float16* dah = static_cast<_Float16*>(da);
-#define MMS_F16_LAUNCH(n, r)                                                                          \
+#define MMS_F16_LAUNCH(n)                                                                             \
   do {                                                                                                \
     if (bwd)                                                                                          \
-      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, r, true>), dim3(grid), dim3(256), lds, s,    \
+      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 2, true>), dim3(grid), dim3(256), lds, s,    \
                          qh, ah, top_diff, top, dqh, dah, N, D8);                                     \
     else                                                                                              \
-      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, r, false>), dim3(grid), dim3(256), lds, s,   \
+      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 2, false>), dim3(grid), dim3(256), lds, s,   \
                          qh, ah, top_diff, top, dqh, dah, N, D8);                                     \
   } while (0)
   if (tree) {
@@ -911,10 +834,10 @@ int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const f
 #define MMS_F16_TREE(n)                                                                               \
   do {                                                                                                \
     if (bwd)                                                                                          \
-      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 1, true, false, true>), dim3(grid1),         \
+      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 1, true, true>), dim3(grid1),                \
                          dim3(256), 16, s, qh, ah, top_diff, top, dqh, dah, N, D8);                   \
     else                                                                                              \
-      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 1, false, false, true>), dim3(grid1),        \
+      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 1, false, true>), dim3(grid1),               \
                          dim3(256), 16, s, qh, ah, top_diff, top, dqh, dah, N, D8);                   \
   } while (0)
     switch (nit1) {
@@ -926,38 +849,32 @@ int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const f
 #undef MMS_F16_TREE
   } else if (rw == 2) {
     switch (nit) {
-      case 1: MMS_F16_LAUNCH(1, 2); break;
-      case 2: MMS_F16_LAUNCH(2, 2); break;
-      case 3: MMS_F16_LAUNCH(3, 2); break;
-      default: MMS_F16_LAUNCH(4, 2); break;
+      case 1: MMS_F16_LAUNCH(1); break;
+      case 2: MMS_F16_LAUNCH(2); break;
+      case 3: MMS_F16_LAUNCH(3); break;
+      default: MMS_F16_LAUNCH(4); break;
     }
-  } else if (!chain_old) {
-    // D > 400, ordered: lane p of wave 0 walks pair p's image (MMS_F16_CHAIN=quad / lanes select round 2's speculative
-    // chains, for A/B timing)
-    static const int wpb = [] { const char* e = std::getenv("MMS_F16_LC_WPB"); const int v = e ? std::atoi(e) : 8;
-                                return v == 4 || v == 16 ? v : 8; }();        // dev-only A/B of the workgroup size
+  } else {
+    // D > 400, ordered: lane p of wave 0 walks pair p's image
+    constexpr int wpb = 8;                            // 4 / 8 / 16 waves measured alike (profiles/r03_f16_lanewalk.txt)
     const unsigned gridw = (unsigned)((N + wpb - 1) / wpb);
     const size_t ldsw = ((size_t)wpb * (2 * D8 + 1) + 4) * sizeof(float4);
-#define MMS_F16_LCW(n, w)                                                                             \
+#define MMS_F16_LC(n)                                                                                 \
   do {                                                                                                \
     static bool once = [] {                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&euclid_rows_lanechain_f16_kernel<n, true, w>),  \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&euclid_rows_lanechain_f16_kernel<n, true, wpb>),  \
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&euclid_rows_lanechain_f16_kernel<n, false, w>), \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&euclid_rows_lanechain_f16_kernel<n, false, wpb>), \
                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                    \
       return true;                                                                                    \
     }();                                                                                              \
     (void)once;                                                                                       \
     if (bwd)                                                                                          \
-      hipLaunchKernelGGL((euclid_rows_lanechain_f16_kernel<n, true, w>), dim3(gridw), dim3(64 * w), ldsw, \
+      hipLaunchKernelGGL((euclid_rows_lanechain_f16_kernel<n, true, wpb>), dim3(gridw), dim3(64 * wpb), ldsw, \
                          s, qh, ah, top_diff, top, dqh, dah, N, D8);                                  \
     else                                                                                              \
-      hipLaunchKernelGGL((euclid_rows_lanechain_f16_kernel<n, false, w>), dim3(gridw), dim3(64 * w), ldsw, \
+      hipLaunchKernelGGL((euclid_rows_lanechain_f16_kernel<n, false, wpb>), dim3(gridw), dim3(64 * wpb), ldsw, \
                          s, qh, ah, top_diff, top, dqh, dah, N, D8);                                  \
-  } while (0)
-#define MMS_F16_LC(n)                                                                                 \
-  do {                                                                                                \
-    if (wpb == 4) MMS_F16_LCW(n, 4); else if (wpb == 16) MMS_F16_LCW(n, 16); else MMS_F16_LCW(n, 8);  \
   } while (0)
     switch (nit) {
       case 1: MMS_F16_LC(1); break;
@@ -965,32 +882,7 @@ int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const f
       case 3: MMS_F16_LC(3); break;
       default: MMS_F16_LC(4); break;
     }
-#undef MMS_F16_LCW
 #undef MMS_F16_LC
-  } else if (!quad) {
-    switch (nit) {
-      case 1: MMS_F16_LAUNCH(1, 1); break;
-      case 2: MMS_F16_LAUNCH(2, 1); break;
-      case 3: MMS_F16_LAUNCH(3, 1); break;
-      default: MMS_F16_LAUNCH(4, 1); break;
-    }
-  } else {
-#define MMS_F16_QUAD(n)                                                                               \
-  do {                                                                                                \
-    if (bwd)                                                                                          \
-      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 1, true, true>), dim3(grid), dim3(256), lds, \
-                         s, qh, ah, top_diff, top, dqh, dah, N, D8);                                  \
-    else                                                                                              \
-      hipLaunchKernelGGL((euclid_rows_wave_f16_kernel<n, 1, false, true>), dim3(grid), dim3(256),     \
-                         lds, s, qh, ah, top_diff, top, dqh, dah, N, D8);                             \
-  } while (0)
-    switch (nit) {
-      case 1: MMS_F16_QUAD(1); break;
-      case 2: MMS_F16_QUAD(2); break;
-      case 3: MMS_F16_QUAD(3); break;
-      default: MMS_F16_QUAD(4); break;
-    }
-#undef MMS_F16_QUAD
   }
 #undef MMS_F16_LAUNCH
   return launch_status();
@@ -1342,19 +1234,11 @@ struct CrossAcc {
         const int k = k0 + lk + 8 * y;
         if (k >= W2) continue;
         float T;
-#if defined(MMS_XABL) && MMS_XABL == 1   // dev-only timing ablation (tools/crossbench.hip): no sqrt / divide
-        if (MODE == 1) {
-          T = get(x, y);
-        } else
-#endif
         if (MODE == 1) {
           T = 1.0f / (1.0f + sqrtf(get(x, y)));
         } else {
           T = get(x, y) / n0v[x] / n1v[y];
         }
-#if defined(MMS_XABL) && MMS_XABL == 3   // dev-only timing ablation: no stores
-        if (T != T + 1.0f && T == 12345.678f)
-#endif
         top[((size_t)n * W1 + j) * W2 + k] = T;
       }
     }
@@ -1448,9 +1332,6 @@ __global__ __launch_bounds__(256) void cross_fwd_kernel(
       as[wave][(r + lrow) * LS + lcol] = (valid && k0 + r + lrow < W2 && lcol < dn) ? ra[r / 2] : 0.f;
     __syncthreads();
     if (d0 + DC < D) fetch(d0 + DC);
-#if defined(MMS_XABL) && MMS_XABL == 2   // dev-only timing ablation: no arithmetic
-    if (dn > 0) continue;
-#endif
     acc.accumulate(&qs[wave][lj * LS], &as[wave][lk * LS], LS, dn);
   }
   if (!valid) return;
@@ -1545,9 +1426,7 @@ __global__ __launch_bounds__(128) void cross_fwd_image_kernel(
   const int lj = lane >> 3, lk = lane & 7;
   CrossAcc<RJ, RK, MODE> acc;
   acc.clear();
-#if !(defined(MMS_XABL) && MMS_XABL == 2)
   acc.accumulate(reinterpret_cast<const float*>(qs4) + lj * D, reinterpret_cast<const float*>(as4) + lk * D, D, D);
-#endif
   if (!valid) return;
   acc.finish(top, norm0, norm1, n, 0, 0, lj, lk, W1, W2);
 }
@@ -2040,9 +1919,12 @@ void set_euclid_backward_mode(int m) { t_euclid_bwd_mode = m; }
 // widths with a specialised kernel: 100-d, 200-d and 300-d GloVe (D4 = 25, 50, 75)
 static bool pair32_width(int D) { return D == 300 || D == 200 || D == 100; }
 
-template <bool FWD, bool BWD, int WPB>
-static void launch_pair32w(const float* q, const float* a, const float* top_in, const float* top_diff,
-                           float* top_out, float* dq, float* da, int N, int D, hipStream_t s) {
+// Eight waves (16 pairs) per workgroup: N = 4096 is then 256 workgroups, one per CU, two waves
+// per SIMD -- measured 3 % faster HBM-cold than 512 workgroups of four waves (dispatch ramp).
+template <bool FWD, bool BWD>
+static void launch_pair32(const float* q, const float* a, const float* top_in, const float* top_diff,
+                          float* top_out, float* dq, float* da, int N, int D, hipStream_t s) {
+  constexpr int WPB = 8;
   const unsigned grid = (unsigned)((N + 2 * WPB - 1) / (2 * WPB));
   const bool exact = BWD && euclid_backward_mode() == MMS_EUCLID_BWD_REFERENCE;
   // Which global-memory layout (same results bit for bit; tests/test_gpu_parity.py runs both for every kind
@@ -2083,24 +1965,6 @@ static void launch_pair32w(const float* q, const float* a, const float* top_in, 
   switch (D) { MMS_P32(25) MMS_P32(50) MMS_P32(75) }
 #undef MMS_P32
 #undef MMS_P32_GO
-}
-
-// Eight waves (16 pairs) per workgroup: N = 4096 is then 256 workgroups, one per CU, two waves
-// per SIMD -- measured 3 % faster HBM-cold than 512 workgroups of four waves (dispatch ramp).
-template <bool FWD, bool BWD>
-static void launch_pair32(const float* q, const float* a, const float* top_in, const float* top_diff,
-                          float* top_out, float* dq, float* da, int N, int D, hipStream_t s) {
-  // dev switch for A/B timing (tools/layers_probe.py): MMS_PAIR32_WPB_FWD / _BWD / _FUSED = 2, 4, 8 or 16
-  static const int wpb = [] {
-    const char* e = std::getenv(FWD && BWD ? "MMS_PAIR32_WPB_FUSED" : FWD ? "MMS_PAIR32_WPB_FWD" : "MMS_PAIR32_WPB_BWD");
-    return e ? std::atoi(e) : 8;
-  }();
-  switch (wpb) {
-    case 2: launch_pair32w<FWD, BWD, 2>(q, a, top_in, top_diff, top_out, dq, da, N, D, s); break;
-    case 4: launch_pair32w<FWD, BWD, 4>(q, a, top_in, top_diff, top_out, dq, da, N, D, s); break;
-    case 16: launch_pair32w<FWD, BWD, 16>(q, a, top_in, top_diff, top_out, dq, da, N, D, s); break;
-    default: launch_pair32w<FWD, BWD, 8>(q, a, top_in, top_diff, top_out, dq, da, N, D, s); break;
-  }
 }
 
 template <bool FWD, bool BWD>

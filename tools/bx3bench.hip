@@ -87,31 +87,6 @@ int main(int argc, char** argv) {
     std::sort(t.begin(), t.end());
     printf("%-52s median %8.2f us  min %8.2f   %6.1f TFLOP/s (fp32-equivalent)\n", name, t[2], t[0], flop / t[2] / 1e6);
   };
-#ifdef MMS_BX3_STAMPS
-  unsigned long long* sb; CK(hipMalloc(&sb, 1024 * 16 * 8)); CK(hipMemset(sb, 0, 1024 * 16 * 8));
-  CK(hipMemcpyToSymbol(HIP_SYMBOL(bx3_stamp_buf), &sb, sizeof(sb)));
-  auto stamps = [&](const char* name, int nwg) {
-    std::vector<unsigned long long> h(1024 * 16);
-    CK(hipMemcpy(h.data(), sb, h.size() * 8, hipMemcpyDeviceToHost));
-    unsigned long long tmin = ~0ull;
-    for (int b = 0; b < nwg; ++b) if (h[b * 16]) tmin = std::min(tmin, h[b * 16]);
-    std::vector<double> start, b0, loop, epi, clk, end;
-    for (int b = 0; b < nwg; ++b) {
-      const unsigned long long* x = &h[(size_t)b * 16];
-      if (!x[0]) continue;
-      start.push_back((x[0] - tmin) / 100.0); b0.push_back((x[1] - x[0]) / 100.0); loop.push_back((x[2] - x[1]) / 100.0);
-      epi.push_back((x[3] - x[2]) / 100.0); clk.push_back((double)(x[5] - x[4]) / (double)(x[2] - x[1]) * 100.0);
-      end.push_back((x[3] - tmin) / 100.0);
-    }
-    auto med = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; };
-    auto mx = [](std::vector<double>& v) { return v.empty() ? 0.0 : *std::max_element(v.begin(), v.end()); };
-    printf("   stamps %-22s start med %.2f max %.2f us; launch->barrier 0 med %.2f max %.2f; main loop med %.2f max %.2f us @ %.0f MHz; epilogue med %.2f max %.2f; last end %.2f\n",
-           name, med(start), mx(start), med(b0), mx(b0), med(loop), mx(loop), med(clk), med(epi), mx(epi), mx(end));
-    CK(hipMemset(sb, 0, 1024 * 16 * 8));
-  };
-#else
-  auto stamps = [&](const char*, int) {};
-#endif
   const double fl = 2.0 * N * K * K;
   const unsigned rblk = (unsigned)(((long long)N * K + 255) / 256);
   auto fwd_args = [&] {
@@ -182,12 +157,10 @@ int main(int argc, char** argv) {
     panel_launch(p, true, st); }, fl);
   run("bx3 split W only", [&] { bx3_split_b(W, K, 1, K, K, img, st); }, 0);
   run("bx3 fwd Q.W + rowdot (image ready)", [&] { bx3_launch(fwd_args(), st); }, fl);
-  stamps("fwd + rowdot", 256);
   run("bx3 fwd Q.W + rowdot (split + product)", [&] { bx3_split_b(W, K, 1, K, K, img, st, top, 1, N); bx3_launch(fwd_args(), st); }, fl);
   run("bx3 fwd Q.W, no store (rowdot only)", [&] { Bx3Args p = fwd_args(); p.C = nullptr; bx3_launch(p, st); }, fl);
   run("bx3 Q.W, store only (no rowdot)", [&] { Bx3Args p = fwd_args(); p.Y = nullptr; p.rowdot = nullptr; bx3_launch(p, st); }, fl);
   run("bx3 Q.W, no store, no rowdot", [&] { Bx3Args p = fwd_args(); p.Y = nullptr; p.rowdot = nullptr; p.C = nullptr; bx3_launch(p, st); }, fl);
-  stamps("no store no rowdot", 256);
   run("bx3 dq = dT . A W^T (split W^T + product)", [&] { bx3_split_b(W, 1, K, K, K, img, st); bx3_launch(dq_args(), st); }, fl);
   run("bx3 dW slabs (split-K product only)", [&] { bx3_tn_launch(tn, st); }, fl);
   run("bx3 dW slabs + slab sum", [&] { bx3_tn_launch(tn, st);
@@ -195,7 +168,6 @@ int main(int argc, char** argv) {
   { float* da; CK(hipMalloc(&da, (size_t)N * K * 4));
     run("bx3 dq + side job da = dT . qw (split W^T + product)", [&] {
       bx3_split_b(W, 1, K, K, K, img, st); Bx3Args p = dq_args(); p.side_in = qw; p.side_out = da; p.side_scale = dT; p.side_ld = K; p.side_cols = K;
-      bx3_launch(p, st); }, fl);
-    stamps("dq + side job", 256); }
+      bx3_launch(p, st); }, fl); }
   return 0;
 }

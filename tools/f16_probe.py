@@ -1,5 +1,5 @@
 """tools/f16_probe.py -- dev-only: cfg 5's shard (8192 x 1024 fp16 storage) fused fwd+bwd, hipGraph-replayed,
-cache-warm and HBM-cold; MMS_F16_CHAIN=lanes selects the per-lane chain for A/B."""
+cache-warm and HBM-cold; MMS_F16_TREE=1 selects the tree sum."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -33,5 +33,5 @@ for ring in (1, 12):
         e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e3 / 48)
     ts.sort()
-    print("f16 %d x %d chain=%s %s: median %.2f us  min %.2f" % (N, D, "tree-sum" if os.environ.get("MMS_F16_TREE") == "1" else os.environ.get("MMS_F16_CHAIN", "lane-walk (default)"),
+    print("f16 %d x %d chain=%s %s: median %.2f us  min %.2f" % (N, D, "tree-sum" if os.environ.get("MMS_F16_TREE") == "1" else "lane-walk (default)",
           "warm" if ring == 1 else "cold", ts[len(ts) // 2], ts[0]))

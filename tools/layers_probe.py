@@ -1,5 +1,5 @@
 """tools/layers_probe.py -- dev-only: the Layer-API sequence at cfg 2 (Forward launch, Backward launch), forward-only
-and backward-only, HBM-cold ring, hipGraph-replayed; env MMS_PAIR32_WPB_{FWD,BWD} select waves per workgroup."""
+and backward-only, HBM-cold ring, hipGraph-replayed."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -33,8 +33,7 @@ def timeit(name, step):
         e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e3 / (8 * G))
     ts.sort()
-    print("%-22s wpb fwd=%s bwd=%s: median %.3f us  min %.3f" % (name, os.environ.get("MMS_PAIR32_WPB_FWD", "8"),
-          os.environ.get("MMS_PAIR32_WPB_BWD", "8"), ts[3], ts[0]))
+    print("%-22s median %.3f us  min %.3f" % (name, ts[3], ts[0]))
 fwd = lambda i: capi.simcross_forward(1, q[i], a[i], top[i])
 bwd = lambda i: capi.simcross_backward(1, q[i], a[i], top[i], dT[i], dq[i], da[i])
 timeit("forward only", fwd)
