@@ -245,7 +245,12 @@ int mms_simmatrix_forward_f32(int N, int K1, int K2, const float* q,
  * fp32 (csrc/bx3_gemm.h; the three dropped are <= 2^-24 relative) -- 16 x the fp32 pipe's rate per instruction for 6 x
  * the instructions.  Results agree with the fp32-MFMA product of mms_simmatrix_forward_f32 to fp32 rounding (both are
  * inside the 1e-5 contract of this BLAS-backed layer: the reference calls cblas_sgemm, no defined order); an input
- * holding an infinity yields NaN where the fp32 product yields inf.  The backward calls below take the same route for
+ * holding an infinity yields NaN where the fp32 product yields inf.  The three planes hold an operand exactly while its
+ * last mantissa bit is at least 2^-133, bf16's smallest subnormal, i.e. for magnitudes from 2^-110 up; a smaller element
+ * enters the product rounded to a multiple of 2^-133 (nothing is flushed to zero: absolute error <= 2^-134 per element,
+ * relative 2^-24 at 2^-110 growing to 2^-8 at 2^-126); a magnitude of 2^128 - 2^119 (3.3962e38) or more rounds the
+ * first plane to infinity and, like an infinity, makes its row NaN (tests/test_gpu_matrix_pipe_accuracy.py holds each
+ * kept plane product to a componentwise 2^-20 against fp64).  The backward calls below take the same route for
  * dq (and da) when handed this workspace.  mms_set_matrix_mode(1) pins every product to the fp32 pipe (process-wide;
  * 0 = default), mms_get_matrix_mode() reads it. */
 int mms_simmatrix_forward_ws_f32(int N, int K1, int K2, const float* q,
