@@ -386,6 +386,57 @@ size_t mms_triplet_workspace_bytes(int N);
 int mms_triplet_workspace_init(void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Fused training step of the COSINE metric (dist_mode 0), one launch:
+ *   s_pos = SimCross_cosine(q, a_pos), s_neg = SimCross_cosine(q, a_neg)   (N,1,1,1)
+ *   loss  = PairRankLoss(s_pos, s_neg, y)                 (margin, loss_weight)
+ *   backward through PairRankLoss and both SimCross layers:
+ *   dq = dq(pos) + dq(neg) (Net::Init's Split sum, in that order: one fp32 add of the two rounded values),
+ *   da_pos, da_neg.
+ * Equivalent net: two SimCross layers with `dist_mode: 0` sharing bottom q (sim_cross_layer.cpp:112-139 forward,
+ * :226-250 backward) feeding PairRankLoss (pair_rank_loss_layer.cpp:26-84), geometry W1 = W2 = 1.  It replaces
+ * seven launches (two mms_simcross_forward_f32, mms_pairrank_forward_f32 / _backward_f32, two
+ * mms_simcross_backward_f32, mms_split_backward_f32) and reads q, a_pos, a_neg once and writes dq, da_pos, da_neg
+ * once: 6*N*D*4 bytes.  ||q|| is computed once and serves both branches.
+ * Numerics:
+ *   - s_pos, s_neg, norm_q, norm_pos, norm_neg equal what mms_simcross_forward_f32(0, ...) writes for the same rows
+ *     BIT FOR BIT (same per-lane accumulation order and reduction as the unfused kernel that serves the width: one
+ *     definition of the device code, csrc/cosine_math.h), so a ranking of training-time scores is the ranking a
+ *     scoring call gives.  Against the reference they are within 1e-5 (its dot products are cblas_sdot: no order).
+ *   - dq, da_pos, da_neg equal mms_simcross_backward_f32(0, ...) twice + mms_split_backward_f32 given those scores,
+ *     bit for bit: per-pair factors 1/n0/n1, T/n0^2, T/n1^2 and 0 + g*(...) per element at D = 100 / 200 / 300 with
+ *     16-byte-aligned arrays, the reference's expression written out elsewhere, as in the unfused kernels.  g+ / g-
+ *     are PairRankLoss's (strict `ordered > 0` unless mms_set_pairrank_hinge_mode says otherwise).
+ *     The unfused calls choose their kernel per call from D and the 16-byte alignment of the arrays they are given;
+ *     this step chooses once, from q, a_pos, a_neg (sum order) and dq, da_pos, da_neg (backward expression).  The
+ *     two agree bitwise whenever the unfused calls of both branches would take the same kernel -- always, except
+ *     when exactly one of a_pos / a_neg (or of the gradient arrays) breaks 16-byte alignment; then the step uses
+ *     the scalar order for both branches and the 1e-5 contract holds.
+ *   - loss: as for mms_triplet_euclid_step_f32 -- within 2e-6 of the exact mean of the bit-exact per-triplet terms
+ *     (hence within 1e-5 of the reference's value); in MMS_LOSS_SUM_REFERENCE mode the reference-order fp32 running
+ *     sum of the terms formed from this step's own scores.  `loss` may be NULL (no reduction).
+ *   - a zero q or answer row gives the reference's 0/0: NaN exactly where the unfused chain gives NaN.
+ *   - deterministic: no atomics on floats, two calls give identical bits.
+ * norm_q / norm_pos / norm_neg: (N) each, what the layers cache as norm0 / norm1; any of them may be NULL.
+ * workspace: the Euclid step's -- mms_triplet_workspace_bytes(N), mms_triplet_workspace_init, same ownership rules,
+ * same finish modes (mms_set_triplet_finish_mode; in-launch at D = 100 / 200 / 300 with aligned inputs and at most
+ * 131072 triplets, second launch otherwise).  A cosine term is at most margin + 2, so the in-launch domain (terms
+ * below 2^10) admits the same margins.  N == 0 is a no-op; a workspace that is too small, NULL or not 8-byte aligned
+ * returns MMS_ERR_WORKSPACE.
+ * Measured (tools/triplet_cosine_probe.py, HBM-cold ring, graph-replayed, profiles/triplet_cosine_probe.txt): 8.45 us
+ * per 4096 x 300 step (0.44 of 8 TB/s on 6*N*D*4 bytes) against 26.7 us for the seven launches and 9.47 us for the
+ * Euclid step in the same run; 16384 x 300: 26.7 against 64.2 and 29.8 us.
+ * ------------------------------------------------------------------------- */
+int mms_triplet_cosine_step_f32(int N, int D, float margin, float loss_weight,
+                                const float* q, const float* a_pos,
+                                const float* a_neg, const float* y,
+                                float* s_pos, float* s_neg,
+                                float* norm_q, float* norm_pos, float* norm_neg,
+                                float* loss,
+                                float* dq, float* da_pos, float* da_neg,
+                                void* workspace, size_t workspace_bytes,
+                                void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Fused training step of the LEARNED metric (cfg 3's arithmetic):
  *   s_pos_i = q_i^T W a_pos_i, s_neg_i = q_i^T W a_neg_i          SimMatrix x 2, W shared (sim_matrix_layer.cpp:53-65)
  *   loss = PairRankLoss(s_pos, s_neg, y)                            (pair_rank_loss_layer.cpp:26-52)

@@ -45,6 +45,7 @@ _SIGNATURES = {
     "mms_triplet_simmatrix_workspace_bytes": (_sz, [_i, _i, _i]),
     "mms_triplet_simmatrix_step_f32": (_i, [_i, _i, _i, _f, _f] + [_vp] * 12 + [_vp, _sz, _vp]),
     "mms_triplet_euclid_step_f32": (_i, [_i, _i, _f, _f] + [_vp] * 11 + [_sz, _vp]),
+    "mms_triplet_cosine_step_f32": (_i, [_i, _i, _f, _f] + [_vp] * 14 + [_sz, _vp]),
     "mms_simcross_euclid_forward_f16": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "mms_simcross_euclid_forward_backward_f16": (_i, [_i, _i] + [_vp] * 7),
     "mms_simcross_cosine_forward_f16": (_i, [_i, _i] + [_vp] * 5 + [_vp]),
@@ -370,6 +371,26 @@ def triplet_euclid_step(q, a_pos, a_neg, y, s_pos, s_neg, loss, dq, da_pos, da_n
         _ptr(a_neg, "a_neg"), _ptr(y, "y"), _ptr(s_pos, "s_pos"), _ptr(s_neg, "s_neg"),
         _ptr(loss, "loss", True), _ptr(dq, "dq"), _ptr(da_pos, "da_pos"), _ptr(da_neg, "da_neg"),
         wsp, wsb, _stream()), "mms_triplet_euclid_step_f32")
+
+
+def triplet_cosine_step(q, a_pos, a_neg, y, s_pos, s_neg, loss, dq, da_pos, da_neg, margin=1.0,
+                        loss_weight=1.0, norms=None, ws=None):
+    """The fused cosine step (include/mms.h: mms_triplet_cosine_step_f32).  `norms`: None, or (norm_q, norm_pos,
+    norm_neg) tensors of N floats, any of which may be None.  `ws`: a TripletWorkspace, as for triplet_euclid_step."""
+    N, D = q.shape[0], q.shape[-1]
+    if ws is None:
+        ws = _default_triplet_ws.setdefault(q.device, TripletWorkspace())
+    if not isinstance(ws, TripletWorkspace):
+        raise TypeError("triplet_cosine_step needs a capi.TripletWorkspace (its arrival words must stay zero "
+                        "between launches; a general Workspace is overwritten by other calls)")
+    nq, npos, nneg = norms if norms is not None else (None, None, None)
+    wsp, wsb = ws.get(lib().mms_triplet_workspace_bytes(N), q.device)
+    check(lib().mms_triplet_cosine_step_f32(
+        N, D, float(margin), float(loss_weight), _ptr(q, "q"), _ptr(a_pos, "a_pos"),
+        _ptr(a_neg, "a_neg"), _ptr(y, "y"), _ptr(s_pos, "s_pos"), _ptr(s_neg, "s_neg"),
+        _ptr(nq, "norm_q", True), _ptr(npos, "norm_pos", True), _ptr(nneg, "norm_neg", True),
+        _ptr(loss, "loss", True), _ptr(dq, "dq"), _ptr(da_pos, "da_pos"), _ptr(da_neg, "da_neg"),
+        wsp, wsb, _stream()), "mms_triplet_cosine_step_f32")
 
 
 def triplet_simmatrix_step(q, a_pos, a_neg, y, W, s_pos, s_neg, loss, dq, da_pos, da_neg, dW, margin=1.0,

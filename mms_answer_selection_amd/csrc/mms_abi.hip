@@ -60,6 +60,10 @@ int pairrank_backward(int count, float top_diff, const float* y, const float* or
                       const float* similar, float* da, float* db, hipStream_t s);
 size_t triplet_workspace_bytes(int N);
 int triplet_workspace_init(void* ws, size_t ws_bytes, hipStream_t s);
+int triplet_cosine_step(int N, int D, float margin, float loss_weight, const float* q, const float* ap,
+                        const float* an, const float* y, float* s_pos, float* s_neg, float* norm_q,
+                        float* norm_pos, float* norm_neg, float* loss, float* dq, float* dap, float* dan,
+                        void* ws, size_t ws_bytes, hipStream_t s);
 int triplet_euclid_step(int N, int D, float margin, float loss_weight, const float* q,
                         const float* ap, const float* an, const float* y, float* s_pos,
                         float* s_neg, float* loss, float* dq, float* dap, float* dan, void* ws,
@@ -501,6 +505,20 @@ int mms_triplet_euclid_step_f32(int N, int D, float margin, float loss_weight, c
     return MMS_ERR_INVALID_ARG;
   return triplet_euclid_step(N, D, margin, loss_weight, q, a_pos, a_neg, y, s_pos, s_neg, loss,
                              dq, da_pos, da_neg, workspace, workspace_bytes, as_stream(stream));
+}
+
+int mms_triplet_cosine_step_f32(int N, int D, float margin, float loss_weight, const float* q,
+                                const float* a_pos, const float* a_neg, const float* y,
+                                float* s_pos, float* s_neg, float* norm_q, float* norm_pos,
+                                float* norm_neg, float* loss, float* dq, float* da_pos,
+                                float* da_neg, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  if (N < 0 || D <= 0 || (long long)N * D > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
+  if (N == 0) return MMS_OK;                                                           // an empty batch: nothing enqueued
+  if (!q || !a_pos || !a_neg || !y || !s_pos || !s_neg || !dq || !da_pos || !da_neg)   // loss and the norms may be NULL
+    return MMS_ERR_INVALID_ARG;
+  return triplet_cosine_step(N, D, margin, loss_weight, q, a_pos, a_neg, y, s_pos, s_neg, norm_q, norm_pos,
+                             norm_neg, loss, dq, da_pos, da_neg, workspace, workspace_bytes, as_stream(stream));
 }
 
 size_t mms_rank_workspace_bytes(int n) { return n > 0 ? rank_workspace_bytes(n) : 0; }

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cosine_math.h"
 #include "euclid_math.h"
 #include "pairrank_math.h"
 #include "mms_common.h"
@@ -242,6 +243,54 @@ int pairrank_backward(int count, float top_diff, const float* y, const float* or
 }
 
 // ======================= fused (q, a+, a-) training step =====================
+// In-launch loss sum of the width-specialised fused steps (Euclid and cosine): see "loss scalar" in
+// triplet32x2_kernel for the scheme and its measurements.  A wave's terms are added to (fx_sum, fx_bad) by every
+// lane alike; lane 0 then calls arrive() ONCE per wave, every wave of the launch, and finish() after its stores.
+struct LossArrival {
+  unsigned long long fx_sum = 0, fx_bad = 0;
+  bool top_wait = false;
+  unsigned long long top_old = 0, top_pay = 0;
+  __device__ __forceinline__ void add(float tm, double fx_scale) {
+    const bool ok = tm >= 0.f && tm < (float)(1 << kFxTermBits);
+    fx_sum += ok ? (unsigned long long)((double)tm * fx_scale) : 0ull;
+    fx_bad += ok ? 0ull : 1ull;
+  }
+  template <int WPB>
+  __device__ __forceinline__ void arrive(unsigned long long* wg_arrivals, unsigned long long* __restrict__ ticket) {
+    const unsigned long long pay = (1ull << 60) | (fx_bad ? kFxOne : 0ull) | fx_sum;
+    const unsigned long long old = __hip_atomic_fetch_add(wg_arrivals, pay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if ((old >> 60) == (unsigned long long)(WPB - 1)) {
+      const unsigned long long wg = old + pay;
+      const unsigned grp = blockIdx.x / kTicketGroup;
+      const unsigned gsize = min((unsigned)kTicketGroup, gridDim.x - (unsigned)kTicketGroup * grp);
+      const unsigned long long gpay = kFxOne | (wg & kFxSumMask);
+      if ((wg >> kFxSumBits) & 0xffull)
+        __hip_atomic_fetch_or(ticket + grp, kFxPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long gold = __hip_atomic_fetch_add(ticket + grp, gpay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (((gold >> kFxSumBits) & 0x7ffull) == (unsigned long long)(gsize - 1)) {
+        const unsigned long long g = gold + gpay;
+        __hip_atomic_store(ticket + grp, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        top_pay = kFxOne | (g & kFxSumMask);
+        if (g & kFxPoison) __hip_atomic_fetch_or(ticket + kTicketTop, kFxPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        top_old = __hip_atomic_fetch_add(ticket + kTicketTop, top_pay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        top_wait = true;
+      }
+    }
+  }
+  __device__ __forceinline__ void finish(unsigned long long* __restrict__ ticket, float* __restrict__ loss, double fx_scale,
+                                         int N) const {
+    if (top_wait) {
+      const unsigned ngrp = (gridDim.x + kTicketGroup - 1) / kTicketGroup;
+      if (((top_old >> kFxSumBits) & 0x7ffull) == (unsigned long long)(ngrp - 1)) {
+        const unsigned long long all = top_old + top_pay;
+        __hip_atomic_store(ticket + kTicketTop, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const float sum = (float)((double)(all & kFxSumMask) / fx_scale);
+        *loss = (all & kFxPoison) ? __builtin_nanf("") : sum / (float)N;                       // pair_rank_loss_layer.cpp:49
+      }
+    }
+  }
+};
+
 // Euclidean SimCross on (q,a+) and (q,a-), PairRankLoss on the two score
 // columns, and the whole backward, in one launch (+ a one-block loss finish).
 // Same wave-centric structure as euclid_rows_wave_kernel: a wave owns ONE
@@ -452,9 +501,7 @@ __global__ __launch_bounds__(64 * WPB) void triplet32x2_kernel(
   // XCD's L2) cost ~1.9 us, about what the second launch costs (1.9-2.3 us): 10.0 vs 10.2 us per step.
   // With the second launch a pass stores as soon as its scores are known.
   constexpr bool LATE = INL;
-  unsigned long long fx_sum = 0, fx_bad = 0;
-  bool top_wait = false;
-  unsigned long long top_old = 0, top_pay = 0;
+  LossArrival arr;
   EuclidCoef k0[2], k1[2];
   float c0[2] = {0.f, 0.f}, c1[2] = {0.f, 0.f}, rr0[2] = {0.f, 0.f}, rr1[2] = {0.f, 0.f};
   auto store_pass = [&](int t) {                   // gradients of triplet t's float4s (a slot can hold both triplets': masked)
@@ -529,31 +576,8 @@ __global__ __launch_bounds__(64 * WPB) void triplet32x2_kernel(
       rr1[t] = (float)rcp_newton((double)(Tn - 1.0f) + 1e-9);
     }
     if (INL) {
-      const float tm = have ? pt.term : 0.f;
-      const bool ok = tm >= 0.f && tm < (float)(1 << kFxTermBits);
-      fx_sum += ok ? (unsigned long long)((double)tm * fx_scale) : 0ull;
-      fx_bad += ok ? 0ull : 1ull;
-      if (t == 1 && lane == 0) {                   // the wave's two terms arrive together ("loss scalar" above)
-        const unsigned long long pay = (1ull << 60) | (fx_bad ? kFxOne : 0ull) | fx_sum;
-        const unsigned long long old = __hip_atomic_fetch_add(&wg_arrivals, pay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if ((old >> 60) == (unsigned long long)(WPB - 1)) {
-          const unsigned long long wg = old + pay;
-          const unsigned grp = blockIdx.x / kTicketGroup;
-          const unsigned gsize = min((unsigned)kTicketGroup, gridDim.x - (unsigned)kTicketGroup * grp);
-          const unsigned long long gpay = kFxOne | (wg & kFxSumMask);
-          if ((wg >> kFxSumBits) & 0xffull)
-            __hip_atomic_fetch_or(ticket + grp, kFxPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const unsigned long long gold = __hip_atomic_fetch_add(ticket + grp, gpay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (((gold >> kFxSumBits) & 0x7ffull) == (unsigned long long)(gsize - 1)) {
-            const unsigned long long g = gold + gpay;
-            __hip_atomic_store(ticket + grp, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            top_pay = kFxOne | (g & kFxSumMask);
-            if (g & kFxPoison) __hip_atomic_fetch_or(ticket + kTicketTop, kFxPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            top_old = __hip_atomic_fetch_add(ticket + kTicketTop, top_pay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            top_wait = true;
-          }
-        }
-      }
+      arr.add(have ? pt.term : 0.f, fx_scale);
+      if (t == 1 && lane == 0) arr.template arrive<WPB>(&wg_arrivals, ticket);   // the wave's two terms arrive together ("loss scalar" above)
     } else {
       if (lane == 0 && have) partials[row] = pt.term;
     }
@@ -562,15 +586,7 @@ __global__ __launch_bounds__(64 * WPB) void triplet32x2_kernel(
   }
   if (LATE) { store_pass(0); store_pass(1); }
   if (!INL) return;
-  if (top_wait) {
-    const unsigned ngrp = (gridDim.x + kTicketGroup - 1) / kTicketGroup;
-    if (((top_old >> kFxSumBits) & 0x7ffull) == (unsigned long long)(ngrp - 1)) {
-      const unsigned long long all = top_old + top_pay;
-      __hip_atomic_store(ticket + kTicketTop, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float sum = (float)((double)(all & kFxSumMask) / fx_scale);
-      *loss = (all & kFxPoison) ? __builtin_nanf("") : sum / (float)N;                       // pair_rank_loss_layer.cpp:49
-    }
-  }
+  arr.finish(ticket, loss, fx_scale, N);
 }
 
 // Generic fallback (any D / alignment): a workgroup owns ROWS triplets.
@@ -733,6 +749,303 @@ int triplet_euclid_step(int N, int D, float margin, float loss_weight, const flo
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kPairThreads), 0, s, partials, nparts, N,
                        loss);
   return launch_status();
+}
+
+int triplet_loss_from_terms(const float* terms, int N, float* loss, hipStream_t s);
+
+// ======================= fused cosine (q, a+, a-) training step =====================
+// SimCross dist_mode 0 on (q,a+) and (q,a-), PairRankLoss on the two score columns and the whole backward in one
+// launch (include/mms.h: mms_triplet_cosine_step_f32).  No ordered chain: five dot products per triplet (qq, pp, nn,
+// qp, qn -- qq ONCE for both branches, where the two layers would each compute it), accumulated per lane and reduced
+// exactly as the unfused kernel that serves the width does (cosine_math.h), so that scores, norms and gradients
+// carry that kernel's bits.
+//
+// Width-specialised (D = 100 / 200 / 300, inputs 16-byte aligned): the data movement of cosine_pair32_kernel -- 32
+// lanes per triplet, two triplets per wave, every float4 of q, a+ and a- requested up front (9 per lane at D = 300)
+// and kept for the backward, half-wave DPP sums, streaming stores.  Every lane of a half holds its triplet's scalars
+// (T+, T-, the hinge term, g+, g-), so nothing is broadcast.  The loss goes through the arrival words of the Euclid
+// step (LossArrival), the atomics issued before the gradient stores.  VOUT = false (a gradient array that is not
+// 16-byte aligned): the unfused backward takes cosine_rows_kernel's scalar path there, so its expression and scalar
+// stores are used.
+template <int D4C, int WPB, bool INL, bool VOUT>
+__global__ __launch_bounds__(64 * WPB) void triplet_cosine32_kernel(
+    int N, float margin, float s0, float s1, const float* __restrict__ q,
+    const float* __restrict__ ap, const float* __restrict__ an, const float* __restrict__ y,
+    float* __restrict__ s_pos, float* __restrict__ s_neg, float* __restrict__ norm_q,
+    float* __restrict__ norm_pos, float* __restrict__ norm_neg, float* __restrict__ partials,
+    float* __restrict__ dq, float* __restrict__ dap, float* __restrict__ dan, int hinge_ge,
+    unsigned long long* __restrict__ ticket, float* __restrict__ loss, double fx_scale) {
+  constexpr int NIT = (D4C + 31) / 32;
+  __shared__ unsigned long long wg_arrivals;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane >> 5, j = lane & 31;
+  if (INL) {
+    if (threadIdx.x == 0) wg_arrivals = 0;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+  const long long want = ((long long)blockIdx.x * WPB + wave) * 2 + grp;
+  const bool have = want < N;
+  const long long row = have ? want : (long long)N - 1;
+  const float4* q4 = reinterpret_cast<const float4*>(q) + row * D4C;
+  const float4* p4 = reinterpret_cast<const float4*>(ap) + row * D4C;
+  const float4* m4 = reinterpret_cast<const float4*>(an) + row * D4C;
+  float4 x[NIT], u[NIT], v[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = j + 32 * it;
+    const int ii = i < D4C ? i : 0;              // clamp: keep the load unconditional
+    x[it] = q4[ii]; u[it] = p4[ii]; v[it] = m4[ii];
+  }
+  float yy = y[row];
+  float sqq = 0.f, spp = 0.f, snn = 0.f, sqp = 0.f, sqn = 0.f;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if (j + 32 * it < D4C) {
+      cosine_acc4(sqq, x[it], x[it]); cosine_acc4(spp, u[it], u[it]); cosine_acc4(snn, v[it], v[it]);
+      cosine_acc4(sqp, x[it], u[it]); cosine_acc4(sqn, x[it], v[it]);
+    }
+  }
+  sqq = half_wave_sum(sqq); spp = half_wave_sum(spp); snn = half_wave_sum(snn);
+  sqp = half_wave_sum(sqp); sqn = half_wave_sum(sqn);
+  const CosineScore cp = cosine_score(sqq, spp, sqp), cn = cosine_score(sqq, snn, sqn);   // cp.n0 == cn.n0
+  asm volatile("" : "+v"(yy));   // in a register before any store, or its wait becomes vmcnt(0) behind them (see euclid_pair32_kernel)
+  const PairTerm pt = pair_term(cp.T, cn.T, yy, margin);
+  float ga, gb;
+  pair_grad(yy, pt.ordered, pt.similar, s0, s1, ga, gb, hinge_ge != 0);
+  LossArrival arr;
+  if (INL) {
+    const float tm = have ? pt.term : 0.f;
+    arr.add(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(tm), 0)), fx_scale);
+    arr.add(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(tm), 32)), fx_scale);
+    if (lane == 0) arr.template arrive<WPB>(&wg_arrivals, ticket);   // the wave's two terms arrive together
+  } else {
+    if (j == 0 && have) partials[row] = pt.term;
+  }
+  if (j == 0 && have) {
+    s_pos[row] = cp.T; s_neg[row] = cn.T;
+    if (norm_q) norm_q[row] = cp.n0;
+    if (norm_pos) norm_pos[row] = cp.n1;
+    if (norm_neg) norm_neg[row] = cn.n1;
+  }
+  // Layer by layer: each SimCross backward writes dq_branch = 0 + g*(...), Net::Init's Split layer adds the two.
+  if (VOUT) {
+    const CosineFactors fp = cosine_factors(cp.T, cp.n0, cp.n1), fn = cosine_factors(cn.T, cn.n0, cn.n1);
+    float4* dq4 = reinterpret_cast<float4*>(dq) + row * D4C;
+    float4* dp4 = reinterpret_cast<float4*>(dap) + row * D4C;
+    float4* dn4 = reinterpret_cast<float4*>(dan) + row * D4C;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = j + 32 * it;
+      if (i < D4C && have) {
+        const float4 qp = cosine_grad4_fac(ga, fp.inv01, fp.cq, u[it], x[it]);
+        const float4 qn = cosine_grad4_fac(gb, fn.inv01, fn.cq, v[it], x[it]);
+        float4 oq;
+        oq.x = qp.x + qn.x; oq.y = qp.y + qn.y; oq.z = qp.z + qn.z; oq.w = qp.w + qn.w;
+        stream_store(dq4 + i, oq);
+        stream_store(dp4 + i, cosine_grad4_fac(ga, fp.inv01, fp.ca, x[it], u[it]));
+        stream_store(dn4 + i, cosine_grad4_fac(gb, fn.inv01, fn.ca, x[it], v[it]));
+      }
+    }
+  } else {
+    const float n00 = cp.n0 * cp.n0, npp = cp.n1 * cp.n1, nnn = cn.n1 * cn.n1;
+    float* dqr = dq + row * (4 * D4C);
+    float* dpr = dap + row * (4 * D4C);
+    float* dnr = dan + row * (4 * D4C);
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = j + 32 * it;
+      if (i < D4C && have) {
+        const float4 qp = cosine_grad4_div(ga, cp.n0, cp.n1, cp.T, n00, u[it], x[it]);
+        const float4 qn = cosine_grad4_div(gb, cn.n0, cn.n1, cn.T, n00, v[it], x[it]);
+        const float4 op = cosine_grad4_div(ga, cp.n0, cp.n1, cp.T, npp, x[it], u[it]);
+        const float4 on = cosine_grad4_div(gb, cn.n0, cn.n1, cn.T, nnn, x[it], v[it]);
+        dqr[4 * i] = qp.x + qn.x; dqr[4 * i + 1] = qp.y + qn.y; dqr[4 * i + 2] = qp.z + qn.z; dqr[4 * i + 3] = qp.w + qn.w;
+        dpr[4 * i] = op.x; dpr[4 * i + 1] = op.y; dpr[4 * i + 2] = op.z; dpr[4 * i + 3] = op.w;
+        dnr[4 * i] = on.x; dnr[4 * i + 1] = on.y; dnr[4 * i + 2] = on.z; dnr[4 * i + 3] = on.w;
+      }
+    }
+  }
+  if (INL) arr.finish(ticket, loss, fx_scale, N);
+}
+
+// Any other width that is a multiple of 4 up to 1024, all six arrays 16-byte aligned: a wave owns ONE triplet (the
+// shape of triplet_wave_kernel), its float4s of q, a+ and a- requested up front and kept for the backward.  Sum
+// order and backward expression are cosine_rows_kernel<VEC4>'s, the kernel the unfused calls use for these widths.
+template <int NIT>
+__global__ __launch_bounds__(256) void triplet_cosine_wave_kernel(
+    int N, int D4, float margin, float s0, float s1, const float* __restrict__ q,
+    const float* __restrict__ ap, const float* __restrict__ an, const float* __restrict__ y,
+    float* __restrict__ s_pos, float* __restrict__ s_neg, float* __restrict__ norm_q,
+    float* __restrict__ norm_pos, float* __restrict__ norm_neg, float* __restrict__ partials,
+    float* __restrict__ dq, float* __restrict__ dap, float* __restrict__ dan, int hinge_ge) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= N) return;
+  const size_t base4 = (size_t)row * D4;
+  const float4* q4 = reinterpret_cast<const float4*>(q) + base4;
+  const float4* p4 = reinterpret_cast<const float4*>(ap) + base4;
+  const float4* m4 = reinterpret_cast<const float4*>(an) + base4;
+  float4 x[NIT], u[NIT], v[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    const int ii = i < D4 ? i : 0;
+    x[it] = q4[ii]; u[it] = p4[ii]; v[it] = m4[ii];
+  }
+  float yy = y[row];
+  float sqq = 0.f, spp = 0.f, snn = 0.f, sqp = 0.f, sqn = 0.f;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if (lane + 64 * it < D4) {
+      cosine_acc4(sqq, x[it], x[it]); cosine_acc4(spp, u[it], u[it]); cosine_acc4(snn, v[it], v[it]);
+      cosine_acc4(sqp, x[it], u[it]); cosine_acc4(sqn, x[it], v[it]);
+    }
+  }
+  sqq = wave_sum(sqq); spp = wave_sum(spp); snn = wave_sum(snn); sqp = wave_sum(sqp); sqn = wave_sum(sqn);
+  const CosineScore cp = cosine_score(sqq, spp, sqp), cn = cosine_score(sqq, snn, sqn);
+  asm volatile("" : "+v"(yy));
+  const PairTerm pt = pair_term(cp.T, cn.T, yy, margin);
+  float ga, gb;
+  pair_grad(yy, pt.ordered, pt.similar, s0, s1, ga, gb, hinge_ge != 0);
+  if (lane == 0) {
+    s_pos[row] = cp.T; s_neg[row] = cn.T; partials[row] = pt.term;
+    if (norm_q) norm_q[row] = cp.n0;
+    if (norm_pos) norm_pos[row] = cp.n1;
+    if (norm_neg) norm_neg[row] = cn.n1;
+  }
+  const float n00 = cp.n0 * cp.n0, npp = cp.n1 * cp.n1, nnn = cn.n1 * cn.n1;
+  float4* dq4 = reinterpret_cast<float4*>(dq) + base4;
+  float4* dp4 = reinterpret_cast<float4*>(dap) + base4;
+  float4* dn4 = reinterpret_cast<float4*>(dan) + base4;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    if (i >= D4) break;
+    const float4 qp = cosine_grad4_div(ga, cp.n0, cp.n1, cp.T, n00, u[it], x[it]);
+    const float4 qn = cosine_grad4_div(gb, cn.n0, cn.n1, cn.T, n00, v[it], x[it]);
+    float4 oq;
+    oq.x = qp.x + qn.x; oq.y = qp.y + qn.y; oq.z = qp.z + qn.z; oq.w = qp.w + qn.w;
+    stream_store(dq4 + i, oq);
+    stream_store(dp4 + i, cosine_grad4_div(ga, cp.n0, cp.n1, cp.T, npp, x[it], u[it]));
+    stream_store(dn4 + i, cosine_grad4_div(gb, cn.n0, cn.n1, cn.T, nnn, x[it], v[it]));
+  }
+}
+
+// Generic tail (any D, any alignment, widths beyond 1024): a wave per triplet, the two loops of cosine_rows_kernel.
+// VIN: D % 4 == 0 and q, a+, a- 16-byte aligned -- the unfused FORWARD then sums float4-wise, so this one does; the
+// backward re-reads the row (it was just read: L2) and stores element by element, whatever the gradients' alignment.
+template <bool VIN>
+__global__ __launch_bounds__(256) void triplet_cosine_rows_kernel(
+    int N, int D, float margin, float s0, float s1, const float* __restrict__ q,
+    const float* __restrict__ ap, const float* __restrict__ an, const float* __restrict__ y,
+    float* __restrict__ s_pos, float* __restrict__ s_neg, float* __restrict__ norm_q,
+    float* __restrict__ norm_pos, float* __restrict__ norm_neg, float* __restrict__ partials,
+    float* __restrict__ dq, float* __restrict__ dap, float* __restrict__ dan, int hinge_ge) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const size_t base = (size_t)row * D;
+  const float* qr = q + base;
+  const float* pr = ap + base;
+  const float* mr = an + base;
+  float yy = y[row];
+  float sqq = 0.f, spp = 0.f, snn = 0.f, sqp = 0.f, sqn = 0.f;
+  if (VIN) {
+    const float4* q4 = reinterpret_cast<const float4*>(qr);
+    const float4* p4 = reinterpret_cast<const float4*>(pr);
+    const float4* m4 = reinterpret_cast<const float4*>(mr);
+    for (int i = lane; i < (D >> 2); i += 64) {
+      const float4 x = q4[i], u = p4[i], v = m4[i];
+      cosine_acc4(sqq, x, x); cosine_acc4(spp, u, u); cosine_acc4(snn, v, v);
+      cosine_acc4(sqp, x, u); cosine_acc4(sqn, x, v);
+    }
+  } else {
+    for (int i = lane; i < D; i += 64) {
+      const float x = qr[i], u = pr[i], v = mr[i];
+      cosine_acc1(sqq, x, x); cosine_acc1(spp, u, u); cosine_acc1(snn, v, v);
+      cosine_acc1(sqp, x, u); cosine_acc1(sqn, x, v);
+    }
+  }
+  sqq = wave_sum(sqq); spp = wave_sum(spp); snn = wave_sum(snn); sqp = wave_sum(sqp); sqn = wave_sum(sqn);
+  const CosineScore cp = cosine_score(sqq, spp, sqp), cn = cosine_score(sqq, snn, sqn);
+  asm volatile("" : "+v"(yy));
+  const PairTerm pt = pair_term(cp.T, cn.T, yy, margin);
+  float ga, gb;
+  pair_grad(yy, pt.ordered, pt.similar, s0, s1, ga, gb, hinge_ge != 0);
+  if (lane == 0) {
+    s_pos[row] = cp.T; s_neg[row] = cn.T; partials[row] = pt.term;
+    if (norm_q) norm_q[row] = cp.n0;
+    if (norm_pos) norm_pos[row] = cp.n1;
+    if (norm_neg) norm_neg[row] = cn.n1;
+  }
+  const float n00 = cp.n0 * cp.n0, npp = cp.n1 * cp.n1, nnn = cn.n1 * cn.n1;
+  for (int i = lane; i < D; i += 64) {
+    const float x = qr[i], u = pr[i], v = mr[i];
+    dq[base + i] = cosine_grad_div(ga, cp.n0, cp.n1, cp.T, n00, u, x) + cosine_grad_div(gb, cn.n0, cn.n1, cn.T, n00, v, x);
+    dap[base + i] = cosine_grad_div(ga, cp.n0, cp.n1, cp.T, npp, x, u);
+    dan[base + i] = cosine_grad_div(gb, cn.n0, cn.n1, cn.T, nnn, x, v);
+  }
+}
+
+int triplet_cosine_step(int N, int D, float margin, float loss_weight, const float* q, const float* ap,
+                        const float* an, const float* y, float* s_pos, float* s_neg, float* norm_q,
+                        float* norm_pos, float* norm_neg, float* loss, float* dq, float* dap, float* dan,
+                        void* ws, size_t ws_bytes, hipStream_t s) {
+  if (N == 0) return MMS_OK;
+  if (ws == nullptr || ws_bytes < triplet_workspace_bytes(N)) return MMS_ERR_WORKSPACE;
+  const float scale = loss_weight / (float)N;  // pair_rank_loss_layer.cpp:64, count = N*1
+  const float s0 = -1.0f * scale, s1 = 1.0f * scale;
+  if (reinterpret_cast<uintptr_t>(ws) & 7u) return MMS_ERR_WORKSPACE;
+  unsigned long long* const tickets = static_cast<unsigned long long*>(ws);
+  float* partials = reinterpret_cast<float*>(static_cast<char*>(ws) + kTicketBytes);
+  const int hge = pairrank_hinge_mode() == MMS_PAIRRANK_HINGE_GPU ? 1 : 0;
+  // The unfused forward picks its kernel -- and with it the sum order -- from D and the alignment of its INPUTS; the
+  // unfused backward picks its expression from the alignment of the gradients as well.
+  const bool vin = (D % 4 == 0) && aligned16(q) && aligned16(ap) && aligned16(an);
+  const bool vout = aligned16(dq) && aligned16(dap) && aligned16(dan);
+  if (vin && (D == 300 || D == 200 || D == 100)) {
+    constexpr int WPB = 8;
+    const unsigned grid = (unsigned)((N + WPB * 2 - 1) / (WPB * 2));   // two triplets per wave
+    const unsigned ngrp = (grid + kTicketGroup - 1) / kTicketGroup;
+    unsigned long long* tk = (triplet_finish_mode() != MMS_TRIPLET_FINISH_INLAUNCH || ngrp > (unsigned)kTicketTop ||
+                              loss_sum_mode() == MMS_LOSS_SUM_REFERENCE || loss == nullptr)
+                                 ? nullptr : tickets;
+    int lg = 0;
+    while (((long long)1 << lg) < (long long)N) ++lg;
+    const double fx_scale = std::ldexp(1.0, kFxSumBits - kFxTermBits - lg);
+#define MMS_C32_GO(d4, inl, vo)                                                                            \
+  hipLaunchKernelGGL((triplet_cosine32_kernel<d4, WPB, inl, vo>), dim3(grid), dim3(64 * WPB), 0, s, N,     \
+                     margin, s0, s1, q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, \
+                     dap, dan, hge, tk, loss, fx_scale)
+#define MMS_C32(d4)                                                                            \
+  case 4 * d4:                                                                                 \
+    if (vout) { if (tk) MMS_C32_GO(d4, true, true); else MMS_C32_GO(d4, false, true); }        \
+    else      { if (tk) MMS_C32_GO(d4, true, false); else MMS_C32_GO(d4, false, false); }      \
+    break;
+    switch (D) { MMS_C32(25) MMS_C32(50) MMS_C32(75) }
+#undef MMS_C32
+#undef MMS_C32_GO
+    if (tk) return launch_status();               // the loss was reduced inside the launch
+  } else if (vin && vout && D <= 1024) {
+    const int D4 = D / 4;
+    const unsigned grid = (unsigned)((N + 3) / 4);
+#define MMS_NIT_CASE(n)                                                                                     \
+  case n:                                                                                                   \
+    hipLaunchKernelGGL((triplet_cosine_wave_kernel<n>), dim3(grid), dim3(256), 0, s, N, D4, margin, s0, s1, \
+                       q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge); \
+    break;
+    switch ((D4 + 63) / 64) { MMS_NIT_CASE(1) MMS_NIT_CASE(2) MMS_NIT_CASE(3) MMS_NIT_CASE(4) }
+#undef MMS_NIT_CASE
+  } else {
+    const unsigned grid = (unsigned)((N + 3) / 4);
+    if (vin)
+      hipLaunchKernelGGL((triplet_cosine_rows_kernel<true>), dim3(grid), dim3(256), 0, s, N, D, margin, s0, s1,
+                         q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge);
+    else
+      hipLaunchKernelGGL((triplet_cosine_rows_kernel<false>), dim3(grid), dim3(256), 0, s, N, D, margin, s0, s1,
+                         q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge);
+  }
+  if (loss == nullptr) return launch_status();     // the caller does not want the scalar: no reduction at all
+  return triplet_loss_from_terms(partials, N, loss, s);
 }
 
 // loss = (sum of the N per-triplet terms) / N from a device array of terms: the tail of both fused steps

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cosine_math.h"
 #include "euclid_math.h"
 #include "mms_common.h"
 
@@ -972,20 +973,17 @@ __global__ __launch_bounds__(256) void cosine_rows_kernel(
       const float4* a4 = reinterpret_cast<const float4*>(ar);
       for (int i = lane; i < (D >> 2); i += 64) {
         const float4 x = q4[i], y = a4[i];
-        sqq += x.x * x.x; sqq += x.y * x.y; sqq += x.z * x.z; sqq += x.w * x.w;
-        saa += y.x * y.x; saa += y.y * y.y; saa += y.z * y.z; saa += y.w * y.w;
-        sqa += x.x * y.x; sqa += x.y * y.y; sqa += x.z * y.z; sqa += x.w * y.w;
+        cosine_acc4(sqq, x, x); cosine_acc4(saa, y, y); cosine_acc4(sqa, x, y);
       }
     } else {
       for (int i = lane; i < D; i += 64) {
         const float x = qr[i], y = ar[i];
-        sqq += x * x; saa += y * y; sqa += x * y;
+        cosine_acc1(sqq, x, x); cosine_acc1(saa, y, y); cosine_acc1(sqa, x, y);
       }
     }
     sqq = wave_sum(sqq); saa = wave_sum(saa); sqa = wave_sum(sqa);
-    n0 = sqrtf(sqq);
-    n1 = sqrtf(saa);
-    T = sqa / n0 / n1;  // two successive divisions (:135)
+    const CosineScore c = cosine_score(sqq, saa, sqa);
+    T = c.T; n0 = c.n0; n1 = c.n1;
     if (BWD) asm volatile("" : "+v"(g));
     if (lane == 0) { top[row] = T; norm0[row] = n0; norm1[row] = n1; }
   } else {
@@ -1003,23 +1001,16 @@ __global__ __launch_bounds__(256) void cosine_rows_kernel(
     float4* da4 = reinterpret_cast<float4*>(dar);
     for (int i = lane; i < (D >> 2); i += 64) {
       const float4 x = q4[i], y = a4[i];
-      float4 o0, o1;
-      o0.x = 0.f + g * (y.x / n0 / n1 - x.x * T / n00);
-      o0.y = 0.f + g * (y.y / n0 / n1 - x.y * T / n00);
-      o0.z = 0.f + g * (y.z / n0 / n1 - x.z * T / n00);
-      o0.w = 0.f + g * (y.w / n0 / n1 - x.w * T / n00);
-      o1.x = 0.f + g * (x.x / n0 / n1 - y.x * T / n11);
-      o1.y = 0.f + g * (x.y / n0 / n1 - y.y * T / n11);
-      o1.z = 0.f + g * (x.z / n0 / n1 - y.z * T / n11);
-      o1.w = 0.f + g * (x.w / n0 / n1 - y.w * T / n11);
+      const float4 o0 = cosine_grad4_div(g, n0, n1, T, n00, y, x);
+      const float4 o1 = cosine_grad4_div(g, n0, n1, T, n11, x, y);
       stream_store(dq4 + i, o0);
       stream_store(da4 + i, o1);
     }
   } else {
     for (int i = lane; i < D; i += 64) {
       const float x = qr[i], y = ar[i];
-      dqr[i] = 0.f + g * (y / n0 / n1 - x * T / n00);
-      dar[i] = 0.f + g * (x / n0 / n1 - y * T / n11);
+      dqr[i] = cosine_grad_div(g, n0, n1, T, n00, y, x);
+      dar[i] = cosine_grad_div(g, n0, n1, T, n11, x, y);
     }
   }
 }
@@ -1058,22 +1049,19 @@ __global__ __launch_bounds__(64 * WPB) void cosine_pair32_kernel(
     for (int it = 0; it < NIT; ++it) {
       if (j + 32 * it < D4C) {
         const float4 u = x[it], v = y[it];
-        sqq += u.x * u.x; sqq += u.y * u.y; sqq += u.z * u.z; sqq += u.w * u.w;
-        saa += v.x * v.x; saa += v.y * v.y; saa += v.z * v.z; saa += v.w * v.w;
-        sqa += u.x * v.x; sqa += u.y * v.y; sqa += u.z * v.z; sqa += u.w * v.w;
+        cosine_acc4(sqq, u, u); cosine_acc4(saa, v, v); cosine_acc4(sqa, u, v);
       }
     }
     sqq = half_wave_sum(sqq); saa = half_wave_sum(saa); sqa = half_wave_sum(sqa);
-    n0 = sqrtf(sqq);                             // the NORM is cached, as on the CPU (:118)
-    n1 = sqrtf(saa);
-    T = sqa / n0 / n1;                           // two successive divisions (:135)
+    const CosineScore c = cosine_score(sqq, saa, sqa);
+    T = c.T; n0 = c.n0; n1 = c.n1;
     if (j == 0 && have) { top[row] = T; norm0[row] = n0; norm1[row] = n1; }
   } else {
     T = top[row]; n0 = norm0[row]; n1 = norm1[row];
   }
   if (!BWD) return;
   const float g = top_diff[row];
-  const float inv01 = 1.0f / n0 / n1, cq = T / (n0 * n0), ca = T / (n1 * n1);
+  const CosineFactors f = cosine_factors(T, n0, n1);
   float4* dq4 = reinterpret_cast<float4*>(dq) + (size_t)row * D4C;
   float4* da4 = reinterpret_cast<float4*>(da) + (size_t)row * D4C;
 #pragma unroll
@@ -1081,11 +1069,8 @@ __global__ __launch_bounds__(64 * WPB) void cosine_pair32_kernel(
     const int i = j + 32 * it;
     if (i < D4C && have) {
       const float4 u = x[it], v = y[it];
-      float4 o0, o1;
-      o0.x = 0.f + g * (v.x * inv01 - u.x * cq); o0.y = 0.f + g * (v.y * inv01 - u.y * cq);
-      o0.z = 0.f + g * (v.z * inv01 - u.z * cq); o0.w = 0.f + g * (v.w * inv01 - u.w * cq);
-      o1.x = 0.f + g * (u.x * inv01 - v.x * ca); o1.y = 0.f + g * (u.y * inv01 - v.y * ca);
-      o1.z = 0.f + g * (u.z * inv01 - v.z * ca); o1.w = 0.f + g * (u.w * inv01 - v.w * ca);
+      const float4 o0 = cosine_grad4_fac(g, f.inv01, f.cq, v, u);
+      const float4 o1 = cosine_grad4_fac(g, f.inv01, f.ca, u, v);
       stream_store(dq4 + i, o0);
       stream_store(da4 + i, o1);
     }

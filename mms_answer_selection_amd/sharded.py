@@ -95,7 +95,7 @@ def all_reduce_loss(local_sum, n_total, group=None):
 
 def shard_loss_weight(loss_weight, n_local, n_total):
     """The `top_diff` / `loss_weight` to hand a PairRankLoss backward (mms_pairrank_backward_f32) or the fused
-    triplet step (mms_triplet_euclid_step_f32) that runs on ONE RANK'S SHARD of the batch.
+    triplet step (mms_triplet_euclid_step_f32 / mms_triplet_cosine_step_f32) that runs on ONE RANK'S SHARD of the batch.
 
     The reference scales every gradient element by top_diff / bottom[0]->count() -- the count of the WHOLE
     batch (pair_rank_loss_layer.cpp:62-64).  The C ABI divides by the count it is given, which on a shard is
@@ -110,7 +110,7 @@ def shard_loss_weight(loss_weight, n_local, n_total):
 
 def all_reduce_shard_losses(local_mean_loss, n_local, n_total, loss_weight=1.0, group=None):
     """The loss of the WHOLE batch from the per-shard losses.  The C ABI's loss outputs (mms_pairrank_forward_f32,
-    mms_triplet_euclid_step_f32) are the UNWEIGHTED mean over the elements they were given, so a shard's share of
+    mms_triplet_euclid_step_f32, mms_triplet_cosine_step_f32) are the UNWEIGHTED mean over the elements they were given, so a shard's share of
     the batch mean is n_local / n_total of it; the Layer's loss weight multiplies the result
     (layer.hpp:462-481)."""
     t = local_mean_loss.clone() * (float(loss_weight) * float(n_local) / float(n_total))
