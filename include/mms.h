@@ -602,6 +602,44 @@ int mms_embed_simcross_bilinear_forward_f32(int N, int W1, int W2, int D, int M,
                                             const float* W, const float* bias, float* top, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * FM: second-order factorization-machine pooling over the channels of a blob
+ * (src/caffe/layers/fm_layer.cpp, fm_param { bias_term }, caffe.proto:415-420).
+ * x is contiguous (N, C, dim): element (i, k, j) at i*C*dim + k*dim + j, which is
+ * what the reference reads (channels() and height(); width() is ignored, so a
+ * blob with width > 1 is NOT this layout).  Column 0 of a channel is its linear
+ * term, columns 1..dim-1 its latent factors:
+ *   top[i] = 1/2 sum_{j>=1} [ (sum_k x_ikj)^2 - sum_k x_ikj^2 ] + sum_k x_ik0 + bias
+ * top is (N, 1), the shape PairRankLoss consumes.  Any C >= 1, dim >= 1, N >= 0;
+ * MMS_ERR_INVALID_ARG for N < 0, C <= 0, dim <= 0, N*C*dim > INT_MAX (the
+ * reference indexes with int) or a NULL required array with N > 0; N == 0
+ * launches nothing.  One launch per call, no workspace, no atomics.  All results
+ * are BIT-IDENTICAL to the reference CPU code: its loop order fixes them
+ * (one ordered chain of (dim-1)(C+1) + C + 1 adds per sample).
+ * ------------------------------------------------------------------------- */
+
+/* Replaces FMLayer<float>::Forward_cpu / Forward_gpu
+ *   src/caffe/layers/fm_layer.cpp:33-62, fm_layer.cu:12-15 (which calls the CPU code).
+ * bias: blobs_[0], ONE device float; NULL = bias_term false.  top: N floats. */
+int mms_fm_forward_f32(int N, int C, int dim, const float* x, const float* bias, float* top, void* stream);
+
+/* Replaces FMLayer<float>::Backward_cpu / Backward_gpu
+ *   src/caffe/layers/fm_layer.cpp:65-99, fm_layer.cu:17-21.
+ * bottom_diff (N*C*dim floats; NULL = propagate_down[0] false): every element is
+ * OVERWRITTEN; it must not alias x.  bias_diff (ONE device float; NULL = no bias
+ * term, or param_propagate_down_[0] false) is OVERWRITTEN with the ascending sum
+ * of top_diff, as the reference zeroes it itself (:77) -- it is not accumulated
+ * into.  x and top_diff are required even when bottom_diff is NULL. */
+int mms_fm_backward_f32(int N, int C, int dim, const float* x, const float* top_diff, float* bottom_diff,
+                        float* bias_diff, void* stream);
+
+/* Both of the above in one launch, for a host that knows top_diff up front (as
+ * mms_simcross_forward_backward_f32): x is read from HBM once; top, bottom_diff
+ * and bias_diff hold the same bits as after the two separate calls.  bottom_diff
+ * is required (and must not alias x); bias and bias_diff are each optional. */
+int mms_fm_forward_backward_f32(int N, int C, int dim, const float* x, const float* bias, const float* top_diff,
+                                float* top, float* bottom_diff, float* bias_diff, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Batch feed: dst[i,:] = src[perm[first+i],:], i < rows,
  * for a dataset (src_rows, row_elems) resident in HBM; perm (src_rows ints on
  * the device) or NULL for the identity; first + rows <= src_rows.
@@ -644,6 +682,11 @@ int mms_pairrank_forward_f64(int count, double margin, const double* a, const do
 int mms_pairrank_backward_f64(int count, double top_diff, const double* y, const double* ordered,
                               const double* similar, int propagate_down0, int propagate_down1,
                               double* da, double* db, void* stream);
+/* FMLayer<double>: same arguments and errors as mms_fm_forward_f32 / mms_fm_backward_f32, same loop order, the
+ * bits of the reference's double instantiation (one thread per output; csrc/fm.hip). */
+int mms_fm_forward_f64(int N, int C, int dim, const double* x, const double* bias, double* top, void* stream);
+int mms_fm_backward_f64(int N, int C, int dim, const double* x, const double* top_diff, double* bottom_diff,
+                        double* bias_diff, void* stream);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,11 @@ _SIGNATURES = {
     "mms_simmatrix_backward_f64": (_i, [_i] * 3 + [_vp] * 4 + [_i] * 3 + [_vp] * 4),
     "mms_pairrank_forward_f64": (_i, [_i, C.c_double] + [_vp] * 7),
     "mms_pairrank_backward_f64": (_i, [_i, C.c_double] + [_vp] * 3 + [_i, _i] + [_vp] * 3),
+    "mms_fm_forward_f32": (_i, [_i] * 3 + [_vp] * 4),
+    "mms_fm_backward_f32": (_i, [_i] * 3 + [_vp] * 5),
+    "mms_fm_forward_backward_f32": (_i, [_i] * 3 + [_vp] * 7),
+    "mms_fm_forward_f64": (_i, [_i] * 3 + [_vp] * 4),
+    "mms_fm_backward_f64": (_i, [_i] * 3 + [_vp] * 5),
     "mms_set_euclid_backward_mode": (_i, [_i]),
     "mms_get_euclid_backward_mode": (_i, []),
     "mms_null_launch": (_i, [_i, _vp]),
@@ -326,6 +331,30 @@ def pairrank_backward(y, ordered, similar, da, db, top_diff=1.0, propagate_down=
         y.numel(), float(top_diff), _ptr(y, "y"), _ptr(ordered, "ordered"),
         _ptr(similar, "similar"), int(bool(propagate_down[0])), int(bool(propagate_down[1])),
         _ptr(da, "da", True), _ptr(db, "db", True), _stream()), "mms_pairrank_backward_f32")
+
+
+def fm_forward(x, top, bias=None):
+    """FM pooling (include/mms.h: mms_fm_forward_f32).  x (N, C, dim); top N floats; bias one float or None."""
+    N, C, dim = x.shape
+    check(lib().mms_fm_forward_f32(N, C, dim, _ptr(x, "x"), _ptr(bias, "bias", True), _ptr(top, "top"), _stream()),
+          "mms_fm_forward_f32")
+
+
+def fm_backward(x, top_diff, bottom_diff=None, bias_diff=None):
+    """bottom_diff None = propagate_down[0] false; bias_diff None = no bias term or param_propagate_down false.
+    Both are overwritten."""
+    N, C, dim = x.shape
+    check(lib().mms_fm_backward_f32(
+        N, C, dim, _ptr(x, "x"), _ptr(top_diff, "top_diff"), _ptr(bottom_diff, "bottom_diff", True),
+        _ptr(bias_diff, "bias_diff", True), _stream()), "mms_fm_backward_f32")
+
+
+def fm_forward_backward(x, top_diff, top, bottom_diff, bias=None, bias_diff=None):
+    N, C, dim = x.shape
+    check(lib().mms_fm_forward_backward_f32(
+        N, C, dim, _ptr(x, "x"), _ptr(bias, "bias", True), _ptr(top_diff, "top_diff"), _ptr(top, "top"),
+        _ptr(bottom_diff, "bottom_diff"), _ptr(bias_diff, "bias_diff", True), _stream()),
+        "mms_fm_forward_backward_f32")
 
 
 class TripletWorkspace:
@@ -704,3 +733,17 @@ def pairrank_backward_f64(y, ordered, similar, da, db, top_diff=1.0, propagate_d
         y.numel(), float(top_diff), _ptr(y, "y", dtype=_D), _ptr(ordered, "ordered", dtype=_D),
         _ptr(similar, "similar", dtype=_D), int(bool(propagate_down[0])), int(bool(propagate_down[1])),
         _ptr(da, "da", True, _D), _ptr(db, "db", True, _D), _stream()), "mms_pairrank_backward_f64")
+
+
+def fm_forward_f64(x, top, bias=None):
+    N, C, dim = x.shape
+    check(lib().mms_fm_forward_f64(N, C, dim, _ptr(x, "x", dtype=_D), _ptr(bias, "bias", True, _D),
+                                   _ptr(top, "top", dtype=_D), _stream()), "mms_fm_forward_f64")
+
+
+def fm_backward_f64(x, top_diff, bottom_diff=None, bias_diff=None):
+    N, C, dim = x.shape
+    check(lib().mms_fm_backward_f64(
+        N, C, dim, _ptr(x, "x", dtype=_D), _ptr(top_diff, "top_diff", dtype=_D),
+        _ptr(bottom_diff, "bottom_diff", True, _D), _ptr(bias_diff, "bias_diff", True, _D), _stream()),
+        "mms_fm_backward_f64")
