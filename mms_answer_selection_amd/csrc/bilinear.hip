@@ -22,7 +22,7 @@
 // Deterministic: split-K partial slabs are summed in a fixed order, no atomics.
 #include <type_traits>
 
-#include "mms_common.h"
+#include "mms_internal.h"
 #include "panel_gemm.h"
 #include "bx3_gemm.h"
 
@@ -800,6 +800,16 @@ static unsigned ew_blocks(long long n) {
   return (unsigned)b;
 }
 
+// next problem of a grouped reduction: its blocks follow the previous problem's (first[cnt] = blocks so far)
+static void reduce_group_add(ReduceGroup& rg, const float* part, float* out, long long n, int splits, int accumulate = 0) {
+  const int i = rg.cnt++;
+  rg.part[i] = part; rg.out[i] = out; rg.n[i] = n; rg.splits[i] = splits; rg.accumulate[i] = accumulate;
+  for (int j = i + 1; j <= kGroupMax; ++j) rg.first[j] = rg.first[i] + (int)ew_blocks(n);
+}
+static void reduce_group_launch(const ReduceGroup& rg, hipStream_t s) {
+  hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(rg.first[rg.cnt]), dim3(256), 0, s, rg);
+}
+
 // Split count for a product with a long K (the dW products: K = pairs).  Workgroups = tiles x batch x
 // splits; the chip takes them 256 x (workgroups per CU) at a time, so the count should (a) reach ~3 per CU
 // and (b) nearly FILL its last round: 25 tiles x 32 splits = 800 is 3.1 per CU -- a fourth round for 12 %
@@ -827,25 +837,24 @@ static int pick_ksplit(int Mt, int Nt, int K, int* kchunk, int batch = 1) {
 }
 
 // ------------------------------ workspace layout ----------------------------
-struct BilinearWs {
-  size_t u_off, v_off, part_off, mpart_off, mpart2_off, total;
-  int ksplit, kchunk;
-};
-static bool pair_bwd_fits(int N, int W1, int W2, int D, int M) {      // = pair_bwd_eligible (defined with the kernel)
-  return W1 <= 48 && W2 <= 48 && D <= 64 && W1 * W2 > 1 && N <= 256 && (long long)N * M <= 65535;
+// the word grids the fused per-(pair, measure) kernels stage whole in LDS (bilinear_pair_bwd_kernel,
+// bilinear_pairm_fwd_kernel): image row stride, most words per sentence, widest embedding
+constexpr int FB_LS = 68, FB_W = 48, FB_D = 64;
+// does the fused per-pair backward (and its forward twin) take this shape?  Sizes the workspace AND picks the kernel.
+static bool pair_bwd_eligible(int N, int W1, int W2, int D, int M) {
+  return W1 <= FB_W && W2 <= FB_W && D <= FB_D && W1 * W2 > 1 && N <= 256 && (long long)N * M <= 65535;
 }
 // The sentence-vector geometry with ONE measure (W1 = W2 = 1, M = 1: BASELINE cfg 3 written as a SimCross layer) IS
 // SimMatrix's arithmetic -- T_n = q_n^T W a_n (+ bias), dW = sum_n dT_n q_n a_n^T, dq_n = dT_n W a_n,
 // da_n = dT_n W^T q_n -- so it takes SimMatrix's panel-GEMM launches (row dot and row scale as epilogues) instead
 // of the generic GEMM + rowdot / rowscale launches: 45 + 136 us -> the SimMatrix figures (recomputing Q.W).
-size_t simmatrix_workspace_bytes(int N, int K1, int K2);
-int simmatrix_forward(int N, int K1, int K2, const float* q, const float* a, const float* W, float* top, float* qw,
-                      hipStream_t s, const float* rd_bias, void* ws = nullptr, size_t ws_bytes = 0);
-int simmatrix_backward(int N, int K1, int K2, const float* q, const float* a, const float* W,
-                       const float* top_diff, int ppd, int pd0, int pd1, float* dq, float* da,
-                       float* dW, const float* qw, void* ws, size_t ws_bytes, hipStream_t s);
 static bool bilinear_as_simmatrix(int W1, int W2, int M) { return W1 == 1 && W2 == 1 && M == 1; }
 
+struct BilinearWs {
+  size_t u_off, v_off, part_off, mpart_off, mpart2_off, total;
+  size_t sm_off;                 // bilinear_as_simmatrix: [Q.W, N x D] at 0, SimMatrix's own workspace from here
+  int ksplit, kchunk;
+};
 static BilinearWs bilinear_ws(int N, int W1, int W2, int D, int M) {
   BilinearWs w{};
   const size_t u = (size_t)M * N * W1 * D, v = (size_t)M * N * W2 * D;
@@ -854,13 +863,14 @@ static BilinearWs bilinear_ws(int N, int W1, int W2, int D, int M) {
   w.v_off = round_up(u * sizeof(float), 256);
   w.part_off = w.v_off + round_up(v * sizeof(float), 256);
   // split-K slabs of dW -- or, when the fused per-pair backward runs, one D x D partial per (pair, measure)
-  const size_t slabs = pair_bwd_fits(N, W1, W2, D, M) && N > w.ksplit ? (size_t)N : (size_t)w.ksplit;
+  const size_t slabs = pair_bwd_eligible(N, W1, W2, D, M) && N > w.ksplit ? (size_t)N : (size_t)w.ksplit;
   w.mpart_off = w.part_off + round_up(slabs * M * D * D * sizeof(float), 256);
   // per-measure partial products of dQ and of dA (M > 1 only): [M][N*W1][D], [M][N*W2][D]
   w.mpart2_off = w.mpart_off + (M > 1 ? round_up(u * sizeof(float), 256) : 0);
   w.total = w.mpart2_off + (M > 1 ? round_up(v * sizeof(float), 256) : 0);
-  if (bilinear_as_simmatrix(W1, W2, M)) {            // [Q.W, N x D][SimMatrix's own workspace]
-    const size_t sm = round_up((size_t)N * D * sizeof(float), 256) + simmatrix_workspace_bytes(N, D, D);
+  if (bilinear_as_simmatrix(W1, W2, M)) {
+    w.sm_off = round_up((size_t)N * D * sizeof(float), 256);
+    const size_t sm = w.sm_off + simmatrix_workspace_bytes(N, D, D);
     if (sm > w.total) w.total = sm;
   }
   return w;
@@ -1067,7 +1077,7 @@ __global__ __launch_bounds__(256) void bilinear_pair_fwd_kernel(
 // on v_mfma_f32_16x16x4_f32, the 16 x 16 output tiles of a phase dealt round-robin to the four waves.  The sums
 // the reference takes in place -- dQ_n over m (sim_cross_layer.cpp:291-294), dA_n over m (:296-299), dW_m over n
 // (:286-289) -- are taken afterwards by ONE grouped reduction launch in the same ascending orders.
-constexpr int FB_LS = 68, FB_W = 48, FB_D = 64;
+// (FB_LS, FB_W, FB_D: with the workspace layout above, which they size)
 // KSW / KSD: k-steps of 4 over a word axis / the embedding axis, fixed at compile time so that a tile's operand
 // reads are ALL issued before its MFMAs (a rolled read-read-MFMA loop paid an LDS round trip per k-step: 17.6 us);
 // the images are zero beyond W and D, so steps past the real extent add exact zeros.
@@ -1289,8 +1299,29 @@ __global__ __launch_bounds__(512) void bilinear_pairm_fwd_kernel(
     }
   }
 }
-static bool pair_bwd_eligible(int N, int W1, int W2, int D, int M) {
-  return W1 <= FB_W && W2 <= FB_W && D <= FB_D && W1 * W2 > 1 && N <= 256 && (long long)N * M <= 65535;
+
+// The fused word-grid forward, when one of its two kernels takes the shape: one workgroup per pair for large batches
+// (evaluation: the 1517 TREC-QA test candidates, 89 -> 59 us), one per (pair, measure) for training batches -- at 50
+// pairs the per-pair form and the two small GEMMs both sit at the launch floor.  `g`: Embed fused in (q = a = the table).
+// Returns whether it launched.
+static bool pair_fwd_launch(int N, int W1, int W2, int D, int M, const float* q, const float* a, const float* W,
+                            const float* bias, float* top, hipStream_t s,
+                            const PairGather g = PairGather{nullptr, nullptr, 0, nullptr}) {
+  if (W1 <= PF_ROWS && W2 <= PF_ROWS && D <= 16 * PF_TD && W1 * W2 > 1 && N >= 512) {
+    if (D <= 52)
+      hipLaunchKernelGGL(bilinear_pair_fwd_kernel<13>, dim3(N), dim3(256), 0, s, N, W1, W2, D, M, q, a, W, bias, top, g);
+    else
+      hipLaunchKernelGGL(bilinear_pair_fwd_kernel<16>, dim3(N), dim3(256), 0, s, N, W1, W2, D, M, q, a, W, bias, top, g);
+    return true;
+  }
+  if (pair_bwd_eligible(N, W1, W2, D, M)) {
+    if (D <= 52)
+      hipLaunchKernelGGL((bilinear_pairm_fwd_kernel<13>), dim3(N * M), dim3(512), 0, s, N, W1, W2, D, M, q, a, W, bias, top, g);
+    else
+      hipLaunchKernelGGL((bilinear_pairm_fwd_kernel<16>), dim3(N * M), dim3(512), 0, s, N, W1, W2, D, M, q, a, W, bias, top, g);
+    return true;
+  }
+  return false;
 }
 
 // top = SimCross_bilinear(Embed(index_q), Embed(index_a)) in ONE launch, for the word-grid geometries the two
@@ -1301,24 +1332,9 @@ int embed_bilinear_forward(int N, int W1, int W2, int D, int M, int K, const flo
                            const float* index_a, const float* table, const float* embed_bias, const float* W,
                            const float* bias, float* top, hipStream_t s) {
   if (N == 0) return MMS_OK;
-  const PairGather g{index_q, index_a, K, embed_bias};
-  if (W1 <= PF_ROWS && W2 <= PF_ROWS && D <= 16 * PF_TD && W1 * W2 > 1 && N >= 512) {
-    if (D <= 52)
-      hipLaunchKernelGGL(bilinear_pair_fwd_kernel<13>, dim3(N), dim3(256), 0, s, N, W1, W2, D, M, table, table, W,
-                         bias, top, g);
-    else
-      hipLaunchKernelGGL(bilinear_pair_fwd_kernel<16>, dim3(N), dim3(256), 0, s, N, W1, W2, D, M, table, table, W,
-                         bias, top, g);
-    return launch_status();
-  }
-  if (pair_bwd_eligible(N, W1, W2, D, M)) {
-    if (D <= 52)
-      hipLaunchKernelGGL((bilinear_pairm_fwd_kernel<13>), dim3(N * M), dim3(512), 0, s, N, W1, W2, D, M, table, table, W, bias, top, g);
-    else
-      hipLaunchKernelGGL((bilinear_pairm_fwd_kernel<16>), dim3(N * M), dim3(512), 0, s, N, W1, W2, D, M, table, table, W, bias, top, g);
-    return launch_status();
-  }
-  return MMS_ERR_UNSUPPORTED;
+  if (!pair_fwd_launch(N, W1, W2, D, M, table, table, W, bias, top, s, PairGather{index_q, index_a, K, embed_bias}))
+    return MMS_ERR_UNSUPPORTED;
+  return launch_status();
 }
 
 int bilinear_forward(int N, int W1, int W2, int D, int M, const float* q, const float* a,
@@ -1327,29 +1343,9 @@ int bilinear_forward(int N, int W1, int W2, int D, int M, const float* q, const 
   const BilinearWs lay = bilinear_ws(N, W1, W2, D, M);
   if (!ws || ws_bytes < lay.total) return MMS_ERR_WORKSPACE;
   if (bilinear_as_simmatrix(W1, W2, M))
-  {
-    const size_t off = round_up((size_t)N * D * sizeof(float), 256);      // [Q.W][SimMatrix's own workspace]
-    return simmatrix_forward(N, D, D, q, a, W, top, static_cast<float*>(ws), s, bias, static_cast<char*>(ws) + off,
-                             ws_bytes - off);
-  }
-  // large batches only (evaluation: the 1517 TREC-QA test candidates, 89 -> 59 us): at the training batch of
-  // 50 pairs both forms sit at the launch floor and the two small GEMMs are marginally quicker
-  if (W1 <= PF_ROWS && W2 <= PF_ROWS && D <= 16 * PF_TD && W1 * W2 > 1 && N >= 512) {
-    if (D <= 52)
-      hipLaunchKernelGGL(bilinear_pair_fwd_kernel<13>, dim3(N), dim3(256), 0, s, N, W1, W2, D, M, q, a, W,
-                         bias, top);
-    else
-      hipLaunchKernelGGL(bilinear_pair_fwd_kernel<16>, dim3(N), dim3(256), 0, s, N, W1, W2, D, M, q, a, W,
-                         bias, top);
-    return launch_status();
-  }
-  if (pair_bwd_eligible(N, W1, W2, D, M)) {          // training batches: one launch, one workgroup per (pair, measure)
-    if (D <= 52)
-      hipLaunchKernelGGL((bilinear_pairm_fwd_kernel<13>), dim3(N * M), dim3(512), 0, s, N, W1, W2, D, M, q, a, W, bias, top);
-    else
-      hipLaunchKernelGGL((bilinear_pairm_fwd_kernel<16>), dim3(N * M), dim3(512), 0, s, N, W1, W2, D, M, q, a, W, bias, top);
-    return launch_status();
-  }
+    return simmatrix_forward(N, D, D, q, a, W, top, static_cast<float*>(ws), s, bias, static_cast<char*>(ws) + lay.sm_off,
+                             ws_bytes - lay.sm_off);
+  if (pair_fwd_launch(N, W1, W2, D, M, q, a, W, bias, top, s)) return launch_status();
   float* tmp = reinterpret_cast<float*>(static_cast<char*>(ws) + lay.u_off);
   const long long R = (long long)N * W1;
   // tmp[m] = Q_all W_m   (:148-149, batched over all pairs)
@@ -1399,23 +1395,14 @@ int bilinear_backward(int N, int W1, int W2, int D, int M, const float* q, const
       hipLaunchKernelGGL((bilinear_pair_bwd_kernel<12, 16>), dim3(N * M), dim3(512), 0, s, N, W1, W2, D, M, q, a, W,
                          top_diff, mq, ma, part);
     ReduceGroup rg{};
-    const long long nWt = (long long)M * D * D;
-    int first = 0, cnt = 0;
-    auto add = [&](const float* p, float* o, long long n, int splits) {
-      rg.part[cnt] = p; rg.out[cnt] = o; rg.n[cnt] = n; rg.splits[cnt] = splits; rg.first[cnt] = first;
-      first += (int)ew_blocks(n);
-      ++cnt;
-    };
-    if (M > 1) { add(mq, dq, R1 * D, M); add(ma, da, R2 * D, M); }
-    add(part, dW, nWt, N);                           // W.diff is overwritten (:256), pairs summed ascending
-    if (bias_term) {
-      // bias.diff += dT_n, n ascending (:301-304): top_diff IS the [pair][M*W1*W2] stack of addends
-      add(top_diff, dbias, (long long)M * W1 * W2, N);
-      rg.accumulate[cnt - 1] = 1;
+    if (M > 1) {
+      reduce_group_add(rg, mq, dq, R1 * D, M);
+      reduce_group_add(rg, ma, da, R2 * D, M);
     }
-    for (int i = cnt; i <= kGroupMax; ++i) rg.first[i] = first;
-    rg.cnt = cnt;
-    hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(first), dim3(256), 0, s, rg);
+    reduce_group_add(rg, part, dW, (long long)M * D * D, N);      // W.diff is overwritten (:256), pairs summed ascending
+    // bias.diff += dT_n, n ascending (:301-304): top_diff IS the [pair][M*W1*W2] stack of addends
+    if (bias_term) reduce_group_add(rg, top_diff, dbias, (long long)M * W1 * W2, N, 1);
+    reduce_group_launch(rg, s);
     return launch_status();
   }
   // dbias first: it depends on nothing the products write
@@ -1433,33 +1420,25 @@ int bilinear_backward(int N, int W1, int W2, int D, int M, const float* q, const
   if (bilinear_as_simmatrix(W1, W2, M)) {
     // W.diff is OVERWRITTEN by SimCross (:256) where SimMatrix accumulates: start from zero (0 + x = x exactly)
     if (hipMemsetAsync(dW, 0, sizeof(float) * (size_t)D * D, s) != hipSuccess) return MMS_ERR_LAUNCH;
-    const size_t off = round_up((size_t)N * D * sizeof(float), 256);
-    return simmatrix_backward(N, D, D, q, a, W, top_diff, 1, 1, 1, dq, da, dW, nullptr, base + off,
-                              ws_bytes - off, s);
+    return simmatrix_backward(N, D, D, q, a, W, top_diff, 1, 1, 1, dq, da, dW, nullptr, base + lay.sm_off,
+                              ws_bytes - lay.sm_off, s);
   }
   // U_nm = dT_nm A_n  (W1 x D x W2) ;  V_nm = dT_nm^T Q_n  (W2 x D x W1)
-  if (W1 == 1 && W2 == 1 && M == 1) {
-    hipLaunchKernelGGL(rowscale_kernel, dim3(ew_blocks(R2 * D)), dim3(256), 0, s, a, top_diff, U,
-                       R2, D);
-    hipLaunchKernelGGL(rowscale_kernel, dim3(ew_blocks(R1 * D)), dim3(256), 0, s, q, top_diff, V,
-                       R1, D);
-  } else {
-    GemmArgs guv[2];
-    guv[0] = gemm_args(W1, D, W2, top_diff, W2, 1, a, D, 1, U, D);
-    guv[0].nb1 = M;
-    guv[0].a_b0 = (long long)M * W1 * W2; guv[0].a_b1 = (long long)W1 * W2;
-    guv[0].b_b0 = (long long)W2 * D; guv[0].b_b1 = 0;
-    guv[0].c_b0 = (long long)W1 * D; guv[0].c_b1 = R1 * D;
-    guv[1] = gemm_args(W2, D, W1, top_diff, 1, W2, q, D, 1, V, D);
-    guv[1].nb1 = M;
-    guv[1].a_b0 = (long long)M * W1 * W2; guv[1].a_b1 = (long long)W1 * W2;
-    guv[1].b_b0 = (long long)W1 * D; guv[1].b_b1 = 0;
-    guv[1].c_b0 = (long long)W2 * D; guv[1].c_b1 = R2 * D;
-    const int nb[2] = {N, N};
-    if (!gemm_launch_group(guv, nb, 2, s)) {      // small batches: U and V in one launch
-      gemm_launch(guv[0], N, s);
-      gemm_launch(guv[1], N, s);
-    }
+  GemmArgs guv[2];
+  guv[0] = gemm_args(W1, D, W2, top_diff, W2, 1, a, D, 1, U, D);
+  guv[0].nb1 = M;
+  guv[0].a_b0 = (long long)M * W1 * W2; guv[0].a_b1 = (long long)W1 * W2;
+  guv[0].b_b0 = (long long)W2 * D; guv[0].b_b1 = 0;
+  guv[0].c_b0 = (long long)W1 * D; guv[0].c_b1 = R1 * D;
+  guv[1] = gemm_args(W2, D, W1, top_diff, 1, W2, q, D, 1, V, D);
+  guv[1].nb1 = M;
+  guv[1].a_b0 = (long long)M * W1 * W2; guv[1].a_b1 = (long long)W1 * W2;
+  guv[1].b_b0 = (long long)W1 * D; guv[1].b_b1 = 0;
+  guv[1].c_b0 = (long long)W2 * D; guv[1].c_b1 = R2 * D;
+  const int nb[2] = {N, N};
+  if (!gemm_launch_group(guv, nb, 2, s)) {      // small batches: U and V in one launch
+    gemm_launch(guv[0], N, s);
+    gemm_launch(guv[1], N, s);
   }
   // dQ_all = sum_m U_m W_m^T ; dA_all = sum_m V_m W_m   (:291-299; m = 0 overwrites, which also realises
   // the unconditional zeroing of :176-177) ; dW_m = Q_all^T U_m  (:286-289), K = N*W1 split across
@@ -1497,19 +1476,10 @@ int bilinear_backward(int N, int W1, int W2, int D, int M, const float* q, const
       gemm_launch(g3[2], 1, s);
     }
     ReduceGroup rg{};
-    const float* parts[3] = {mq, ma, part};
-    float* outs[3] = {dq, da, dW};
-    const long long ns[3] = {R1 * D, R2 * D, nW};
-    const int sp[3] = {M, M, lay.ksplit};
-    int first = 0;
-    for (int i = 0; i < 3; ++i) {
-      rg.part[i] = parts[i]; rg.out[i] = outs[i]; rg.n[i] = ns[i]; rg.splits[i] = sp[i];
-      rg.first[i] = first;
-      first += (int)ew_blocks(ns[i]);
-    }
-    rg.first[3] = first;
-    rg.cnt = 3;
-    hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(first), dim3(256), 0, s, rg);
+    reduce_group_add(rg, mq, dq, R1 * D, M);
+    reduce_group_add(rg, ma, da, R2 * D, M);
+    reduce_group_add(rg, part, dW, nW, lay.ksplit);
+    reduce_group_launch(rg, s);
   }
   return launch_status();
 }
@@ -1531,15 +1501,23 @@ int set_matrix_mode(int mode) {
 int get_matrix_mode() { return g_matrix_mode; }
 // below this many rows the fp32 kernel's 64-row panels fill the chip better and the split launch is not worth its 3 us
 static bool bx3_rows_worth(int M) { return M >= 2048; }
+// May this call put its tall-times-weight products on the bf16 pipe?  `need`: the total of the call's workspace layout.
+static bool bx3_pipe_ok(int mode, const void* ws, size_t ws_bytes, size_t need, int N) {
+  return mode == 0 && ws && ws_bytes >= need && bx3_rows_worth(N);
+}
+// How the panel kernel / the bf16-pipe kernel split the N pairs of the dW product Q^T B (K1 x K2): read by the launch
+// (panel_dw_args, bx3_dw_args) and by the workspace layouts, which size the slabs for whichever kernel runs
+static int panel_dw_split(int N, int K1, int* kchunk) { return panel_pick_ksplit((K1 + 63) / 64, 1, N, kchunk); }
+static int bx3_dw_split(int N, int K1, int K2, int* kchunk) { return bx3_tn_pick_chunks(N, bx3_tn_quads(K1, K2), kchunk); }
+
 static SimMatrixWs simmatrix_ws(int N, int K1, int K2) {
   SimMatrixWs w{};
-  w.ksplit = pick_ksplit(K1, K2, N, &w.kchunk);
-  int pchunk = 0;
-  const int psplit = panel_pick_ksplit((K1 + 63) / 64, 1, N, &pchunk);   // the panel kernel's split (if it runs)
+  w.ksplit = pick_ksplit(K1, K2, N, &w.kchunk);                           // gemm32's split (if it runs)
+  int chunk = 0;
+  const int psplit = panel_dw_split(N, K1, &chunk);
   w.u_off = 0;
   w.part_off = round_up((size_t)N * K2 * sizeof(float), 256);
-  int tchunk = 0;
-  const int tsplit = bx3_tn_pick_chunks(N, bx3_tn_quads(K1, K2), &tchunk);      // the split-bf16 dW kernel's split (if it runs)
+  const int tsplit = bx3_dw_split(N, K1, K2, &chunk);
   int slabs = psplit > w.ksplit ? psplit : w.ksplit;
   if (tsplit > slabs) slabs = tsplit;
   w.wt_off = w.part_off + round_up((size_t)slabs * K1 * K2 * sizeof(float), 256);
@@ -1550,37 +1528,105 @@ static SimMatrixWs simmatrix_ws(int N, int K1, int K2) {
 }
 size_t simmatrix_workspace_bytes(int N, int K1, int K2) { return simmatrix_ws(N, K1, K2).total; }
 
+static bx3_u4* simmatrix_img(void* ws, const SimMatrixWs& lay) {
+  return reinterpret_cast<bx3_u4*>(static_cast<char*>(ws) + lay.img_off);
+}
+
+// ---- the launch sequences the entry points below are put together from ----
+// X W on the bf16 pipe, X (N, K1) fp32 or (x_half) IEEE half, through the split image of W built at `img`: any of
+// C = the product (scaled by rowscale[i] per row when given: then a bottom diff, stored streaming) and
+// rowdot[i] = (rd_bias[0] +) row i of it . y_i (y stored like X).  Returns false, nothing launched, when not eligible.
+static bool bx3_xw(int N, int K1, int K2, const void* x, int x_half, const float* W, bx3_u4* img, float* C, const void* y,
+                   float* rowdot, const float* rd_bias, const float* rowscale, hipStream_t s) {
+  Bx3Args b{};
+  b.M = N; b.N = K2; b.K = K1; b.A = static_cast<const float*>(x); b.lda = K1; b.a_half = x_half; b.img = img;
+  if (C) { b.C = C; b.ldc = K2; }
+  if (y) { b.Y = static_cast<const float*>(y); b.ldy = K2; b.rowdot = rowdot; b.rd_stride = 1; b.rd_bias = rd_bias; }
+  b.rowscale = rowscale; b.stream_c = rowscale != nullptr;
+  if (!bx3_eligible(b)) return false;
+  // the image of W; its launch also zeroes the scores when two column groups add their halves into them
+  bx3_split_b(W, K2, 1, K1, K2, img, s, bx3_groups(K2) == 2 ? rowdot : nullptr, 1, N);
+  bx3_launch(b, s);
+  return true;
+}
+
+// dW += Q^T diag(kscale) B   (:73-80, accumulating), split over the N pairs into slabs at `part`, on the bf16 pipe: both
+// operands (fp32, or IEEE half with ab_half) split on the fly (bx3_gemm.h, bx3_tn_kernel), slabs summed in chunk order
+static Bx3TnArgs bx3_dw_args(int N, int K1, int K2, const void* q, const void* b, int ab_half, const float* kscale,
+                             float* part) {
+  Bx3TnArgs t{};
+  t.M = K1; t.N = K2; t.K = N; t.A = static_cast<const float*>(q); t.lda = K1; t.B = static_cast<const float*>(b); t.ldb = K2;
+  t.kscale = kscale; t.ab_half = ab_half; t.C = part; t.c_ks = (long long)K1 * K2;
+  t.nchunks = bx3_dw_split(N, K1, K2, &t.kchunk);
+  return t;
+}
+// dq_img: where the reduction's launch also builds the split image of W^T (the dq product's operand), or null.
+// Returns whether it ran.
+static bool bx3_dw(const Bx3TnArgs& t, float* dW, const float* W, bx3_u4* dq_img, hipStream_t s) {
+  if (!bx3_tn_eligible(t)) return false;
+  bx3_tn_launch(t, s);
+  const unsigned rb = ew_blocks(t.c_ks);
+  if (dq_img) {
+    const Bx3SplitArgs sp = bx3_split_args(W, 1, t.N, t.N, t.M, dq_img);
+    hipLaunchKernelGGL(splitk_reduce_split_kernel, dim3(rb + bx3_split_blocks(sp)), dim3(256), 0, s, t.C, t.nchunks, t.c_ks,
+                       dW, 1, (int)rb, sp);
+  } else {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb), dim3(256), 0, s, t.C, t.nchunks, t.c_ks, dW, 1);
+  }
+  return true;
+}
+
+// The same product on the fp32 panel kernel: A(i, k = pair) = q_k[i] * kscale[k] (kscale is not optional there)
+static PanelArgs panel_dw_args(int N, int K1, int K2, const float* q, const float* b, const float* kscale, float* part) {
+  PanelArgs p = panel_args(K1, K2, N, q, K1, b, K2, part, K2);
+  p.kscale = kscale;
+  p.ksplit = panel_dw_split(N, K1, &p.kchunk);
+  p.c_ks = (long long)K1 * K2;
+  return p;
+}
+static bool panel_dw_eligible(const PanelArgs& p) { return p.ksplit > 1 && panel_eligible(p, false); }
+// dq_wt: where the reduction's launch also writes W^T (the dq product's k-major operand), or null.  Returns whether it ran.
+static bool panel_dw(const PanelArgs& p, float* dW, const float* W, float* dq_wt, hipStream_t s) {
+  if (!panel_dw_eligible(p)) return false;
+  panel_launch(p, false, s);
+  const unsigned rb = ew_blocks(p.c_ks);
+  if (dq_wt) {
+    const unsigned tb = (unsigned)(((p.N + 31) / 32) * ((p.M + 31) / 32));
+    hipLaunchKernelGGL(splitk_reduce_transpose_kernel, dim3(rb + tb), dim3(256), 0, s, p.C, p.ksplit, p.c_ks, dW, 1, (int)rb,
+                       W, dq_wt, p.M, p.N);
+  } else {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb), dim3(256), 0, s, p.C, p.ksplit, p.c_ks, dW, 1);
+  }
+  return true;
+}
+
+// C = diag(rowscale) X W on the fp32 pipe (rowscale may be null), with the row dot against y (+ rd_bias) as the
+// epilogue when y is given: the panel kernel, else gemm32 (+ rowdot_kernel).  A scaled product is a bottom diff, read
+// next by another layer and not by this call: stored streaming.
+static void fp32_xw(int N, int K1, int K2, const float* x, const float* W, float* C, const float* y, float* rowdot,
+                    const float* rd_bias, const float* rowscale, hipStream_t s) {
+  PanelArgs p = panel_args(N, K2, K1, x, K1, W, K2, C, K2);
+  if (y) { p.Y = y; p.ldy = K2; p.rowdot = rowdot; p.rd_stride = 1; p.rd_bias = rd_bias; }
+  p.rowscale = rowscale; p.stream_c = rowscale != nullptr;
+  if (panel_eligible(p, true)) {
+    panel_launch(p, true, s);
+    return;
+  }
+  GemmArgs g = gemm_args(N, K2, K1, x, K1, 1, W, K2, 1, C, K2);
+  g.rowscale = rowscale; g.stream_c = rowscale != nullptr;
+  gemm_launch(g, 1, s);
+  if (y)
+    hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, y, C, rd_bias, rowdot, (long long)N,
+                       K2, 1LL);
+}
+
+// qw = Q W  (:60-61) ; top_i = a_i . qw_i  (:62-64).  rd_bias: SimCross bilinear's bias (one scalar at W1 = W2 = 1), else null
 int simmatrix_forward(int N, int K1, int K2, const float* q, const float* a, const float* W,
                       float* top, float* qw, hipStream_t s, const float* rd_bias, void* ws, size_t ws_bytes) {
-  // qw = Q W  (:60-61) ; top_i = a_i . qw_i  (:62-64)
-  if (g_matrix_mode == 0 && ws && bx3_rows_worth(N)) {
-    const SimMatrixWs lay = simmatrix_ws(N, K1, K2);
-    Bx3Args b{};
-    b.M = N; b.N = K2; b.K = K1; b.A = q; b.lda = K1; b.C = qw; b.ldc = K2;
-    b.Y = a; b.ldy = K2; b.rowdot = top; b.rd_stride = 1; b.rd_bias = rd_bias;
-    if (ws_bytes >= lay.total && bx3_eligible(b)) {
-      bx3_u4* img = reinterpret_cast<bx3_u4*>(static_cast<char*>(ws) + lay.img_off);
-      b.img = img;
-      // the image of W; its launch also zeroes the scores when two column groups add their halves into them
-      bx3_split_b(W, K2, 1, K1, K2, img, s, bx3_groups(K2) == 2 ? top : nullptr, 1, N);
-      bx3_launch(b, s);
-      return launch_status();
-    }
-  }
-  {
-    // one launch: the row dot is the product's epilogue
-    PanelArgs p = panel_args(N, K2, K1, q, K1, W, K2, qw, K2);
-    p.Y = a; p.ldy = K2; p.rowdot = top; p.rd_stride = 1;
-    p.rd_bias = rd_bias;                        // SimCross bilinear's bias (one scalar at W1 = W2 = 1), else null
-    if (panel_eligible(p, true)) {
-      panel_launch(p, true, s);
-      return launch_status();
-    }
-  }
-  GemmArgs g = gemm_args(N, K2, K1, q, K1, 1, W, K2, 1, qw, K2);
-  gemm_launch(g, 1, s);
-  hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, a, qw, rd_bias,
-                     top, (long long)N, K2, 1LL);
+  const SimMatrixWs lay = simmatrix_ws(N, K1, K2);
+  if (!bx3_pipe_ok(g_matrix_mode, ws, ws_bytes, lay.total, N) ||
+      !bx3_xw(N, K1, K2, q, 0, W, simmatrix_img(ws, lay), qw, a, top, rd_bias, nullptr, s))
+    fp32_xw(N, K1, K2, q, W, qw, a, top, rd_bias, nullptr, s);
   return launch_status();
 }
 
@@ -1591,17 +1637,7 @@ int simmatrix_forward(int N, int K1, int K2, const float* q, const float* a, con
 // shapes outside the kernel are MMS_ERR_UNSUPPORTED.
 int simmatrix_forward_f16(int N, int K1, int K2, const void* q, const void* a, const float* W, float* top, void* ws,
                           size_t ws_bytes, hipStream_t s) {
-  const SimMatrixWs lay = simmatrix_ws(N, K1, K2);
-  if (!ws || ws_bytes < lay.total) return MMS_ERR_WORKSPACE;
-  Bx3Args b{};
-  b.M = N; b.N = K2; b.K = K1; b.A = static_cast<const float*>(q); b.lda = K1; b.a_half = 1;
-  b.Y = static_cast<const float*>(a); b.ldy = K2; b.rowdot = top; b.rd_stride = 1;
-  if (!bx3_eligible(b)) return MMS_ERR_UNSUPPORTED;
-  bx3_u4* img = reinterpret_cast<bx3_u4*>(static_cast<char*>(ws) + lay.img_off);
-  b.img = img;
-  bx3_split_b(W, K2, 1, K1, K2, img, s, bx3_groups(K2) == 2 ? top : nullptr, 1, N);
-  bx3_launch(b, s);
-  return launch_status();
+  return simmatrix_forward_train_f16(N, K1, K2, q, a, W, top, nullptr, ws, ws_bytes, s);
 }
 
 // da (halves) = diag(dT) . P  (P fp32: the training forward's Q.W), RNE at the store
@@ -1625,56 +1661,34 @@ int simmatrix_forward_train_f16(int N, int K1, int K2, const void* q, const void
                                 void* ws, size_t ws_bytes, hipStream_t s) {
   const SimMatrixWs lay = simmatrix_ws(N, K1, K2);
   if (!ws || ws_bytes < lay.total) return MMS_ERR_WORKSPACE;
-  Bx3Args b{};
-  b.M = N; b.N = K2; b.K = K1; b.A = static_cast<const float*>(q); b.lda = K1; b.a_half = 1; b.C = qw; b.ldc = K2;
-  b.Y = static_cast<const float*>(a); b.ldy = K2; b.rowdot = top; b.rd_stride = 1;
-  if (!bx3_eligible(b)) return MMS_ERR_UNSUPPORTED;
-  bx3_u4* img = reinterpret_cast<bx3_u4*>(static_cast<char*>(ws) + lay.img_off);
-  b.img = img;
-  bx3_split_b(W, K2, 1, K1, K2, img, s, bx3_groups(K2) == 2 ? top : nullptr, 1, N);
-  bx3_launch(b, s);
+  if (!bx3_xw(N, K1, K2, q, 1, W, simmatrix_img(ws, lay), qw, a, top, nullptr, nullptr, s)) return MMS_ERR_UNSUPPORTED;
   return launch_status();
 }
 int simmatrix_backward_f16(int N, int K1, int K2, const void* q, const void* a, const float* W, const float* qw,
                            const float* top_diff, void* dq, void* da, float* dW, void* ws, size_t ws_bytes, hipStream_t s) {
   const SimMatrixWs lay = simmatrix_ws(N, K1, K2);
   if (!ws || ws_bytes < lay.total) return MMS_ERR_WORKSPACE;
-  char* base = static_cast<char*>(ws);
-  float* part = reinterpret_cast<float*>(base + lay.part_off);
-  bx3_u4* img = reinterpret_cast<bx3_u4*>(base + lay.img_off);
-  Bx3TnArgs t{};
-  t.M = K1; t.N = K2; t.K = N; t.A = static_cast<const float*>(q); t.lda = K1; t.B = static_cast<const float*>(a); t.ldb = K2;
-  t.kscale = top_diff; t.C = part; t.c_ks = (long long)K1 * K2; t.ab_half = 1;
-  t.nchunks = bx3_tn_pick_chunks(N, bx3_tn_quads(K1, K2), &t.kchunk);
+  float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + lay.part_off);
+  bx3_u4* img = simmatrix_img(ws, lay);
+  const Bx3TnArgs t = bx3_dw_args(N, K1, K2, q, a, 1, top_diff, part);
   Bx3Args bq{};
   bq.M = N; bq.N = K1; bq.K = K2; bq.A = static_cast<const float*>(a); bq.lda = K2; bq.a_half = 1;
   bq.C = static_cast<float*>(dq); bq.ldc = K1; bq.c_half = 1; bq.rowscale = top_diff; bq.stream_c = 1; bq.img = img;
-  bool da_side = false;
+  bool da_written = false;
   if (dq && da && qw && K2 >= 8) {                 // da rides in the dq launch's loader waves (as in the fp32 path)
     bq.side_in = qw; bq.side_out = static_cast<float*>(da); bq.side_scale = top_diff; bq.side_ld = K2; bq.side_cols = K2;
     bq.side_half = 1;
-    da_side = bx3_eligible(bq);
-    if (!da_side) { bq.side_in = nullptr; bq.side_out = nullptr; bq.side_scale = nullptr; bq.side_half = 0; }
+    da_written = bx3_eligible(bq);
+    if (!da_written) { bq.side_in = nullptr; bq.side_out = nullptr; bq.side_scale = nullptr; bq.side_half = 0; }
   }
   if ((dW && !bx3_tn_eligible(t)) || (dq && !bx3_eligible(bq)) || (da && (!qw || (K2 & 3) != 0 || !aligned16(qw) ||
                                                                          (reinterpret_cast<uintptr_t>(da) & 7u) != 0)))
     return MMS_ERR_UNSUPPORTED;
-  if (dW) {
-    // dW += Q^T diag(dT) A   (:73-80), both operands widened and split on the fly
-    bx3_tn_launch(t, s);
-    const unsigned rb = ew_blocks((long long)K1 * K2);
-    if (dq) {
-      const Bx3SplitArgs sp = bx3_split_args(W, 1, K2, K2, K1, img);
-      hipLaunchKernelGGL(splitk_reduce_split_kernel, dim3(rb + bx3_split_blocks(sp)), dim3(256), 0, s, part, t.nchunks,
-                         (long long)K1 * K2, dW, 1, (int)rb, sp);
-    } else {
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb), dim3(256), 0, s, part, t.nchunks, (long long)K1 * K2, dW, 1);
-    }
-  } else if (dq) {
-    bx3_split_b(W, 1, K2, K2, K1, img, s);
-  }
+  // dW += Q^T diag(dT) A   (:73-80), both operands widened and split on the fly; W^T's image for dq built beside its sum
+  if (dW) bx3_dw(t, dW, W, dq ? img : nullptr, s);
+  else if (dq) bx3_split_b(W, 1, K2, K2, K1, img, s);
   if (dq) bx3_launch(bq, s);                       // dq_j = dT_j * (W a_j)   (:88, NoTrans)
-  if (da && !da_side)                              // da_j = dT_j * (W^T q_j) (:88, Trans): the forward's product, scaled
+  if (da && !da_written)                           // da_j = dT_j * (W^T q_j) (:88, Trans): the forward's product, scaled
     hipLaunchKernelGGL(rowscale_to_half_kernel, dim3(ew_blocks((long long)N * (K2 / 4))), dim3(256), 0, s,
                        reinterpret_cast<const float4*>(qw), top_diff, da, (long long)N, K2 / 4);
   return launch_status();
@@ -1687,110 +1701,74 @@ int simmatrix_backward(int N, int K1, int K2, const float* q, const float* a, co
                        const float* top_diff, int ppd, int pd0, int pd1, float* dq, float* da,
                        float* dW, const float* qw, void* ws, size_t ws_bytes, hipStream_t s) {
   const SimMatrixWs lay = simmatrix_ws(N, K1, K2);
-  // will the dq product take the panel kernel (and need W^T)?  Then its transpose rides in the dW reduction's launch.
-  float* const Wt_ws = (ws && ws_bytes >= lay.total) ? reinterpret_cast<float*>(static_cast<char*>(ws) + lay.wt_off) : nullptr;
-  bool dq_panel = false, wt_done = false;
-  Bx3Args bq{};                                 // the dq product on the bf16 pipe (matrix mode 0), if it can run there
-  bool dq_bx3 = false;
-  if (pd0 && g_matrix_mode == 0 && ws && ws_bytes >= lay.total && bx3_rows_worth(N)) {
+  const bool ws_ok = ws && ws_bytes >= lay.total;
+  if (ppd && !ws_ok) return MMS_ERR_WORKSPACE;
+  const bool bx3_ok = bx3_pipe_ok(g_matrix_mode, ws, ws_bytes, lay.total, N);
+  char* base = static_cast<char*>(ws);
+
+  // The dq product is planned first: the dW reduction's launch also builds the form of W that dq reads -- the split
+  // image of W^T (bf16 pipe) or W^T itself (panel kernel) -- when dq will take that pipe.  dq_img / dq_wt: where, or null.
+  Bx3Args bq{};                                 // dq_j = dT_j * (W a_j)   (:88, NoTrans, beta 0): B(k, n) = W[n][k]
+  bx3_u4* dq_img = nullptr;
+  if (pd0 && bx3_ok) {
     bq.M = N; bq.N = K1; bq.K = K2; bq.A = a; bq.lda = K2; bq.C = dq; bq.ldc = K1; bq.rowscale = top_diff; bq.stream_c = 1;
-    if (pd1 && qw && (K2 & 3) == 0 && K2 >= 8) {
+    bq.img = simmatrix_img(ws, lay);
+    if (pd1 && qw && (K2 & 3) == 0 && K2 >= 8) {  // da rides in the dq launch's loader waves, if the kernel takes it so
       bq.side_in = qw; bq.side_out = da; bq.side_scale = top_diff; bq.side_ld = K2; bq.side_cols = K2;
+      if (!bx3_eligible(bq)) { bq.side_in = nullptr; bq.side_out = nullptr; bq.side_scale = nullptr; }
     }
-    dq_bx3 = bx3_eligible(bq);
-    if (!dq_bx3 && bq.side_in) { bq.side_in = nullptr; bq.side_out = nullptr; bq.side_scale = nullptr; dq_bx3 = bx3_eligible(bq); }
+    if (bx3_eligible(bq)) dq_img = simmatrix_img(ws, lay);
   }
-  if (pd0 && Wt_ws && !dq_bx3) {
-    PanelArgs pq = panel_args(N, K1, K2, a, K2, Wt_ws, K1, dq, K1);
+  PanelArgs pq{};                               // the same product on the panel kernel: B(k, n) = Wt[k][n]
+  float* dq_wt = nullptr;
+  if (pd0 && !dq_img && ws_ok) {
+    float* Wt = reinterpret_cast<float*>(base + lay.wt_off);
+    pq = panel_args(N, K1, K2, a, K2, Wt, K1, dq, K1);
     pq.rowscale = top_diff;
-    dq_panel = panel_eligible(pq, true);
+    pq.stream_c = 1;                            // read next by another layer, not by this call
+    if (panel_eligible(pq, true)) dq_wt = Wt;
   }
+
+  // dW += sum_i dT_i q_i a_i^T = Q^T (diag(dT) A)   (:73-80, accumulating)
+  bool w_form_built = false;                    // the dW reduction's launch has produced what dq_img / dq_wt points to
   if (ppd) {
-    if (!ws || ws_bytes < lay.total) return MMS_ERR_WORKSPACE;
-    char* base = static_cast<char*>(ws);
-    float* U = reinterpret_cast<float*>(base + lay.u_off);
     float* part = reinterpret_cast<float*>(base + lay.part_off);
-    // dW += sum_i dT_i q_i a_i^T = Q^T (diag(dT) A)   (:73-80, accumulating)
-    bool dw_done = false;
-    if (g_matrix_mode == 0 && bx3_rows_worth(N)) {
-      // on the bf16 pipe: both operands split on the fly (bx3_gemm.h, bx3_tn_kernel), slabs summed in chunk order
-      Bx3TnArgs t{};
-      t.M = K1; t.N = K2; t.K = N; t.A = q; t.lda = K1; t.B = a; t.ldb = K2; t.kscale = top_diff; t.C = part;
-      t.c_ks = (long long)K1 * K2;
-      t.nchunks = bx3_tn_pick_chunks(N, bx3_tn_quads(K1, K2), &t.kchunk);
-      if (bx3_tn_eligible(t)) {
-        bx3_tn_launch(t, s);
-        const unsigned rb = ew_blocks((long long)K1 * K2);
-        if (dq_bx3) {                            // the image of W^T for the dq product rides in the reduction's launch
-          bx3_u4* img = reinterpret_cast<bx3_u4*>(static_cast<char*>(ws) + lay.img_off);
-          const Bx3SplitArgs sp = bx3_split_args(W, 1, K2, K2, K1, img);
-          hipLaunchKernelGGL(splitk_reduce_split_kernel, dim3(rb + bx3_split_blocks(sp)), dim3(256), 0, s, part, t.nchunks,
-                             (long long)K1 * K2, dW, 1, (int)rb, sp);
-          wt_done = true;
-        } else {
-          hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb), dim3(256), 0, s, part, t.nchunks, (long long)K1 * K2, dW, 1);
-        }
-        dw_done = true;
+    if (bx3_ok && bx3_dw(bx3_dw_args(N, K1, K2, q, a, 0, top_diff, part), dW, W, dq_img, s)) {
+      w_form_built = dq_img != nullptr;
+    } else if (panel_dw(panel_dw_args(N, K1, K2, q, a, top_diff, part), dW, W, dq_wt, s)) {
+      w_form_built = dq_wt != nullptr;
+    } else {
+      GemmArgs g = gemm_args(K1, K2, N, q, 1, K1, a, K2, 1, part, K2);
+      g.ksplit = lay.ksplit; g.kchunk = lay.kchunk; g.c_ks = (long long)K1 * K2;
+      g.bkscale = top_diff;                       // B(k = pair, j) = dT_k * a_k[j], scaled on load
+      if (!gemm_fast_variant(g)) {                // generic kernel: materialise U = diag(dT) A first
+        float* U = reinterpret_cast<float*>(base + lay.u_off);
+        hipLaunchKernelGGL(rowscale_kernel, dim3(ew_blocks((long long)N * K2)), dim3(256), 0, s, a, top_diff, U, (long long)N, K2);
+        g.B = U;
+        g.bkscale = nullptr;
       }
-    }
-    if (!dw_done) {
-      PanelArgs p = panel_args(K1, K2, N, q, K1, a, K2, part, K2);
-      p.kscale = top_diff;                      // A(i, k = pair) = q_k[i] * dT_k
-      p.ksplit = panel_pick_ksplit(p.row_blocks, 1, N, &p.kchunk);
-      p.c_ks = (long long)K1 * K2;
-      if (p.ksplit > 1 && panel_eligible(p, false)) {
-        panel_launch(p, false, s);
-        const unsigned rb = ew_blocks((long long)K1 * K2);
-        if (dq_panel) {
-          const unsigned tb = (unsigned)(((K2 + 31) / 32) * ((K1 + 31) / 32));
-          hipLaunchKernelGGL(splitk_reduce_transpose_kernel, dim3(rb + tb), dim3(256), 0, s, part, p.ksplit,
-                             (long long)K1 * K2, dW, 1, (int)rb, W, Wt_ws, K1, K2);
-          wt_done = true;
-        } else {
-          hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb), dim3(256), 0, s, part, p.ksplit, (long long)K1 * K2, dW, 1);
-        }
-        dw_done = true;
-      }
-    }
-    if (!dw_done) {
-    GemmArgs g = gemm_args(K1, K2, N, q, 1, K1, a, K2, 1, part, K2);
-    g.ksplit = lay.ksplit; g.kchunk = lay.kchunk; g.c_ks = (long long)K1 * K2;
-    g.bkscale = top_diff;                       // B(k = pair, j) = dT_k * a_k[j], scaled on load
-    if (!gemm_fast_variant(g)) {                // generic kernel: materialise U = diag(dT) A first
-      hipLaunchKernelGGL(rowscale_kernel, dim3(ew_blocks((long long)N * K2)), dim3(256), 0, s, a,
-                         top_diff, U, (long long)N, K2);
-      g.B = U;
-      g.bkscale = nullptr;
-    }
-    gemm_launch(g, 1, s);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(ew_blocks((long long)K1 * K2)), dim3(256), 0, s,
-                       part, lay.ksplit, (long long)K1 * K2, dW, 1);
+      gemm_launch(g, 1, s);
+      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(ew_blocks(g.c_ks)), dim3(256), 0, s, part, lay.ksplit, g.c_ks, dW, 1);
     }
   }
-  bool da_done = false;
-  if (pd0 && dq_bx3) {
-    // dq_j = dT_j * (W a_j)   (:88, NoTrans, beta 0): B(k, n) = W[n][k], split straight from W's rows
-    bx3_u4* img = reinterpret_cast<bx3_u4*>(static_cast<char*>(ws) + lay.img_off);
-    bq.img = img;
-    if (!wt_done) bx3_split_b(W, 1, K2, K2, K1, img, s);
+
+  // dq
+  bool da_written = false;                      // by the dq launch's side job
+  if (dq_img) {
+    if (!w_form_built) bx3_split_b(W, 1, K2, K2, K1, dq_img, s);     // split straight from W's rows
     bx3_launch(bq, s);
-    da_done = bq.side_in != nullptr;
+    da_written = bq.side_in != nullptr;
   } else if (pd0) {
-    // dq_j = dT_j * (W a_j)   (:88, NoTrans, beta 0)
-    float* Wt = Wt_ws;
-    PanelArgs p = panel_args(N, K1, K2, a, K2, Wt, K1, dq, K1);     // B(k, n) = W[n][k] = Wt[k][n]
-    p.rowscale = top_diff;
-    p.stream_c = 1;                             // read next by another layer, not by this call
-    if (pd1 && qw && K2 <= 304) {
+    if (dq_wt && pd1 && qw && K2 <= 304) {
       // da_j = dT_j * (row j of the forward's Q.W): a streaming pass with no arithmetic to speak of, carried
       // by this product's loader waves while its compute waves keep the matrix pipe busy
-      p.side_in = qw; p.side_out = da; p.side_scale = top_diff; p.side_ld = K2; p.side_cols = K2;
+      pq.side_in = qw; pq.side_out = da; pq.side_scale = top_diff; pq.side_ld = K2; pq.side_cols = K2;
     }
-    if (Wt && panel_eligible(p, true)) {
-      if (!wt_done)
-        hipLaunchKernelGGL(pg_transpose_kernel, dim3((K2 + 31) / 32, (K1 + 31) / 32), dim3(256), 0, s, W, Wt, K1, K2);
-      panel_launch(p, true, s);
-      da_done = p.side_in != nullptr;
+    if (dq_wt && panel_eligible(pq, true)) {
+      if (!w_form_built)
+        hipLaunchKernelGGL(pg_transpose_kernel, dim3((K2 + 31) / 32, (K1 + 31) / 32), dim3(256), 0, s, W, dq_wt, K1, K2);
+      panel_launch(pq, true, s);
+      da_written = pq.side_in != nullptr;
     } else {
       GemmArgs g = gemm_args(N, K1, K2, a, K2, 1, W, 1, K2, dq, K1);
       g.rowscale = top_diff;
@@ -1798,44 +1776,21 @@ int simmatrix_backward(int N, int K1, int K2, const float* q, const float* a, co
       gemm_launch(g, 1, s);
     }
   }
-  if (da_done) {
-    // written by the dq launch
-  } else if (pd1 && qw) {
-    if ((K2 & 3) == 0 && aligned16(qw) && aligned16(da)) {
+
+  // da_j = dT_j * (W^T q_j)   (:88, Trans, beta 0)
+  if (!pd1 || da_written) {
+    // not wanted, or written by the dq launch
+  } else if (qw) {
+    if ((K2 & 3) == 0 && aligned16(qw) && aligned16(da))
       hipLaunchKernelGGL(rowscale4_kernel, dim3(ew_blocks((long long)N * (K2 / 4))), dim3(256), 0, s,
-                         reinterpret_cast<const float4*>(qw), top_diff, reinterpret_cast<float4*>(da),
-                         (long long)N, K2 / 4);
-    } else {
-      const float* x = qw;
-      hipLaunchKernelGGL(rowscale_inplace_ok_kernel, dim3(ew_blocks((long long)N * K2)), dim3(256), 0, s, x,
-                         top_diff, da, (long long)N, K2);
-    }
-  } else if (pd1 && g_matrix_mode == 0 && ws && ws_bytes >= lay.total && bx3_rows_worth(N) && [&] {
-               // da_j = dT_j * (W^T q_j)   (:88, Trans, beta 0): the forward's product (same kernel, same image, same
-               // k order: the bits of the cached form above), scaled in its epilogue
-               Bx3Args b{};
-               b.M = N; b.N = K2; b.K = K1; b.A = q; b.lda = K1; b.C = da; b.ldc = K2; b.rowscale = top_diff; b.stream_c = 1;
-               if (!bx3_eligible(b)) return false;
-               bx3_u4* img = reinterpret_cast<bx3_u4*>(static_cast<char*>(ws) + lay.img_off);
-               b.img = img;
-               bx3_split_b(W, K2, 1, K1, K2, img, s);
-               bx3_launch(b, s);
-               return true;
-             }()) {
-    // written by the launch above
-  } else if (pd1) {
-    // da_j = dT_j * (W^T q_j)   (:88, Trans, beta 0)
-    PanelArgs p = panel_args(N, K2, K1, q, K1, W, K2, da, K2);
-    p.rowscale = top_diff;
-    p.stream_c = 1;                             // read next by another layer, not by this call
-    if (panel_eligible(p, true)) {
-      panel_launch(p, true, s);
-    } else {
-      GemmArgs g = gemm_args(N, K2, K1, q, K1, 1, W, K2, 1, da, K2);
-      g.rowscale = top_diff;
-      g.stream_c = 1;
-      gemm_launch(g, 1, s);
-    }
+                         reinterpret_cast<const float4*>(qw), top_diff, reinterpret_cast<float4*>(da), (long long)N, K2 / 4);
+    else
+      hipLaunchKernelGGL(rowscale_inplace_ok_kernel, dim3(ew_blocks((long long)N * K2)), dim3(256), 0, s, qw, top_diff, da,
+                         (long long)N, K2);
+  } else if (!bx3_ok || !bx3_xw(N, K1, K2, q, 0, W, simmatrix_img(ws, lay), da, nullptr, nullptr, nullptr, top_diff, s)) {
+    // (on the bf16 pipe it is the forward's product -- same kernel, same image, same k order: the bits of the cached
+    // form above -- scaled in its epilogue)
+    fp32_xw(N, K1, K2, q, W, da, nullptr, nullptr, nullptr, top_diff, s);
   }
   return launch_status();
 }
@@ -1849,36 +1804,30 @@ int simmatrix_backward(int N, int K1, int K2, const float* q, const float* a, co
 //   dq = B W^T   (the Split sum of the two branches' dq_i = g W a_i, :88 NoTrans, as one product);
 //   dW += Q^T B  (the two branches' sum_i g_i q_i a_i^T, :73-80, as one split-K product).
 // Neither P nor the (N, 1) score gradients reach HBM.
-int triplet_loss_from_terms(const float* terms, int N, float* loss, hipStream_t s);
-int pairrank_hinge_mode();
-
 struct TripSimWs {
   size_t b_off, terms_off, ones_off, wt_off, part_off, img_off, total;
-  int ksplit, kchunk;
 };
 static TripSimWs tripsim_ws(int N, int K1, int K2) {
   TripSimWs w{};
-  w.ksplit = panel_pick_ksplit((K1 + 63) / 64, 1, N, &w.kchunk);
   size_t o = 0;
   auto take = [&](size_t b) { size_t at = o; o += round_up(b, 256); return at; };
   w.b_off = take((size_t)N * K2 * sizeof(float));
   w.terms_off = take((size_t)N * sizeof(float));
   w.ones_off = take((size_t)N * sizeof(float));
   w.wt_off = take((size_t)K1 * K2 * sizeof(float));
-  int tchunk = 0;
-  const int tsplit = bx3_tn_pick_chunks(N, bx3_tn_quads(K1, K2), &tchunk);   // the bf16-pipe dW kernel's split (if it runs)
-  const int slabs = tsplit > w.ksplit ? tsplit : (w.ksplit > 0 ? w.ksplit : 1);
+  int chunk = 0;
+  const int psplit = panel_dw_split(N, K1, &chunk), tsplit = bx3_dw_split(N, K1, K2, &chunk);
+  const int slabs = tsplit > psplit ? tsplit : (psplit > 0 ? psplit : 1);
   w.part_off = take((size_t)slabs * K1 * K2 * sizeof(float));
   w.img_off = take(bx3_image_bytes(K1, K2));                                  // the split image of W^T (dq on the bf16 pipe)
   w.total = o;
   return w;
 }
-size_t triplet_simmatrix_workspace_bytes(int N, int K1, int K2) { return tripsim_ws(N, K1, K2).total; }
 
-// MMS_ERR_UNSUPPORTED when the shapes are outside the panel kernel (the caller then runs the layers one by one)
-int triplet_simmatrix_step(int N, int K1, int K2, float margin, float loss_weight, const float* q, const float* ap,
-                           const float* an, const float* y, const float* W, float* s_pos, float* s_neg, float* loss,
-                           float* dq, float* dap, float* dan, float* dW, void* ws, size_t ws_bytes, hipStream_t s) {
+// MMS_ERR_UNSUPPORTED when the shapes are outside the panel kernel (triplet_simmatrix_step then runs the layers one by one)
+static int tripsim_fused(int N, int K1, int K2, float margin, float loss_weight, const float* q, const float* ap,
+                         const float* an, const float* y, const float* W, float* s_pos, float* s_neg, float* loss,
+                         float* dq, float* dap, float* dan, float* dW, void* ws, size_t ws_bytes, hipStream_t s) {
   const TripSimWs lay = tripsim_ws(N, K1, K2);
   if (!ws || ws_bytes < lay.total) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(ws);
@@ -1897,24 +1846,18 @@ int triplet_simmatrix_step(int N, int K1, int K2, float margin, float loss_weigh
   // dq = B W^T  (B(k, n) = W[n][k] = Wt[k][n])
   PanelArgs p2 = panel_args(N, K1, K2, B, K2, Wt, K1, dq, K1);
   p2.stream_c = 1;
-  // dW += Q^T B, split over the pairs
-  PanelArgs p3 = panel_args(K1, K2, N, q, K1, B, K2, part, K2);
-  p3.kscale = ones;
-  p3.ksplit = lay.ksplit; p3.kchunk = lay.kchunk; p3.c_ks = (long long)K1 * K2;
-  if (!panel_eligible(p1, true) || !panel_eligible(p2, true) || p3.ksplit <= 1 || !panel_eligible(p3, false))
-    return MMS_ERR_UNSUPPORTED;
-  // (the ones are the fp32 split-K kernel's k-scale; the bf16-pipe dW kernel takes "no scale" as such)
-  Bx3TnArgs t{};
+  // dW += Q^T B, split over the pairs (the ones are the fp32 split-K kernel's k-scale; the bf16-pipe kernel takes "no
+  // scale" as such)
+  const PanelArgs p3 = panel_dw_args(N, K1, K2, q, B, ones, part);
+  if (!panel_eligible(p1, true) || !panel_eligible(p2, true) || !panel_dw_eligible(p3)) return MMS_ERR_UNSUPPORTED;
+  // The two backward products on the bf16 pipe (matrix mode 0; bx3_gemm.h): dW += Q^T B from both operands split on the
+  // fly, dq = B W^T with the image of W^T built in the reduction's launch.  (The forward stays on the fp32 pipe: its
+  // epilogue needs whole rows of Q W in one workgroup, the bf16 kernel's workgroups own half a row each.)
+  const Bx3TnArgs t = bx3_dw_args(N, K1, K2, q, B, 0, nullptr, part);
+  bx3_u4* img = reinterpret_cast<bx3_u4*>(base + lay.img_off);
   Bx3Args bq{};
-  bool back_bx3 = false;
-  if (g_matrix_mode == 0 && bx3_rows_worth(N)) {
-    t.M = K1; t.N = K2; t.K = N; t.A = q; t.lda = K1; t.B = B; t.ldb = K2; t.kscale = nullptr; t.C = part;
-    t.c_ks = (long long)K1 * K2;
-    t.nchunks = bx3_tn_pick_chunks(N, bx3_tn_quads(K1, K2), &t.kchunk);
-    bq.M = N; bq.N = K1; bq.K = K2; bq.A = B; bq.lda = K2; bq.C = dq; bq.ldc = K1; bq.stream_c = 1;
-    bq.img = reinterpret_cast<bx3_u4*>(base + lay.img_off);
-    back_bx3 = bx3_tn_eligible(t) && bx3_eligible(bq);
-  }
+  bq.M = N; bq.N = K1; bq.K = K2; bq.A = B; bq.lda = K2; bq.C = dq; bq.ldc = K1; bq.stream_c = 1; bq.img = img;
+  const bool back_bx3 = bx3_pipe_ok(g_matrix_mode, ws, ws_bytes, lay.total, N) && bx3_tn_eligible(t) && bx3_eligible(bq);
   if (!back_bx3 &&
       hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ones), 0x3f800000, (size_t)N, s) != hipSuccess) return MMS_ERR_LAUNCH;
   panel_launch(p1, true, s);
@@ -1922,26 +1865,59 @@ int triplet_simmatrix_step(int N, int K1, int K2, float margin, float loss_weigh
     const int rc = triplet_loss_from_terms(terms, N, loss, s);
     if (rc != MMS_OK) return rc;
   }
-  // The two backward products on the bf16 pipe (matrix mode 0; bx3_gemm.h): dW += Q^T B from both operands split on the
-  // fly, dq = B W^T with the image of W^T built in the reduction's launch.  (The forward stays on the fp32 pipe: its
-  // epilogue needs whole rows of Q W in one workgroup, the bf16 kernel's workgroups own half a row each.)
   if (back_bx3) {
-    bx3_tn_launch(t, s);
-    const unsigned rb = ew_blocks((long long)K1 * K2);
-    const Bx3SplitArgs sp = bx3_split_args(W, 1, K2, K2, K1, const_cast<bx3_u4*>(bq.img));
-    hipLaunchKernelGGL(splitk_reduce_split_kernel, dim3(rb + bx3_split_blocks(sp)), dim3(256), 0, s, part, t.nchunks,
-                       (long long)K1 * K2, dW, 1, (int)rb, sp);
+    bx3_dw(t, dW, W, img, s);
     bx3_launch(bq, s);
-    return launch_status();
+  } else {
+    panel_dw(p3, dW, W, Wt, s);
+    panel_launch(p2, true, s);
   }
-  panel_launch(p3, false, s);
-  {
-    const unsigned rb = ew_blocks((long long)K1 * K2), tb = (unsigned)(((K2 + 31) / 32) * ((K1 + 31) / 32));
-    hipLaunchKernelGGL(splitk_reduce_transpose_kernel, dim3(rb + tb), dim3(256), 0, s, part, p3.ksplit,
-                       (long long)K1 * K2, dW, 1, (int)rb, W, Wt, K1, K2);
-  }
-  panel_launch(p2, true, s);
   return launch_status();
+}
+
+// The layers one by one, inside the call, for the shapes the fused route refuses:
+// SimMatrix x 2 -> PairRankLoss -> PairRankLoss backward -> SimMatrix backward x 2 -> Split sum
+struct TripSimSlow {
+  size_t qwp, qwn, ord, sim, gsp, gsn, dq2, lossf, prws, smws, total;
+};
+static TripSimSlow tripsim_slow_layout(int N, int K1, int K2) {
+  TripSimSlow w{};
+  size_t o = 0;
+  auto take = [&](size_t b) { size_t at = o; o += round_up(b, 256); return at; };
+  w.qwp = take((size_t)N * K2 * 4); w.qwn = take((size_t)N * K2 * 4);
+  w.ord = take((size_t)N * 4); w.sim = take((size_t)N * 4); w.gsp = take((size_t)N * 4); w.gsn = take((size_t)N * 4);
+  w.dq2 = take((size_t)N * K1 * 4); w.lossf = take(256);
+  w.prws = take(pairrank_workspace_bytes(N)); w.smws = take(simmatrix_workspace_bytes(N, K1, K2));
+  w.total = o;
+  return w;
+}
+size_t triplet_simmatrix_workspace_bytes(int N, int K1, int K2) {
+  const size_t fast = tripsim_ws(N, K1, K2).total, slow = tripsim_slow_layout(N, K1, K2).total;
+  return fast > slow ? fast : slow;
+}
+
+int triplet_simmatrix_step(int N, int K1, int K2, float margin, float loss_weight, const float* q, const float* ap,
+                           const float* an, const float* y, const float* W, float* s_pos, float* s_neg, float* loss,
+                           float* dq, float* dap, float* dan, float* dW, void* ws, size_t ws_bytes, hipStream_t s) {
+  const int rc = tripsim_fused(N, K1, K2, margin, loss_weight, q, ap, an, y, W, s_pos, s_neg, loss, dq, dap, dan, dW, ws,
+                               ws_bytes, s);
+  if (rc != MMS_ERR_UNSUPPORTED) return rc;
+  const TripSimSlow lay = tripsim_slow_layout(N, K1, K2);
+  if (ws_bytes < lay.total) return MMS_ERR_WORKSPACE;
+  char* base = static_cast<char*>(ws);
+  auto f = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+  const size_t smb = simmatrix_workspace_bytes(N, K1, K2);
+  int r = simmatrix_forward(N, K1, K2, q, ap, W, s_pos, f(lay.qwp), s, nullptr);
+  if (r == MMS_OK) r = simmatrix_forward(N, K1, K2, q, an, W, s_neg, f(lay.qwn), s, nullptr);
+  if (r == MMS_OK) r = pairrank_forward(N, margin, s_pos, s_neg, y, f(lay.ord), f(lay.sim), loss ? loss : f(lay.lossf),
+                                       base + lay.prws, pairrank_workspace_bytes(N), s);
+  if (r == MMS_OK) r = pairrank_backward(N, loss_weight, y, f(lay.ord), f(lay.sim), f(lay.gsp), f(lay.gsn), s);
+  if (r == MMS_OK) r = simmatrix_backward(N, K1, K2, q, ap, W, f(lay.gsp), 1, 1, 1, dq, dap, dW, f(lay.qwp), base + lay.smws, smb, s);
+  if (r == MMS_OK) r = simmatrix_backward(N, K1, K2, q, an, W, f(lay.gsn), 1, 1, 1, f(lay.dq2), dan, dW, f(lay.qwn),
+                                         base + lay.smws, smb, s);
+  if (r != MMS_OK) return r;
+  const float* two[2] = {dq, f(lay.dq2)};
+  return split_sum(N * K1, 2, two, dq, s);                      // Split: pos + neg, in place on pos
 }
 
 }  // namespace mms

@@ -19,7 +19,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "mms_common.h"
+#include "mms_internal.h"
 
 namespace mms {
 

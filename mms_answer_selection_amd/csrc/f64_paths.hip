@@ -15,7 +15,7 @@
 //   * cosine, bilinear, SimMatrix: k-ascending dot products (one legal BLAS
 //     order), compared at 1e-12 relative in the tests.
 // Same entry-point semantics as the _f32 functions of include/mms.h.
-#include "mms_common.h"
+#include "mms_internal.h"
 
 namespace mms {
 namespace {

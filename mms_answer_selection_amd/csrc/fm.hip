@@ -14,7 +14,7 @@
 // form of euclid_rows_lanechain_f16_kernel (simcross_elementwise.hip) -- exact by construction, no speculation.
 #include <limits.h>
 
-#include "mms_common.h"
+#include "mms_internal.h"
 
 namespace mms {
 namespace {

@@ -1,127 +1,6 @@
 // csrc/mms_abi.hip -- extern "C" entry points declared in include/mms.h:
 // argument validation and dispatch only; kernels live in the sibling files.
-#include "mms_common.h"
-
-namespace mms {
-// simcross_elementwise.hip
-int simcross_elementwise_forward(int mode, int N, int W1, int W2, int D, const float* q,
-                                 const float* a, float* top, float* norm0, float* norm1,
-                                 hipStream_t s);
-int simcross_elementwise_backward(int mode, int N, int W1, int W2, int D, const float* q,
-                                  const float* a, const float* top, const float* top_diff,
-                                  const float* norm0, const float* norm1, float* dq, float* da,
-                                  hipStream_t s);
-int simcross_elementwise_forward_backward(int mode, int N, int W1, int W2, int D, const float* q,
-                                          const float* a, const float* top_diff, float* top,
-                                          float* norm0, float* norm1, float* dq, float* da,
-                                          hipStream_t s);
-int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff,
-                             float* top, void* dq, void* da, bool bwd, hipStream_t s);
-int simcross_cosine_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top,
-                             float* norm0, float* norm1, void* dq, void* da, bool bwd, hipStream_t s);
-// bilinear.hip
-size_t bilinear_workspace_bytes(int N, int W1, int W2, int D, int M);
-int bilinear_forward(int N, int W1, int W2, int D, int M, const float* q, const float* a,
-                     const float* W, const float* bias, float* top, void* ws, size_t ws_bytes,
-                     hipStream_t s);
-int bilinear_backward(int N, int W1, int W2, int D, int M, const float* q, const float* a,
-                      const float* W, int bias_term, const float* top_diff, float* dq, float* da,
-                      float* dW, float* dbias, void* ws, size_t ws_bytes, hipStream_t s);
-int embed_bilinear_forward(int N, int W1, int W2, int D, int M, int K, const float* index_q,
-                           const float* index_a, const float* table, const float* embed_bias, const float* W,
-                           const float* bias, float* top, hipStream_t s);
-size_t simmatrix_workspace_bytes(int N, int K1, int K2);
-int simmatrix_forward(int N, int K1, int K2, const float* q, const float* a, const float* W,
-                      float* top, float* qw, hipStream_t s, const float* rd_bias, void* ws = nullptr, size_t ws_bytes = 0);
-int set_matrix_mode(int mode);
-int get_matrix_mode();
-int simmatrix_forward_f16(int N, int K1, int K2, const void* q, const void* a, const float* W, float* top, void* ws,
-                          size_t ws_bytes, hipStream_t s);
-int simmatrix_forward_train_f16(int N, int K1, int K2, const void* q, const void* a, const float* W, float* top, float* qw,
-                                void* ws, size_t ws_bytes, hipStream_t s);
-int simmatrix_backward_f16(int N, int K1, int K2, const void* q, const void* a, const float* W, const float* qw,
-                           const float* top_diff, void* dq, void* da, float* dW, void* ws, size_t ws_bytes, hipStream_t s);
-int embed_simcross_forward(int mode, int N, int W1, int W2, int D, int K, const float* index_q,
-                           const float* index_a, const float* weight, const float* embed_bias, float* top,
-                           float* norm0, float* norm1, hipStream_t s);
-int simmatrix_backward(int N, int K1, int K2, const float* q, const float* a, const float* W,
-                       const float* top_diff, int ppd, int pd0, int pd1, float* dq, float* da,
-                       float* dW, const float* qw, void* ws, size_t ws_bytes, hipStream_t s);
-size_t triplet_simmatrix_workspace_bytes(int N, int K1, int K2);
-int triplet_simmatrix_step(int N, int K1, int K2, float margin, float loss_weight, const float* q, const float* ap,
-                           const float* an, const float* y, const float* W, float* s_pos, float* s_neg, float* loss,
-                           float* dq, float* dap, float* dan, float* dW, void* ws, size_t ws_bytes, hipStream_t s);
-// pairrank.hip
-size_t pairrank_workspace_bytes(int count);
-int pairrank_forward(int count, float margin, const float* a, const float* b, const float* y,
-                     float* ordered, float* similar, float* loss, void* ws, size_t ws_bytes,
-                     hipStream_t s);
-int pairrank_backward(int count, float top_diff, const float* y, const float* ordered,
-                      const float* similar, float* da, float* db, hipStream_t s);
-size_t triplet_workspace_bytes(int N);
-int triplet_workspace_init(void* ws, size_t ws_bytes, hipStream_t s);
-int triplet_cosine_step(int N, int D, float margin, float loss_weight, const float* q, const float* ap,
-                        const float* an, const float* y, float* s_pos, float* s_neg, float* norm_q,
-                        float* norm_pos, float* norm_neg, float* loss, float* dq, float* dap, float* dan,
-                        void* ws, size_t ws_bytes, hipStream_t s);
-int triplet_euclid_step(int N, int D, float margin, float loss_weight, const float* q,
-                        const float* ap, const float* an, const float* y, float* s_pos,
-                        float* s_neg, float* loss, float* dq, float* dap, float* dan, void* ws,
-                        size_t ws_bytes, hipStream_t s);
-// ranking.hip
-size_t rank_workspace_bytes(int n);
-int rank_map_mrr(int n, int fixed_axis, const float* prob, const float* label, const float* group,
-                 float* map_out, float* mrr_out, int* effective, void* ws, size_t ws_bytes,
-                 hipStream_t s);
-int rank_auc(int n, int dim, int fixed_axis, int inner, const float* prob, const float* label, int has_ignore,
-             int ignore_label, float* auc_out, void* ws, size_t ws_bytes, hipStream_t s);
-int rank_accuracy(int count, const float* a, const float* b, const float* label, float* out,
-                  void* ws, size_t ws_bytes, hipStream_t s);
-// embed.hip
-size_t embed_workspace_bytes(int M, int N);
-int embed_forward(int M, int N, int K, const float* index, const float* weight, const float* bias,
-                  float* top, hipStream_t s);
-int embed_backward(int M, int N, int K, const float* index, const float* top_diff,
-                   float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes, hipStream_t s);
-int embed_backward_pair(int M0, int M1, int N, int K, const float* index0, const float* top_diff0, const float* index1,
-                        const float* top_diff1, float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes,
-                        hipStream_t s, int index_ready);
-bool embed_pair_index_supported(int M0, int M1, int K);
-int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const float* index1, const float* weight,
-                       const float* bias, float* top0, float* top1, void* index_ws, size_t index_ws_bytes, hipStream_t s);
-int euclid_backward_mode();
-void set_euclid_backward_mode(int m);
-int pairrank_hinge_mode();
-void set_pairrank_hinge_mode(int m);
-int triplet_finish_mode();
-void set_triplet_finish_mode(int m);
-int loss_sum_mode();
-void set_loss_sum_mode(int m);
-int rank_tie_mode();
-void set_rank_tie_mode(int m);
-int f16_distance_mode();
-void set_f16_distance_mode(int m);
-// f64_paths.hip
-size_t simcross_workspace_bytes_f64(int mode, int N, int W1, int W2, int D, int M);
-int simcross_forward_f64(int mode, int N, int W1, int W2, int D, int M, const double* q, const double* a,
-                         const double* W, const double* bias, double* top, double* norm0, double* norm1,
-                         void* ws, size_t ws_bytes, hipStream_t s);
-int simcross_backward_f64(int mode, int N, int W1, int W2, int D, int M, const double* q, const double* a,
-                          const double* W, int bias_term, const double* top, const double* top_diff,
-                          const double* norm0, const double* norm1, int pd0, int pd1, double* dq, double* da,
-                          double* dW, double* dbias, void* ws, size_t ws_bytes, hipStream_t s);
-int simmatrix_forward_f64(int N, int K1, int K2, const double* q, const double* a, const double* W,
-                          double* top, double* scratch, hipStream_t s);
-int simmatrix_backward_f64(int N, int K1, int K2, const double* q, const double* a, const double* W,
-                           const double* top_diff, int ppd, int pd0, int pd1, double* dq, double* da,
-                           double* dW, hipStream_t s);
-int pairrank_forward_f64(int count, double margin, const double* a, const double* b, const double* y,
-                         double* ordered, double* similar, double* loss, hipStream_t s);
-int pairrank_backward_f64(int count, double top_diff, const double* y, const double* ordered,
-                          const double* similar, double* da, double* db, hipStream_t s);
-int feed_gather_rows(int rows, int row_elems, int src_rows, const float* src, const int* perm, int first,
-                     float* dst, hipStream_t s);
-}  // namespace mms
+#include "mms_internal.h"
 
 using namespace mms;
 
@@ -169,6 +48,17 @@ __global__ __launch_bounds__(256) void split_sum_kernel(int n, int k, SplitPtrs 
     for (int j = carry ? 0 : 1; j < k; ++j) v = v + s.p[j][i];
     out[i] = v;
   }
+}
+// bottom_diff = the sum of ntop >= 1 top diffs of count > 0 elements, in index order (Split's backward)
+int split_sum(int count, int ntop, const float* const* top_diffs, float* bottom_diff, hipStream_t s) {
+  const unsigned grid = (unsigned)((count + 255) / 256 < 2048 ? (count + 255) / 256 : 2048);
+  for (int first = 0; first < ntop; first += 8) {
+    SplitPtrs sp{};
+    const int k = ntop - first < 8 ? ntop - first : 8;
+    for (int j = 0; j < k; ++j) sp.p[j] = top_diffs[first + j];
+    hipLaunchKernelGGL(split_sum_kernel, dim3(grid), dim3(256), 0, s, count, k, sp, first > 0 ? 1 : 0, bottom_diff);
+  }
+  return launch_status();
 }
 }  // namespace mms
 
@@ -434,28 +324,9 @@ int mms_pairrank_backward_f32(int count, float top_diff, const float* y, const f
                            propagate_down1 ? db : nullptr, as_stream(stream));
 }
 
-// ---- fused learned-metric triplet step ----------------------------------------------------------------------------
-namespace {
-struct TripSimSlow {                                  // the layers one by one, inside the call (shapes outside the fast path)
-  size_t qwp, qwn, ord, sim, gsp, gsn, dq2, lossf, prws, smws, total;
-};
-TripSimSlow tripsim_slow_layout(int N, int K1, int K2) {
-  TripSimSlow w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { size_t at = o; o += mms::round_up(b, 256); return at; };
-  w.qwp = take((size_t)N * K2 * 4); w.qwn = take((size_t)N * K2 * 4);
-  w.ord = take((size_t)N * 4); w.sim = take((size_t)N * 4); w.gsp = take((size_t)N * 4); w.gsn = take((size_t)N * 4);
-  w.dq2 = take((size_t)N * K1 * 4); w.lossf = take(256);
-  w.prws = take(mms::pairrank_workspace_bytes(N)); w.smws = take(mms::simmatrix_workspace_bytes(N, K1, K2));
-  w.total = o;
-  return w;
-}
-}  // namespace
-
 size_t mms_triplet_simmatrix_workspace_bytes(int N, int K1, int K2) {
   if (N <= 0 || K1 <= 0 || K2 <= 0) return 0;
-  const size_t fast = mms::triplet_simmatrix_workspace_bytes(N, K1, K2), slow = tripsim_slow_layout(N, K1, K2).total;
-  return fast > slow ? fast : slow;
+  return triplet_simmatrix_workspace_bytes(N, K1, K2);
 }
 
 int mms_triplet_simmatrix_step_f32(int N, int K1, int K2, float margin, float loss_weight, const float* q,
@@ -466,27 +337,9 @@ int mms_triplet_simmatrix_step_f32(int N, int K1, int K2, float margin, float lo
     return MMS_ERR_INVALID_ARG;
   if (!q || !a_pos || !a_neg || !y || !W || !s_pos || !s_neg || !dq || !da_pos || !da_neg || !dW)   // loss may be NULL
     return MMS_ERR_INVALID_ARG;
-  if (!workspace || workspace_bytes < mms_triplet_simmatrix_workspace_bytes(N, K1, K2)) return MMS_ERR_WORKSPACE;
-  hipStream_t s = as_stream(stream);
-  const int rc = mms::triplet_simmatrix_step(N, K1, K2, margin, loss_weight, q, a_pos, a_neg, y, W, s_pos, s_neg, loss,
-                                             dq, da_pos, da_neg, dW, workspace, workspace_bytes, s);
-  if (rc != MMS_ERR_UNSUPPORTED) return rc;
-  // layer by layer: SimMatrix x 2 -> PairRankLoss -> PairRankLoss backward -> SimMatrix backward x 2 -> Split sum
-  const TripSimSlow lay = tripsim_slow_layout(N, K1, K2);
-  char* base = static_cast<char*>(workspace);
-  auto f = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
-  int r = mms::simmatrix_forward(N, K1, K2, q, a_pos, W, s_pos, f(lay.qwp), s, nullptr);
-  if (r == MMS_OK) r = mms::simmatrix_forward(N, K1, K2, q, a_neg, W, s_neg, f(lay.qwn), s, nullptr);
-  if (r == MMS_OK) r = mms::pairrank_forward(N, margin, s_pos, s_neg, y, f(lay.ord), f(lay.sim), loss ? loss : f(lay.lossf),
-                                            base + lay.prws, mms::pairrank_workspace_bytes(N), s);
-  if (r == MMS_OK) r = mms::pairrank_backward(N, loss_weight, y, f(lay.ord), f(lay.sim), f(lay.gsp), f(lay.gsn), s);
-  if (r == MMS_OK) r = mms::simmatrix_backward(N, K1, K2, q, a_pos, W, f(lay.gsp), 1, 1, 1, dq, da_pos, dW, f(lay.qwp),
-                                              base + lay.smws, mms::simmatrix_workspace_bytes(N, K1, K2), s);
-  if (r == MMS_OK) r = mms::simmatrix_backward(N, K1, K2, q, a_neg, W, f(lay.gsn), 1, 1, 1, f(lay.dq2), da_neg, dW, f(lay.qwn),
-                                              base + lay.smws, mms::simmatrix_workspace_bytes(N, K1, K2), s);
-  if (r != MMS_OK) return r;
-  const float* two[2] = {dq, f(lay.dq2)};
-  return mms_split_backward_f32(N * K1, 2, two, dq, stream);
+  if (!workspace || workspace_bytes < triplet_simmatrix_workspace_bytes(N, K1, K2)) return MMS_ERR_WORKSPACE;
+  return triplet_simmatrix_step(N, K1, K2, margin, loss_weight, q, a_pos, a_neg, y, W, s_pos, s_neg, loss, dq, da_pos,
+                                da_neg, dW, workspace, workspace_bytes, as_stream(stream));
 }
 
 size_t mms_triplet_workspace_bytes(int N) { return N > 0 ? triplet_workspace_bytes(N) : 0; }
@@ -646,15 +499,7 @@ int mms_split_backward_f32(int count, int ntop, const float* const* top_diffs, f
   if (count < 0 || ntop < 1 || !top_diffs || (count > 0 && !bottom_diff)) return MMS_ERR_INVALID_ARG;
   for (int i = 0; i < ntop; ++i) if (count > 0 && !top_diffs[i]) return MMS_ERR_INVALID_ARG;
   if (count == 0) return MMS_OK;
-  const unsigned grid = (unsigned)((count + 255) / 256 < 2048 ? (count + 255) / 256 : 2048);
-  for (int first = 0; first < ntop; first += 8) {
-    mms::SplitPtrs s{};
-    const int k = ntop - first < 8 ? ntop - first : 8;
-    for (int j = 0; j < k; ++j) s.p[j] = top_diffs[first + j];
-    hipLaunchKernelGGL(mms::split_sum_kernel, dim3(grid), dim3(256), 0, as_stream(stream), count, k, s, first > 0 ? 1 : 0,
-                       bottom_diff);
-  }
-  return launch_status();
+  return split_sum(count, ntop, top_diffs, bottom_diff, as_stream(stream));
 }
 int mms_dot_f64(int n, const double* x, const double* y, double* out, void* stream) {
   if (n < 0 || !out || (n > 0 && (!x || !y))) return MMS_ERR_INVALID_ARG;

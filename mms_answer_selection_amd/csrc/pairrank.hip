@@ -19,11 +19,9 @@
 #include "cosine_math.h"
 #include "euclid_math.h"
 #include "pairrank_math.h"
-#include "mms_common.h"
+#include "mms_internal.h"
 
 namespace mms {
-
-int euclid_backward_mode();   // simcross_elementwise.hip
 
 // Which comparison gates the hinge term of the backward (include/mms.h: mms_set_pairrank_hinge_mode):
 // the reference's Backward_cpu uses `ordered > 0` (pair_rank_loss_layer.cpp:76), its Backward_gpu kernel
@@ -750,8 +748,6 @@ int triplet_euclid_step(int N, int D, float margin, float loss_weight, const flo
                        loss);
   return launch_status();
 }
-
-int triplet_loss_from_terms(const float* terms, int N, float* loss, hipStream_t s);
 
 // ======================= fused cosine (q, a+, a-) training step =====================
 // SimCross dist_mode 0 on (q,a+) and (q,a-), PairRankLoss on the two score columns and the whole backward in one

@@ -26,7 +26,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "libstdcxx_sort.h"
-#include "mms_common.h"
+#include "mms_internal.h"
 
 namespace mms {
 

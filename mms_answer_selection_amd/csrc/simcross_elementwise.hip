@@ -27,7 +27,7 @@
 
 #include "cosine_math.h"
 #include "euclid_math.h"
-#include "mms_common.h"
+#include "mms_internal.h"
 
 namespace mms {
 
