@@ -688,6 +688,41 @@ int mms_fm_forward_f64(int N, int C, int dim, const double* x, const double* bia
 int mms_fm_backward_f64(int N, int C, int dim, const double* x, const double* top_diff, double* bottom_diff,
                         double* bias_diff, void* stream);
 
+/* EmbedLayer<double> (embed_layer.cpp:135-180): the arguments, errors and M == 0 behaviour of mms_embed_forward_f32 /
+ * mms_embed_backward_f32 with every float* a double* (word ids are doubles: Caffe feeds them as Dtype).  top and
+ * weight_diff carry the bits of the reference's double instantiation (same inverted index, the per-row sums in n
+ * order), bias_diff is BLAS-ordered there: ~1e-12.  Rows move in 16-byte accesses in the forward when N is even and
+ * weight / bias / top are 16-byte aligned.  workspace: mms_embed_workspace_bytes_f64(M, N).  The pair and the fused
+ * Embed calls exist for float only. */
+size_t mms_embed_workspace_bytes_f64(int M, int N);
+int mms_embed_forward_f64(int M, int N, int K, const double* index, const double* weight,
+                          const double* bias, double* top, void* stream);
+int mms_embed_backward_f64(int M, int N, int K, const double* index, const double* top_diff,
+                           double* weight_diff, double* bias_diff, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* MAPLayer / MRRLayer / AUCLayer / RankAccuracyLayer<double>: the arguments and errors of the _f32 calls.  The
+ * reference's comparators take std::pair<float, int> for every Dtype (map_layer.cpp:34, mrr_layer.cpp:33,
+ * auc_layer.cpp:42 -- AUC's vector holds pair<Dtype, int>, std::sort converts its elements for the comparator), so
+ * items are ORDERED by their scores narrowed to float: two doubles that differ below float precision are a tie, to
+ * which mms_set_rank_tie_mode applies as it does to float ties.  Labels and groups are int(x).  The folds
+ * (ap += ++rank / (Dtype)(i + 1), map += ap / rank, mrr += 1.0 / (rank + 1), AUC's sum of integers, the final
+ * divisions) run in double: the bits of the reference's double instantiation.  workspace:
+ * mms_rank_workspace_bytes_f64(n). */
+size_t mms_rank_workspace_bytes_f64(int n);
+int mms_rank_map_mrr_f64(int n, int fixed_axis, const double* prob, const double* label,
+                         const double* group, double* map_out, double* mrr_out,
+                         int* effective_out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int mms_rank_auc_f64(int n, int dim, int fixed_axis, const double* prob, const double* label,
+                     int has_ignore_label, int ignore_label, double* auc_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int mms_rank_auc_nd_f64(int outer, int channels, int inner, int fixed_axis, const double* prob,
+                        const double* label, int has_ignore_label, int ignore_label, double* auc_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int mms_rank_accuracy_f64(int count, const double* a, const double* b, const double* label,
+                          double* acc_out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,14 @@ _SIGNATURES = {
     "mms_rank_auc_f32": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "mms_rank_auc_nd_f32": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "mms_rank_accuracy_f32": (_i, [_i] + [_vp] * 5 + [_sz, _vp]),
+    "mms_rank_workspace_bytes_f64": (_sz, [_i]),
+    "mms_rank_map_mrr_f64": (_i, [_i, _i] + [_vp] * 7 + [_sz, _vp]),
+    "mms_rank_auc_f64": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "mms_rank_auc_nd_f64": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "mms_rank_accuracy_f64": (_i, [_i] + [_vp] * 5 + [_sz, _vp]),
+    "mms_embed_workspace_bytes_f64": (_sz, [_i, _i]),
+    "mms_embed_forward_f64": (_i, [_i, _i, _i] + [_vp] * 5),
+    "mms_embed_backward_f64": (_i, [_i, _i, _i] + [_vp] * 5 + [_sz, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -747,3 +755,68 @@ def fm_backward_f64(x, top_diff, bottom_diff=None, bias_diff=None):
         N, C, dim, _ptr(x, "x", dtype=_D), _ptr(top_diff, "top_diff", dtype=_D),
         _ptr(bottom_diff, "bottom_diff", True, _D), _ptr(bias_diff, "bias_diff", True, _D), _stream()),
         "mms_fm_backward_f64")
+
+
+def embed_forward_f64(index, weight, top, bias=None):
+    M, (K, N) = index.numel(), weight.shape
+    check(lib().mms_embed_forward_f64(M, N, K, _ptr(index, "index", dtype=_D), _ptr(weight, "weight", dtype=_D),
+                                      _ptr(bias, "bias", True, _D), _ptr(top, "top", dtype=_D), _stream()),
+          "mms_embed_forward_f64")
+
+
+def embed_backward_f64(index, top_diff, weight_diff, bias_diff=None, ws=None, shape=None):
+    """weight_diff or bias_diff may be None; `shape` = (K, N) is then needed when weight_diff is None."""
+    K, N = shape if shape is not None else weight_diff.shape
+    M = index.numel()
+    wsp, wsb = (ws or _default_ws).get(lib().mms_embed_workspace_bytes_f64(M, N), index.device)
+    check(lib().mms_embed_backward_f64(M, N, K, _ptr(index, "index", dtype=_D), _ptr(top_diff, "top_diff", dtype=_D),
+                                       _ptr(weight_diff, "weight_diff", True, _D),
+                                       _ptr(bias_diff, "bias_diff", True, _D), wsp, wsb, _stream()),
+          "mms_embed_backward_f64")
+
+
+def rank_map_mrr_f64(prob, label, group, fixed_axis=1, ws=None):
+    """-> (MAP, MRR, effective groups): two numpy float64 scalars and an int."""
+    n = label.numel()
+    wsp, wsb = (ws or _default_ws).get(lib().mms_rank_workspace_bytes_f64(n), prob.device)
+    out = torch.empty(2, dtype=_D, device=prob.device)
+    eff = torch.empty(1, dtype=torch.int32, device=prob.device)
+    check(lib().mms_rank_map_mrr_f64(
+        n, int(fixed_axis), _ptr(prob, "prob", dtype=_D), _ptr(label, "label", dtype=_D), _ptr(group, "group", dtype=_D),
+        out.data_ptr(), out.data_ptr() + 8, eff.data_ptr(), wsp, wsb, _stream()), "mms_rank_map_mrr_f64")
+    o = out.cpu().numpy()
+    return o[0], o[1], int(eff.item())
+
+
+def rank_auc_f64(prob, label, fixed_axis=1, ignore_label=None, ws=None):
+    n = label.numel()
+    wsp, wsb = (ws or _default_ws).get(lib().mms_rank_workspace_bytes_f64(n), prob.device)
+    out = torch.empty(1, dtype=_D, device=prob.device)
+    check(lib().mms_rank_auc_f64(
+        n, int(prob.shape[1]), int(fixed_axis), _ptr(prob, "prob", dtype=_D), _ptr(label, "label", dtype=_D),
+        int(ignore_label is not None), int(ignore_label or 0), out.data_ptr(), wsp, wsb, _stream()),
+        "mms_rank_auc_f64")
+    return out.cpu().numpy()[0]
+
+
+def rank_auc_nd_f64(prob, label, axis=1, fixed_axis=1, ignore_label=None, ws=None):
+    shape = tuple(prob.shape)
+    axis = axis % len(shape)
+    outer = int(np.prod(shape[:axis])) if axis else 1
+    inner = int(np.prod(shape[axis + 1:])) if axis + 1 < len(shape) else 1
+    wsp, wsb = (ws or _default_ws).get(lib().mms_rank_workspace_bytes_f64(outer * inner), prob.device)
+    out = torch.empty(1, dtype=_D, device=prob.device)
+    check(lib().mms_rank_auc_nd_f64(
+        outer, int(shape[axis]), inner, int(fixed_axis), _ptr(prob, "prob", dtype=_D), _ptr(label, "label", dtype=_D),
+        int(ignore_label is not None), int(ignore_label or 0), out.data_ptr(), wsp, wsb, _stream()),
+        "mms_rank_auc_nd_f64")
+    return out.cpu().numpy()[0]
+
+
+def rank_accuracy_f64(a, b, label, ws=None):
+    wsp, wsb = (ws or _default_ws).get(max(4096, lib().mms_rank_workspace_bytes_f64(1)), a.device)
+    out = torch.empty(1, dtype=_D, device=a.device)
+    check(lib().mms_rank_accuracy_f64(a.numel(), _ptr(a, "a", dtype=_D), _ptr(b, "b", dtype=_D),
+                                      _ptr(label, "label", dtype=_D), out.data_ptr(), wsp, wsb, _stream()),
+          "mms_rank_accuracy_f64")
+    return out.cpu().numpy()[0]

@@ -547,8 +547,8 @@ class LayerRegisterer {
   }
 };
 
-// float for every layer; float AND double (common.hpp:41-44) for the three layers of the path,
-// whose C ABI has _f64 entry points (the *_FD macros below).
+// float for every layer; float AND double (common.hpp:41-44) for the layers whose C ABI has _f64
+// entry points -- the three layers of the path, Embed, MRR, AUC and RankAccuracy (the *_FD macros below).
 #define REGISTER_LAYER_CREATOR(type, creator) \
   static LayerRegisterer<float> g_creator_f_##type(#type, creator<float>)
 #define REGISTER_LAYER_CLASS(type)                                                    \

@@ -27,35 +27,55 @@ namespace mms {
 // of two Embed layers that share one table (network_v4's w2v_q / w2v_a, do_trec_qa_clean.py:452-467), whose Backward
 // calls the reference runs one after the other into the same weight diff (embed_layer.cpp:155-180): row n of the
 // concatenation is layer 0's row n, or layer 1's row n - M0.  A single layer is M0 = M, second = null.
+// T: the element type (float or double, the two the reference instantiates); the pair calls are float only.
+template <class T>
 struct EmbedSrc {
-  const float* index0; const float* diff0; int M0;
-  const float* index1; const float* diff1;
-  __device__ __forceinline__ float index(int n) const { return n < M0 ? index0[n] : index1[n - M0]; }
-  __device__ __forceinline__ const float* row(unsigned n, int N) const {
+  const T* index0; const T* diff0; int M0;
+  const T* index1; const T* diff1;
+  __device__ __forceinline__ T index(int n) const { return n < M0 ? index0[n] : index1[n - M0]; }
+  __device__ __forceinline__ const T* row(unsigned n, int N) const {
     return (int)n < M0 ? diff0 + (size_t)n * N : diff1 + (size_t)(n - M0) * N;
   }
 };
 
+// gemm(M,N,1) of the bias term: alpha*(1*bias) + beta*top, one rounded add
+template <class T>
+__device__ __forceinline__ T embed_add_bias(T b, T v) { return (T)1 * ((T)1 * b) + (T)1 * v; }
+// PAIRS (double only): N is even and weight / bias / top are 16-byte aligned, so every row is -- a lane moves two
+// columns per 16-byte access; any other N or base takes the one-column loop.  Same adds, same bits.
+template <class T, bool PAIRS = false>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(int M, int N, int K,
-                                                        const float* __restrict__ index,
-                                                        const float* __restrict__ weight,
-                                                        const float* __restrict__ bias,
-                                                        float* __restrict__ top) {
+                                                        const T* __restrict__ index,
+                                                        const T* __restrict__ weight,
+                                                        const T* __restrict__ bias,
+                                                        T* __restrict__ top) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);   // one wave per output row
   if (n >= M) return;
   const int lane = threadIdx.x & 63;
   int idx = (int)index[n];
   idx = idx < 0 ? 0 : (idx >= K ? K - 1 : idx);        // the reference only DCHECKs; stay in bounds
-  const float* w = weight + (size_t)idx * N;
-  float* t = top + (size_t)n * N;
-  for (int d = lane; d < N; d += 64) {
-    float v = w[d];
-    if (bias) v = 1.0f * (1.0f * bias[d]) + 1.0f * v;   // gemm(M,N,1): alpha*(1*bias) + beta*top
-    t[d] = v;
+  const T* w = weight + (size_t)idx * N;
+  T* t = top + (size_t)n * N;
+  if constexpr (PAIRS) {
+    const double2* w2 = reinterpret_cast<const double2*>(w);
+    const double2* b2 = reinterpret_cast<const double2*>(bias);
+    double2* t2 = reinterpret_cast<double2*>(t);
+    for (int d = lane; d < N / 2; d += 64) {
+      double2 v = w2[d];
+      if (bias) { const double2 b = b2[d]; v.x = embed_add_bias(b.x, v.x); v.y = embed_add_bias(b.y, v.y); }
+      t2[d] = v;
+    }
+  } else {
+    for (int d = lane; d < N; d += 64) {
+      T v = w[d];
+      if (bias) v = embed_add_bias(bias[d], v);
+      t[d] = v;
+    }
   }
 }
 
-__global__ __launch_bounds__(256) void embed_keys_kernel(int M, int K, EmbedSrc src,
+template <class T>
+__global__ __launch_bounds__(256) void embed_keys_kernel(int M, int K, EmbedSrc<T> src,
                                                          unsigned* __restrict__ keys,
                                                          unsigned* __restrict__ vals) {
   const int n = blockIdx.x * 256 + threadIdx.x;
@@ -81,12 +101,13 @@ __global__ __launch_bounds__(256) void embed_head_flags_kernel(int M, const unsi
 // ahead, then CH/8 independent loads per thread, all issued before the first LDS write).  One
 // memory round trip per chunk instead of two per row -- the zero-pad word id owns thousands
 // of rows of a TREC-QA batch.  Short segments (<= CH rows: nearly every id) are one chunk.
-template <int CH, int GW>   // GW gathering waves; block = 64 * (GW + 1) threads
+template <int CH, int GW, class T>   // GW gathering waves; block = 64 * (GW + 1) threads
 __global__ __launch_bounds__(64 * (GW + 1)) void embed_bwd_seg_kernel(
     int M, int N, const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
     const unsigned* __restrict__ heads, const unsigned* __restrict__ nseg,
-    EmbedSrc src, float* __restrict__ weight_diff, int rmin, int rmax) {
-  extern __shared__ float seg_buf[];             // [2][CH][64] floats, then [2][CH] row numbers
+    EmbedSrc<T> src, T* __restrict__ weight_diff, int rmin, int rmax) {
+  extern __shared__ __align__(16) unsigned char seg_raw[];
+  T* seg_buf = reinterpret_cast<T*>(seg_raw);    // [2][CH][64] elements, then [2][CH] row numbers
   constexpr int RPT = CH / GW;                   // rows per gathering thread per chunk
   static_assert(CH % GW == 0, "chunk rows must divide evenly over the gathering waves");
   unsigned* vbuf = reinterpret_cast<unsigned*>(seg_buf + 2 * CH * 64);
@@ -104,7 +125,7 @@ __global__ __launch_bounds__(64 * (GW + 1)) void embed_bwd_seg_kernel(
   };
   auto gather = [&](int b, int r0) {             // rows rg, rg + GW, ... of the chunk, column `col`
     if (gt < 0) return;
-    float x[RPT];
+    T x[RPT];
 #pragma unroll
     for (int u = 0; u < RPT; ++u) x[u] = src.row(vbuf[b * CH + rg + u * GW], N)[gcol];
 #pragma unroll
@@ -116,22 +137,22 @@ __global__ __launch_bounds__(64 * (GW + 1)) void embed_bwd_seg_kernel(
   if (CH < R) stage_rows(1, CH);
   __syncthreads();
   const bool adder = tid < 64 && c0 + tid < N;
-  float acc = adder ? weight_diff[(size_t)idx * N + c0 + tid] : 0.f;
+  T acc = adder ? weight_diff[(size_t)idx * N + c0 + tid] : (T)0;
   for (int r0 = 0, b = 0; r0 < R; r0 += CH, b ^= 1) {
     if (r0 + 2 * CH < R) stage_rows(b, r0 + 2 * CH);      // vbuf[b] was consumed before the last barrier
     if (r0 + CH < R) gather(b ^ 1, r0 + CH);              // row numbers staged one iteration ago
     if (adder) {
       const int rows = min(CH, R - r0);
-      const float* colp = seg_buf + (size_t)b * CH * 64 + tid;
+      const T* colp = seg_buf + (size_t)b * CH * 64 + tid;
       int row = 0;
       for (; row + 8 <= rows; row += 8) {
-        float v[8];
+        T v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = colp[(row + u) * 64];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) acc = 1.0f * v[u] + acc;     // caffe_axpy(alpha = 1), n ascending
+        for (int u = 0; u < 8; ++u) acc = (T)1 * v[u] + acc;     // caffe_axpy(alpha = 1), n ascending
       }
-      for (; row < rows; ++row) acc = 1.0f * colp[row * 64] + acc;
+      for (; row < rows; ++row) acc = (T)1 * colp[row * 64] + acc;
     }
     __syncthreads();                                        // chunk r0 + CH is in seg_buf[b ^ 1], its successor's rows in vbuf[b]
   }
@@ -146,25 +167,25 @@ __global__ __launch_bounds__(64 * (GW + 1)) void embed_bwd_seg_kernel(
 // chip idle anyway: the partial sums in the workgroups NEXT to the one-workgroup inverted-index build, the final sum
 // in workgroups appended to the short-segment launch (3 launches per backward pass instead of 5).
 constexpr int kBiasChunk = 128;
-template <int LANES>                                  // blockDim.x == 64 * LANES
-__device__ __forceinline__ void embed_bias_partial_body(int c, int M, int N, const EmbedSrc& src,
-                                                        float* __restrict__ partial, float (*red)[64]) {
+template <int LANES, class T>                         // blockDim.x == 64 * LANES
+__device__ __forceinline__ void embed_bias_partial_body(int c, int M, int N, const EmbedSrc<T>& src,
+                                                        T* __restrict__ partial, T (*red)[64]) {
   const int ry = threadIdx.x >> 6, dl = threadIdx.x & 63;
   const int n0 = c * kBiasChunk, n1 = min(M, n0 + kBiasChunk);
   for (int d0 = 0; d0 < N; d0 += 64) {
     const int d = min(d0 + dl, N - 1);
-    float s = 0.f;
+    T s = 0;
     for (int nb = n0 + ry; nb < n1; nb += 8 * LANES) {
-      float v[8];
+      T v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] = src.row((unsigned)min(nb + LANES * u, M - 1), N)[d];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) s += (nb + LANES * u < n1) ? v[u] : 0.f;
+      for (int u = 0; u < 8; ++u) s += (nb + LANES * u < n1) ? v[u] : (T)0;
     }
     red[ry][dl] = s;
     __syncthreads();
     if (ry == 0 && d0 + dl < N) {
-      float t = red[0][dl];
+      T t = red[0][dl];
 #pragma unroll
       for (int l = 1; l < LANES; ++l) t += red[l][dl];
       partial[(size_t)c * N + d0 + dl] = t;
@@ -172,27 +193,30 @@ __device__ __forceinline__ void embed_bias_partial_body(int c, int M, int N, con
     __syncthreads();
   }
 }
-__device__ __forceinline__ void embed_bias_finish_body(int d, int chunks, int N, const float* __restrict__ partial,
-                                                       float* __restrict__ bias_diff) {
+template <class T>
+__device__ __forceinline__ void embed_bias_finish_body(int d, int chunks, int N, const T* __restrict__ partial,
+                                                       T* __restrict__ bias_diff) {
   if (d >= N) return;
-  float s = 0.f;
+  T s = 0;
   for (int c0 = 0; c0 < chunks; c0 += 8) {       // eight loads in flight, same c-ascending order
-    float v[8];
+    T v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) v[u] = partial[(size_t)min(c0 + u, chunks - 1) * N + d];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) s += (c0 + u < chunks) ? v[u] : 0.f;
+    for (int u = 0; u < 8; ++u) s += (c0 + u < chunks) ? v[u] : (T)0;
   }
-  bias_diff[d] = 1.0f * s + 1.0f * bias_diff[d];
+  bias_diff[d] = (T)1 * s + (T)1 * bias_diff[d];
 }
-__global__ __launch_bounds__(256) void embed_bias_partial_kernel(int M, int N, EmbedSrc src,
-                                                                 float* __restrict__ partial) {
-  __shared__ float red[4][64];
+template <class T>
+__global__ __launch_bounds__(256) void embed_bias_partial_kernel(int M, int N, EmbedSrc<T> src,
+                                                                 T* __restrict__ partial) {
+  __shared__ T red[4][64];
   embed_bias_partial_body<4>((int)blockIdx.x, M, N, src, partial, red);
 }
+template <class T>
 __global__ __launch_bounds__(256) void embed_bias_finish_kernel(int chunks, int N,
-                                                                const float* __restrict__ partial,
-                                                                float* __restrict__ bias_diff) {
+                                                                const T* __restrict__ partial,
+                                                                T* __restrict__ bias_diff) {
   embed_bias_finish_body((int)(blockIdx.x * 256 + threadIdx.x), chunks, N, partial, bias_diff);
 }
 
@@ -201,7 +225,8 @@ __global__ __launch_bounds__(256) void embed_bias_finish_kernel(int chunks, int 
 // of the head positions and their count -- in ONE workgroup and one launch instead of the dozen
 // launches of the device-wide sort + select (each a few microseconds of pure latency).
 constexpr int kPrepThreads = 1024, kPrepItems = 4, kPrepMax = kPrepThreads * kPrepItems;
-__device__ __forceinline__ void embed_prep_body(int M, int K, unsigned bits, const EmbedSrc& src,
+template <class T>
+__device__ __forceinline__ void embed_prep_body(int M, int K, unsigned bits, const EmbedSrc<T>& src,
                                                 unsigned* __restrict__ keys, unsigned* __restrict__ vals,
                                                 unsigned* __restrict__ heads, unsigned* __restrict__ nseg) {
   using sort_t = rocprim::block_radix_sort<unsigned, kPrepThreads, kPrepItems, unsigned>;
@@ -243,12 +268,13 @@ __device__ __forceinline__ void embed_prep_body(int M, int K, unsigned bits, con
   }
   if (t == 0) nseg[0] = total;
 }
+template <class T>
 __global__ __launch_bounds__(kPrepThreads) void embed_prep_small_kernel(
-    int M, int K, unsigned bits, EmbedSrc src, unsigned* __restrict__ keys,
+    int M, int K, unsigned bits, EmbedSrc<T> src, unsigned* __restrict__ keys,
     unsigned* __restrict__ vals, unsigned* __restrict__ heads, unsigned* __restrict__ nseg,
-    int N, float* __restrict__ bias_partial) {
+    int N, T* __restrict__ bias_partial) {
   if (blockIdx.x > 0) {                          // riders: the bias gradient's partial sums (bias_partial != null)
-    __shared__ float red[kPrepThreads / 64][64];
+    __shared__ T red[kPrepThreads / 64][64];
     embed_bias_partial_body<kPrepThreads / 64>((int)blockIdx.x - 1, M, N, src, bias_partial, red);
     return;
   }
@@ -261,7 +287,7 @@ __global__ __launch_bounds__(kPrepThreads) void embed_prep_small_kernel(
 // them keep the rest of the chip busy.  The backward pass (embed_backward_pair with index_ready) then starts at the
 // segment kernels.
 __global__ __launch_bounds__(kPrepThreads) void embed_fwd_pair_kernel(
-    int M0, int M1, int N, int K, EmbedSrc src, const float* __restrict__ weight, const float* __restrict__ bias,
+    int M0, int M1, int N, int K, EmbedSrc<float> src, const float* __restrict__ weight, const float* __restrict__ bias,
     float* __restrict__ top0, float* __restrict__ top1, int build, unsigned bits, unsigned* __restrict__ keys,
     unsigned* __restrict__ vals, unsigned* __restrict__ heads, unsigned* __restrict__ nseg) {
   const int M = M0 + M1;
@@ -278,7 +304,7 @@ __global__ __launch_bounds__(kPrepThreads) void embed_fwd_pair_kernel(
   float* t = n < M0 ? top0 + (size_t)n * N : top1 + (size_t)(n - M0) * N;
   for (int d = lane; d < N; d += 64) {
     float v = w[d];
-    if (bias) v = 1.0f * (1.0f * bias[d]) + 1.0f * v;   // gemm(M,N,1): alpha*(1*bias) + beta*top, as embed_fwd_kernel
+    if (bias) v = embed_add_bias(bias[d], v);            // as embed_fwd_kernel
     t[d] = v;
   }
 }
@@ -286,11 +312,12 @@ __global__ __launch_bounds__(kPrepThreads) void embed_fwd_pair_kernel(
 // Short segments (nearly every word id: a handful of rows): one WAVE per (id, 64-column slice),
 // four per workgroup, no LDS and no barrier -- the row numbers and then the rows are requested
 // all at once (8 or 32 unconditional loads with clamped addresses), then added in order.
+template <class T>
 __global__ __launch_bounds__(256) void embed_bwd_short_kernel(
     int M, int N, const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
     const unsigned* __restrict__ heads, const unsigned* __restrict__ nseg,
-    EmbedSrc src, float* __restrict__ weight_diff, int seg_blocks, int bias_chunks,
-    const float* __restrict__ bias_partial, float* __restrict__ bias_diff) {
+    EmbedSrc<T> src, T* __restrict__ weight_diff, int seg_blocks, int bias_chunks,
+    const T* __restrict__ bias_partial, T* __restrict__ bias_diff) {
   if ((int)blockIdx.x >= seg_blocks) {           // riders: the bias gradient's final sum (the partials are a launch old)
     if (blockIdx.y == 0)
       embed_bias_finish_body(((int)blockIdx.x - seg_blocks) * 256 + (int)threadIdx.x, bias_chunks, N, bias_partial, bias_diff);
@@ -305,25 +332,25 @@ __global__ __launch_bounds__(256) void embed_bwd_short_kernel(
   if (R > 32) return;                            // embed_bwd_seg_kernel's
   const unsigned idx = keys[p];
   const int gc = min(c, N - 1);
-  float acc = weight_diff[(size_t)idx * N + gc];
+  T acc = weight_diff[(size_t)idx * N + gc];
   if (R <= 8) {
-    float x[8];
+    T x[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) x[u] = src.row(vals[p + min(u, R - 1)], N)[gc];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) if (u < R) acc = 1.0f * x[u] + acc;
+    for (int u = 0; u < 8; ++u) if (u < R) acc = (T)1 * x[u] + acc;
   } else {
-    float x[32];
+    T x[32];
 #pragma unroll
     for (int u = 0; u < 32; ++u) x[u] = src.row(vals[p + min(u, R - 1)], N)[gc];
 #pragma unroll
-    for (int u = 0; u < 32; ++u) if (u < R) acc = 1.0f * x[u] + acc;
+    for (int u = 0; u < 32; ++u) if (u < R) acc = (T)1 * x[u] + acc;
   }
   if (c < N) weight_diff[(size_t)idx * N + c] = acc;
 }
 
 struct EmbedWs { size_t k0, k1, v0, v1, flags, heads, nseg, partial, temp, total; int chunks; };
-static EmbedWs embed_ws(int M, int N) {
+static EmbedWs embed_ws(int M, int N, size_t elem) {   // elem: bytes of the element type (the bias partial sums)
   EmbedWs w{};
   size_t o = 0;
   auto take = [&](size_t b) { size_t at = o; o += round_up(b, 256); return at; };
@@ -331,24 +358,37 @@ static EmbedWs embed_ws(int M, int N) {
   w.v0 = take((size_t)M * 4); w.v1 = take((size_t)M * 4);
   w.flags = take((size_t)M); w.heads = take((size_t)M * 4); w.nseg = take(256);
   w.chunks = (M + kBiasChunk - 1) / kBiasChunk;
-  w.partial = take((size_t)w.chunks * N * 4);
+  w.partial = take((size_t)w.chunks * N * elem);
   w.temp = o;
   w.total = o + (size_t)M * 8 + (4u << 20);
   return w;
 }
-size_t embed_workspace_bytes(int M, int N) { return embed_ws(M, N).total; }
+size_t embed_workspace_bytes(int M, int N) { return embed_ws(M, N, sizeof(float)).total; }
+size_t embed_workspace_bytes_f64(int M, int N) { return embed_ws(M, N, sizeof(double)).total; }
 
-int embed_forward(int M, int N, int K, const float* index, const float* weight, const float* bias,
-                  float* top, hipStream_t s) {
-  hipLaunchKernelGGL(embed_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, M, N, K, index,
+template <class T>
+int embed_forward(int M, int N, int K, const T* index, const T* weight, const T* bias,
+                  T* top, hipStream_t s) {
+  if constexpr (sizeof(T) == 8) {
+    if (N % 2 == 0 && aligned16(weight) && aligned16(bias) && aligned16(top)) {
+      hipLaunchKernelGGL((embed_fwd_kernel<T, true>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, M, N, K, index,
+                         weight, bias, top);
+      return launch_status();
+    }
+  }
+  hipLaunchKernelGGL(embed_fwd_kernel<T>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, M, N, K, index,
                      weight, bias, top);
   return launch_status();
 }
 
-static int embed_backward_src(int M, int N, int K, const EmbedSrc& src,
-                              float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes, hipStream_t s,
+// rows per chunk of the long-segment kernel: two chunks of 64 columns (+ row numbers) in the CU's 160 KB of LDS
+template <class T> constexpr int kSegChunk = sizeof(T) == 4 ? 256 : 128;
+
+template <class T>
+static int embed_backward_src(int M, int N, int K, const EmbedSrc<T>& src,
+                              T* weight_diff, T* bias_diff, void* ws, size_t ws_bytes, hipStream_t s,
                               bool index_ready = false) {
-  const EmbedWs lay = embed_ws(M, N);
+  const EmbedWs lay = embed_ws(M, N, sizeof(T));
   if (!ws || ws_bytes < lay.temp) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(ws);
   auto* k0 = reinterpret_cast<unsigned*>(base + lay.k0);
@@ -364,16 +404,16 @@ static int embed_backward_src(int M, int N, int K, const EmbedSrc& src,
     if (index_ready && M <= kPrepMax && bits < 32) {
       // keys / vals / heads / nseg of this workspace were written by embed_forward_pair for these very ids
       if (bias_diff) {
-        hipLaunchKernelGGL(embed_bias_partial_kernel, dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N, src,
-                           reinterpret_cast<float*>(base + lay.partial));
+        hipLaunchKernelGGL(embed_bias_partial_kernel<T>, dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N, src,
+                           reinterpret_cast<T*>(base + lay.partial));
         bias_rides = true;                          // (the final sum still rides with the short-segment launch)
       }
     } else if (M <= kPrepMax && bits < 32) {
       bias_rides = bias_diff != nullptr;
-      hipLaunchKernelGGL(embed_prep_small_kernel, dim3(1u + (bias_rides ? (unsigned)lay.chunks : 0u)), dim3(kPrepThreads), 0,
-                         s, M, K, bits, src, k1, v1, heads, nseg, N, reinterpret_cast<float*>(base + lay.partial));
+      hipLaunchKernelGGL(embed_prep_small_kernel<T>, dim3(1u + (bias_rides ? (unsigned)lay.chunks : 0u)), dim3(kPrepThreads), 0,
+                         s, M, K, bits, src, k1, v1, heads, nseg, N, reinterpret_cast<T*>(base + lay.partial));
     } else {
-      hipLaunchKernelGGL(embed_keys_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, M, K, src,
+      hipLaunchKernelGGL(embed_keys_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, M, K, src,
                          k0, v0);
       size_t need = 0;
       if (rocprim::radix_sort_pairs(nullptr, need, k0, k1, v0, v1, (size_t)M, 0u, bits, s) != hipSuccess)
@@ -392,33 +432,41 @@ static int embed_backward_src(int M, int N, int K, const EmbedSrc& src,
         return MMS_ERR_LAUNCH;
     }
     const dim3 grid((unsigned)std::min(M, K), (unsigned)((N + 63) / 64));   // at most min(M, K) distinct ids
-    constexpr size_t kLongLds = 2 * 256 * (64 * sizeof(float) + sizeof(unsigned));   // 130 KB of the CU's 160 KB
+    constexpr int CH = kSegChunk<T>;
+    constexpr size_t kLongLds = 2 * CH * (64 * sizeof(T) + sizeof(unsigned));   // 130 KB of the CU's 160 KB
     static const hipError_t once = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&embed_bwd_seg_kernel<256, 8>),
+        reinterpret_cast<const void*>(&embed_bwd_seg_kernel<CH, 8, T>),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLds);
     (void)once;
     const unsigned seg_blocks = (grid.x + 3) / 4, fin_blocks = bias_rides ? (unsigned)((N + 255) / 256) : 0u;
-    hipLaunchKernelGGL(embed_bwd_short_kernel, dim3(seg_blocks + fin_blocks, grid.y), dim3(256), 0, s, M, N, k1, v1,
+    hipLaunchKernelGGL(embed_bwd_short_kernel<T>, dim3(seg_blocks + fin_blocks, grid.y), dim3(256), 0, s, M, N, k1, v1,
                        heads, nseg, src, weight_diff, (int)seg_blocks, lay.chunks,
-                       reinterpret_cast<const float*>(base + lay.partial), bias_diff);
-    hipLaunchKernelGGL((embed_bwd_seg_kernel<256, 8>), grid, dim3(576), kLongLds, s, M, N, k1, v1, heads, nseg,
+                       reinterpret_cast<const T*>(base + lay.partial), bias_diff);
+    hipLaunchKernelGGL((embed_bwd_seg_kernel<CH, 8, T>), grid, dim3(576), kLongLds, s, M, N, k1, v1, heads, nseg,
                        src, weight_diff, 33, 0x7fffffff);
   }
   if (bias_diff && !bias_rides) {
-    float* partial = reinterpret_cast<float*>(base + lay.partial);
-    hipLaunchKernelGGL(embed_bias_partial_kernel, dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N,
+    T* partial = reinterpret_cast<T*>(base + lay.partial);
+    hipLaunchKernelGGL(embed_bias_partial_kernel<T>, dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N,
                        src, partial);
-    hipLaunchKernelGGL(embed_bias_finish_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
+    hipLaunchKernelGGL(embed_bias_finish_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
                        lay.chunks, N, partial, bias_diff);
   }
   return launch_status();
 }
 
-int embed_backward(int M, int N, int K, const float* index, const float* top_diff,
-                   float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes, hipStream_t s) {
-  const EmbedSrc src{index, top_diff, M, nullptr, nullptr};
+template <class T>
+int embed_backward(int M, int N, int K, const T* index, const T* top_diff,
+                   T* weight_diff, T* bias_diff, void* ws, size_t ws_bytes, hipStream_t s) {
+  const EmbedSrc<T> src{index, top_diff, M, nullptr, nullptr};
   return embed_backward_src(M, N, K, src, weight_diff, bias_diff, ws, ws_bytes, s);
 }
+// Layer<float> and Layer<double>: the two instantiations the reference makes (INSTANTIATE_CLASS, common.hpp:41-44)
+template int embed_forward<float>(int, int, int, const float*, const float*, const float*, float*, hipStream_t);
+template int embed_forward<double>(int, int, int, const double*, const double*, const double*, double*, hipStream_t);
+template int embed_backward<float>(int, int, int, const float*, const float*, float*, float*, void*, size_t, hipStream_t);
+template int embed_backward<double>(int, int, int, const double*, const double*, double*, double*, void*, size_t,
+                                    hipStream_t);
 
 // Two Embed layers over ONE table: layer 0's Backward, then layer 1's, as one pass over the concatenation of their
 // rows (the inverted index is built once, every table row is read and written once, the bias gradient is one sum).
@@ -426,7 +474,7 @@ int embed_backward(int M, int N, int K, const float* index, const float* top_dif
 int embed_backward_pair(int M0, int M1, int N, int K, const float* index0, const float* top_diff0, const float* index1,
                         const float* top_diff1, float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes,
                         hipStream_t s, int index_ready) {
-  const EmbedSrc src{index0, top_diff0, M0, index1, top_diff1};
+  const EmbedSrc<float> src{index0, top_diff0, M0, index1, top_diff1};
   return embed_backward_src(M0 + M1, N, K, src, weight_diff, bias_diff, ws, ws_bytes, s, index_ready != 0);
 }
 
@@ -443,13 +491,13 @@ bool embed_pair_index_supported(int M0, int M1, int K) {
 int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const float* index1, const float* weight,
                        const float* bias, float* top0, float* top1, void* index_ws, size_t index_ws_bytes, hipStream_t s) {
   const int M = M0 + M1;
-  const EmbedWs lay = embed_ws(M, N);
+  const EmbedWs lay = embed_ws(M, N, sizeof(float));
   const bool build = index_ws != nullptr && embed_pair_index_supported(M0, M1, K);
   if (build && index_ws_bytes < lay.temp) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(index_ws);
   unsigned bits = 1;
   while (bits < 32 && (1ull << bits) < (unsigned long long)K) ++bits;
-  const EmbedSrc src{index0, nullptr, M0, index1, nullptr};
+  const EmbedSrc<float> src{index0, nullptr, M0, index1, nullptr};
   const unsigned rows_per_wg = kPrepThreads / 64;
   hipLaunchKernelGGL(embed_fwd_pair_kernel, dim3((unsigned)((M + rows_per_wg - 1) / rows_per_wg) + (build ? 1u : 0u)),
                      dim3(kPrepThreads), 0, s, M0, M1, N, K, src, weight, bias, top0, top1, build ? 1 : 0, bits,

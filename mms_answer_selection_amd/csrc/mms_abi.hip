@@ -62,6 +62,63 @@ int split_sum(int count, int ntop, const float* const* top_diffs, float* bottom_
 }
 }  // namespace mms
 
+// The argument rules of the Embed and ranking-metric calls, once for both element types (the _f32 / _f64 twins below).
+namespace {
+template <class T>
+int rank_map_mrr_abi(int n, int fixed_axis, const T* prob, const T* label, const T* group, T* map_out, T* mrr_out,
+                     int* effective_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n <= 0 || fixed_axis < 0 || (long long)n * (fixed_axis + 1) > 0x7fffffffLL)
+    return MMS_ERR_INVALID_ARG;
+  if (!prob || !label || !group) return MMS_ERR_INVALID_ARG;
+  return rank_map_mrr(n, fixed_axis, prob, label, group, map_out, mrr_out, effective_out,
+                      workspace, workspace_bytes, as_stream(stream));
+}
+template <class T>
+int rank_auc_abi(int n, int dim, int fixed_axis, const T* prob, const T* label, int has_ignore_label, int ignore_label,
+                 T* auc_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n <= 0 || dim <= 0 || fixed_axis < 0 || fixed_axis >= dim ||
+      (long long)n * dim > 0x7fffffffLL)
+    return MMS_ERR_INVALID_ARG;
+  if (!prob || !label || !auc_out) return MMS_ERR_INVALID_ARG;
+  return rank_auc(n, dim, fixed_axis, 1, prob, label, has_ignore_label, ignore_label, auc_out,
+                  workspace, workspace_bytes, as_stream(stream));
+}
+template <class T>
+int rank_auc_nd_abi(int outer, int channels, int inner, int fixed_axis, const T* prob, const T* label,
+                    int has_ignore_label, int ignore_label, T* auc_out, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  if (outer <= 0 || channels <= 0 || inner <= 0 || fixed_axis < 0 || fixed_axis >= channels ||
+      (long long)outer * channels * inner > 0x7fffffffLL)
+    return MMS_ERR_INVALID_ARG;
+  if (!prob || !label || !auc_out) return MMS_ERR_INVALID_ARG;
+  return rank_auc(outer * inner, channels * inner, fixed_axis, inner, prob, label, has_ignore_label, ignore_label,
+                  auc_out, workspace, workspace_bytes, as_stream(stream));
+}
+template <class T>
+int rank_accuracy_abi(int count, const T* a, const T* b, const T* label, T* acc_out, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  if (count <= 0) return MMS_ERR_INVALID_ARG;
+  if (!a || !b || !label || !acc_out) return MMS_ERR_INVALID_ARG;
+  return rank_accuracy(count, a, b, label, acc_out, workspace, workspace_bytes, as_stream(stream));
+}
+template <class T>
+int embed_forward_abi(int M, int N, int K, const T* index, const T* weight, const T* bias, T* top, void* stream) {
+  if (M < 0 || N <= 0 || K <= 0 || (long long)M * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
+  if (M == 0) return MMS_OK;
+  if (!index || !weight || !top) return MMS_ERR_INVALID_ARG;
+  return embed_forward(M, N, K, index, weight, bias, top, as_stream(stream));
+}
+template <class T>
+int embed_backward_abi(int M, int N, int K, const T* index, const T* top_diff, T* weight_diff, T* bias_diff,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (M < 0 || N <= 0 || K <= 0 || (long long)M * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
+  if (M == 0 || (!weight_diff && !bias_diff)) return MMS_OK;
+  if (!index || !top_diff) return MMS_ERR_INVALID_ARG;
+  return embed_backward(M, N, K, index, top_diff, weight_diff, bias_diff, workspace, workspace_bytes,
+                        as_stream(stream));
+}
+}  // namespace
+
 extern "C" {
 
 int mms_version(void) { return MMS_VERSION; }
@@ -379,40 +436,27 @@ size_t mms_rank_workspace_bytes(int n) { return n > 0 ? rank_workspace_bytes(n) 
 int mms_rank_map_mrr_f32(int n, int fixed_axis, const float* prob, const float* label,
                          const float* group, float* map_out, float* mrr_out, int* effective_out,
                          void* workspace, size_t workspace_bytes, void* stream) {
-  if (n <= 0 || fixed_axis < 0 || (long long)n * (fixed_axis + 1) > 0x7fffffffLL)
-    return MMS_ERR_INVALID_ARG;
-  if (!prob || !label || !group) return MMS_ERR_INVALID_ARG;
-  return rank_map_mrr(n, fixed_axis, prob, label, group, map_out, mrr_out, effective_out,
-                      workspace, workspace_bytes, as_stream(stream));
+  return rank_map_mrr_abi(n, fixed_axis, prob, label, group, map_out, mrr_out, effective_out, workspace,
+                          workspace_bytes, stream);
 }
 
 int mms_rank_auc_f32(int n, int dim, int fixed_axis, const float* prob, const float* label,
                      int has_ignore_label, int ignore_label, float* auc_out, void* workspace,
                      size_t workspace_bytes, void* stream) {
-  if (n <= 0 || dim <= 0 || fixed_axis < 0 || fixed_axis >= dim ||
-      (long long)n * dim > 0x7fffffffLL)
-    return MMS_ERR_INVALID_ARG;
-  if (!prob || !label || !auc_out) return MMS_ERR_INVALID_ARG;
-  return rank_auc(n, dim, fixed_axis, 1, prob, label, has_ignore_label, ignore_label, auc_out,
-                  workspace, workspace_bytes, as_stream(stream));
+  return rank_auc_abi(n, dim, fixed_axis, prob, label, has_ignore_label, ignore_label, auc_out, workspace,
+                      workspace_bytes, stream);
 }
 
 int mms_rank_auc_nd_f32(int outer, int channels, int inner, int fixed_axis, const float* prob,
                         const float* label, int has_ignore_label, int ignore_label, float* auc_out,
                         void* workspace, size_t workspace_bytes, void* stream) {
-  if (outer <= 0 || channels <= 0 || inner <= 0 || fixed_axis < 0 || fixed_axis >= channels ||
-      (long long)outer * channels * inner > 0x7fffffffLL)
-    return MMS_ERR_INVALID_ARG;
-  if (!prob || !label || !auc_out) return MMS_ERR_INVALID_ARG;
-  return rank_auc(outer * inner, channels * inner, fixed_axis, inner, prob, label, has_ignore_label, ignore_label,
-                  auc_out, workspace, workspace_bytes, as_stream(stream));
+  return rank_auc_nd_abi(outer, channels, inner, fixed_axis, prob, label, has_ignore_label, ignore_label, auc_out,
+                         workspace, workspace_bytes, stream);
 }
 
 int mms_rank_accuracy_f32(int count, const float* a, const float* b, const float* label,
                           float* acc_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (count <= 0) return MMS_ERR_INVALID_ARG;
-  if (!a || !b || !label || !acc_out) return MMS_ERR_INVALID_ARG;
-  return rank_accuracy(count, a, b, label, acc_out, workspace, workspace_bytes, as_stream(stream));
+  return rank_accuracy_abi(count, a, b, label, acc_out, workspace, workspace_bytes, stream);
 }
 
 int mms_embed_backward_pair_f32(int M0, int M1, int N, int K, const float* index0, const float* top_diff0,
@@ -453,20 +497,13 @@ size_t mms_embed_workspace_bytes(int M, int N) { return (M > 0 && N > 0) ? embed
 
 int mms_embed_forward_f32(int M, int N, int K, const float* index, const float* weight,
                           const float* bias, float* top, void* stream) {
-  if (M < 0 || N <= 0 || K <= 0 || (long long)M * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
-  if (M == 0) return MMS_OK;
-  if (!index || !weight || !top) return MMS_ERR_INVALID_ARG;
-  return embed_forward(M, N, K, index, weight, bias, top, as_stream(stream));
+  return embed_forward_abi(M, N, K, index, weight, bias, top, stream);
 }
 
 int mms_embed_backward_f32(int M, int N, int K, const float* index, const float* top_diff,
                            float* weight_diff, float* bias_diff, void* workspace,
                            size_t workspace_bytes, void* stream) {
-  if (M < 0 || N <= 0 || K <= 0 || (long long)M * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
-  if (M == 0 || (!weight_diff && !bias_diff)) return MMS_OK;
-  if (!index || !top_diff) return MMS_ERR_INVALID_ARG;
-  return embed_backward(M, N, K, index, top_diff, weight_diff, bias_diff, workspace, workspace_bytes,
-                        as_stream(stream));
+  return embed_backward_abi(M, N, K, index, top_diff, weight_diff, bias_diff, workspace, workspace_bytes, stream);
 }
 
 int mms_feed_gather_rows_f32(int rows, int row_elems, int src_rows, const float* src, const int* perm,
@@ -612,6 +649,45 @@ int mms_pairrank_backward_f64(int count, double top_diff, const double* y, const
   if ((propagate_down0 && !da) || (propagate_down1 && !db)) return MMS_ERR_INVALID_ARG;
   return pairrank_backward_f64(count, top_diff, y, ordered, similar, propagate_down0 ? da : nullptr,
                                propagate_down1 ? db : nullptr, as_stream(stream));
+}
+
+size_t mms_rank_workspace_bytes_f64(int n) { return n > 0 ? rank_workspace_bytes_f64(n) : 0; }
+int mms_rank_map_mrr_f64(int n, int fixed_axis, const double* prob, const double* label,
+                         const double* group, double* map_out, double* mrr_out, int* effective_out,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  return rank_map_mrr_abi(n, fixed_axis, prob, label, group, map_out, mrr_out, effective_out, workspace,
+                          workspace_bytes, stream);
+}
+
+int mms_rank_auc_f64(int n, int dim, int fixed_axis, const double* prob, const double* label,
+                     int has_ignore_label, int ignore_label, double* auc_out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  return rank_auc_abi(n, dim, fixed_axis, prob, label, has_ignore_label, ignore_label, auc_out, workspace,
+                      workspace_bytes, stream);
+}
+
+int mms_rank_auc_nd_f64(int outer, int channels, int inner, int fixed_axis, const double* prob,
+                        const double* label, int has_ignore_label, int ignore_label, double* auc_out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  return rank_auc_nd_abi(outer, channels, inner, fixed_axis, prob, label, has_ignore_label, ignore_label, auc_out,
+                         workspace, workspace_bytes, stream);
+}
+
+int mms_rank_accuracy_f64(int count, const double* a, const double* b, const double* label,
+                          double* acc_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return rank_accuracy_abi(count, a, b, label, acc_out, workspace, workspace_bytes, stream);
+}
+
+size_t mms_embed_workspace_bytes_f64(int M, int N) { return (M > 0 && N > 0) ? embed_workspace_bytes_f64(M, N) : 0; }
+int mms_embed_forward_f64(int M, int N, int K, const double* index, const double* weight,
+                          const double* bias, double* top, void* stream) {
+  return embed_forward_abi(M, N, K, index, weight, bias, top, stream);
+}
+
+int mms_embed_backward_f64(int M, int N, int K, const double* index, const double* top_diff,
+                           double* weight_diff, double* bias_diff, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return embed_backward_abi(M, N, K, index, top_diff, weight_diff, bias_diff, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -76,21 +76,27 @@ void set_triplet_finish_mode(int m);
 int loss_sum_mode();
 void set_loss_sum_mode(int m);
 // ranking.hip
+// (T = float or double: the folds run in T, the order is that of the scores narrowed to float for both)
 size_t rank_workspace_bytes(int n);
-int rank_map_mrr(int n, int fixed_axis, const float* prob, const float* label, const float* group, float* map_out,
-                 float* mrr_out, int* effective, void* ws, size_t ws_bytes, hipStream_t s);
-int rank_auc(int n, int dim, int fixed_axis, int inner, const float* prob, const float* label, int has_ignore,
-             int ignore_label, float* auc_out, void* ws, size_t ws_bytes, hipStream_t s);
-int rank_accuracy(int count, const float* a, const float* b, const float* label, float* out, void* ws, size_t ws_bytes,
-                  hipStream_t s);
+size_t rank_workspace_bytes_f64(int n);
+template <class T>
+int rank_map_mrr(int n, int fixed_axis, const T* prob, const T* label, const T* group, T* map_out, T* mrr_out,
+                 int* effective, void* ws, size_t ws_bytes, hipStream_t s);
+template <class T>
+int rank_auc(int n, int dim, int fixed_axis, int inner, const T* prob, const T* label, int has_ignore, int ignore_label,
+             T* auc_out, void* ws, size_t ws_bytes, hipStream_t s);
+template <class T>
+int rank_accuracy(int count, const T* a, const T* b, const T* label, T* out, void* ws, size_t ws_bytes, hipStream_t s);
 int rank_tie_mode();
 void set_rank_tie_mode(int m);
 // embed.hip
 size_t embed_workspace_bytes(int M, int N);
-int embed_forward(int M, int N, int K, const float* index, const float* weight, const float* bias, float* top,
-                  hipStream_t s);
-int embed_backward(int M, int N, int K, const float* index, const float* top_diff, float* weight_diff, float* bias_diff,
-                   void* ws, size_t ws_bytes, hipStream_t s);
+size_t embed_workspace_bytes_f64(int M, int N);
+template <class T>
+int embed_forward(int M, int N, int K, const T* index, const T* weight, const T* bias, T* top, hipStream_t s);
+template <class T>
+int embed_backward(int M, int N, int K, const T* index, const T* top_diff, T* weight_diff, T* bias_diff, void* ws,
+                   size_t ws_bytes, hipStream_t s);
 int embed_backward_pair(int M0, int M1, int N, int K, const float* index0, const float* top_diff0, const float* index1,
                         const float* top_diff1, float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes,
                         hipStream_t s, int index_ready);

@@ -46,16 +46,32 @@ __device__ __forceinline__ unsigned desc_bits(float s) {
 
 // item i = (outer o, inner j) = (i / inner, i % inner); its score is prob[o*stride + offset*inner + j]
 // (auc_layer.cpp:75-76; inner = 1 for MAP / MRR and for prob (N, C))
+// T = double: the reference's comparators take std::pair<float, int> for every Dtype (map_layer.cpp:34, mrr_layer.cpp:33,
+// auc_layer.cpp:42 -- AUC's vector holds pair<Dtype, int>, but std::sort hands its elements to that comparator through
+// the converting constructor), so the ORDER is always that of the scores narrowed to float: one key for both types.
+// Only the folds below run in Dtype.
+template <class T>
 __device__ __forceinline__ unsigned long long rank_key(int i, int stride, int offset, int inner,
-                                                        const float* __restrict__ prob,
-                                                        const float* __restrict__ group) {
+                                                        const T* __restrict__ prob,
+                                                        const T* __restrict__ group) {
   const unsigned g = group ? (unsigned)((int)group[i]) + 0x80000000u : 0u;   // map<int,...> key order
   const int o = i / inner, j = i - o * inner;
-  return ((unsigned long long)g << 32) | desc_bits(prob[(size_t)o * stride + (size_t)offset * inner + j]);
+  return ((unsigned long long)g << 32) | desc_bits((float)prob[(size_t)o * stride + (size_t)offset * inner + j]);
 }
+// a lane's value of the element type, by compile-time or wave-uniform lane number
+__device__ __forceinline__ float wave_readlane(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+__device__ __forceinline__ double wave_readlane(double v, int l) {
+  const long long b = __double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+template <class T>
 __global__ __launch_bounds__(256) void rank_keys_kernel(int n, int stride, int offset, int inner,
-                                                        const float* __restrict__ prob,
-                                                        const float* __restrict__ group,
+                                                        const T* __restrict__ prob,
+                                                        const T* __restrict__ group,
                                                         unsigned long long* __restrict__ keys,
                                                         unsigned* __restrict__ vals) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -69,20 +85,20 @@ __global__ __launch_bounds__(256) void rank_keys_kernel(int n, int stride, int o
 // for MAP (a label == 1 and a label != 1 present, :80-92); bit 1: it counts for MRR
 // (a label == 1 and a label == 0 present, mrr_layer.cpp:61-73).
 // BYPOS: `label` is already in sorted order (label[p]); otherwise it is gathered through the permutation
-template <bool BYPOS = false>
+template <bool BYPOS = false, class T>
 __device__ __forceinline__ void rank_bucket_at(int i, int n, const unsigned long long* keys,
-                                               const unsigned* vals, const float* label,
-                                               float* ap_out, int* rank_out, int* flags) {
+                                               const unsigned* vals, const T* label,
+                                               T* ap_out, int* rank_out, int* flags) {
   const unsigned g = (unsigned)(keys[i] >> 32);
   int fl = 0;
   if (i == 0 || (unsigned)(keys[i - 1] >> 32) != g) {
-    float ap = 0.f;
+    T ap = 0;
     int map_rank = 0, not_one = 0, zero = 0, mrr_rank = -1;
     for (int p = i; p < n && (unsigned)(keys[p] >> 32) == g; ++p) {
       const int lab = (int)(BYPOS ? label[p] : label[vals[p]]);
       const int pos = p - i;
       if (lab == 1) {
-        ap += (++map_rank) / (float)(pos + 1);
+        ap += (++map_rank) / (T)(pos + 1);
         if (mrr_rank < 0) mrr_rank = pos;
       } else {
         not_one = 1;
@@ -94,20 +110,22 @@ __device__ __forceinline__ void rank_bucket_at(int i, int n, const unsigned long
   }
   flags[i] = fl;
 }
+template <class T>
 __global__ __launch_bounds__(256) void rank_bucket_pos_kernel(int n,
                                                               const unsigned long long* __restrict__ keys,
-                                                              const float* __restrict__ lab_pos,
-                                                              float* __restrict__ ap_out,
+                                                              const T* __restrict__ lab_pos,
+                                                              T* __restrict__ ap_out,
                                                               int* __restrict__ rank_out,
                                                               int* __restrict__ flags) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) rank_bucket_at<true>(i, n, keys, nullptr, lab_pos, ap_out, rank_out, flags);
 }
+template <class T>
 __global__ __launch_bounds__(256) void rank_bucket_kernel(int n,
                                                           const unsigned long long* __restrict__ keys,
                                                           const unsigned* __restrict__ vals,
-                                                          const float* __restrict__ label,
-                                                          float* __restrict__ ap_out,
+                                                          const T* __restrict__ label,
+                                                          T* __restrict__ ap_out,
                                                           int* __restrict__ rank_out,
                                                           int* __restrict__ flags) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -119,13 +137,14 @@ __global__ __launch_bounds__(256) void rank_bucket_kernel(int n,
 // positions per coalesced load (four loads in flight) instead of one dependent load per
 // position: ballots pick the positions that carry a bucket result, and the wave-uniform
 // running sums are advanced in position order with v_readlane.
-__device__ __forceinline__ void rank_fold_wave(int lane, int n, const float* ap, const int* rank,
-                                               const int* flags, float* __restrict__ map_out,
-                                               float* __restrict__ mrr_out, int* __restrict__ effective) {
-  float map_ = 0.f, mrr = 0.f;
+template <class T>
+__device__ __forceinline__ void rank_fold_wave(int lane, int n, const T* ap, const int* rank,
+                                               const int* flags, T* __restrict__ map_out,
+                                               T* __restrict__ mrr_out, int* __restrict__ effective) {
+  T map_ = 0, mrr = 0;
   int eff_map = 0, eff_mrr = 0;
   int nfl[4], nrk[4];
-  float na[4];
+  T na[4];
   auto fetch = [&](int base) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -138,7 +157,7 @@ __device__ __forceinline__ void rank_fold_wave(int lane, int n, const float* ap,
   fetch(0);
   for (int base = 0; base < n; base += 256) {
     int fl[4], rk[4];
-    float a[4];
+    T a[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       fl[u] = (base + 64 * u + lane < n) ? nfl[u] : 0;
@@ -154,12 +173,12 @@ __device__ __forceinline__ void rank_fold_wave(int lane, int n, const float* ap,
       while (m1) {                                                   // map_layer.cpp:93-94
         const int l = __ffsll((long long)m1) - 1;
         m1 &= m1 - 1;
-        map_ += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a[u]), l));
+        map_ += wave_readlane(a[u], l);
       }
-      while (m2) {   // mrr += 1.0/(mrr_rank+1): float + double, stored back to float (mrr_layer.cpp:75)
+      while (m2) {   // mrr += 1.0/(mrr_rank+1): Dtype + double, stored back to Dtype (mrr_layer.cpp:75)
         const int l = __ffsll((long long)m2) - 1;
         m2 &= m2 - 1;
-        mrr = (float)((double)mrr + 1.0 / (__builtin_amdgcn_readlane(rk[u], l) + 1));
+        mrr = (T)((double)mrr + 1.0 / (__builtin_amdgcn_readlane(rk[u], l) + 1));
       }
     }
   }
@@ -169,11 +188,12 @@ __device__ __forceinline__ void rank_fold_wave(int lane, int n, const float* ap,
     if (effective) *effective = eff_map;
   }
 }
-__global__ __launch_bounds__(64) void rank_fold_kernel(int n, const float* __restrict__ ap,
+template <class T>
+__global__ __launch_bounds__(64) void rank_fold_kernel(int n, const T* __restrict__ ap,
                                                        const int* __restrict__ rank,
                                                        const int* __restrict__ flags,
-                                                       float* __restrict__ map_out,
-                                                       float* __restrict__ mrr_out,
+                                                       T* __restrict__ map_out,
+                                                       T* __restrict__ mrr_out,
                                                        int* __restrict__ effective) {
   rank_fold_wave(threadIdx.x, n, ap, rank, flags, map_out, mrr_out, effective);
 }
@@ -192,12 +212,13 @@ __device__ __forceinline__ int wave_inclusive_scan_i32(int v, int lane) {
   }
   return v;
 }
+template <class T>
 __device__ __forceinline__ void auc_fold_wave(int lane, int n, const unsigned* vals,
-                                              const float* __restrict__ label, int has_ignore,
-                                              int ignore_label, float* __restrict__ auc_out) {
-  float auc = 0.f;
+                                              const T* __restrict__ label, int has_ignore,
+                                              int ignore_label, T* __restrict__ auc_out) {
+  T auc = 0;
   int high = 0, count = 0;
-  float nxt[4];
+  T nxt[4];
   auto fetch = [&](int base) {                    // clamped addresses: unconditional loads
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -220,19 +241,20 @@ __device__ __forceinline__ void auc_fold_wave(int lane, int n, const unsigned* v
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int incl = high + wave_inclusive_scan_i32(lab[u], lane);
-      const float term = use[u] ? (float)(incl * (1 - lab[u])) : 0.f;   // skipped items add +0: exact (auc >= 0 ... or any)
+      const T term = use[u] ? (T)(incl * (1 - lab[u])) : (T)0;   // skipped items add +0: exact (auc >= 0 ... or any)
       count += __popcll(__ballot(use[u]));
       high = __builtin_amdgcn_readlane(incl, 63);
 #pragma unroll
       for (int l = 0; l < 64; ++l)
-        auc += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(term), l));
+        auc += wave_readlane(term, l);
     }
   }
-  if (lane == 0) *auc_out = high > 0 ? auc / high / (count - high) : 0.f;
+  if (lane == 0) *auc_out = high > 0 ? auc / high / (count - high) : (T)0;
 }
+template <class T>
 __global__ __launch_bounds__(64) void auc_fold_kernel(int n, const unsigned* __restrict__ vals,
-                                                      const float* __restrict__ label, int has_ignore,
-                                                      int ignore_label, float* __restrict__ auc_out) {
+                                                      const T* __restrict__ label, int has_ignore,
+                                                      int ignore_label, T* __restrict__ auc_out) {
   auc_fold_wave(threadIdx.x, n, vals, label, has_ignore, ignore_label, auc_out);
 }
 
@@ -243,10 +265,11 @@ __global__ __launch_bounds__(64) void auc_fold_kernel(int n, const unsigned* __r
 // (push_back) order -- sequential by nature, hence opt-in: a few microseconds for a TREC-QA candidate group, but
 // milliseconds for AUC's single bucket of thousands of items.
 constexpr int kTieLds = 4096;
+template <class T>
 __global__ __launch_bounds__(256) void rank_ties_detect_kernel(int n, const unsigned long long* __restrict__ keys,
                                                                const unsigned* __restrict__ vals,
-                                                               const float* __restrict__ label,
-                                                               float* __restrict__ lab_pos, int* __restrict__ work,
+                                                               const T* __restrict__ label,
+                                                               T* __restrict__ lab_pos, int* __restrict__ work,
                                                                int* __restrict__ nwork) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -265,13 +288,14 @@ __global__ __launch_bounds__(256) void rank_ties_detect_kernel(int n, const unsi
     work[2 * w + 1] = m;
   }
 }
+template <class T>
 __global__ __launch_bounds__(64) void rank_ties_emulate_kernel(int stride, int offset, int inner,
-                                                               const float* __restrict__ prob,
-                                                               const float* __restrict__ label,
+                                                               const T* __restrict__ prob,
+                                                               const T* __restrict__ label,
                                                                const unsigned* __restrict__ vals,
                                                                const int* __restrict__ work,
                                                                const int* __restrict__ nwork, int skip_ignored,
-                                                               int ignore_label, float* __restrict__ lab_pos,
+                                                               int ignore_label, T* __restrict__ lab_pos,
                                                                SortItem* __restrict__ g_items,
                                                                unsigned* __restrict__ g_idx) {
   __shared__ SortItem s_items[kTieLds];
@@ -310,13 +334,13 @@ __global__ __launch_bounds__(64) void rank_ties_emulate_kernel(int stride, int o
       const int idx = (int)ix[j], lab = (int)label[idx];
       if (skip_ignored && lab == ignore_label) continue;                        // auc_layer.cpp:68-70: never pushed
       const int o = idx / inner, jj = idx - o * inner;
-      it[used].key = prob[(size_t)o * stride + (size_t)offset * inner + jj];
+      it[used].key = (float)prob[(size_t)o * stride + (size_t)offset * inner + jj];   // pair<float, int>
       it[used].lab = lab;
       ++used;
     }
     libstdcxx_sort(it, used);
-    for (int j = 0; j < used; ++j) lab_pos[start + j] = (float)it[j].lab;
-    for (int j = used; j < m; ++j) lab_pos[start + j] = (float)ignore_label;    // skipped items: behind the rest, still skipped
+    for (int j = 0; j < used; ++j) lab_pos[start + j] = (T)it[j].lab;
+    for (int j = used; j < m; ++j) lab_pos[start + j] = (T)ignore_label;    // skipped items: behind the rest, still skipped
   }
 }
 
@@ -327,19 +351,19 @@ __global__ __launch_bounds__(64) void rank_ties_emulate_kernel(int stride, int o
 // bits.  Measured with the capacity at 2048: 1,517 items 47 us against 45-51 us for the multi-launch path -- one
 // CU's LDS and barriers are no faster than rocPRIM's several launches at that size -- so it serves n <= 512 only.
 constexpr int kRankSmall = 512;
-template <int MODE>                                  // 0: MAP / MRR, 1: AUC
+template <int MODE, class T>                         // 0: MAP / MRR, 1: AUC
 __global__ __launch_bounds__(1024) void rank_small_kernel(int n, int stride, int offset, int inner,
-                                                          const float* __restrict__ prob,
-                                                          const float* __restrict__ label,
-                                                          const float* __restrict__ group, int has_ignore,
-                                                          int ignore_label, float* __restrict__ out0,
-                                                          float* __restrict__ out1, int* __restrict__ effective) {
+                                                          const T* __restrict__ prob,
+                                                          const T* __restrict__ label,
+                                                          const T* __restrict__ group, int has_ignore,
+                                                          int ignore_label, T* __restrict__ out0,
+                                                          T* __restrict__ out1, int* __restrict__ effective) {
   __shared__ unsigned long long keys[kRankSmall];
   __shared__ unsigned vals[kRankSmall];
-  __shared__ float ap[MODE == 0 ? kRankSmall : 1];
+  __shared__ T ap[MODE == 0 ? kRankSmall : 1];
   __shared__ int rk[MODE == 0 ? kRankSmall : 1];
   __shared__ int fl[MODE == 0 ? kRankSmall : 1];
-  __shared__ float slab[MODE == 0 ? kRankSmall : 1];   // labels in sorted order: the bucket walks read LDS only
+  __shared__ T slab[MODE == 0 ? kRankSmall : 1];   // labels in sorted order: the bucket walks read LDS only
   const int t = threadIdx.x;
   int P = 64;
   while (P < n) P <<= 1;                             // sorted size: a power of two, padded with maximal keys
@@ -383,18 +407,18 @@ __global__ __launch_bounds__(1024) void rank_small_kernel(int n, int stride, int
 // (ping-pong buffers).  Then the sorted (key, index) pairs are written to LDS once and the SAME bucket walks and the
 // SAME one-wave fold run on them: same expressions, same order, same bits.
 constexpr int kRankMid = 2048;
-template <int MODE>                                  // 0: MAP / MRR, 1: AUC
+template <int MODE, class T>                         // 0: MAP / MRR, 1: AUC
 __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int offset, int inner,
-                                                        const float* __restrict__ prob,
-                                                        const float* __restrict__ label,
-                                                        const float* __restrict__ group, int has_ignore,
-                                                        int ignore_label, float* __restrict__ out0,
-                                                        float* __restrict__ out1, int* __restrict__ effective) {
+                                                        const T* __restrict__ prob,
+                                                        const T* __restrict__ label,
+                                                        const T* __restrict__ group, int has_ignore,
+                                                        int ignore_label, T* __restrict__ out0,
+                                                        T* __restrict__ out1, int* __restrict__ effective) {
   __shared__ unsigned long long keys[kRankMid];
   __shared__ unsigned vals[kRankMid];
   __shared__ unsigned long long xk[kRankMid];          // the second exchange buffer (cross-wave passes)
   __shared__ unsigned xv[kRankMid];
-  __shared__ float ap[MODE == 0 ? kRankMid : 1];
+  __shared__ T ap[MODE == 0 ? kRankMid : 1];
   __shared__ int rk[MODE == 0 ? kRankMid + 1 : 1];     // + 1: as `hd` it holds B + 1 <= 2049 bucket bounds
   __shared__ int fl[MODE == 0 ? kRankMid : 1];
   __shared__ float slab[MODE == 0 ? kRankMid : 1];
@@ -520,7 +544,7 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
     // positive's term map_rank / (pos + 1) and every bucket's ap / map_rank and 1.0 / (mrr_rank + 1) by its own
     // thread; what is left sequential is adds over loads whose addresses are known up front.
     int* hd = rk;                                    // compacted bucket heads, hd[B] = n  (rk / fl / ap are free until the end)
-    float* term = ap;
+    T* term = ap;
     __shared__ int wtot[2][16];
     __shared__ int nb_s;
     const int i0 = 2 * t, i1 = 2 * t + 1, lane = t & 63, wv = t >> 6;
@@ -563,7 +587,7 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
         const int bkt = (e ? a1 : a0) - 1, head = hd[bkt];
         const int before = head ? (int)xv[head - 1] : 0;               // positives in front of the bucket
         const int lab = e ? l1 : l0, mr = (int)(e ? b1 : b0) - before;
-        term[i] = lab == 1 ? mr / (float)(i - head + 1) : 0.f;
+        term[i] = lab == 1 ? mr / (T)(i - head + 1) : (T)0;
       }
     }
     __syncthreads();
@@ -571,18 +595,18 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
     // (x + 0.0f == x: the non-positive items add nothing), its flags and its two quotients, stored for the fold.  The
     // bucket's extent is known, so the loads run ahead of the adds.  The walks read hd / term / slab / xv only; the
     // fold's arrays alias keys / xk / fl, which nothing reads between the barrier above and the one below.
-    float* bap = reinterpret_cast<float*>(keys);     // (the sorted keys are not needed any more)
+    T* bap = reinterpret_cast<T*>(keys);             // (the sorted keys are not needed any more)
     double* binv = reinterpret_cast<double*>(xk);
     int* bfl = fl;
     for (int bk = t; bk < B; bk += 1024) {
-      float b_ap = 0.f;
+      T b_ap = 0;
       double b_inv = 0.0;
       int b_fl = 0;
       const int head = hd[bk], end = hd[bk + 1];
-      float apv = 0.f;
+      T apv = 0;
       int not_one = 0, zero = 0, first = -1;
       for (int p = head; p < end; p += 8) {
-        float tv[8];
+        T tv[8];
         int lv[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) { const int q = p + u < end ? p + u : end - 1; tv[u] = term[q]; lv[u] = __float_as_int(slab[q]); }
@@ -603,12 +627,12 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
     __syncthreads();
     // the fold over the buckets in sorted (ascending group) order: running sums only, one wave, 64 buckets per step
     if (t < 64) {
-      float map_ = 0.f, mrr = 0.f;
+      T map_ = 0, mrr = 0;
       int eff_map = 0, eff_mrr = 0;
       for (int base = 0; base < B; base += 64) {
         const int bi = base + lane < B ? base + lane : B - 1;
-        const float la = bap[bi];
-        const long long li = __double_as_longlong(binv[bi]);
+        const T la = bap[bi];
+        const double li = binv[bi];
         const int lf = base + lane < B ? bfl[bi] : 0;
         unsigned long long m1 = __ballot(lf & 1), m2 = __ballot(lf & 2);
         eff_map += __popcll(m1);
@@ -616,14 +640,12 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
         while (m1) {                                                   // map_layer.cpp:93-94
           const int l = __ffsll((long long)m1) - 1;
           m1 &= m1 - 1;
-          map_ += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(la), l));
+          map_ += wave_readlane(la, l);
         }
-        while (m2) {   // mrr += 1.0/(mrr_rank+1): float + double, stored back to float (mrr_layer.cpp:75)
+        while (m2) {   // mrr += 1.0/(mrr_rank+1): Dtype + double, stored back to Dtype (mrr_layer.cpp:75)
           const int l = __ffsll((long long)m2) - 1;
           m2 &= m2 - 1;
-          const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(li & 0xffffffffll), l);
-          const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(li >> 32), l);
-          mrr = (float)((double)mrr + __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)));
+          mrr = (T)((double)mrr + wave_readlane(li, l));
         }
       }
       if (lane == 0) {
@@ -637,9 +659,10 @@ __global__ __launch_bounds__(1024) void rank_mid_kernel(int n, int stride, int o
   }
 }
 
-__global__ __launch_bounds__(256) void rank_accuracy_kernel(int count, const float* __restrict__ a,
-                                                            const float* __restrict__ b,
-                                                            const float* __restrict__ label,
+template <class T>
+__global__ __launch_bounds__(256) void rank_accuracy_kernel(int count, const T* __restrict__ a,
+                                                            const T* __restrict__ b,
+                                                            const T* __restrict__ label,
                                                             unsigned* __restrict__ partial) {
   __shared__ unsigned red[4];
   unsigned c = 0;
@@ -650,13 +673,14 @@ __global__ __launch_bounds__(256) void rank_accuracy_kernel(int count, const flo
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
+template <class T>
 __global__ void rank_accuracy_finish_kernel(int blocks, int count, const unsigned* __restrict__ partial,
-                                            float* __restrict__ out) {
+                                            T* __restrict__ out) {
   if (threadIdx.x != 0) return;
   unsigned long long c = 0;
   for (int i = 0; i < blocks; ++i) c += partial[i];
-  // the reference accumulates 0/1 into a float: exact up to 2^24, then it sticks
-  float acc = c > 16777216ull ? 16777216.f : (float)c;
+  // the reference accumulates 0/1 into a Dtype: for float exact up to 2^24, then it sticks (a double never gets there)
+  T acc = sizeof(T) == 4 && c > 16777216ull ? (T)16777216 : (T)c;
   *out = acc / count;
 }
 
@@ -664,20 +688,21 @@ __global__ void rank_accuracy_finish_kernel(int blocks, int count, const unsigne
 struct RankWs {
   size_t keys0, keys1, vals0, vals1, ap, rr, flags, labpos, work, nwork, titems, tidx, temp, total;
 };
-static RankWs rank_ws(int n) {
+static RankWs rank_ws(int n, size_t elem) {          // elem: bytes of the element type (ap and labpos hold Dtype)
   RankWs w{};
   size_t o = 0;
   auto take = [&](size_t b) { size_t at = o; o += round_up(b, 256); return at; };
   w.keys0 = take((size_t)n * 8); w.keys1 = take((size_t)n * 8);
   w.vals0 = take((size_t)n * 4); w.vals1 = take((size_t)n * 4);
-  w.ap = take((size_t)n * 4); w.rr = take((size_t)n * 4); w.flags = take((size_t)n * 4);
-  w.labpos = take((size_t)n * 4); w.work = take((size_t)n * 8); w.nwork = take(256);      // MMS_RANK_TIES_LIBSTDCXX
+  w.ap = take((size_t)n * elem); w.rr = take((size_t)n * 4); w.flags = take((size_t)n * 4);
+  w.labpos = take((size_t)n * elem); w.work = take((size_t)n * 8); w.nwork = take(256);      // MMS_RANK_TIES_LIBSTDCXX
   w.titems = take((size_t)n * sizeof(SortItem)); w.tidx = take((size_t)n * 4);
   w.temp = o;
   w.total = o + (size_t)n * 8 + (4u << 20);   // generous bound for rocPRIM's scratch; checked at run time
   return w;
 }
-size_t rank_workspace_bytes(int n) { return rank_ws(n).total; }
+size_t rank_workspace_bytes(int n) { return rank_ws(n, sizeof(float)).total; }
+size_t rank_workspace_bytes_f64(int n) { return rank_ws(n, sizeof(double)).total; }
 
 static int sort_pairs(const RankWs& lay, char* base, size_t ws_bytes, int n, unsigned bits,
                       hipStream_t s) {
@@ -695,26 +720,27 @@ static int sort_pairs(const RankWs& lay, char* base, size_t ws_bytes, int n, uns
   return MMS_OK;
 }
 
-int rank_map_mrr(int n, int fixed_axis, const float* prob, const float* label, const float* group,
-                 float* map_out, float* mrr_out, int* effective, void* ws, size_t ws_bytes,
+template <class T>
+int rank_map_mrr(int n, int fixed_axis, const T* prob, const T* label, const T* group,
+                 T* map_out, T* mrr_out, int* effective, void* ws, size_t ws_bytes,
                  hipStream_t s) {
   const bool libstd = rank_tie_mode() == MMS_RANK_TIES_LIBSTDCXX;
   if (n > 0 && n <= kRankSmall && !libstd) {         // evaluation-sized: one workgroup, one launch
-    hipLaunchKernelGGL(rank_small_kernel<0>, dim3(1), dim3(1024), 0, s, n, fixed_axis + 1, fixed_axis, 1, prob,
+    hipLaunchKernelGGL((rank_small_kernel<0, T>), dim3(1), dim3(1024), 0, s, n, fixed_axis + 1, fixed_axis, 1, prob,
                        label, group, 0, 0, map_out, mrr_out, effective);
     return launch_status();
   }
   if (n > kRankSmall && n <= kRankMid && !libstd) {  // a test split's worth (1,517 candidates): still one launch
-    hipLaunchKernelGGL(rank_mid_kernel<0>, dim3(1), dim3(1024), 0, s, n, fixed_axis + 1, fixed_axis, 1, prob,
+    hipLaunchKernelGGL((rank_mid_kernel<0, T>), dim3(1), dim3(1024), 0, s, n, fixed_axis + 1, fixed_axis, 1, prob,
                        label, group, 0, 0, map_out, mrr_out, effective);
     return launch_status();
   }
-  const RankWs lay = rank_ws(n);
+  const RankWs lay = rank_ws(n, sizeof(T));
   if (!ws || ws_bytes < lay.temp) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(ws);
   const unsigned grid = (unsigned)((n + 255) / 256);
   // score of item i: prob[i*(fixed_axis+1) + fixed_axis]  (map_layer.cpp:50, mrr_layer.cpp:49)
-  hipLaunchKernelGGL(rank_keys_kernel, dim3(grid), dim3(256), 0, s, n, fixed_axis + 1, fixed_axis, 1,
+  hipLaunchKernelGGL(rank_keys_kernel<T>, dim3(grid), dim3(256), 0, s, n, fixed_axis + 1, fixed_axis, 1,
                      prob, group, reinterpret_cast<unsigned long long*>(base + lay.keys0),
                      reinterpret_cast<unsigned*>(base + lay.vals0));
   int rc = sort_pairs(lay, base, ws_bytes, n, 64u, s);
@@ -722,50 +748,51 @@ int rank_map_mrr(int n, int fixed_axis, const float* prob, const float* label, c
   auto* keys = reinterpret_cast<unsigned long long*>(base + lay.keys1);
   auto* vals = reinterpret_cast<unsigned*>(base + lay.vals1);
   if (libstd) {
-    auto* labpos = reinterpret_cast<float*>(base + lay.labpos);
+    auto* labpos = reinterpret_cast<T*>(base + lay.labpos);
     auto* work = reinterpret_cast<int*>(base + lay.work);
     auto* nwork = reinterpret_cast<int*>(base + lay.nwork);
     if (hipMemsetAsync(nwork, 0, sizeof(int), s) != hipSuccess) return MMS_ERR_LAUNCH;
-    hipLaunchKernelGGL(rank_ties_detect_kernel, dim3(grid), dim3(256), 0, s, n, keys, vals, label, labpos, work, nwork);
-    hipLaunchKernelGGL(rank_ties_emulate_kernel, dim3(256), dim3(64), 0, s, fixed_axis + 1, fixed_axis, 1, prob, label,
+    hipLaunchKernelGGL(rank_ties_detect_kernel<T>, dim3(grid), dim3(256), 0, s, n, keys, vals, label, labpos, work, nwork);
+    hipLaunchKernelGGL(rank_ties_emulate_kernel<T>, dim3(256), dim3(64), 0, s, fixed_axis + 1, fixed_axis, 1, prob, label,
                        vals, work, nwork, 0, 0, labpos, reinterpret_cast<SortItem*>(base + lay.titems),
                        reinterpret_cast<unsigned*>(base + lay.tidx));
-    hipLaunchKernelGGL(rank_bucket_pos_kernel, dim3(grid), dim3(256), 0, s, n, keys, labpos,
-                       reinterpret_cast<float*>(base + lay.ap), reinterpret_cast<int*>(base + lay.rr),
+    hipLaunchKernelGGL(rank_bucket_pos_kernel<T>, dim3(grid), dim3(256), 0, s, n, keys, labpos,
+                       reinterpret_cast<T*>(base + lay.ap), reinterpret_cast<int*>(base + lay.rr),
                        reinterpret_cast<int*>(base + lay.flags));
   } else
-  hipLaunchKernelGGL(rank_bucket_kernel, dim3(grid), dim3(256), 0, s, n, keys, vals, label,
-                     reinterpret_cast<float*>(base + lay.ap), reinterpret_cast<int*>(base + lay.rr),
+  hipLaunchKernelGGL(rank_bucket_kernel<T>, dim3(grid), dim3(256), 0, s, n, keys, vals, label,
+                     reinterpret_cast<T*>(base + lay.ap), reinterpret_cast<int*>(base + lay.rr),
                      reinterpret_cast<int*>(base + lay.flags));
-  hipLaunchKernelGGL(rank_fold_kernel, dim3(1), dim3(64), 0, s, n,
-                     reinterpret_cast<float*>(base + lay.ap), reinterpret_cast<int*>(base + lay.rr),
+  hipLaunchKernelGGL(rank_fold_kernel<T>, dim3(1), dim3(64), 0, s, n,
+                     reinterpret_cast<T*>(base + lay.ap), reinterpret_cast<int*>(base + lay.rr),
                      reinterpret_cast<int*>(base + lay.flags), map_out, mrr_out, effective);
   return launch_status();
 }
 
-// n = outer * inner items; dim = channels * inner floats per outer index
-int rank_auc(int n, int dim, int fixed_axis, int inner, const float* prob, const float* label, int has_ignore,
-             int ignore_label, float* auc_out, void* ws, size_t ws_bytes, hipStream_t s) {
+// n = outer * inner items; dim = channels * inner elements per outer index
+template <class T>
+int rank_auc(int n, int dim, int fixed_axis, int inner, const T* prob, const T* label, int has_ignore,
+             int ignore_label, T* auc_out, void* ws, size_t ws_bytes, hipStream_t s) {
   const bool libstd = rank_tie_mode() == MMS_RANK_TIES_LIBSTDCXX;
   if (n > 0 && n <= kRankSmall && !libstd) {
-    hipLaunchKernelGGL(rank_small_kernel<1>, dim3(1), dim3(1024), 0, s, n, dim, fixed_axis, inner, prob, label,
-                       static_cast<const float*>(nullptr), has_ignore, ignore_label, auc_out,
-                       static_cast<float*>(nullptr), static_cast<int*>(nullptr));
+    hipLaunchKernelGGL((rank_small_kernel<1, T>), dim3(1), dim3(1024), 0, s, n, dim, fixed_axis, inner, prob, label,
+                       static_cast<const T*>(nullptr), has_ignore, ignore_label, auc_out,
+                       static_cast<T*>(nullptr), static_cast<int*>(nullptr));
     return launch_status();
   }
   if (n > kRankSmall && n <= kRankMid && !libstd) {
-    hipLaunchKernelGGL(rank_mid_kernel<1>, dim3(1), dim3(1024), 0, s, n, dim, fixed_axis, inner, prob, label,
-                       static_cast<const float*>(nullptr), has_ignore, ignore_label, auc_out,
-                       static_cast<float*>(nullptr), static_cast<int*>(nullptr));
+    hipLaunchKernelGGL((rank_mid_kernel<1, T>), dim3(1), dim3(1024), 0, s, n, dim, fixed_axis, inner, prob, label,
+                       static_cast<const T*>(nullptr), has_ignore, ignore_label, auc_out,
+                       static_cast<T*>(nullptr), static_cast<int*>(nullptr));
     return launch_status();
   }
-  const RankWs lay = rank_ws(n);
+  const RankWs lay = rank_ws(n, sizeof(T));
   if (!ws || ws_bytes < lay.temp) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(ws);
   const unsigned grid = (unsigned)((n + 255) / 256);
   // score of item i: prob[i*dim + fixed_axis]  (auc_layer.cpp:75-76 with inner_num = 1)
-  hipLaunchKernelGGL(rank_keys_kernel, dim3(grid), dim3(256), 0, s, n, dim, fixed_axis, inner, prob,
-                     static_cast<const float*>(nullptr),
+  hipLaunchKernelGGL(rank_keys_kernel<T>, dim3(grid), dim3(256), 0, s, n, dim, fixed_axis, inner, prob,
+                     static_cast<const T*>(nullptr),
                      reinterpret_cast<unsigned long long*>(base + lay.keys0),
                      reinterpret_cast<unsigned*>(base + lay.vals0));
   int rc = sort_pairs(lay, base, ws_bytes, n, 32u, s);
@@ -773,34 +800,44 @@ int rank_auc(int n, int dim, int fixed_axis, int inner, const float* prob, const
   if (libstd) {
     auto* keys = reinterpret_cast<unsigned long long*>(base + lay.keys1);
     auto* vals = reinterpret_cast<unsigned*>(base + lay.vals1);
-    auto* labpos = reinterpret_cast<float*>(base + lay.labpos);
+    auto* labpos = reinterpret_cast<T*>(base + lay.labpos);
     auto* work = reinterpret_cast<int*>(base + lay.work);
     auto* nwork = reinterpret_cast<int*>(base + lay.nwork);
     if (hipMemsetAsync(nwork, 0, sizeof(int), s) != hipSuccess) return MMS_ERR_LAUNCH;
-    hipLaunchKernelGGL(rank_ties_detect_kernel, dim3(grid), dim3(256), 0, s, n, keys, vals, label, labpos, work, nwork);
-    hipLaunchKernelGGL(rank_ties_emulate_kernel, dim3(1), dim3(64), 0, s, dim, fixed_axis, inner, prob, label, vals,
+    hipLaunchKernelGGL(rank_ties_detect_kernel<T>, dim3(grid), dim3(256), 0, s, n, keys, vals, label, labpos, work, nwork);
+    hipLaunchKernelGGL(rank_ties_emulate_kernel<T>, dim3(1), dim3(64), 0, s, dim, fixed_axis, inner, prob, label, vals,
                        work, nwork, has_ignore, ignore_label, labpos, reinterpret_cast<SortItem*>(base + lay.titems),
                        reinterpret_cast<unsigned*>(base + lay.tidx));
-    hipLaunchKernelGGL(auc_fold_kernel, dim3(1), dim3(64), 0, s, n, static_cast<const unsigned*>(nullptr), labpos,
+    hipLaunchKernelGGL(auc_fold_kernel<T>, dim3(1), dim3(64), 0, s, n, static_cast<const unsigned*>(nullptr), labpos,
                        has_ignore, ignore_label, auc_out);
     return launch_status();
   }
-  hipLaunchKernelGGL(auc_fold_kernel, dim3(1), dim3(64), 0, s, n,
+  hipLaunchKernelGGL(auc_fold_kernel<T>, dim3(1), dim3(64), 0, s, n,
                      reinterpret_cast<unsigned*>(base + lay.vals1), label, has_ignore, ignore_label,
                      auc_out);
   return launch_status();
 }
 
-int rank_accuracy(int count, const float* a, const float* b, const float* label, float* out,
+template <class T>
+int rank_accuracy(int count, const T* a, const T* b, const T* label, T* out,
                   void* ws, size_t ws_bytes, hipStream_t s) {
   int blocks = (count + 1023) / 1024;
   if (blocks > 1024) blocks = 1024;
   if (blocks < 1) blocks = 1;
   if (!ws || ws_bytes < (size_t)blocks * sizeof(unsigned)) return MMS_ERR_WORKSPACE;
   unsigned* partial = static_cast<unsigned*>(ws);
-  hipLaunchKernelGGL(rank_accuracy_kernel, dim3(blocks), dim3(256), 0, s, count, a, b, label, partial);
-  hipLaunchKernelGGL(rank_accuracy_finish_kernel, dim3(1), dim3(64), 0, s, blocks, count, partial, out);
+  hipLaunchKernelGGL(rank_accuracy_kernel<T>, dim3(blocks), dim3(256), 0, s, count, a, b, label, partial);
+  hipLaunchKernelGGL(rank_accuracy_finish_kernel<T>, dim3(1), dim3(64), 0, s, blocks, count, partial, out);
   return launch_status();
 }
+
+// Layer<float> and Layer<double>: the two instantiations the reference makes (INSTANTIATE_CLASS, common.hpp:41-44)
+#define MMS_RANK_INSTANTIATE(T)                                                                                          \
+  template int rank_map_mrr<T>(int, int, const T*, const T*, const T*, T*, T*, int*, void*, size_t, hipStream_t);        \
+  template int rank_auc<T>(int, int, int, int, const T*, const T*, int, int, T*, void*, size_t, hipStream_t);            \
+  template int rank_accuracy<T>(int, const T*, const T*, const T*, T*, void*, size_t, hipStream_t)
+MMS_RANK_INSTANTIATE(float);
+MMS_RANK_INSTANTIATE(double);
+#undef MMS_RANK_INSTANTIATE
 
 }  // namespace mms
