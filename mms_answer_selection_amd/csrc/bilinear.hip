@@ -832,8 +832,10 @@ static int pick_ksplit(int Mt, int Nt, int K, int* kchunk, int batch = 1) {
   }
   int chunk = (int)((K + best - 1) / best);
   chunk = (chunk + 31) / 32 * 32;               // a multiple of either k-tile depth (16, 32)
+  if (chunk < 32) chunk = 32;                   // K == 0 (the workspace size of an empty batch): one split, no division by zero
   *kchunk = chunk;
-  return (K + chunk - 1) / chunk;
+  const int splits = (K + chunk - 1) / chunk;
+  return splits > 0 ? splits : 1;
 }
 
 // ------------------------------ workspace layout ----------------------------

@@ -684,8 +684,10 @@ inline int bx3_tn_pick_chunks(int K, int quads, int* kchunk) {
   if (want < 1) want = 1;
   int chunk = (K + want - 1) / want;
   chunk = (chunk + 31) / 32 * 32;
+  if (chunk < 32) chunk = 32;            // K == 0 (the workspace size of an empty batch): one split, no division by zero
   *kchunk = chunk;
-  return (K + chunk - 1) / chunk;
+  const int splits = (K + chunk - 1) / chunk;
+  return splits > 0 ? splits : 1;
 }
 inline int bx3_tn_quads(int M, int N) { return ((M + BX3TN_Q - 1) / BX3TN_Q) * ((N + BX3TN_Q - 1) / BX3TN_Q); }
 

@@ -776,8 +776,10 @@ inline int panel_pick_ksplit(int row_blocks, int nb, int K, int* kchunk) {
   if (want < 1) want = 1;
   int chunk = (K + want - 1) / want;
   chunk = (chunk + 31) / 32 * 32;
+  if (chunk < 32) chunk = 32;            // K == 0 (the workspace size of an empty batch): one split, no division by zero
   *kchunk = chunk;
-  return (K + chunk - 1) / chunk;
+  const int splits = (K + chunk - 1) / chunk;
+  return splits > 0 ? splits : 1;
 }
 
 // out (cols x rows) = in^T (in: rows x cols, row-major): the weight handed to the panel kernel as a k-major B
