@@ -543,8 +543,9 @@ def embed_forward(index, weight, top, bias=None):
           "mms_embed_forward_f32")
 
 
-def embed_backward(index, top_diff, weight_diff, bias_diff=None, ws=None):
-    M, (K, N) = index.numel(), weight_diff.shape
+def embed_backward(index, top_diff, weight_diff, bias_diff=None, ws=None, shape=None):
+    """weight_diff or bias_diff may be None; `shape` = (K, N) is then needed when weight_diff is None."""
+    M, (K, N) = index.numel(), (shape if shape is not None else weight_diff.shape)
     wsp, wsb = (ws or _default_ws).get(lib().mms_embed_workspace_bytes(M, N), index.device)
     check(lib().mms_embed_backward_f32(M, N, K, _ptr(index, "index"), _ptr(top_diff, "top_diff"),
                                        _ptr(weight_diff, "weight_diff", True),
@@ -552,9 +553,10 @@ def embed_backward(index, top_diff, weight_diff, bias_diff=None, ws=None):
           "mms_embed_backward_f32")
 
 
-def embed_backward_pair(index0, index1, top_diff0, top_diff1, weight_diff, bias_diff=None, ws=None):
-    """Backward of two Embed layers over one table in one pass: layer 0's rows, then layer 1's (include/mms.h)."""
-    M0, M1, (K, N) = index0.numel(), index1.numel(), weight_diff.shape
+def embed_backward_pair(index0, index1, top_diff0, top_diff1, weight_diff, bias_diff=None, ws=None, shape=None):
+    """Backward of two Embed layers over one table in one pass: layer 0's rows, then layer 1's (include/mms.h).
+    `shape` = (K, N) as in embed_backward."""
+    M0, M1, (K, N) = index0.numel(), index1.numel(), (shape if shape is not None else weight_diff.shape)
     wsp, wsb = (ws or _default_ws).get(lib().mms_embed_workspace_bytes(M0 + M1, N), index0.device)
     check(lib().mms_embed_backward_pair_f32(M0, M1, N, K, _ptr(index0, "index0"), _ptr(top_diff0, "top_diff0"),
                                             _ptr(index1, "index1"), _ptr(top_diff1, "top_diff1"),
@@ -589,9 +591,9 @@ def embed_forward_pair(index0, index1, weight, top0, top1, bias=None, index=None
     return built
 
 
-def embed_backward_pair_indexed(index0, index1, top_diff0, top_diff1, weight_diff, index, bias_diff=None):
+def embed_backward_pair_indexed(index0, index1, top_diff0, top_diff1, weight_diff, index, bias_diff=None, shape=None):
     """embed_backward_pair with the index embed_forward_pair(index0, index1, ..., index=index) built (same order)."""
-    M0, M1, (K, N) = index0.numel(), index1.numel(), weight_diff.shape
+    M0, M1, (K, N) = index0.numel(), index1.numel(), (shape if shape is not None else weight_diff.shape)
     if index.buf is None:
         raise MMSError("embed_backward_pair_indexed: no index was built (embed_forward_pair returned False); use "
                        "embed_backward_pair")
