@@ -225,8 +225,24 @@ __device__ __forceinline__ float2v chain_sum_lds_pk(const float4* r4, int n4, fl
 // LDS image of one pair: its D4 float4 squares followed by all-zero float4 up
 // to 3*h4, h4 = ceil(D4/3); segment g is [g*h4, (g+1)*h4).  Adding +0 to the
 // non-negative running sum is exact, so every lane runs the same h4 steps.
-__device__ __forceinline__ int spec_h4(int D4) { return (D4 + 2) / 3; }
-__device__ __forceinline__ int spec_stride4(int D4) { return 3 * spec_h4(D4); }
+__host__ __device__ __forceinline__ int spec_h4(int D4) { return (D4 + 2) / 3; }
+__host__ __device__ __forceinline__ int spec_stride4(int D4) { return 3 * spec_h4(D4); }
+
+// Host-side facts about the kernels built on this scheme (simcross_rows.hip and the fused triplet steps of
+// pairrank.hip route on them; each is written here and nowhere else).
+// Dynamic LDS of a workgroup of `waves` waves that each hold `pairs_per_wave` images of D4 float4.
+inline size_t spec_image_lds(int waves, int pairs_per_wave, int D4) {
+  return (size_t)waves * pairs_per_wave * spec_stride4(D4) * sizeof(float4);
+}
+// Widths with a kernel specialised at compile time: 100-d, 200-d and 300-d GloVe (D4 = 25, 50, 75).
+inline bool glove_width(int D) { return D == 300 || D == 200 || D == 100; }
+// A wave kernel keeps a pair in registers, at most four 16-byte loads per operand per lane of a whole wave.
+inline bool wave_width_ok(int D) { return D <= 1024; }
+// Two pairs per wave (32 candidate lanes each) only while the narrower windows hold: at D = 1024 the ordered
+// fp32 sum of a 344-term segment strays sigma ~ 6 ulp from its tree-sum prediction, the +-12 / +-15 windows
+// of 32 lanes missed on 3.4 % of pairs and the exact re-walks ate the gain at cfg 5's shard
+// size (19.5 vs 18.6 us; 125 vs 149 us at 65536 pairs).  One pair per wave beyond.
+inline int wave_pairs(int D) { return D <= 400 ? 2 : 1; }
 
 template <int LPR> struct SpecPlan;
 template <> struct SpecPlan<32> { static constexpr int H1 = 12, L1 = 13, H2 = 15; };
@@ -269,7 +285,7 @@ __device__ __forceinline__ float chain_sum_speculative(const float4* img4, int D
 }
 
 // Compile-time-length variants for the widths the wave-pair kernel is specialised
-// for (simcross_elementwise.hip: euclid_pair32_kernel).  H4 (float4s per segment)
+// for (simcross_rows.hip: euclid_pair32_kernel).  H4 (float4s per segment)
 // is a constant, so
 //  * the segment's LDS reads are all issued up front into registers (two waves
 //    per SIMD leave 256 VGPRs per lane) -- and BEFORE the window centres are

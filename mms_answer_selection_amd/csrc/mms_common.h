@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mms.h"
 
 namespace mms {
@@ -18,6 +20,17 @@ inline int launch_status() {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
+
+// A runtime bool as a template argument: with_bool(flag, [&](auto B) { launch K<..., decltype(B)::value> }).
+// Both instantiations of the lambda exist, as with `if (flag) K<true> else K<false>` written out.
+template <class F>
+inline void with_bool(bool flag, F&& f) {
+  if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+
+// The kernels K<NIT, ...> for NIT = 1..4 (16-byte loads per operand per lane) as one row of a table of kernel
+// pointers: `static constexpr decltype(&K<1, ...>) kernels[4] = MMS_NIT4(K, ...)`, launched as kernels[nit - 1].
+#define MMS_NIT4(K, ...) {K<1, __VA_ARGS__>, K<2, __VA_ARGS__>, K<3, __VA_ARGS__>, K<4, __VA_ARGS__>}
 
 // Write-once streaming stores (bottom diffs: written here, read by another kernel much
 // later): the non-temporal form does not allocate in L2, so the NEXT launch's reads are not

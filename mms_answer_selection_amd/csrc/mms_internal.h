@@ -6,7 +6,25 @@
 #include "mms_common.h"
 
 namespace mms {
-// simcross_elementwise.hip
+// simcross_rows.hip (W1 == W2 == 1)
+// false: no rows kernel serves this Euclid forward or fused launch, and the word-grid kernels take it.  `exact`:
+// euclid_backward_mode() == MMS_EUCLID_BWD_REFERENCE, read once by the entry point.  Instantiated for
+// <true, false>, <false, true> and <true, true>.
+template <bool FWD, bool BWD>
+bool launch_euclid_rows(int N, int D, const float* q, const float* a, const float* top_in, const float* top_diff,
+                        float* top_out, float* dq, float* da, bool exact, hipStream_t s);
+template <bool FWD, bool BWD>
+void launch_cosine_rows(int N, int D, const float* q, const float* a, const float* top_diff, float* top, float* norm0,
+                        float* norm1, float* dq, float* da, hipStream_t s);
+int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top, void* dq,
+                             void* da, bool bwd, hipStream_t s);
+int simcross_cosine_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top, float* norm0,
+                             float* norm1, void* dq, void* da, bool bwd, hipStream_t s);
+int euclid_backward_mode();
+void set_euclid_backward_mode(int m);
+int f16_distance_mode();
+void set_f16_distance_mode(int m);
+// simcross_cross.hip
 int simcross_elementwise_forward(int mode, int N, int W1, int W2, int D, const float* q, const float* a, float* top,
                                  float* norm0, float* norm1, hipStream_t s);
 int simcross_elementwise_backward(int mode, int N, int W1, int W2, int D, const float* q, const float* a, const float* top,
@@ -15,17 +33,9 @@ int simcross_elementwise_backward(int mode, int N, int W1, int W2, int D, const 
 int simcross_elementwise_forward_backward(int mode, int N, int W1, int W2, int D, const float* q, const float* a,
                                           const float* top_diff, float* top, float* norm0, float* norm1, float* dq,
                                           float* da, hipStream_t s);
-int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top, void* dq,
-                             void* da, bool bwd, hipStream_t s);
-int simcross_cosine_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top, float* norm0,
-                             float* norm1, void* dq, void* da, bool bwd, hipStream_t s);
 int embed_simcross_forward(int mode, int N, int W1, int W2, int D, int K, const float* index_q, const float* index_a,
                            const float* weight, const float* embed_bias, float* top, float* norm0, float* norm1,
                            hipStream_t s);
-int euclid_backward_mode();
-void set_euclid_backward_mode(int m);
-int f16_distance_mode();
-void set_f16_distance_mode(int m);
 // bilinear.hip
 size_t bilinear_workspace_bytes(int N, int W1, int W2, int D, int M);
 int bilinear_forward(int N, int W1, int W2, int D, int M, const float* q, const float* a, const float* W,

@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256) void triplet_wave_kernel(
 }
 
 // Width-specialised step (D = 100 / 200 / 300), the triplet counterpart of euclid_pair32_kernel
-// (simcross_elementwise.hip): D4C known at compile time, eight waves per workgroup, no early exit, N first
+// (simcross_rows.hip): D4C known at compile time, eight waves per workgroup, no early exit, N first
 // for the kernarg preload, streaming stores.  EXACT as in euclid_pair32_kernel (include/mms.h:
 // mms_set_euclid_backward_mode).
 // A wave owns triplets 2w and 2w+1: their rows of q, a+ and a- are ONE dense run of 2*D4C float4 per array
@@ -685,7 +685,7 @@ int triplet_euclid_step(int N, int D, float margin, float loss_weight, const flo
   const bool v = (D % 4 == 0) && aligned16(q) && aligned16(ap) && aligned16(an) &&
                  aligned16(dq) && aligned16(dap) && aligned16(dan);
   int nparts;
-  if (v && (D == 300 || D == 200 || D == 100)) {
+  if (v && glove_width(D)) {
     constexpr int WPB = 8;
     nparts = N;
     const unsigned grid = (unsigned)((N + WPB * 2 - 1) / (WPB * 2));   // two triplets per wave
@@ -713,24 +713,17 @@ int triplet_euclid_step(int N, int D, float margin, float loss_weight, const flo
 #undef MMS_T32
 #undef MMS_T32_GO
     if (tk) return launch_status();               // the loss was reduced inside the launch
-  } else if (v && D <= 1024) {
+  } else if (v && wave_width_ok(D)) {
     const int D4 = D / 4;
     const int nit = (D4 + 63) / 64;
     nparts = N;
     const unsigned grid = (unsigned)((N + 3) / 4);
-    const size_t lds = (size_t)4 * 2 * 3 * ((D4 + 2) / 3) * sizeof(float4);
-    const bool spec = D <= 400;   // +-15 ulp window: see euclid_math.h
-#define MMS_NIT_CASE(n)                                                                         \
-  case n:                                                                                       \
-    if (spec)                                                                                   \
-      hipLaunchKernelGGL((triplet_wave_kernel<n, true>), dim3(grid), dim3(256), lds, s, N, D4,  \
-                         margin, s0, s1, q, ap, an, y, s_pos, s_neg, partials, dq, dap, dan, hge);   \
-    else                                                                                        \
-      hipLaunchKernelGGL((triplet_wave_kernel<n, false>), dim3(grid), dim3(256), lds, s, N, D4, \
-                         margin, s0, s1, q, ap, an, y, s_pos, s_neg, partials, dq, dap, dan, hge);   \
-    break;
-    switch (nit) { MMS_NIT_CASE(1) MMS_NIT_CASE(2) MMS_NIT_CASE(3) MMS_NIT_CASE(4) }
-#undef MMS_NIT_CASE
+    const size_t lds = spec_image_lds(4, 2, D4);   // one triplet per wave: the images of its two pairs
+    const bool spec = wave_pairs(D) == 2;          // the +-15 ulp window of 32 lanes holds: see euclid_math.h
+    static constexpr decltype(&triplet_wave_kernel<1, true>) kernels[2][4] = {MMS_NIT4(triplet_wave_kernel, false),
+                                                                              MMS_NIT4(triplet_wave_kernel, true)};
+    hipLaunchKernelGGL(kernels[spec][nit - 1], dim3(grid), dim3(256), lds, s, N, D4, margin, s0, s1, q, ap, an, y,
+                       s_pos, s_neg, partials, dq, dap, dan, hge);
   } else {
     const size_t lds = 2 * (size_t)kTripRows * D * sizeof(float);
     if (lds > 96 * 1024) return MMS_ERR_UNSUPPORTED;
@@ -998,7 +991,7 @@ int triplet_cosine_step(int N, int D, float margin, float loss_weight, const flo
   // unfused backward picks its expression from the alignment of the gradients as well.
   const bool vin = (D % 4 == 0) && aligned16(q) && aligned16(ap) && aligned16(an);
   const bool vout = aligned16(dq) && aligned16(dap) && aligned16(dan);
-  if (vin && (D == 300 || D == 200 || D == 100)) {
+  if (vin && glove_width(D)) {
     constexpr int WPB = 8;
     const unsigned grid = (unsigned)((N + WPB * 2 - 1) / (WPB * 2));   // two triplets per wave
     const unsigned ngrp = (grid + kTicketGroup - 1) / kTicketGroup;
@@ -1021,24 +1014,17 @@ int triplet_cosine_step(int N, int D, float margin, float loss_weight, const flo
 #undef MMS_C32
 #undef MMS_C32_GO
     if (tk) return launch_status();               // the loss was reduced inside the launch
-  } else if (vin && vout && D <= 1024) {
+  } else if (vin && vout && wave_width_ok(D)) {
     const int D4 = D / 4;
-    const unsigned grid = (unsigned)((N + 3) / 4);
-#define MMS_NIT_CASE(n)                                                                                     \
-  case n:                                                                                                   \
-    hipLaunchKernelGGL((triplet_cosine_wave_kernel<n>), dim3(grid), dim3(256), 0, s, N, D4, margin, s0, s1, \
-                       q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge); \
-    break;
-    switch ((D4 + 63) / 64) { MMS_NIT_CASE(1) MMS_NIT_CASE(2) MMS_NIT_CASE(3) MMS_NIT_CASE(4) }
-#undef MMS_NIT_CASE
+    static constexpr decltype(&triplet_cosine_wave_kernel<1>) kernels[4] = {
+        triplet_cosine_wave_kernel<1>, triplet_cosine_wave_kernel<2>, triplet_cosine_wave_kernel<3>,
+        triplet_cosine_wave_kernel<4>};
+    hipLaunchKernelGGL(kernels[(D4 + 63) / 64 - 1], dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, D4, margin, s0,
+                       s1, q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge);
   } else {
-    const unsigned grid = (unsigned)((N + 3) / 4);
-    if (vin)
-      hipLaunchKernelGGL((triplet_cosine_rows_kernel<true>), dim3(grid), dim3(256), 0, s, N, D, margin, s0, s1,
-                         q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge);
-    else
-      hipLaunchKernelGGL((triplet_cosine_rows_kernel<false>), dim3(grid), dim3(256), 0, s, N, D, margin, s0, s1,
-                         q, ap, an, y, s_pos, s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge);
+    hipLaunchKernelGGL((vin ? triplet_cosine_rows_kernel<true> : triplet_cosine_rows_kernel<false>),
+                       dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, D, margin, s0, s1, q, ap, an, y, s_pos,
+                       s_neg, norm_q, norm_pos, norm_neg, partials, dq, dap, dan, hge);
   }
   if (loss == nullptr) return launch_status();     // the caller does not want the scalar: no reduction at all
   return triplet_loss_from_terms(partials, N, loss, s);

@@ -1,0 +1,1178 @@
+// csrc/simcross_rows.hip -- SimCross dist_mode 0 (cosine) and 1 (Euclidean) for W1 == W2 == 1 (sentence-vector
+// pairs; BASELINE cfg 2/5), fp32 and fp16 storage, for gfx950.  HBM-bound: no MFMA here.  The word-grid kernels
+// and the three fp32 entry points, which try this side first, are in simcross_cross.hip.
+//
+// Reference semantics (all file:line in src/caffe/layers/sim_cross_layer.cpp):
+//   Euclid fwd  :96-111   T = 1/(1+sqrt(sum_d (q-a)^2)), d ascending, fp32.
+//   Euclid bwd  :208-225  tt = dT*T*T*T*(q-a)/(T-1+1e-9) (double divide); dq[d] = tt, da[d] = -tt.
+//   Cosine fwd  :112-139  n0,n1 = sqrt(dot) cached; T = dot/n0/n1.
+//   Cosine bwd  :226-250.
+//
+// A workgroup owns ROWS consecutive pairs, streams them with 16-byte loads into LDS, and ONE lane per pair walks d
+// ascending so the sum has the reference's order bit for bit.  The forward+backward fusion keeps q-a in LDS (or in
+// registers) so q and a are read from HBM once.
+//
+// Compiled with -ffp-contract=off: the reference CPU build has no FMA
+// contraction, so mul and add must round separately to match it bitwise.
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+
+#include "cosine_math.h"
+#include "euclid_math.h"
+#include "mms_internal.h"
+
+namespace mms {
+
+// ---- wave-centric kernel (the fast path) ------------------------------------
+// A wave owns RW (1 or 2) consecutive pairs (RW*D/4 float4 per operand); the
+// four waves of a workgroup are independent (no workgroup barrier).  Timeline
+// of one wave:
+//   1. ALL its 16-byte loads of q and a are issued back to back (NIT per
+//      operand per lane, predicated) -- nothing waits inside a loop;
+//   2. diff = q-a stays in registers; diff^2 goes to the wave's LDS slice;
+//   3. the d-ascending sum of each pair's squares -- the reference's summation
+//      order -- is evaluated by the pair's 64/RW lanes with the speculative
+//      two-segment scheme of euclid_math.h (bit-exact, half the chain length);
+//   4. every lane derives T and the backward coefficients of its pair
+//      (wave-uniform per lane group; no LDS round trip);
+//   5. every lane turns its register-resident diffs into dq / da and stores
+//      16 bytes per lane.
+// FWD only stops after 3; BWD only skips 2-3 and reads T from memory.
+template <int NIT, int RW, bool FWD, bool BWD>
+__global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
+    const float* __restrict__ q, const float* __restrict__ a,
+    const float* __restrict__ top_in, const float* __restrict__ top_diff,
+    float* __restrict__ top_out, float* __restrict__ dq, float* __restrict__ da, int N,
+    int D4) {
+  constexpr int LPR = 64 / RW;                   // lanes per pair
+  extern __shared__ float4 lds4[];               // [4 waves][RW split images] (euclid_math.h)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row0 = (blockIdx.x * 4 + wave) * RW;
+  if (row0 >= N) return;                         // whole wave leaves; no block barrier below
+  const int rows = min(RW, N - row0);
+  const int n4 = rows * D4;
+  const size_t base4 = (size_t)row0 * D4;
+  const float4* q4 = reinterpret_cast<const float4*>(q) + base4;
+  const float4* a4 = reinterpret_cast<const float4*>(a) + base4;
+  const int st4 = spec_stride4(D4);
+  float4* sq4 = lds4 + (size_t)wave * RW * st4;
+
+  float4 x[NIT], y[NIT], df[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    const int ii = i < n4 ? i : 0;               // clamp: keep the load unconditional
+    x[it] = q4[ii];
+    y[it] = a4[ii];
+  }
+  // this lane's pair for the chain / coefficient work
+  const int grp = lane / LPR, j = lane % LPR;
+  const int grow = min(grp, rows - 1);           // a missing 2nd pair mirrors the 1st (results unused)
+  float T = 0.f;
+  if (!FWD) T = top_in[row0 + grow];
+  float g = 0.f;
+  if (BWD) g = top_diff[row0 + grow];
+
+  float2v pred[RW];                              // per pair: (pred1, pred2) partial sums
+#pragma unroll
+  for (int r = 0; r < RW; ++r) pred[r] = (float2v){0.f, 0.f};
+  const int h4 = spec_h4(D4);
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    df[it].x = x[it].x - y[it].x; df[it].y = x[it].y - y[it].y;
+    df[it].z = x[it].z - y[it].z; df[it].w = x[it].w - y[it].w;
+    if (FWD) {
+      const int i = lane + 64 * it;
+      float4 s;
+      s.x = df[it].x * df[it].x; s.y = df[it].y * df[it].y;
+      s.z = df[it].z * df[it].z; s.w = df[it].w * df[it].w;
+      // image slot of this float4 (pair r's image starts at r*st4) and its tree-sum
+      // contribution to the two predictions of the pair it belongs to
+      const bool r1 = (RW == 2) && (i >= D4);
+      const int ir = r1 ? i - D4 : i;
+      if (i < n4) sq4[r1 ? i + (st4 - D4) : i] = s;
+      const float s4 = (i < n4) ? (s.x + s.y) + (s.z + s.w) : 0.f;
+      float2v c;                                   // (segment-0 part, segments-0-1 part)
+      c.x = (ir < h4) ? s4 : 0.f;
+      c.y = (ir < 2 * h4) ? s4 : 0.f;
+      const float2v z2 = {0.f, 0.f};
+      pred[0] += r1 ? z2 : c;
+      if (RW == 2) pred[RW - 1] += r1 ? c : z2;
+    }
+  }
+  if (FWD) {
+    // zero pad at the end of each image (0..2 entries)
+    const int npad = st4 - D4;
+    if (lane < RW * npad) sq4[(lane / npad) * st4 + D4 + (lane % npad)] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float my1 = 0.f, my2 = 0.f;
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+      const float p1 = wave_sum(pred[r].x), p2 = wave_sum(pred[r].y);
+      if (r == grow) { my1 = p1; my2 = p2; }
+    }
+    wave_lds_sync();
+    const float dist = chain_sum_speculative<LPR>(sq4 + grow * st4, D4, my1, my2, j, grp * LPR);
+    T = 1.0f / (1.0f + sqrtf(dist));            // :106-107
+    if (BWD) asm volatile("" : "+v"(g));        // in a register before the store of T (see euclid_pair32_kernel)
+    if (j == 0 && grp < rows) top_out[row0 + grp] = T;
+  }
+  if (!BWD) return;
+
+  // coefficients of this lane group's pair, then of the pairs this lane's elements belong to
+  const EuclidCoef mine = euclid_coef(T, g);
+  EuclidCoef kr[RW];
+#pragma unroll
+  for (int r = 0; r < RW; ++r) {
+    // lane r*LPR is a compile-time lane: v_readlane (no LDS round trip as with ds_bpermute)
+    kr[r].c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.c), r * LPR));
+    {
+      const long long dn = __double_as_longlong(mine.den), rc = __double_as_longlong(mine.rcp);
+      const unsigned dlo = __builtin_amdgcn_readlane((int)(unsigned)dn, r * LPR);
+      const unsigned dhi = __builtin_amdgcn_readlane((int)(unsigned)(dn >> 32), r * LPR);
+      const unsigned rlo = __builtin_amdgcn_readlane((int)(unsigned)rc, r * LPR);
+      const unsigned rhi = __builtin_amdgcn_readlane((int)(unsigned)(rc >> 32), r * LPR);
+      kr[r].den = __longlong_as_double((long long)(((unsigned long long)dhi << 32) | dlo));
+      kr[r].rcp = __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
+    }
+  }
+  float4* dq4 = reinterpret_cast<float4*>(dq) + base4;
+  float4* da4 = reinterpret_cast<float4*>(da) + base4;
+  // all NIT float4s as ONE straight-line block (their instruction chains interleave),
+  // then a single wave-level branch for the rare exact re-computation
+  float4 t[NIT];
+  bool any_risky = false;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    const EuclidCoef& k = (RW == 2 && i >= D4) ? kr[RW - 1] : kr[0];
+    bool risky;
+    t[it] = euclid_tt4_fast(k, df[it], risky);
+    any_risky |= risky && (i < n4);
+  }
+  if (any_risky) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = lane + 64 * it;
+      const EuclidCoef& k = (RW == 2 && i >= D4) ? kr[RW - 1] : kr[0];
+      t[it] = euclid_tt4_exact(k, df[it]);
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    if (i >= n4) break;
+    // dq = 0 + tt ; da = 0 + (-tt)   (:176-177 zero, :219-220 accumulate once)
+    float4 o0, o1;
+    o0.x = 0.f + t[it].x; o0.y = 0.f + t[it].y; o0.z = 0.f + t[it].z; o0.w = 0.f + t[it].w;
+    o1.x = 0.f + (-t[it].x); o1.y = 0.f + (-t[it].y); o1.z = 0.f + (-t[it].z); o1.w = 0.f + (-t[it].w);
+    stream_store(dq4 + i, o0);
+    stream_store(da4 + i, o1);
+  }
+}
+
+// ---- width-specialised wave-pair kernel (the headline configuration) ----------
+// Same algorithm as euclid_rows_wave_kernel<.., RW = 2, ..> for D/4 = D4C known at
+// compile time, with the layout made ROW-ALIGNED: lanes 0-31 own pair 2w, lanes
+// 32-63 pair 2w+1, lane j holds float4s j, j+32, j+64 of its pair.  A lane then
+// belongs to ONE pair for everything it does (loads, squares, speculation lane,
+// coefficients, stores): no per-slot pair masks, no cross-lane broadcast of the
+// coefficients, half-wave DPP sums, and every loop bound is a constant, so the
+// chain is straight-line code.  About 40 % fewer wave-instructions than the
+// generic kernel, which is what bounds this kernel.
+//
+// EXACT selects the arithmetic of the backward term tt = dT*T^3*(q-a)/(T-1+1e-9):
+//   true : the reference's bits (fp32 product, DOUBLE divisor, one rounding to
+//          float) through the checked reciprocal fast path of euclid_math.h;
+//   false: fp32 throughout, tt = (c*(q-a)) * fl32(1/den): at most 2 ulp from the
+//          reference's value (1.2e-7 relative against the 1e-5 bar), a third of
+//          the instructions.  The FORWARD value T is bit-exact in both.
+template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB>
+__global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
+    int N, const float* __restrict__ q, const float* __restrict__ a,
+    const float* __restrict__ top_in, const float* __restrict__ top_diff,
+    float* __restrict__ top_out, float* __restrict__ dq, float* __restrict__ da) {
+  // N first: with -amdgpu-kernarg-preload-count the leading arguments arrive in SGPRs at wave
+  // start, so the loads below do not wait on a scalar fetch of the argument block
+  constexpr int NIT = (D4C + 31) / 32;
+  constexpr int LASTN = D4C - 32 * (NIT - 1);    // lanes with a float4 in the last slot
+  constexpr int H4 = (D4C + 2) / 3, ST4 = 3 * H4;
+  __shared__ float4 lds4[FWD ? WPB * 2 * ST4 : 1];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int grp = lane >> 5, j = lane & 31;
+  // No early exit: a wave past the end works on the last pair and stores nothing, so that no
+  // branch (and no wait on the kernel arguments) stands between wave start and the loads.
+  const int want = (blockIdx.x * WPB + wave) * 2 + grp;
+  const bool have = want < N;
+  const int row = have ? want : N - 1;
+  const float4* q4 = reinterpret_cast<const float4*>(q) + (size_t)row * D4C;
+  const float4* a4 = reinterpret_cast<const float4*>(a) + (size_t)row * D4C;
+  const bool last_ok = (LASTN >= 32) || (j < LASTN);
+
+  float T = 0.f;
+  if (!FWD) T = top_in[row];
+  float g = 0.f;
+  if (BWD) g = top_diff[row];
+  float4 x[NIT], y[NIT], df[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = (it < NIT - 1 || last_ok) ? j + 32 * it : 0;   // clamp: keep the load unconditional
+    x[it] = q4[i];
+    y[it] = a4[i];
+  }
+
+  float p1 = 0.f, p2 = 0.f;
+  float4* img = lds4 + (wave * 2 + grp) * ST4;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    df[it].x = x[it].x - y[it].x; df[it].y = x[it].y - y[it].y;
+    df[it].z = x[it].z - y[it].z; df[it].w = x[it].w - y[it].w;
+    if (FWD) {
+      const bool valid = (it < NIT - 1) || last_ok;
+      float4 s;
+      s.x = df[it].x * df[it].x; s.y = df[it].y * df[it].y;
+      s.z = df[it].z * df[it].z; s.w = df[it].w * df[it].w;
+      if (valid) img[j + 32 * it] = s;
+      const float s4 = valid ? (s.x + s.y) + (s.z + s.w) : 0.f;
+      const int i = j + 32 * it;
+      // tree-sum contributions to the two window centres (segment 0; segments 0-1)
+      if (32 * it + 31 < H4) p1 += s4;
+      else if (32 * it < H4) p1 += (i < H4) ? s4 : 0.f;
+      if (32 * it + 31 < 2 * H4) p2 += s4;
+      else if (32 * it < 2 * H4) p2 += (i < 2 * H4) ? s4 : 0.f;
+    }
+  }
+  if (FWD) {
+    if (ST4 > D4C && j < ST4 - D4C) img[D4C + j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    wave_lds_sync();
+    SpecSegment<H4> sg;
+    sg.load(img + spec_seg32(j) * H4);          // in flight while the window centres are reduced
+    p1 = half_wave_sum(p1);
+    p2 = half_wave_sum(p2);
+    __builtin_amdgcn_s_setprio(3);
+    const float2v start = spec_start32(p1, p2, j);
+    const float2v end = sg.chain(start);
+    bool hit;
+    float dist = spec_resolve_halves(start, end, j, &hit);
+    if (!hit) {                                 // uniform per half; exact re-walk of this lane's pair
+      dist = chain_sum_lds(img, ST4, 0.0f);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    T = 1.0f / (1.0f + sqrtf(dist));            // :106-107
+    // g is pinned as "in a register" HERE, before the store of T: left to the compiler, its first use came
+    // after that store (issued under a lane mask, so the wait could not be counted) and every wave sat in
+    // s_waitcnt vmcnt(0) until the store was acknowledged
+    if (BWD) asm volatile("" : "+v"(g));
+    if (j == 0 && have) top_out[row] = T;
+  }
+  if (!BWD) return;
+
+  float4* dq4 = reinterpret_cast<float4*>(dq) + (size_t)row * D4C;
+  float4* da4 = reinterpret_cast<float4*>(da) + (size_t)row * D4C;
+  if (!FWD) {                                   // all requests landed before the first store (see euclid_block_kernel)
+    asm volatile("" : "+v"(T), "+v"(g));
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+      asm volatile("" : "+v"(df[it].x), "+v"(df[it].y), "+v"(df[it].z), "+v"(df[it].w));
+  }
+  float4 t[NIT];
+  if (EXACT) {
+    const EuclidCoef k = euclid_coef(T, g);
+    bool any_risky = false;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      bool risky;
+      t[it] = euclid_tt4_fast(k, df[it], risky);
+      any_risky |= risky && ((it < NIT - 1) || last_ok);
+    }
+    if (any_risky) {
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) t[it] = euclid_tt4_exact(k, df[it]);
+    }
+  } else {
+    const float c = g * T * T * T;
+    const float r = (float)rcp_newton((double)(T - 1.0f) + 1e-9);
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      t[it].x = (c * df[it].x) * r; t[it].y = (c * df[it].y) * r;
+      t[it].z = (c * df[it].z) * r; t[it].w = (c * df[it].w) * r;
+    }
+  }
+  if (have) {
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if (!((it < NIT - 1) || last_ok)) break;
+    // dq = 0 + tt ; da = 0 + (-tt)   (:176-177 zero, :219-220 accumulate once)
+    float4 o0, o1;
+    o0.x = 0.f + t[it].x; o0.y = 0.f + t[it].y; o0.z = 0.f + t[it].z; o0.w = 0.f + t[it].w;
+    o1.x = 0.f + (-t[it].x); o1.y = 0.f + (-t[it].y); o1.z = 0.f + (-t[it].z); o1.w = 0.f + (-t[it].w);
+    stream_store(dq4 + j + 32 * it, o0);
+    stream_store(da4 + j + 32 * it, o1);
+  }
+  }
+}
+
+// ---- the same algorithm with the global-memory side laid out by WORKGROUP, not by pair ----------
+// Measured (tools/launchbench.hip, profiles/r02_launchbench.txt): HBM-cold, a launch whose waves each read
+// two 512-byte pieces 1200 bytes apart per load instruction (the row-aligned layout above) takes 4.4 us for
+// q and a of cfg 2, a launch whose workgroup reads its rows as ONE dense run (instruction `it` of all its
+// waves covers a contiguous span) takes 3.6 us -- the speed of a flat one-float4-per-thread read; the
+// write side behaves the same (6.5 vs 5.5 us for a backward-shaped launch).  What costs is the order in
+// which a CU's requests reach a DRAM page: three visits at different times against one.
+// So: a workgroup of WPB waves owns R = 2*WPB consecutive pairs = C = R*D4C consecutive float4 of q and of
+// a; thread t loads float4s t, t+T, t+2T ... of that run (and stores dq / da the same way).  The squares
+// go to LDS at (pair, column) -- the image layout the chain wants -- and after ONE workgroup barrier each
+// half-wave walks its pair's chain exactly as in euclid_pair32_kernel (same predictions, same windows,
+// same bits).  A thread's float4s belong to whatever pairs they fall in, so the backward reads T (and the
+// per-pair coefficients) by pair index: from LDS when this launch computed T, from top_in otherwise -- a
+// backward-only launch has no LDS traffic and no barrier at all.
+// SPAN = waves that share one dense run: WPB (the whole workgroup, one barrier) or 1 (each wave reads its own two
+// rows as a dense run and synchronises with nobody: the chain phases of a CU's waves then start as their own data
+// arrives instead of all at once).
+template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB, int SPAN = WPB>
+__global__ __launch_bounds__(64 * WPB) void euclid_block_kernel(
+    int N, const float* __restrict__ q, const float* __restrict__ a,
+    const float* __restrict__ top_in, const float* __restrict__ top_diff,
+    float* __restrict__ top_out, float* __restrict__ dq, float* __restrict__ da) {
+  static_assert(SPAN == WPB || SPAN == 1, "a dense run belongs to the workgroup or to one wave");
+  constexpr int T = 64 * SPAN, R = 2 * SPAN, C = R * D4C;
+  constexpr int NSPAN = WPB / SPAN;                          // runs per workgroup
+  constexpr int NIT = (C + T - 1) / T;                       // float4s per operand per thread
+  constexpr int PNIT = (D4C + 31) / 32, LASTN = D4C - 32 * (PNIT - 1);
+  constexpr int H4 = (D4C + 2) / 3, ST4 = 3 * H4;
+  __shared__ float4 lds4_all[FWD ? NSPAN * R * ST4 : 1];
+  __shared__ float Tl_all[(FWD && BWD) ? NSPAN * R : 1];
+  const int span = (SPAN == WPB) ? 0 : (int)(threadIdx.x >> 6);
+  const int tid = (SPAN == WPB) ? (int)threadIdx.x : (int)(threadIdx.x & 63);
+  float4* lds4 = lds4_all + (FWD ? span * R * ST4 : 0);
+  float* Tl = Tl_all + ((FWD && BWD) ? span * R : 0);
+  const long long run = (long long)blockIdx.x * NSPAN + span;   // index of this dense run
+  const long long total4 = (long long)N * D4C;
+  const long long b = run * C;
+  const float4* q4 = reinterpret_cast<const float4*>(q);
+  const float4* a4 = reinterpret_cast<const float4*>(a);
+
+  float4 x[NIT], y[NIT], df[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = tid + T * it;
+    long long gi = b + ((NIT * T == C || i < C) ? i : 0);     // clamp: keep the load unconditional
+    gi = gi < total4 ? gi : total4 - 1;                       // a run past the end reads the last float4
+    x[it] = q4[gi];
+    y[it] = a4[gi];
+  }
+  // per-float4 pair coefficients of a backward-only launch: requested with the operands
+  float Tg[NIT], gg[NIT];
+  if (BWD) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + T * it;
+      long long row = run * R + ((NIT * T == C || i < C) ? i : 0) / D4C;
+      row = row < N ? row : N - 1;
+      gg[it] = top_diff[row];
+      if (!FWD) Tg[it] = top_in[row];
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    df[it].x = x[it].x - y[it].x; df[it].y = x[it].y - y[it].y;
+    df[it].z = x[it].z - y[it].z; df[it].w = x[it].w - y[it].w;
+    if (FWD) {
+      const int i = tid + T * it;
+      float4 s;
+      s.x = df[it].x * df[it].x; s.y = df[it].y * df[it].y;
+      s.z = df[it].z * df[it].z; s.w = df[it].w * df[it].w;
+      if (NIT * T == C || i < C) lds4[(ST4 == D4C) ? i : (i / D4C) * ST4 + (i % D4C)] = s;
+    }
+  }
+  if (FWD) {
+    if constexpr (ST4 > D4C) {                              // zero tail of each image
+      if (tid < R * (ST4 - D4C))
+        lds4[(tid / (ST4 - D4C)) * ST4 + D4C + tid % (ST4 - D4C)] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (SPAN == WPB) __syncthreads(); else wave_lds_sync();
+    const int wave = tid >> 6, lane = tid & 63;
+    const int grp = lane >> 5, j = lane & 31;
+    const int lp = wave * 2 + grp;
+    const long long row = run * R + lp;
+    const bool have = row < N;
+    const float4* img = lds4 + lp * ST4;
+    SpecSegment<H4> sg;
+    sg.load(img + spec_seg32(j) * H4);          // in flight while the window centres are formed
+    // tree-sum contributions to the two window centres (segment 0; segments 0-1): the same per-lane
+    // terms and the same reduction as euclid_pair32_kernel, read back from the image
+    const bool last_ok = (LASTN >= 32) || (j < LASTN);
+    float p1 = 0.f, p2 = 0.f;
+#pragma unroll
+    for (int it = 0; it < PNIT; ++it) {
+      const bool valid = (it < PNIT - 1) || last_ok;
+      const float4 s = img[valid ? j + 32 * it : 0];
+      const float s4 = valid ? (s.x + s.y) + (s.z + s.w) : 0.f;
+      const int i = j + 32 * it;
+      if (32 * it + 31 < H4) p1 += s4;
+      else if (32 * it < H4) p1 += (i < H4) ? s4 : 0.f;
+      if (32 * it + 31 < 2 * H4) p2 += s4;
+      else if (32 * it < 2 * H4) p2 += (i < 2 * H4) ? s4 : 0.f;
+    }
+    p1 = half_wave_sum(p1);
+    p2 = half_wave_sum(p2);
+    __builtin_amdgcn_s_setprio(3);
+    const float2v start = spec_start32(p1, p2, j);
+    const float2v end = sg.chain(start);
+    bool hit;
+    float dist = spec_resolve_halves(start, end, j, &hit);
+    if (!hit) {                                 // uniform per half; exact re-walk of this lane's pair
+      dist = chain_sum_lds(img, ST4, 0.0f);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    const float Tp = 1.0f / (1.0f + sqrtf(dist));            // :106-107
+    if (BWD) {                                  // in registers before the store of T (see euclid_pair32_kernel)
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) asm volatile("" : "+v"(gg[it]));
+    }
+    if (j == 0) {
+      if (have) top_out[row] = Tp;
+      if (BWD) Tl[lp] = Tp;
+    }
+    if (BWD) { if (SPAN == WPB) __syncthreads(); else wave_lds_sync(); }
+  }
+  if (!BWD) return;
+
+  float4* dq4 = reinterpret_cast<float4*>(dq);
+  float4* da4 = reinterpret_cast<float4*>(da);
+  if (!FWD) {
+    // Everything this thread requested is in registers before its first store.  The stores sit under lane masks
+    // (the end of the batch), so the compiler cannot count them: a load consumed after a store became
+    // s_waitcnt vmcnt(0), i.e. a wait for the ACKNOWLEDGEMENT of the stores already issued -- in the middle of
+    // the store phase of the launch that bounds the headline.
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      asm volatile("" : "+v"(gg[it]), "+v"(Tg[it]));
+      asm volatile("" : "+v"(df[it].x), "+v"(df[it].y), "+v"(df[it].z), "+v"(df[it].w));
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = tid + T * it;
+    const bool live = (NIT * T == C || i < C) && (b + i < total4);
+    const float Tp = FWD ? Tl[((NIT * T == C || i < C) ? i : 0) / D4C] : Tg[it];
+    float4 t;
+    if (EXACT) {
+      const EuclidCoef k = euclid_coef(Tp, gg[it]);
+      t = euclid_tt4(k, df[it]);
+    } else {
+      const float c = gg[it] * Tp * Tp * Tp;
+      const float r = (float)rcp_newton((double)(Tp - 1.0f) + 1e-9);
+      t.x = (c * df[it].x) * r; t.y = (c * df[it].y) * r;
+      t.z = (c * df[it].z) * r; t.w = (c * df[it].w) * r;
+    }
+    if (live) {
+      // dq = 0 + tt ; da = 0 + (-tt)   (:176-177 zero, :219-220 accumulate once)
+      float4 o0, o1;
+      o0.x = 0.f + t.x; o0.y = 0.f + t.y; o0.z = 0.f + t.z; o0.w = 0.f + t.w;
+      o1.x = 0.f + (-t.x); o1.y = 0.f + (-t.y); o1.z = 0.f + (-t.z); o1.w = 0.f + (-t.w);
+      stream_store(dq4 + b + i, o0);
+      stream_store(da4 + b + i, o1);
+    }
+  }
+}
+
+// ---- fp16 storage, fp32 arithmetic (BASELINE cfg 5) --------------------------
+// Same wave-centric structure with one pair per wave (cfg 5 is D = 1024): q, a,
+// dq, da live in HBM as IEEE half (half the bytes per pair: s = 2 in SURVEY
+// 8d's formulas); every half is widened exactly to fp32 on load, ALL arithmetic
+// is the fp32 reference arithmetic in the reference order, and only the final
+// dq / da are rounded (RNE) to half.  The scores stay fp32.  Hence:
+//   top == oracle(fp32(q_half), fp32(a_half)) bit for bit, and
+//   dq  == half(oracle dq) bit for bit.
+// The reference has no fp16 instantiation (common.hpp:41-44); this is an
+// MI355X-side storage format, not a change of the layer's numerics.
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+
+// RW pairs per wave (64 / RW lanes each).  The ordered sum runs with RW == 2 (D <= 400: beyond that its
+// speculation windows of 32 lanes miss too often, see simcross_euclid_rows_f16, and the lane-chain kernel
+// below takes over); a miss re-walks one segment exactly, so results never change, only time.
+// TREE (RW == 1 only): the distance is the TREE sum of the squares that the ordered variants use only to centre
+// their speculation windows -- no ordered chain, 8.3 instead of 19 us at cfg 5's shard.  The reference has no
+// fp16 instantiation, so there is no reference rounding to reproduce; SURVEY 8(d) holds cfg 5 to 1e-3 relative
+// against the fp32 oracle on the fp16-rounded inputs, and this sum is within ~1e-6 of it.  Opt-in
+// (mms_set_f16_distance_mode): the default stays the ordered sum, bit-identical to the fp32 layer's.
+template <int NIT, int RW, bool BWD, bool TREE = false>
+__global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
+    const _Float16* __restrict__ q, const _Float16* __restrict__ a,
+    const float* __restrict__ top_diff, float* __restrict__ top_out,
+    _Float16* __restrict__ dq, _Float16* __restrict__ da, int N, int D8) {
+  constexpr int LPR = 64 / RW;
+  extern __shared__ float4 lds4[];               // [4 waves][RW images] (euclid_math.h)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row0 = (blockIdx.x * 4 + wave) * RW;
+  if (row0 >= N) return;
+  const int rows = min(RW, N - row0);
+  const int n8 = rows * D8;
+  const int D4 = 2 * D8;
+  const size_t base8 = (size_t)row0 * D8;
+  const half8* q8 = reinterpret_cast<const half8*>(q) + base8;
+  const half8* a8 = reinterpret_cast<const half8*>(a) + base8;
+  const int h4 = spec_h4(D4), st4 = 3 * h4;
+  float4* sq4 = lds4 + (size_t)wave * RW * st4;
+
+  half8 x[NIT], y[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    const int ii = i < n8 ? i : 0;
+    x[it] = q8[ii];
+    y[it] = a8[ii];
+  }
+  const int grp = lane / LPR, j = lane % LPR;
+  const int grow = min(grp, rows - 1);           // a missing 2nd pair mirrors the 1st (results unused)
+  float g = 0.f;
+  if (BWD) g = top_diff[row0 + grow];
+
+  float4 df[2 * NIT];
+  float tree_total = 0.f;
+  float2v pred[RW];                              // per pair: (pred1, pred2) partial sums
+#pragma unroll
+  for (int r = 0; r < RW; ++r) pred[r] = (float2v){0.f, 0.f};
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    const bool r1 = (RW == 2) && (i >= D8);
+    const int ir = r1 ? i - D8 : i;              // half8 index inside its pair
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      float4 d;
+      d.x = (float)x[it][4 * hh + 0] - (float)y[it][4 * hh + 0];
+      d.y = (float)x[it][4 * hh + 1] - (float)y[it][4 * hh + 1];
+      d.z = (float)x[it][4 * hh + 2] - (float)y[it][4 * hh + 2];
+      d.w = (float)x[it][4 * hh + 3] - (float)y[it][4 * hh + 3];
+      df[2 * it + hh] = d;
+      float4 s;
+      s.x = d.x * d.x; s.y = d.y * d.y; s.z = d.z * d.z; s.w = d.w * d.w;
+      const int i4 = 2 * ir + hh;                // float4 index inside the pair's image
+      if (!TREE && i < n8) sq4[(r1 ? st4 : 0) + i4] = s;
+      const float s4 = (i < n8) ? (s.x + s.y) + (s.z + s.w) : 0.f;
+      if (TREE) tree_total += s4;
+      float2v c;
+      c.x = (i4 < h4) ? s4 : 0.f;
+      c.y = (i4 < 2 * h4) ? s4 : 0.f;
+      const float2v z2 = {0.f, 0.f};
+      pred[0] += r1 ? z2 : c;
+      if (RW == 2) pred[RW - 1] += r1 ? c : z2;
+    }
+  }
+  const int npad = st4 - D4;
+  if (lane < RW * npad) sq4[(lane / npad) * st4 + D4 + (lane % npad)] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float my1 = 0.f, my2 = 0.f;
+#pragma unroll
+  for (int r = 0; r < RW; ++r) {
+    const float p1 = wave_sum(pred[r].x), p2 = wave_sum(pred[r].y);
+    if (r == grow) { my1 = p1; my2 = p2; }
+  }
+  wave_lds_sync();
+  const float dist = TREE ? wave_sum(tree_total)
+                          : chain_sum_speculative<LPR>(sq4 + grow * st4, D4, my1, my2, j, grp * LPR);
+  const float T = 1.0f / (1.0f + sqrtf(dist));
+  if (BWD) asm volatile("" : "+v"(g));          // in a register before the store of T (see euclid_pair32_kernel)
+  if (j == 0 && grp < rows) top_out[row0 + grp] = T;
+  if (!BWD) return;
+
+  const EuclidCoef mine = euclid_coef(T, g);
+  EuclidCoef kr[RW];
+#pragma unroll
+  for (int r = 0; r < RW; ++r) {                 // lane r*LPR is a compile-time lane: v_readlane
+    kr[r].c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.c), r * LPR));
+    const long long dn = __double_as_longlong(mine.den), rc = __double_as_longlong(mine.rcp);
+    const unsigned dlo = __builtin_amdgcn_readlane((int)(unsigned)dn, r * LPR);
+    const unsigned dhi = __builtin_amdgcn_readlane((int)(unsigned)(dn >> 32), r * LPR);
+    const unsigned rlo = __builtin_amdgcn_readlane((int)(unsigned)rc, r * LPR);
+    const unsigned rhi = __builtin_amdgcn_readlane((int)(unsigned)(rc >> 32), r * LPR);
+    kr[r].den = __longlong_as_double((long long)(((unsigned long long)dhi << 32) | dlo));
+    kr[r].rcp = __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
+  }
+  half8* dq8 = reinterpret_cast<half8*>(dq) + base8;
+  half8* da8 = reinterpret_cast<half8*>(da) + base8;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    if (i >= n8) break;
+    const EuclidCoef& k = (RW == 2 && i >= D8) ? kr[RW - 1] : kr[0];
+    half8 o0, o1;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const float4 t = euclid_tt4(k, df[2 * it + hh]);
+      o0[4 * hh + 0] = (_Float16)(0.f + t.x); o0[4 * hh + 1] = (_Float16)(0.f + t.y);
+      o0[4 * hh + 2] = (_Float16)(0.f + t.z); o0[4 * hh + 3] = (_Float16)(0.f + t.w);
+      o1[4 * hh + 0] = (_Float16)(0.f + (-t.x)); o1[4 * hh + 1] = (_Float16)(0.f + (-t.y));
+      o1[4 * hh + 2] = (_Float16)(0.f + (-t.z)); o1[4 * hh + 3] = (_Float16)(0.f + (-t.w));
+    }
+    stream_store_vec(dq8 + i, o0);
+    stream_store_vec(da8 + i, o1);
+  }
+}
+
+// The ORDERED distance at large D without speculation (round 3; D > 400, where a speculative chain with one pair per
+// wave was 55 % of the launch: 20.2 us at cfg 5's shard against 13.2 here, profiles/r03_f16_lanewalk.txt).  One wave per pair loads,
+// squares and later differentiates its pair exactly as above; the squares go to LDS as the pair's image, and after one
+// workgroup barrier LANE p of wave 0 walks pair p's image front to back -- the reference's d-ascending fp32 sum
+// (sim_cross_layer.cpp:100-106) as 4 D4 dependent adds fed by D4 ds_read_b128, about 2.4 us for D = 1024 whatever the
+// number of lanes walking.  Eight pairs per workgroup, several workgroups per CU: one workgroup's walk hides behind the
+// others' loads and stores (the launch is HBM-bound: 67 MB).  No windows, no misses, no re-walks; bit-identical by
+// construction.
+template <int NIT, bool BWD, int WPB = 8>
+__global__ __launch_bounds__(64 * WPB) void euclid_rows_lanechain_f16_kernel(
+    const _Float16* __restrict__ q, const _Float16* __restrict__ a, const float* __restrict__ top_diff,
+    float* __restrict__ top_out, _Float16* __restrict__ dq, _Float16* __restrict__ da, int N, int D8) {
+  extern __shared__ float4 lc_lds[];             // [WPB pairs][D4 + 1] float4, then WPB floats (the distances)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * WPB + wave;
+  const int rowc = row < N ? row : N - 1;        // a missing pair mirrors the last one (results unused)
+  const int D4 = 2 * D8, st4 = D4 + 1;
+  const half8* q8 = reinterpret_cast<const half8*>(q) + (size_t)rowc * D8;
+  const half8* a8 = reinterpret_cast<const half8*>(a) + (size_t)rowc * D8;
+  float4* img = lc_lds + (size_t)wave * st4;
+  float* dist_lds = reinterpret_cast<float*>(lc_lds + (size_t)WPB * st4);
+
+  half8 x[NIT], y[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it, ii = i < D8 ? i : 0;
+    x[it] = q8[ii];
+    y[it] = a8[ii];
+  }
+  float g = 0.f;
+  if (BWD) g = top_diff[rowc];
+  float4 df[2 * NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      float4 d;
+      d.x = (float)x[it][4 * hh + 0] - (float)y[it][4 * hh + 0];
+      d.y = (float)x[it][4 * hh + 1] - (float)y[it][4 * hh + 1];
+      d.z = (float)x[it][4 * hh + 2] - (float)y[it][4 * hh + 2];
+      d.w = (float)x[it][4 * hh + 3] - (float)y[it][4 * hh + 3];
+      df[2 * it + hh] = d;
+      float4 sq;
+      sq.x = d.x * d.x; sq.y = d.y * d.y; sq.z = d.z * d.z; sq.w = d.w * d.w;
+      if (i < D8) img[2 * i + hh] = sq;
+    }
+  }
+  __syncthreads();
+  if (wave == 0 && lane < WPB) {
+    const float4* mine = lc_lds + (size_t)lane * st4;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int i4 = 0; i4 < D4; ++i4) {
+      const float4 v = mine[i4];
+      acc += v.x; acc += v.y; acc += v.z; acc += v.w;
+    }
+    dist_lds[lane] = acc;
+  }
+  __syncthreads();
+  if (row >= N) return;
+  const float dist = dist_lds[wave];
+  const float T = 1.0f / (1.0f + sqrtf(dist));
+  if (BWD) asm volatile("" : "+v"(g));          // in a register before the store of T (see euclid_pair32_kernel)
+  if (lane == 0) top_out[row] = T;
+  if (!BWD) return;
+  const EuclidCoef k = euclid_coef(T, g);
+  half8* dq8 = reinterpret_cast<half8*>(dq) + (size_t)row * D8;
+  half8* da8 = reinterpret_cast<half8*>(da) + (size_t)row * D8;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    if (i >= D8) break;
+    half8 o0, o1;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const float4 t = euclid_tt4(k, df[2 * it + hh]);
+      o0[4 * hh + 0] = (_Float16)(0.f + t.x); o0[4 * hh + 1] = (_Float16)(0.f + t.y);
+      o0[4 * hh + 2] = (_Float16)(0.f + t.z); o0[4 * hh + 3] = (_Float16)(0.f + t.w);
+      o1[4 * hh + 0] = (_Float16)(0.f + (-t.x)); o1[4 * hh + 1] = (_Float16)(0.f + (-t.y));
+      o1[4 * hh + 2] = (_Float16)(0.f + (-t.z)); o1[4 * hh + 3] = (_Float16)(0.f + (-t.w));
+    }
+    stream_store_vec(dq8 + i, o0);
+    stream_store_vec(da8 + i, o1);
+  }
+}
+
+// fp16-STORAGE cosine, W1 = W2 = 1 (round 3; cfg 5's "multi-modal concat embeddings, fp16" with dist_mode 0): one
+// wave per pair, a lane holds NIT half8 of q and of a (all 16-byte loads up front, kept for the backward), fp32
+// arithmetic on the exactly-widened inputs: three tree sums (the reference's cblas_sdot has no defined order), the
+// reference's T = q.a / nq / na with its two successive divisions (sim_cross_layer.cpp:135) and its cached NORMS
+// (:118); backward through per-pair factors as cosine_pair32_kernel (c1 = g / n0 / n1, c2 = g T / n0^2, c3 = g T / n1^2,
+// IEEE divisions once per pair), gradients stored as RNE halves.  Bytes per pair: reads 2 D s + 4, writes 2 D s + 12.
+template <int NIT, bool BWD>
+__global__ __launch_bounds__(256) void cosine_rows_wave_f16_kernel(
+    const _Float16* __restrict__ q, const _Float16* __restrict__ a, const float* __restrict__ top_diff,
+    float* __restrict__ top, float* __restrict__ norm0, float* __restrict__ norm1,
+    _Float16* __restrict__ dq, _Float16* __restrict__ da, int N, int D8) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const half8* q8 = reinterpret_cast<const half8*>(q) + (size_t)row * D8;
+  const half8* a8 = reinterpret_cast<const half8*>(a) + (size_t)row * D8;
+  half8 x[NIT], y[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it, ic = i < D8 ? i : D8 - 1;
+    x[it] = q8[ic];
+    y[it] = a8[ic];
+  }
+  float g = BWD ? top_diff[row] : 0.f;
+  float sqq = 0.f, saa = 0.f, sqa = 0.f;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if (lane + 64 * it < D8) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xf = (float)x[it][e], yf = (float)y[it][e];
+        sqq += xf * xf; saa += yf * yf; sqa += xf * yf;
+      }
+    }
+  }
+  sqq = wave_sum(sqq); saa = wave_sum(saa); sqa = wave_sum(sqa);
+  const float n0 = sqrtf(sqq), n1 = sqrtf(saa);
+  const float T = sqa / n0 / n1;                       // two successive divisions (:135)
+  if (BWD) asm volatile("" : "+v"(g));
+  if (lane == 0) {
+    top[row] = T;
+    if (norm0) norm0[row] = n0;
+    if (norm1) norm1[row] = n1;
+  }
+  if (!BWD) return;
+  const float c1 = g / n0 / n1, c2 = g * T / (n0 * n0), c3 = g * T / (n1 * n1);
+  half8* dq8 = reinterpret_cast<half8*>(dq) + (size_t)row * D8;
+  half8* da8 = reinterpret_cast<half8*>(da) + (size_t)row * D8;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = lane + 64 * it;
+    if (i < D8) {
+      half8 o0, o1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xf = (float)x[it][e], yf = (float)y[it][e];
+        o0[e] = (_Float16)(0.f + (c1 * yf - c2 * xf));   // dq = g (a / n0 / n1 - q T / n0^2)   (:239-241)
+        o1[e] = (_Float16)(0.f + (c1 * xf - c3 * yf));   // da = g (q / n0 / n1 - a T / n1^2)   (:243-245)
+      }
+      __builtin_nontemporal_store(o0, dq8 + i);
+      __builtin_nontemporal_store(o1, da8 + i);
+    }
+  }
+}
+
+// ---- generic fallback (any D, any alignment): workgroup of ROWS pairs --------
+// Forward (BWD=false) or forward+backward (BWD=true) for W1=W2=1, Euclidean.
+// LDS: diff[ROWS*D] floats (dynamic) + per-row coefficient slots.
+template <int ROWS, int THREADS, bool BWD>
+__global__ __launch_bounds__(THREADS) void euclid_rows_kernel(
+    const float* __restrict__ q, const float* __restrict__ a,
+    const float* __restrict__ top_diff, float* __restrict__ top,
+    float* __restrict__ dq, float* __restrict__ da, int N, int D) {
+  extern __shared__ float4 lds_raw[];
+  float* diff = reinterpret_cast<float*>(lds_raw);
+  __shared__ float cs[ROWS];
+  __shared__ double dens[ROWS];
+
+  const int row0 = blockIdx.x * ROWS;
+  const int rows = min(ROWS, N - row0);
+  const size_t base = (size_t)row0 * D;
+  const int total = rows * D;
+
+  for (int i = threadIdx.x; i < total; i += THREADS) diff[i] = q[base + i] - a[base + i];
+  __syncthreads();
+
+  // One lane per pair: the reference's d-ascending fp32 chain (:100-106).
+  if (threadIdx.x < rows) {
+    const float* r = diff + threadIdx.x * D;
+    float dist = 0.f;
+    for (int d = 0; d < D; ++d) dist += r[d] * r[d];
+    dist = sqrtf(dist);
+    const float T = 1.0f / (1.0f + dist);
+    top[row0 + threadIdx.x] = T;
+    if (BWD) {
+      const EuclidCoef k = euclid_coef(T, top_diff[row0 + threadIdx.x]);
+      cs[threadIdx.x] = k.c;
+      dens[threadIdx.x] = k.den;
+    }
+  }
+  if (!BWD) return;
+  __syncthreads();
+  for (int i = threadIdx.x; i < total; i += THREADS) {
+    const int r = i / D;
+    const float t = euclid_tt_exact(cs[r], dens[r], diff[i]);
+    dq[base + i] = 0.f + t;
+    da[base + i] = 0.f + (-t);
+  }
+}
+
+// Backward alone, generic fallback: pure streaming.
+__global__ __launch_bounds__(256) void euclid_rows_bwd_kernel(
+    const float* __restrict__ q, const float* __restrict__ a,
+    const float* __restrict__ top, const float* __restrict__ top_diff,
+    float* __restrict__ dq, float* __restrict__ da, int total, int D) {
+  const int stride = gridDim.x * blockDim.x;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int r = i / D;
+    const EuclidCoef k = euclid_coef(top[r], top_diff[r]);
+    const float t = euclid_tt_exact(k.c, k.den, q[i] - a[i]);
+    dq[i] = 0.f + t;
+    da[i] = 0.f + (-t);
+  }
+}
+
+// Cosine, W1=W2=1: one wave per pair; three dot products reduced with a fixed
+// butterfly (the reference's order here is whatever its BLAS does).
+// BWD fuses the backward with a known top_diff.
+template <bool VEC4, bool FWD, bool BWD>
+__global__ __launch_bounds__(256) void cosine_rows_kernel(
+    const float* __restrict__ q, const float* __restrict__ a,
+    const float* __restrict__ top_diff, float* __restrict__ top,
+    float* __restrict__ norm0, float* __restrict__ norm1,
+    float* __restrict__ dq, float* __restrict__ da, int N, int D) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const float* qr = q + (size_t)row * D;
+  const float* ar = a + (size_t)row * D;
+  float g = 0.f;
+  if (BWD) g = top_diff[row];                    // requested up front; pinned before the stores of the forward
+  float T, n0, n1;
+  if (FWD) {
+    float sqq = 0.f, saa = 0.f, sqa = 0.f;
+    if (VEC4) {
+      const float4* q4 = reinterpret_cast<const float4*>(qr);
+      const float4* a4 = reinterpret_cast<const float4*>(ar);
+      for (int i = lane; i < (D >> 2); i += 64) {
+        const float4 x = q4[i], y = a4[i];
+        cosine_acc4(sqq, x, x); cosine_acc4(saa, y, y); cosine_acc4(sqa, x, y);
+      }
+    } else {
+      for (int i = lane; i < D; i += 64) {
+        const float x = qr[i], y = ar[i];
+        cosine_acc1(sqq, x, x); cosine_acc1(saa, y, y); cosine_acc1(sqa, x, y);
+      }
+    }
+    sqq = wave_sum(sqq); saa = wave_sum(saa); sqa = wave_sum(sqa);
+    const CosineScore c = cosine_score(sqq, saa, sqa);
+    T = c.T; n0 = c.n0; n1 = c.n1;
+    if (BWD) asm volatile("" : "+v"(g));
+    if (lane == 0) { top[row] = T; norm0[row] = n0; norm1[row] = n1; }
+  } else {
+    T = top[row]; n0 = norm0[row]; n1 = norm1[row];
+  }
+  if (!BWD) return;
+  float* dqr = dq + (size_t)row * D;
+  float* dar = da + (size_t)row * D;
+  // :239-245   dq += g*(a/n0/n1 - q*T/(n0*n0)) ; da += g*(q/n0/n1 - a*T/(n1*n1))
+  const float n00 = n0 * n0, n11 = n1 * n1;
+  if (VEC4) {
+    const float4* q4 = reinterpret_cast<const float4*>(qr);
+    const float4* a4 = reinterpret_cast<const float4*>(ar);
+    float4* dq4 = reinterpret_cast<float4*>(dqr);
+    float4* da4 = reinterpret_cast<float4*>(dar);
+    for (int i = lane; i < (D >> 2); i += 64) {
+      const float4 x = q4[i], y = a4[i];
+      const float4 o0 = cosine_grad4_div(g, n0, n1, T, n00, y, x);
+      const float4 o1 = cosine_grad4_div(g, n0, n1, T, n11, x, y);
+      stream_store(dq4 + i, o0);
+      stream_store(da4 + i, o1);
+    }
+  } else {
+    for (int i = lane; i < D; i += 64) {
+      const float x = qr[i], y = ar[i];
+      dqr[i] = cosine_grad_div(g, n0, n1, T, n00, y, x);
+      dar[i] = cosine_grad_div(g, n0, n1, T, n11, x, y);
+    }
+  }
+}
+
+// Cosine, W1=W2=1, the GloVe widths (D = 100 / 200 / 300): the data movement of
+// euclid_pair32_kernel -- 32 lanes per pair, two pairs per wave, every 16-byte load of q and a issued
+// up front and kept in registers for the backward, half-wave DPP reductions, streaming stores --
+// without the ordered chain (the reference's dot products are cblas_sdot: no defined order, 1e-5
+// contract).  The backward multiplies by per-pair factors 1/n0/n1, T/n0^2, T/n1^2 computed once
+// (IEEE divisions) instead of dividing per element (:239-245 written out costs six divisions per
+// (q_d, a_d)): a few ulp from the reference's expression, inside the same 1e-5.
+template <int D4C, bool FWD, bool BWD, int WPB>
+__global__ __launch_bounds__(64 * WPB) void cosine_pair32_kernel(
+    int N, const float* __restrict__ q, const float* __restrict__ a,
+    const float* __restrict__ top_diff, float* __restrict__ top, float* __restrict__ norm0,
+    float* __restrict__ norm1, float* __restrict__ dq, float* __restrict__ da) {
+  constexpr int NIT = (D4C + 31) / 32;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane >> 5, j = lane & 31;
+  const int want = (blockIdx.x * WPB + wave) * 2 + grp;
+  const bool have = want < N;
+  const int row = have ? want : N - 1;
+  const float4* q4 = reinterpret_cast<const float4*>(q) + (size_t)row * D4C;
+  const float4* a4 = reinterpret_cast<const float4*>(a) + (size_t)row * D4C;
+  float4 x[NIT], y[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = j + 32 * it;
+    const int ii = i < D4C ? i : 0;              // clamp: keep the load unconditional
+    x[it] = q4[ii];
+    y[it] = a4[ii];
+  }
+  float T, n0, n1;
+  if (FWD) {
+    float sqq = 0.f, saa = 0.f, sqa = 0.f;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      if (j + 32 * it < D4C) {
+        const float4 u = x[it], v = y[it];
+        cosine_acc4(sqq, u, u); cosine_acc4(saa, v, v); cosine_acc4(sqa, u, v);
+      }
+    }
+    sqq = half_wave_sum(sqq); saa = half_wave_sum(saa); sqa = half_wave_sum(sqa);
+    const CosineScore c = cosine_score(sqq, saa, sqa);
+    T = c.T; n0 = c.n0; n1 = c.n1;
+    if (j == 0 && have) { top[row] = T; norm0[row] = n0; norm1[row] = n1; }
+  } else {
+    T = top[row]; n0 = norm0[row]; n1 = norm1[row];
+  }
+  if (!BWD) return;
+  const float g = top_diff[row];
+  const CosineFactors f = cosine_factors(T, n0, n1);
+  float4* dq4 = reinterpret_cast<float4*>(dq) + (size_t)row * D4C;
+  float4* da4 = reinterpret_cast<float4*>(da) + (size_t)row * D4C;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = j + 32 * it;
+    if (i < D4C && have) {
+      const float4 u = x[it], v = y[it];
+      const float4 o0 = cosine_grad4_fac(g, f.inv01, f.cq, v, u);
+      const float4 o1 = cosine_grad4_fac(g, f.inv01, f.ca, u, v);
+      stream_store(dq4 + i, o0);
+      stream_store(da4 + i, o1);
+    }
+  }
+}
+
+// ================================= dispatch =================================
+// DESIGN.md 4.4b is the table this section is read against.
+
+// How the fp16-storage kernels sum a pair's squares (include/mms.h: mms_set_f16_distance_mode); per calling thread.
+static thread_local int t_f16_distance_mode = MMS_F16_DISTANCE_ORDERED;
+int f16_distance_mode() { return t_f16_distance_mode; }
+void set_f16_distance_mode(int m) { t_f16_distance_mode = m; }
+
+// Backward arithmetic of the Euclidean term (include/mms.h: mms_set_euclid_backward_mode).  The mode
+// belongs to the calling thread (Caffe drives each GPU from its own thread); a thread that never set it
+// takes the process default from the environment.
+static std::atomic<int> g_euclid_bwd_default{-1};
+static thread_local int t_euclid_bwd_mode = -1;
+int euclid_backward_mode() {
+  if (t_euclid_bwd_mode >= 0) return t_euclid_bwd_mode;
+  int m = g_euclid_bwd_default.load(std::memory_order_relaxed);
+  if (m < 0) {
+    const char* e = std::getenv("MMS_EUCLID_BWD");
+    m = (e && (!std::strcmp(e, "reference") || !std::strcmp(e, "exact") || !std::strcmp(e, "1")))
+            ? MMS_EUCLID_BWD_REFERENCE : MMS_EUCLID_BWD_FP32;
+    g_euclid_bwd_default.store(m, std::memory_order_relaxed);
+  }
+  return m;
+}
+void set_euclid_backward_mode(int m) { t_euclid_bwd_mode = m; }
+
+constexpr int kRows = 8;       // pairs per workgroup in the generic rows kernels
+constexpr int kRowsThreads = 256;
+
+// every array the launch touches (p2, p3: the gradients, null in a forward) takes 16-byte accesses
+static bool vec4_ok(int D, const void* p0, const void* p1, const void* p2, const void* p3) {
+  return (D % 4 == 0) && aligned16(p0) && aligned16(p1) && (!p2 || aligned16(p2)) && (!p3 || aligned16(p3));
+}
+
+// generic rows kernels: LDS needed; the forward falls back to the cross kernels above ~64 KB.
+static size_t rows_lds_bytes(int D) { return (size_t)kRows * D * sizeof(float); }
+static bool rows_fit(int D) { return rows_lds_bytes(D) <= 64 * 1024; }
+
+// Which kernel family serves a launch, from D and the arrays it touches (dq, da null in a forward).
+enum class EuclidRows { kPair32, kWave, kGeneric, kNone };
+static EuclidRows euclid_rows_route(int D, const void* q, const void* a, const void* dq, const void* da) {
+  if (vec4_ok(D, q, a, dq, da) && wave_width_ok(D)) return glove_width(D) ? EuclidRows::kPair32 : EuclidRows::kWave;
+  return rows_fit(D) ? EuclidRows::kGeneric : EuclidRows::kNone;
+}
+enum class CosineRows { kPair32, kVec4, kScalar };
+static CosineRows cosine_rows_route(int D, const void* q, const void* a, const void* dq, const void* da) {
+  if (!vec4_ok(D, q, a, dq, da)) return CosineRows::kScalar;
+  return glove_width(D) ? CosineRows::kPair32 : CosineRows::kVec4;
+}
+
+// Eight waves (16 pairs) per workgroup: N = 4096 is then 256 workgroups, one per CU, two waves
+// per SIMD -- measured 3 % faster HBM-cold than 512 workgroups of four waves (dispatch ramp).
+template <bool FWD, bool BWD>
+static void launch_pair32(const float* q, const float* a, const float* top_in, const float* top_diff,
+                          float* top_out, float* dq, float* da, int N, int D, bool exact, hipStream_t s) {
+  constexpr int WPB = 8;
+  const unsigned grid = (unsigned)((N + 2 * WPB - 1) / (2 * WPB));
+  // Which global-memory layout (same results bit for bit; tests/test_gpu_parity.py runs both for every kind
+  // of launch).  Measured at cfg 2, HBM-cold, graph-replayed (tools/layoutab.sh, profiles/r02_layout_ab.txt):
+  //   backward-only launch      row-aligned 6.27 us, workgroup-dense 4.87 us  -> dense
+  //   forward-only launch       4.87 vs 4.92 us: the chain's tail, not the read pattern, bounds it -> row-aligned
+  //   fused forward+backward    5.65 vs 6.0 us: waves free of workgroup barriers spread the store phase -> row-aligned
+  //   Forward launch then Backward launch (what a Net issues): 8.80 us both row-aligned -> 7.97 us forward
+  //   row-aligned + backward dense.  Both must map workgroup b to the SAME pairs (same waves per workgroup):
+  //   the backward then finds q and a in the L2 of the XCD that read them in the forward; mismatched maps cost
+  //   0.6 us.
+  // Dev switch for A/B timing: MMS_EUCLID_LAYOUT_{FWD,BWD,FUSED} = pair | block | wave (dense run per wave).
+  static const int layout = [] {
+    const char* e = std::getenv(FWD && BWD ? "MMS_EUCLID_LAYOUT_FUSED" : FWD ? "MMS_EUCLID_LAYOUT_FWD" : "MMS_EUCLID_LAYOUT_BWD");
+    if (e) return !std::strcmp(e, "pair") ? 0 : (!std::strcmp(e, "wave") ? 2 : 1);
+    return FWD ? 0 : 1;
+  }();
+  with_bool(BWD && exact, [&](auto E) {   // a forward has no backward term: its EXACT is false
+    constexpr bool EXACT = decltype(E)::value;
+#define MMS_P32(d4)                                                                                  \
+  case 4 * d4:                                                                                       \
+    hipLaunchKernelGGL((layout == 0   ? euclid_pair32_kernel<d4, FWD, BWD, EXACT, WPB>               \
+                        : layout == 1 ? euclid_block_kernel<d4, FWD, BWD, EXACT, WPB>                \
+                                      : euclid_block_kernel<d4, FWD, BWD, EXACT, WPB, 1>),           \
+                       dim3(grid), dim3(64 * WPB), 0, s, N, q, a, top_in, top_diff, top_out, dq, da); \
+    break;
+    switch (D) { MMS_P32(25) MMS_P32(50) MMS_P32(75) }
+#undef MMS_P32
+  });
+}
+
+// wave kernel: RW = wave_pairs(D) pairs per wave, NIT = ceil(RW*D/4 / 64) 16-byte loads per operand per lane
+// (1..4 for every D that euclid_rows_route sends here).
+template <bool FWD, bool BWD>
+static void launch_rows_wave(const float* q, const float* a, const float* top_in,
+                             const float* top_diff, float* top_out, float* dq, float* da, int N,
+                             int D, hipStream_t s) {
+  const int D4 = D / 4;
+  const int rw = wave_pairs(D), nit = (rw * D4 + 63) / 64;
+  const unsigned grid = (unsigned)((N + 4 * rw - 1) / (4 * rw));
+  const size_t lds = FWD ? spec_image_lds(4, rw, D4) : 0;
+  static constexpr decltype(&euclid_rows_wave_kernel<1, 1, FWD, BWD>) kernels[2][4] = {
+      MMS_NIT4(euclid_rows_wave_kernel, 1, FWD, BWD), MMS_NIT4(euclid_rows_wave_kernel, 2, FWD, BWD)};
+  hipLaunchKernelGGL(kernels[rw - 1][nit - 1], dim3(grid), dim3(256), lds, s, q, a, top_in, top_diff, top_out,
+                     dq, da, N, D4);
+}
+
+// Euclid, W1 = W2 = 1.  false: no rows kernel serves this forward (or fused) launch and the caller's word-grid
+// kernels take it; a backward alone is always served (euclid_rows_bwd_kernel streams at any D).
+template <bool FWD, bool BWD>
+bool launch_euclid_rows(int N, int D, const float* q, const float* a, const float* top_in, const float* top_diff,
+                        float* top_out, float* dq, float* da, bool exact, hipStream_t s) {
+  const EuclidRows route = euclid_rows_route(D, q, a, dq, da);
+  if (route == EuclidRows::kPair32) {
+    launch_pair32<FWD, BWD>(q, a, top_in, top_diff, top_out, dq, da, N, D, exact, s);
+  } else if (route == EuclidRows::kWave) {
+    launch_rows_wave<FWD, BWD>(q, a, top_in, top_diff, top_out, dq, da, N, D, s);
+  } else if (!FWD) {
+    const int total = N * D;
+    int blocks = (total + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(euclid_rows_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q, a, top_in, top_diff,
+                       dq, da, total, D);
+  } else if (route == EuclidRows::kGeneric) {
+    hipLaunchKernelGGL((euclid_rows_kernel<kRows, kRowsThreads, BWD>), dim3((unsigned)((N + kRows - 1) / kRows)),
+                       dim3(kRowsThreads), rows_lds_bytes(D), s, q, a, top_diff, top_out, dq, da, N, D);
+  } else {
+    return false;
+  }
+  return true;
+}
+
+// Cosine, W1 = W2 = 1: always served.  A backward alone reads top / norm0 / norm1 through the same parameters the
+// forward writes them through.
+template <bool FWD, bool BWD>
+void launch_cosine_rows(int N, int D, const float* q, const float* a, const float* top_diff, float* top,
+                        float* norm0, float* norm1, float* dq, float* da, hipStream_t s) {
+  const CosineRows route = cosine_rows_route(D, q, a, dq, da);
+  if (route == CosineRows::kPair32) {
+    constexpr int WPB = 8;
+    const unsigned grid = (unsigned)((N + 2 * WPB - 1) / (2 * WPB));
+#define MMS_C32(d4)                                                                                 \
+  case 4 * d4:                                                                                      \
+    hipLaunchKernelGGL((cosine_pair32_kernel<d4, FWD, BWD, WPB>), dim3(grid), dim3(64 * WPB), 0, s, \
+                       N, q, a, top_diff, top, norm0, norm1, dq, da);                               \
+    break;
+    switch (D) { MMS_C32(25) MMS_C32(50) MMS_C32(75) }
+#undef MMS_C32
+  } else {
+    hipLaunchKernelGGL((route == CosineRows::kVec4 ? cosine_rows_kernel<true, FWD, BWD> : cosine_rows_kernel<false, FWD, BWD>),
+                       dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, q, a, top_diff, top, norm0, norm1, dq, da, N, D);
+  }
+}
+
+#define MMS_ROWS_INSTANCE(F, B)                                                                                   \
+  template bool launch_euclid_rows<F, B>(int, int, const float*, const float*, const float*, const float*, float*, \
+                                         float*, float*, bool, hipStream_t);                                      \
+  template void launch_cosine_rows<F, B>(int, int, const float*, const float*, const float*, float*, float*,      \
+                                         float*, float*, float*, hipStream_t);
+MMS_ROWS_INSTANCE(true, false) MMS_ROWS_INSTANCE(false, true) MMS_ROWS_INSTANCE(true, true)
+#undef MMS_ROWS_INSTANCE
+
+// ---- fp16 storage ------------------------------------------------------------
+// half8 accesses of every array touched, at most four per operand per lane of a wave
+static bool f16_rows_ok(int D, const void* q, const void* a, const void* dq, const void* da, bool bwd) {
+  return D % 8 == 0 && D <= 2048 && aligned16(q) && aligned16(a) && (!bwd || (aligned16(dq) && aligned16(da)));
+}
+
+int simcross_cosine_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top,
+                             float* norm0, float* norm1, void* dq, void* da, bool bwd, hipStream_t s) {
+  if (N == 0) return MMS_OK;
+  if (!f16_rows_ok(D, q, a, dq, da, bwd)) return MMS_ERR_UNSUPPORTED;
+  const int D8 = D / 8, nit = (D8 + 63) / 64;
+  static constexpr decltype(&cosine_rows_wave_f16_kernel<1, true>) kernels[2][4] = {
+      MMS_NIT4(cosine_rows_wave_f16_kernel, false), MMS_NIT4(cosine_rows_wave_f16_kernel, true)};
+  hipLaunchKernelGGL(kernels[bwd][nit - 1], dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s,
+                     static_cast<const _Float16*>(q), static_cast<const _Float16*>(a), top_diff, top, norm0, norm1,
+                     static_cast<_Float16*>(dq), static_cast<_Float16*>(da), N, D8);
+  return launch_status();
+}
+
+int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff,
+                             float* top, void* dq, void* da, bool bwd, hipStream_t s) {
+  if (N == 0) return MMS_OK;
+  if (!f16_rows_ok(D, q, a, dq, da, bwd)) return MMS_ERR_UNSUPPORTED;
+  const int D8 = D / 8;
+  const bool tree = f16_distance_mode() == MMS_F16_DISTANCE_TREE;
+  const int rw = tree ? 1 : wave_pairs(D);        // tree sum: one pair per wave whatever D, no speculation windows to fit
+  const int nit = (rw * D8 + 63) / 64;
+  using Kernel = decltype(&euclid_rows_wave_f16_kernel<1, 1, true>);   // the three families share one signature
+  Kernel k;
+  unsigned grid, threads = 256;
+  size_t lds;
+  if (tree) {
+    static constexpr Kernel kernels[2][4] = {MMS_NIT4(euclid_rows_wave_f16_kernel, 1, false, true),
+                                             MMS_NIT4(euclid_rows_wave_f16_kernel, 1, true, true)};
+    k = kernels[bwd][nit - 1];
+    grid = (unsigned)((N + 3) / 4);
+    lds = 16;
+  } else if (rw == 2) {
+    static constexpr Kernel kernels[2][4] = {MMS_NIT4(euclid_rows_wave_f16_kernel, 2, false),
+                                             MMS_NIT4(euclid_rows_wave_f16_kernel, 2, true)};
+    k = kernels[bwd][nit - 1];
+    grid = (unsigned)((N + 4 * rw - 1) / (4 * rw));
+    lds = spec_image_lds(4, rw, 2 * D8);
+  } else {
+    // ordered beyond two pairs per wave: lane p of wave 0 walks pair p's image
+    constexpr int wpb = 8;                            // 4 / 8 / 16 waves measured alike (profiles/r03_f16_lanewalk.txt)
+    static constexpr Kernel kernels[2][4] = {MMS_NIT4(euclid_rows_lanechain_f16_kernel, false, wpb),
+                                             MMS_NIT4(euclid_rows_lanechain_f16_kernel, true, wpb)};
+    static const bool once = [] {
+      for (const auto& row : kernels)
+        for (const Kernel f : row)
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    160 * 1024);
+      return true;
+    }();
+    (void)once;
+    k = kernels[bwd][nit - 1];
+    grid = (unsigned)((N + wpb - 1) / wpb);
+    threads = 64 * wpb;
+    lds = ((size_t)wpb * (2 * D8 + 1) + 4) * sizeof(float4);
+  }
+  hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, s, static_cast<const _Float16*>(q),
+                     static_cast<const _Float16*>(a), top_diff, top, static_cast<_Float16*>(dq),
+                     static_cast<_Float16*>(da), N, D8);
+  return launch_status();
+}
+
+}  // namespace mms

@@ -1,5 +1,5 @@
 """The GloVe-width Euclidean kernels exist in two global-memory layouts (row-aligned `euclid_pair32_kernel`,
-workgroup-dense `euclid_block_kernel`; simcross_elementwise.hip).  The library picks one per kind of launch; the
+workgroup-dense `euclid_block_kernel`; simcross_rows.hip).  The library picks one per kind of launch; the
 other GPU tests therefore see forward = row-aligned, backward = dense, fused = row-aligned.  This one runs the
 opposite choice for all three (a process-wide dev switch, hence the subprocess) against the CPU oracle."""
 import os

@@ -5,7 +5,8 @@ Did a source change alter the code a GPU runs?  No GPU, no torch: OLD and NEW ar
 file that carries HIP fat binaries, or two directories of such files, e.g. the build/ object directories).  Every
 gfx950 code object is unbundled (clang-offload-bundler), and for every kernel the tool reports
   * on which side it exists,
-  * whether its instructions are identical (llvm-objdump -d, addresses stripped, encodings kept),
+  * whether its instructions are identical (llvm-objdump -d, addresses stripped, encodings kept; the fill between
+    a symbol's last instruction and the next symbol is not part of it),
   * whether its resource metadata is identical (VGPR / AGPR / SGPR counts, LDS, scratch, kernarg size, ... from the
     code object's notes).
 Symbols are matched by MANGLED name (shown demangled where a demangler is installed).  MAP.json is a list of
@@ -104,6 +105,12 @@ def disassembly(co):
             cur = syms.setdefault(own, [])
         elif cur is not None and line.strip():
             cur.append(re.sub(r"//\s*[0-9A-Fa-f]+:", "//", line.strip()).replace("<" + own + "+", "<@+"))
+    # What follows a symbol's last instruction is the gap to whatever the linker placed next (zero fill shown as
+    # `...`, s_nop 0 or s_code_end fill; the end-of-section pad after the last kernel of a code object): it depends
+    # on the symbol's neighbours, so it changes when kernels move between sources, and no wave executes it.
+    for isa in syms.values():
+        while isa and re.match(r"^(\.\.\.|s_nop 0|s_code_end)(\s|$)", isa[-1]):
+            isa.pop()
     return syms
 
 
