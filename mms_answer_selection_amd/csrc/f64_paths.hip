@@ -387,17 +387,31 @@ inline G64 g64(int M, int N, int K, const double* A, i64 sam, i64 sak, const dou
   g.C = C; g.ldc = ldc; g.nb1 = 1;
   return g;
 }
-inline void run_g64(const G64& g, int nb0, hipStream_t s) {
-  const i64 tiles64 = (i64)((g.N + G64_T - 1) / G64_T) * ((g.M + G64_T - 1) / G64_T) * nb0 * g.nb1;
-  if ((i64)g.nseg * g.L >= 1024 && tiles64 <= 64) {  // small output, long K: sixteen K streams per tile
-    const dim3 gr((unsigned)((g.N + G64_TK - 1) / G64_TK), (unsigned)((g.M + G64_TK - 1) / G64_TK),
-                  (unsigned)(nb0 * g.nb1));
-    hipLaunchKernelGGL(gemm64_tallk_kernel, gr, dim3(64 * G64_TKW), 0, s, g);
-    return;
+constexpr int G64_GRID_MAX = 65535;                  // gridDim.y and gridDim.z of one launch
+inline void run_g64(const G64& g0, int nb0, hipStream_t s) {
+  // the kernel is chosen ONCE, on the whole problem: a product's route does not depend on how it is sliced
+  const i64 tiles64 = (i64)((g0.N + G64_T - 1) / G64_T) * ((g0.M + G64_T - 1) / G64_T) * nb0 * g0.nb1;
+  const bool tallk = (i64)g0.nseg * g0.L >= 1024 && tiles64 <= 64;  // small output, long K: sixteen K streams per tile
+  const int tile = tallk ? G64_TK : G64_T;
+  // gridDim.z <= 65535: slice the outer batch when (pairs x measures) is larger; gridDim.y <= 65535: slice the rows
+  const int max_b0 = g0.nb1 > G64_GRID_MAX ? 1 : G64_GRID_MAX / g0.nb1;
+  const i64 max_rows = (i64)G64_GRID_MAX * tile;
+  for (int b = 0; b < nb0; b += max_b0) {
+    const int nb = (nb0 - b) < max_b0 ? (nb0 - b) : max_b0;
+    for (i64 r = 0; r < g0.M; r += max_rows) {
+      G64 g = g0;
+      g.M = (int)((g0.M - r) < max_rows ? (g0.M - r) : max_rows);
+      g.A += (i64)b * g.a_b0 + r * g.sam;
+      g.B += (i64)b * g.b_b0;
+      g.C += (i64)b * g.c_b0 + r * g.ldc;
+      if (g.rowscale) g.rowscale += (i64)b * g.rs_b0 + r;
+      if (g.bias) g.bias += r * g.ldbias;
+      const dim3 grid((unsigned)((g.N + tile - 1) / tile), (unsigned)((g.M + tile - 1) / tile),
+                      (unsigned)(nb * g.nb1));
+      if (tallk) hipLaunchKernelGGL(gemm64_tallk_kernel, grid, dim3(64 * G64_TKW), 0, s, g);
+      else hipLaunchKernelGGL(gemm64_kernel, grid, dim3(256), 0, s, g);
+    }
   }
-  const dim3 grid((unsigned)((g.N + G64_T - 1) / G64_T), (unsigned)((g.M + G64_T - 1) / G64_T),
-                  (unsigned)(nb0 * g.nb1));
-  hipLaunchKernelGGL(gemm64_kernel, grid, dim3(256), 0, s, g);
 }
 
 // top[i] = sum_c a[i,c] scratch[i,c], c ascending within a lane, lanes summed in a fixed tree: one wave per row
