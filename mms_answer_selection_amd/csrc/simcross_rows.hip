@@ -187,7 +187,17 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
 //   false: fp32 throughout, tt = (c*(q-a)) * fl32(1/den): at most 2 ulp from the
 //          reference's value (1.2e-7 relative against the 1e-5 bar), a third of
 //          the instructions.  The FORWARD value T is bit-exact in both.
-template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB>
+//
+// SHIFT selects the LINE-ALIGNED lane map.  A row is D4C*16 bytes, no multiple of a 128-byte line at any of the
+// three widths (1200 = 9*128 + 48), so a row starts u = (address >> 4) & 7 float4s into a line and each 16-lane
+// quarter of a half-wave's 512-byte piece straddles three lines where two would do.  With SHIFT lane j, slot `it`
+// holds float4 i = j + 32*it - u of its row: every quarter starts on a line.  A lane whose i falls outside
+// [0, D4C) is idle (clamped load, no square, no store); 32*NIT - 7 >= D4C keeps the row covered.  Only the
+// assignment of columns to lanes changes: the LDS image, the chain and its windows are indexed by i as before,
+// and the tree sums p1 / p2 merely centre the windows, so T has the same bits.  The lane must hold the same
+// column of every array it touches, so the host asks for SHIFT only when they are congruent mod 128
+// (same_line_phase below); u is taken from q.
+template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB, bool SHIFT = false>
 __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     int N, const float* __restrict__ q, const float* __restrict__ a,
     const float* __restrict__ top_in, const float* __restrict__ top_diff,
@@ -195,8 +205,9 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
   // N first: with -amdgpu-kernarg-preload-count the leading arguments arrive in SGPRs at wave
   // start, so the loads below do not wait on a scalar fetch of the argument block
   constexpr int NIT = (D4C + 31) / 32;
-  constexpr int LASTN = D4C - 32 * (NIT - 1);    // lanes with a float4 in the last slot
   constexpr int H4 = (D4C + 2) / 3, ST4 = 3 * H4;
+  constexpr int MAXU = SHIFT ? 7 : 0;            // largest peel at the start of a row
+  static_assert(32 * NIT - MAXU >= D4C, "the shifted slots must still cover the row");
   __shared__ float4 lds4[FWD ? WPB * 2 * ST4 : 1];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int grp = lane >> 5, j = lane & 31;
@@ -207,7 +218,12 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
   const int row = have ? want : N - 1;
   const float4* q4 = reinterpret_cast<const float4*>(q) + (size_t)row * D4C;
   const float4* a4 = reinterpret_cast<const float4*>(a) + (size_t)row * D4C;
-  const bool last_ok = (LASTN >= 32) || (j < LASTN);
+  // column of slot `it`, and whether this lane has one there: only the first slot can start before the row
+  // (SHIFT) and only the last can run past its end
+  const int j0 = SHIFT ? j - (int)((reinterpret_cast<size_t>(q4) >> 4) & 7) : j;
+  const bool first_ok = !SHIFT || j0 >= 0;
+  const bool last_ok = j0 + 32 * (NIT - 1) < D4C;
+  auto valid_slot = [&](int it) { return (it > 0 || first_ok) && (it < NIT - 1 || last_ok); };
 
   float T = 0.f;
   if (!FWD) T = top_in[row];
@@ -216,7 +232,7 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
   float4 x[NIT], y[NIT], df[NIT];
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    const int i = (it < NIT - 1 || last_ok) ? j + 32 * it : 0;   // clamp: keep the load unconditional
+    const int i = valid_slot(it) ? j0 + 32 * it : 0;   // clamp: keep the load unconditional
     x[it] = q4[i];
     y[it] = a4[i];
   }
@@ -228,18 +244,19 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     df[it].x = x[it].x - y[it].x; df[it].y = x[it].y - y[it].y;
     df[it].z = x[it].z - y[it].z; df[it].w = x[it].w - y[it].w;
     if (FWD) {
-      const bool valid = (it < NIT - 1) || last_ok;
+      const bool valid = valid_slot(it);
       float4 s;
       s.x = df[it].x * df[it].x; s.y = df[it].y * df[it].y;
       s.z = df[it].z * df[it].z; s.w = df[it].w * df[it].w;
-      if (valid) img[j + 32 * it] = s;
+      const int i = j0 + 32 * it;
+      if (valid) img[i] = s;
       const float s4 = valid ? (s.x + s.y) + (s.z + s.w) : 0.f;
-      const int i = j + 32 * it;
-      // tree-sum contributions to the two window centres (segment 0; segments 0-1)
+      // tree-sum contributions to the two window centres (segment 0; segments 0-1); the slot's columns
+      // lie in [32*it - MAXU, 32*it + 31]
       if (32 * it + 31 < H4) p1 += s4;
-      else if (32 * it < H4) p1 += (i < H4) ? s4 : 0.f;
+      else if (32 * it - MAXU < H4) p1 += (i < H4) ? s4 : 0.f;
       if (32 * it + 31 < 2 * H4) p2 += s4;
-      else if (32 * it < 2 * H4) p2 += (i < 2 * H4) ? s4 : 0.f;
+      else if (32 * it - MAXU < 2 * H4) p2 += (i < 2 * H4) ? s4 : 0.f;
     }
   }
   if (FWD) {
@@ -283,7 +300,7 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     for (int it = 0; it < NIT; ++it) {
       bool risky;
       t[it] = euclid_tt4_fast(k, df[it], risky);
-      any_risky |= risky && ((it < NIT - 1) || last_ok);
+      any_risky |= risky && valid_slot(it);
     }
     if (any_risky) {
 #pragma unroll
@@ -301,13 +318,13 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
   if (have) {
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    if (!((it < NIT - 1) || last_ok)) break;
+    if (!valid_slot(it)) continue;
     // dq = 0 + tt ; da = 0 + (-tt)   (:176-177 zero, :219-220 accumulate once)
     float4 o0, o1;
     o0.x = 0.f + t[it].x; o0.y = 0.f + t[it].y; o0.z = 0.f + t[it].z; o0.w = 0.f + t[it].w;
     o1.x = 0.f + (-t[it].x); o1.y = 0.f + (-t[it].y); o1.z = 0.f + (-t[it].z); o1.w = 0.f + (-t[it].w);
-    stream_store(dq4 + j + 32 * it, o0);
-    stream_store(da4 + j + 32 * it, o1);
+    stream_store(dq4 + j0 + 32 * it, o0);
+    stream_store(da4 + j0 + 32 * it, o1);
   }
   }
 }
@@ -985,6 +1002,15 @@ static bool vec4_ok(int D, const void* p0, const void* p1, const void* p2, const
   return (D % 4 == 0) && aligned16(p0) && aligned16(p1) && (!p2 || aligned16(p2)) && (!p3 || aligned16(p3));
 }
 
+// The line-aligned lane map of euclid_pair32_kernel (SHIFT) gives a lane the column that sits at the same place
+// of a 128-byte line in every array, so it serves a launch only when all the arrays it touches (as in vec4_ok)
+// start at the same offset within a line.  Allocator-aligned blobs do; views carved at unrelated offsets get
+// the unshifted map.
+static bool same_line_phase(const void* p0, const void* p1, const void* p2, const void* p3) {
+  const auto ph = [](const void* p) { return reinterpret_cast<uintptr_t>(p) & 127; };
+  return ph(p1) == ph(p0) && (!p2 || ph(p2) == ph(p0)) && (!p3 || ph(p3) == ph(p0));
+}
+
 // generic rows kernels: LDS needed; the forward falls back to the cross kernels above ~64 KB.
 static size_t rows_lds_bytes(int D) { return (size_t)kRows * D * sizeof(float); }
 static bool rows_fit(int D) { return rows_lds_bytes(D) <= 64 * 1024; }
@@ -1017,17 +1043,26 @@ static void launch_pair32(const float* q, const float* a, const float* top_in, c
   //   row-aligned + backward dense.  Both must map workgroup b to the SAME pairs (same waves per workgroup):
   //   the backward then finds q and a in the L2 of the XCD that read them in the forward; mismatched maps cost
   //   0.6 us.
+  // The row-aligned kernel's lane map is LINE-ALIGNED when the launch's arrays are congruent mod 128
+  // (same_line_phase; euclid_pair32_kernel's SHIFT).  Probe (tools/launchbench.hip,
+  // profiles/launchbench_lane_map.txt): the bare read of q and a in the row-aligned map 4.43 us, line-aligned
+  // 4.13 us, dense 3.59-3.68 us, at the same bytes and the same L1-to-L2 read requests (one per line either
+  // way) but 24 % fewer L1 line accesses: a 16-lane quarter that starts mid-line looks up three lines, one
+  // that starts on a line two.  The figures above predate the map; with it the Forward launch + dense Backward
+  // launch of bench.py went 7.50 -> 7.22 us per step.
   // Dev switch for A/B timing: MMS_EUCLID_LAYOUT_{FWD,BWD,FUSED} = pair | block | wave (dense run per wave).
   static const int layout = [] {
     const char* e = std::getenv(FWD && BWD ? "MMS_EUCLID_LAYOUT_FUSED" : FWD ? "MMS_EUCLID_LAYOUT_FWD" : "MMS_EUCLID_LAYOUT_BWD");
     if (e) return !std::strcmp(e, "pair") ? 0 : (!std::strcmp(e, "wave") ? 2 : 1);
     return FWD ? 0 : 1;
   }();
+  const bool shift = same_line_phase(q, a, BWD ? dq : nullptr, BWD ? da : nullptr);
   with_bool(BWD && exact, [&](auto E) {   // a forward has no backward term: its EXACT is false
     constexpr bool EXACT = decltype(E)::value;
 #define MMS_P32(d4)                                                                                  \
   case 4 * d4:                                                                                       \
-    hipLaunchKernelGGL((layout == 0   ? euclid_pair32_kernel<d4, FWD, BWD, EXACT, WPB>               \
+    hipLaunchKernelGGL((layout == 0   ? (shift ? euclid_pair32_kernel<d4, FWD, BWD, EXACT, WPB, true> \
+                                               : euclid_pair32_kernel<d4, FWD, BWD, EXACT, WPB>)     \
                         : layout == 1 ? euclid_block_kernel<d4, FWD, BWD, EXACT, WPB>                \
                                       : euclid_block_kernel<d4, FWD, BWD, EXACT, WPB, 1>),           \
                        dim3(grid), dim3(64 * WPB), 0, s, N, q, a, top_in, top_diff, top_out, dq, da); \

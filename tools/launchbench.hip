@@ -42,6 +42,26 @@ template <int WPB> __global__ __launch_bounds__(64 * WPB) void f_pair(const floa
   for (int o = 16; o; o >>= 1) s += __shfl_xor(s, o);
   if (j == 0) top[row] = s;
 }
+// f_pair with a LINE-ALIGNED lane map: a row is 1200 B = 9 lines + 48 B, so row r starts u = (3r mod 8) float4s into
+// a 128-byte line and each 16-lane quarter of f_pair's 512-byte pieces straddles three lines.  Here lane j, slot it
+// holds float4 j + 32*it - u of its row (idle where that falls outside the row; 32*3 - 7 >= 75 still covers it):
+// every quarter starts on a line.  Same rows per wave, same bytes, no barrier.
+__device__ __forceinline__ int line_shift(const float4* row_start) { return (int)((reinterpret_cast<size_t>(row_start) >> 4) & 7); }
+template <int WPB> __global__ __launch_bounds__(64 * WPB) void f_pair_aligned(const float4* __restrict__ q, const float4* __restrict__ a,
+                                                                             float* __restrict__ top, int n) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = min((blockIdx.x * WPB + wave) * 2 + (lane >> 5), n - 1), j = lane & 31;
+  const size_t b = (size_t)row * D4;
+  const int u = line_shift(q + b);
+  float4 x[3], y[3];
+#pragma unroll
+  for (int it = 0; it < 3; ++it) { int i = j + 32 * it - u; int ii = (i >= 0 && i < D4) ? i : 0; x[it] = q[b + ii]; y[it] = a[b + ii]; }
+  float s = 0.f;
+#pragma unroll
+  for (int it = 0; it < 3; ++it) { int i = j + 32 * it - u; s += (i >= 0 && i < D4) ? sum4(x[it], y[it]) : 0.f; }
+  for (int o = 16; o; o >>= 1) s += __shfl_xor(s, o);
+  if (j == 0) top[row] = s;
+}
 // workgroup-blocked linear: a workgroup of T threads owns R rows = R*75 consecutive float4 per operand
 template <int T, int R> __global__ __launch_bounds__(T) void f_block(const float4* __restrict__ q, const float4* __restrict__ a,
                                                                     float* __restrict__ top, int n) {
@@ -91,6 +111,28 @@ template <int WPB> __global__ __launch_bounds__(64 * WPB) void b_pair(const floa
     }
   }
 }
+template <int WPB> __global__ __launch_bounds__(64 * WPB) void b_pair_aligned(const float4* __restrict__ q, const float4* __restrict__ a,
+                                                                             const float* __restrict__ top, const float* __restrict__ dT,
+                                                                             float4* __restrict__ dq, float4* __restrict__ da, int n) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = min((blockIdx.x * WPB + wave) * 2 + (lane >> 5), n - 1), j = lane & 31;
+  const size_t b = (size_t)row * D4;
+  const int u = line_shift(q + b);              // q, a, dq, da are congruent mod 128 here (hipMalloc)
+  float4 x[3], y[3];
+#pragma unroll
+  for (int it = 0; it < 3; ++it) { int i = j + 32 * it - u; int ii = (i >= 0 && i < D4) ? i : 0; x[it] = q[b + ii]; y[it] = a[b + ii]; }
+  const float c = top[row] * dT[row];
+#pragma unroll
+  for (int it = 0; it < 3; ++it) {
+    int i = j + 32 * it - u;
+    if (i >= 0 && i < D4) {
+      v4f_nt o0 = {c * (x[it].x - y[it].x), c * (x[it].y - y[it].y), c * (x[it].z - y[it].z), c * (x[it].w - y[it].w)};
+      v4f_nt o1 = {-o0.x, -o0.y, -o0.z, -o0.w};
+      __builtin_nontemporal_store(o0, (v4f_nt*)(dq + b + i));
+      __builtin_nontemporal_store(o1, (v4f_nt*)(da + b + i));
+    }
+  }
+}
 template <int T, int R> __global__ __launch_bounds__(T) void b_block(const float4* __restrict__ q, const float4* __restrict__ a,
                                                                     const float* __restrict__ top, const float* __restrict__ dT,
                                                                     float4* __restrict__ dq, float4* __restrict__ da, int n) {
@@ -118,7 +160,11 @@ struct Slot { float *q, *a, *dT, *top, *dq, *da; };
 
 int main(int argc, char** argv) {
   const int ring = 64, G = 16, reps = 64;
-  const bool only_empty = argc > 1 && atoi(argv[1]) == 1;
+  // argv[1]: 1 = the empty-kernel chains only; 2 = the lane-map table only (flat / pair / line-aligned pair / block,
+  // for go / no-go against the spread of repeated runs); 3 = plain launches of f_pair then f_pair_aligned over the
+  // ring, no graphs and no timing (what a rocprofv3 --pmc pass counts per kernel)
+  const int mode = argc > 1 ? atoi(argv[1]) : 0;
+  const bool only_empty = mode == 1;
   std::vector<Slot> s(ring);
   const size_t nb = (size_t)N * D * sizeof(float);
   {
@@ -167,22 +213,39 @@ int main(int argc, char** argv) {
     }
     fflush(stdout);
   };
-#define EMPTY(G_, T_) run("empty x1 grid " #G_ " x " #T_, [&](Slot& x, hipStream_t t) { \
-    hipLaunchKernelGGL(empty_kernel<T_>, dim3(G_), dim3(T_), 0, t, N); }, 0.0, false);
-  EMPTY(1, 64) EMPTY(256, 64) EMPTY(256, 256) EMPTY(256, 512) EMPTY(256, 1024) EMPTY(1200, 256) EMPTY(4800, 64) EMPTY(2048, 512)
-  if (only_empty) return 0;
-
 #define Q4 (const float4*)x.q
 #define A4 (const float4*)x.a
+  if (mode == 3) {
+    for (int rep = 0; rep < 4; ++rep)
+      for (auto& x : s) {
+        hipLaunchKernelGGL(f_pair<8>, dim3(N / 16), dim3(512), 0, st, Q4, A4, x.top, N);
+        hipLaunchKernelGGL(f_pair_aligned<8>, dim3(N / 16), dim3(512), 0, st, Q4, A4, x.top, N);
+      }
+    CK(hipStreamSynchronize(st));
+    return 0;
+  }
+#define EMPTY(G_, T_) run("empty x1 grid " #G_ " x " #T_, [&](Slot& x, hipStream_t t) { \
+    hipLaunchKernelGGL(empty_kernel<T_>, dim3(G_), dim3(T_), 0, t, N); }, 0.0, false);
+  if (mode != 2) {
+  EMPTY(1, 64) EMPTY(256, 64) EMPTY(256, 256) EMPTY(256, 512) EMPTY(256, 1024) EMPTY(1200, 256) EMPTY(4800, 64) EMPTY(2048, 512)
+  }
+  if (only_empty) return 0;
+
   // forward-like
   run("F flat 256", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_flat<256>, dim3((n4 + 255) / 256), dim3(256), 0, t, Q4, A4, x.top, n4); }, 2.0 * nb);
+  if (mode != 2) {
   run("F flat 512", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_flat<512>, dim3((n4 + 511) / 512), dim3(512), 0, t, Q4, A4, x.top, n4); }, 2.0 * nb);
   run("F flat 1024", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_flat<1024>, dim3((n4 + 1023) / 1024), dim3(1024), 0, t, Q4, A4, x.top, n4); }, 2.0 * nb);
   run("F flat 64", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_flat<64>, dim3((n4 + 63) / 64), dim3(64), 0, t, Q4, A4, x.top, n4); }, 2.0 * nb);
+  }
   run("F pair 8 waves (library layout)", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_pair<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
+  run("F pair 8 waves, line-aligned lane map", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_pair_aligned<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
+  if (mode != 2) {
   run("F pair 4 waves", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_pair<4>, dim3(N / 8), dim3(256), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
   run("F pair 1 wave", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(f_pair<1>, dim3(N / 2), dim3(64), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
+  }
   run("F block 512 thr x 16 rows", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((f_block<512, 16>), dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
+  if (mode != 2) {
   run("F block 256 thr x 8 rows", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((f_block<256, 8>), dim3(N / 8), dim3(256), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
   run("F block 256 thr x 4 rows", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((f_block<256, 4>), dim3(N / 4), dim3(256), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
   run("F block 128 thr x 2 rows", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((f_block<128, 2>), dim3(N / 2), dim3(128), 0, t, Q4, A4, x.top, N); }, 2.0 * nb);
@@ -190,13 +253,24 @@ int main(int argc, char** argv) {
   // backward-like alone (reads HBM-cold)
   run("B flat 256 nt", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((b_flat<256, true>), dim3((n4 + 255) / 256), dim3(256), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, n4); }, 4.0 * nb);
   run("B flat 256 plain stores", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((b_flat<256, false>), dim3((n4 + 255) / 256), dim3(256), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, n4); }, 4.0 * nb);
+  }
   run("B pair 8 waves (library layout)", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(b_pair<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, N); }, 4.0 * nb);
+  run("B pair 8 waves, line-aligned lane map", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL(b_pair_aligned<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, N); }, 4.0 * nb);
   run("B block 512 thr x 16 rows", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((b_block<512, 16>), dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, N); }, 4.0 * nb);
+  if (mode != 2) {
   run("B block 256 thr x 4 rows", [&](Slot& x, hipStream_t t) { hipLaunchKernelGGL((b_block<256, 4>), dim3(N / 4), dim3(256), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, N); }, 4.0 * nb);
   // the sequence
   run("SEQ F flat 256 + B flat 256 nt", [&](Slot& x, hipStream_t t) {
     hipLaunchKernelGGL(f_flat<256>, dim3((n4 + 255) / 256), dim3(256), 0, t, Q4, A4, x.top, n4);
     hipLaunchKernelGGL((b_flat<256, true>), dim3((n4 + 255) / 256), dim3(256), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, n4); }, 6.0 * nb);
+  }
+  run("SEQ F pair 8 + B block 512x16", [&](Slot& x, hipStream_t t) {
+    hipLaunchKernelGGL(f_pair<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, N);
+    hipLaunchKernelGGL((b_block<512, 16>), dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, N); }, 6.0 * nb);
+  run("SEQ F pair 8 line-aligned + B block 512x16", [&](Slot& x, hipStream_t t) {
+    hipLaunchKernelGGL(f_pair_aligned<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, N);
+    hipLaunchKernelGGL((b_block<512, 16>), dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, N); }, 6.0 * nb);
+  if (mode == 2) return 0;
   run("SEQ F pair 8 + B pair 8", [&](Slot& x, hipStream_t t) {
     hipLaunchKernelGGL(f_pair<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, N);
     hipLaunchKernelGGL(b_pair<8>, dim3(N / 16), dim3(512), 0, t, Q4, A4, x.top, x.dT, (float4*)x.dq, (float4*)x.da, N); }, 6.0 * nb);
