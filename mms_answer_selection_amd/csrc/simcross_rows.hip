@@ -567,7 +567,9 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
       float4 s;
       s.x = d.x * d.x; s.y = d.y * d.y; s.z = d.z * d.z; s.w = d.w * d.w;
       const int i4 = 2 * ir + hh;                // float4 index inside the pair's image
-      if (!TREE && i < n8) sq4[(r1 ? st4 : 0) + i4] = s;
+      if constexpr (!TREE) {
+        if (i < n8) sq4[(r1 ? st4 : 0) + i4] = s;
+      }
       const float s4 = (i < n8) ? (s.x + s.y) + (s.z + s.w) : 0.f;
       if (TREE) tree_total += s4;
       float2v c;
@@ -578,17 +580,23 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
       if (RW == 2) pred[RW - 1] += r1 ? c : z2;
     }
   }
-  const int npad = st4 - D4;
-  if (lane < RW * npad) sq4[(lane / npad) * st4 + D4 + (lane % npad)] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (!TREE) {                         // the tree sum reads no image: its launch has no LDS to pad
+    const int npad = st4 - D4;
+    if (lane < RW * npad) sq4[(lane / npad) * st4 + D4 + (lane % npad)] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   float my1 = 0.f, my2 = 0.f;
 #pragma unroll
   for (int r = 0; r < RW; ++r) {
     const float p1 = wave_sum(pred[r].x), p2 = wave_sum(pred[r].y);
     if (r == grow) { my1 = p1; my2 = p2; }
   }
-  wave_lds_sync();
-  const float dist = TREE ? wave_sum(tree_total)
-                          : chain_sum_speculative<LPR>(sq4 + grow * st4, D4, my1, my2, j, grp * LPR);
+  float dist;
+  if constexpr (TREE) {
+    dist = wave_sum(tree_total);
+  } else {
+    wave_lds_sync();
+    dist = chain_sum_speculative<LPR>(sq4 + grow * st4, D4, my1, my2, j, grp * LPR);
+  }
   const float T = 1.0f / (1.0f + sqrtf(dist));
   if (BWD) asm volatile("" : "+v"(g));          // in a register before the store of T (see euclid_pair32_kernel)
   if (j == 0 && grp < rows) top_out[row0 + grp] = T;
@@ -1179,7 +1187,7 @@ int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const f
                                              MMS_NIT4(euclid_rows_wave_f16_kernel, 1, true, true)};
     k = kernels[bwd][nit - 1];
     grid = (unsigned)((N + 3) / 4);
-    lds = 16;
+    lds = 0;                                          // no image: the tree instantiations touch no LDS
   } else if (rw == 2) {
     static constexpr Kernel kernels[2][4] = {MMS_NIT4(euclid_rows_wave_f16_kernel, 2, false),
                                              MMS_NIT4(euclid_rows_wave_f16_kernel, 2, true)};
