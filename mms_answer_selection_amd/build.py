@@ -21,10 +21,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmms_hip.so")
 LAYER_LIB = os.path.join(HERE, "libmms_caffe.so")
 
-HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "bilinear.hip", "pairrank.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip"]
+HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "gemm32.hip", "bilinear.hip", "simmatrix.hip", "pairrank.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip"]
 def _hip_headers():
-    """Every header under csrc/ is a dependency of every .hip object (panel_gemm.h is included by bilinear.hip,
-    euclid_math.h by three sources, ...): found by glob so that a new header cannot be forgotten."""
+    """Every header under csrc/ is a dependency of every .hip object (panel_gemm.h is included by simmatrix.hip,
+    gemm32.h by three sources, ...): found by glob so that a new header cannot be forgotten."""
     return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")))
 
 

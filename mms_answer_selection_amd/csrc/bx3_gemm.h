@@ -1,6 +1,6 @@
 // csrc/bx3_gemm.h -- the tall-times-small-weight products of the learned-metric paths (C[M x N] = A[M x K] . B[K x N],
 // M = all pairs, N, K <= 320: SimMatrix's Q W and (dT A) W^T, sim_matrix_layer.cpp:60-61, :88) on the BF16 matrix
-// pipe at fp32 accuracy (round 3).  Included by bilinear.hip.
+// pipe at fp32 accuracy (round 3).  Included by simmatrix.hip.
 //
 // Why: v_mfma_f32_16x16x4_f32 runs at the fp32 VECTOR rate (157 TF); round 2/3 measured the fp32 panel kernel at
 // 52-56 % of it with every remedy tried.  The bf16 pipe is 16x faster per instruction-cycle, and an fp32

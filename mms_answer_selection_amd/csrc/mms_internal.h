@@ -36,7 +36,7 @@ int simcross_elementwise_forward_backward(int mode, int N, int W1, int W2, int D
 int embed_simcross_forward(int mode, int N, int W1, int W2, int D, int K, const float* index_q, const float* index_a,
                            const float* weight, const float* embed_bias, float* top, float* norm0, float* norm1,
                            hipStream_t s);
-// bilinear.hip
+// bilinear.hip (SimCross dist_mode 2)
 size_t bilinear_workspace_bytes(int N, int W1, int W2, int D, int M);
 int bilinear_forward(int N, int W1, int W2, int D, int M, const float* q, const float* a, const float* W,
                      const float* bias, float* top, void* ws, size_t ws_bytes, hipStream_t s);
@@ -46,6 +46,7 @@ int bilinear_backward(int N, int W1, int W2, int D, int M, const float* q, const
 int embed_bilinear_forward(int N, int W1, int W2, int D, int M, int K, const float* index_q, const float* index_a,
                            const float* table, const float* embed_bias, const float* W, const float* bias, float* top,
                            hipStream_t s);
+// simmatrix.hip
 int set_matrix_mode(int mode);
 int get_matrix_mode();
 size_t simmatrix_workspace_bytes(int N, int K1, int K2);

@@ -1,6 +1,6 @@
 // csrc/panel_gemm.h -- "panel" fp32-MFMA GEMM for the shapes the learned-metric paths actually have:
 // a TALL operand (all pairs: tens of thousands of rows) times a SMALL square weight (D x D, D <= 304),
-// and the transposed-tall x tall product of the weight gradient.  Included by bilinear.hip.
+// and the transposed-tall x tall product of the weight gradient.  Included by simmatrix.hip.
 //
 //   C[M x N] = A[M x K] . B[K x N],   B(k,n) = B[k*ldb + n],   N <= 16 * NT  (NT = 19: the 300-d width)
 //
@@ -35,7 +35,7 @@
 //   * A_KC = false reads A "transposed" (A(i,k) = A[k*lda + i], scaled by kscale[k]): the weight
 //     gradient dW = Q^T diag(dT) A as a split-K product whose chunks are placed so that the row blocks
 //     of one k-chunk run on ONE XCD (they stream the same rows of B through that XCD's L2).
-// Reference semantics are those of the callers (bilinear.hip header); fp32 rounding differs from the
+// Reference semantics are those of the callers (simmatrix.hip header); fp32 rounding differs from the
 // 64 x 64 kernel's (another k order), inside the 1e-5 contract of these BLAS-backed products.
 #ifndef MMS_PANEL_GEMM_H_
 #define MMS_PANEL_GEMM_H_

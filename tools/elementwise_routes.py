@@ -141,13 +141,14 @@ def build_routes():
     return torch, capi
 
 
-def run():
+def run(build=build_routes):
+    """build: fills ROUTES (tools/learned_metric_routes.py passes its own)"""
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from mms_answer_selection_amd import capi
     if args.lib:
         capi.LIB_PATH = os.path.abspath(args.lib)
-    torch, _ = build_routes()
+    torch, _ = build()
     sep = torch.zeros(1, device="cuda")
     torch.cuda.synchronize()
     if args.labels:
@@ -162,23 +163,29 @@ def run():
     print("%d calls" % len(ROUTES))
 
 
-def listing(out_dir):
+def listing(out_dir, ignore=None, grid3=False):
+    """ignore: regex of foreign kernels that neither belong to a call nor end it (the runtime's own fill kernel, which
+    a hipMemsetAsync inside a call launches); grid3: workgroups as X x Y x Z (the GEMM kernels' grids), not X alone"""
     labels = open(args.labels).read().splitlines()
     f = glob.glob(out_dir + "/**/*kernel_trace.csv", recursive=True)[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
     groups, cur = [], None
     for r in rows:                                   # a run of the library's kernels between two foreign ones = a call
+        if ignore and re.search(ignore, r["Kernel_Name"]):
+            continue
         if re.search(r"\bmms::|_ZN3mms", r["Kernel_Name"]):
             if cur is None:
                 cur = []
                 groups.append(cur)
             wg = int(r["Workgroup_Size_X"])
-            cur.append("    %s  grid %d  workgroup %d  lds %s" % (r["Kernel_Name"], int(r["Grid_Size_X"]) // wg, wg,
-                                                                    r.get("LDS_Block_Size", "?")))
+            grid = "%d" % (int(r["Grid_Size_X"]) // wg)
+            if grid3:
+                grid += " x %d x %d" % tuple(int(r["Grid_Size_" + d]) // int(r["Workgroup_Size_" + d]) for d in "YZ")
+            cur.append("    %s  grid %s  workgroup %d  lds %s" % (r["Kernel_Name"], grid, wg, r.get("LDS_Block_Size", "?")))
         else:
             cur = None
     if len(groups) != len(labels):
-        sys.exit("elementwise_routes: %d labelled calls but %d groups of launches" % (len(labels), len(groups)))
+        sys.exit("%s: %d labelled calls but %d groups of launches" % (sys.argv[0], len(labels), len(groups)))
     for label, grp in zip(labels, groups):
         print(label)
         print("\n".join(grp))

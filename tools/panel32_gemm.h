@@ -29,7 +29,7 @@
 //     scale and the SimMatrix row dot applied on the way: the panel's rows of Y arrive by DMA in the two tile slots
 //     behind the last tile (slots the ring protocol fills anyway), and the two column halves of a row meet in LDS in
 //     a fixed order.  The side job (da = diag(dT) QW) is spread over the main loop, one row pass at a time.
-// Reference semantics: those of the callers (bilinear.hip); results are inside the 1e-5 contract of these
+// Reference semantics: those of the callers (simmatrix.hip); results are inside the 1e-5 contract of these
 // BLAS-backed products (sim_matrix_layer.cpp:53-95, sim_cross_layer.cpp:140-161, 251-305).
 #ifndef MMS_PANEL32_GEMM_H_
 #define MMS_PANEL32_GEMM_H_
