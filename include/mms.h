@@ -224,7 +224,34 @@ int mms_simcross_cosine_forward_backward_f16(int N, int D, const void* q_f16, co
                                              float* top, float* norm0, float* norm1, void* dq_f16, void* da_f16,
                                              void* stream);
 
-/* Device scratch needed by the three calls above (0 is possible). */
+/* fp16-STORAGE SimCross on W1 x W2 WORD GRIDS, dist_mode 0 (cosine) and 1 (Euclid): q (N,W1,D), a (N,W2,D), dq, da IEEE
+ * half in HBM; top, top_diff (N,1,W1,W2) and norm0 (N,W1), norm1 (N,W2) fp32.  No workspace.
+ *   Arithmetic: every half is widened exactly and everything is the fp32 arithmetic of mms_simcross_forward_f32 /
+ *       mms_simcross_backward_f32 on the widened inputs, all sums fp32 in the reference's order: the forward sums d
+ *       ascending per output, dq[j,d] sums over k ascending from 0, da[k,d] over j ascending from 0
+ *       (sim_cross_layer.cpp:96-139, 208-250).  Euclid: top carries the bits of the fp32 call.  Cosine: top and the norms
+ *       carry its bits too (same kernels' order).  mms_set_f16_distance_mode is NOT consulted: the tree sum belongs to
+ *       the rows family (W1 = W2 = 1) above only; here every dist_mode sums in order whatever that mode says.
+ *   Gradients: accumulated in fp32, each element rounded ONCE (RNE) to half when stored; overflow gives +-Inf as RNE does.
+ *   Norms: dist_mode 0: required, written by the forward, read by the backward (as mms_simcross_forward_f32);
+ *       dist_mode 1: ignored, may be NULL.
+ *   Euclid backward: mms_set_euclid_backward_mode is honoured as in mms_simcross_backward_f32 (reference: the fp32
+ *       gradient is the reference's bit for bit before its one rounding to half), read once per call.
+ *   Any D >= 1 and any 2-byte aligned operands: alignment only selects between kernels, never refuses.
+ *   MMS_ERR_UNSUPPORTED: dist_mode 2 (the bilinear mode has no half storage); W1 == 1 && W2 == 1 (use the rows family:
+ *       mms_simcross_euclid_*_f16 / mms_simcross_cosine_*_f16).  MMS_ERR_INVALID_ARG: bad sizes, a NULL required pointer,
+ *       as in the fp32 calls.  N == 0: MMS_OK.  A call that does not return MMS_OK, and N == 0, write nothing.
+ *   mms_simcross_forward_backward_f16: the forward, then the backward, on `stream`; the same bits as the two calls. */
+int mms_simcross_forward_f16(int dist_mode, int N, int W1, int W2, int D, const void* q_f16, const void* a_f16,
+                             float* top, float* norm0, float* norm1, void* stream);
+int mms_simcross_backward_f16(int dist_mode, int N, int W1, int W2, int D, const void* q_f16, const void* a_f16,
+                              const float* top, const float* top_diff, const float* norm0, const float* norm1,
+                              void* dq_f16, void* da_f16, void* stream);
+int mms_simcross_forward_backward_f16(int dist_mode, int N, int W1, int W2, int D, const void* q_f16,
+                                      const void* a_f16, const float* top_diff, float* top, float* norm0,
+                                      float* norm1, void* dq_f16, void* da_f16, void* stream);
+
+/* Device scratch needed by the three fp32 calls above (0 is possible). */
 size_t mms_simcross_workspace_bytes(int dist_mode, int N, int W1, int W2, int D,
                                     int M);
 

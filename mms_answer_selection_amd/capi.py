@@ -50,6 +50,9 @@ _SIGNATURES = {
     "mms_simcross_euclid_forward_backward_f16": (_i, [_i, _i] + [_vp] * 7),
     "mms_simcross_cosine_forward_f16": (_i, [_i, _i] + [_vp] * 5 + [_vp]),
     "mms_simcross_cosine_forward_backward_f16": (_i, [_i, _i] + [_vp] * 8 + [_vp]),
+    "mms_simcross_forward_f16": (_i, [_i] * 5 + [_vp] * 5 + [_vp]),
+    "mms_simcross_backward_f16": (_i, [_i] * 5 + [_vp] * 8 + [_vp]),
+    "mms_simcross_forward_backward_f16": (_i, [_i] * 5 + [_vp] * 8 + [_vp]),
     "mms_embed_workspace_bytes": (_sz, [_i, _i]),
     "mms_embed_forward_f32": (_i, [_i, _i, _i] + [_vp] * 5),
     "mms_embed_backward_f32": (_i, [_i, _i, _i] + [_vp] * 5 + [_sz, _vp]),
@@ -534,6 +537,63 @@ def simcross_cosine_forward_f16(q, a, top, norm0=None, norm1=None):
     check(lib().mms_simcross_cosine_forward_f16(N, D, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(top, "top"),
                                                 _ptr(norm0, "norm0", True), _ptr(norm1, "norm1", True), _stream()),
           "mms_simcross_cosine_forward_f16")
+
+
+def _grid_f16_shape(q, a):
+    """(N, W1, W2, D) of half word grids q (N, W1, D), a (N, W2, D)."""
+    if q.dim() != 3 or a.dim() != 3 or q.shape[0] != a.shape[0] or q.shape[2] != a.shape[2]:
+        raise MMSError("q (N, W1, D) and a (N, W2, D) expected, got %s and %s" % (tuple(q.shape), tuple(a.shape)))
+    return q.shape[0], q.shape[1], a.shape[1], q.shape[2]
+
+
+def _expect_shape(t, shape, name):
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise MMSError("%s must have shape %s (got %s)" % (name, tuple(shape), tuple(t.shape)))
+
+
+def simcross_forward_f16(mode, q, a, top, norm0=None, norm1=None):
+    """fp16-storage SimCross forward on word grids, dist_mode 0 / 1 (include/mms.h: mms_simcross_forward_f16): q, a half
+    tensors; top (N, 1, W1, W2), norm0 (N, W1), norm1 (N, W2) float32, the norms for dist_mode 0 only."""
+    N, W1, W2, D = _grid_f16_shape(q, a)
+    h = torch.float16
+    _expect_shape(top, (N, 1, W1, W2), "top")
+    _expect_shape(norm0, (N, W1), "norm0")
+    _expect_shape(norm1, (N, W2), "norm1")
+    check(lib().mms_simcross_forward_f16(mode, N, W1, W2, D, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(top, "top"),
+                                         _ptr(norm0, "norm0", True), _ptr(norm1, "norm1", True), _stream()),
+          "mms_simcross_forward_f16")
+
+
+def simcross_backward_f16(mode, q, a, top, top_diff, dq, da, norm0=None, norm1=None):
+    """The backward of simcross_forward_f16: dq, da half tensors shaped like q, a (mms_simcross_backward_f16)."""
+    N, W1, W2, D = _grid_f16_shape(q, a)
+    h = torch.float16
+    _expect_shape(top, (N, 1, W1, W2), "top")
+    _expect_shape(top_diff, (N, 1, W1, W2), "top_diff")
+    _expect_shape(norm0, (N, W1), "norm0")
+    _expect_shape(norm1, (N, W2), "norm1")
+    _expect_shape(dq, q.shape, "dq")
+    _expect_shape(da, a.shape, "da")
+    check(lib().mms_simcross_backward_f16(
+        mode, N, W1, W2, D, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(top, "top"), _ptr(top_diff, "top_diff"),
+        _ptr(norm0, "norm0", True), _ptr(norm1, "norm1", True), _ptr(dq, "dq", dtype=h), _ptr(da, "da", dtype=h), _stream()),
+        "mms_simcross_backward_f16")
+
+
+def simcross_forward_backward_f16(mode, q, a, top_diff, top, dq, da, norm0=None, norm1=None):
+    """simcross_forward_f16 then simcross_backward_f16 in one call (mms_simcross_forward_backward_f16)."""
+    N, W1, W2, D = _grid_f16_shape(q, a)
+    h = torch.float16
+    _expect_shape(top, (N, 1, W1, W2), "top")
+    _expect_shape(top_diff, (N, 1, W1, W2), "top_diff")
+    _expect_shape(norm0, (N, W1), "norm0")
+    _expect_shape(norm1, (N, W2), "norm1")
+    _expect_shape(dq, q.shape, "dq")
+    _expect_shape(da, a.shape, "da")
+    check(lib().mms_simcross_forward_backward_f16(
+        mode, N, W1, W2, D, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(top_diff, "top_diff"), _ptr(top, "top"),
+        _ptr(norm0, "norm0", True), _ptr(norm1, "norm1", True), _ptr(dq, "dq", dtype=h), _ptr(da, "da", dtype=h), _stream()),
+        "mms_simcross_forward_backward_f16")
 
 
 def embed_forward(index, weight, top, bias=None):

@@ -71,6 +71,10 @@ __device__ __forceinline__ float euclid_tt(const EuclidCoef& k, float diff) {
   return res;
 }
 
+// The term in the fp32 arithmetic of MMS_EUCLID_BWD_FP32 (include/mms.h): r = fl32(1/den), at most 2 ulp from
+// euclid_tt's value.
+__device__ __forceinline__ float euclid_tt_f32(float c, float r, float diff) { return (c * diff) * r; }
+
 // Four elements that share one coefficient set (a float4 of one pair's row):
 // same arithmetic as euclid_tt, with the rare-case tests made cheaper and
 // RETURNED instead of branched on, so that a caller can run several float4s

@@ -253,6 +253,48 @@ int mms_simcross_euclid_forward_backward_f16(int N, int D, const void* q_f16, co
                                   as_stream(stream));
 }
 
+// The word-grid fp16-storage calls: what all three check before anything else.  MMS_OK: go on.
+static int grid_f16_refusal(int dist_mode, int N, int W1, int W2, int D) {
+  if (!dims_ok(dist_mode, N, W1, W2, D, 1)) return MMS_ERR_INVALID_ARG;
+  if (dist_mode == 2) return MMS_ERR_UNSUPPORTED;                 // the bilinear mode has no half-storage kernels
+  if (W1 == 1 && W2 == 1) return MMS_ERR_UNSUPPORTED;             // the rows family: mms_simcross_{euclid,cosine}_*_f16
+  return MMS_OK;
+}
+
+int mms_simcross_forward_f16(int dist_mode, int N, int W1, int W2, int D, const void* q_f16, const void* a_f16,
+                             float* top, float* norm0, float* norm1, void* stream) {
+  const int rc = grid_f16_refusal(dist_mode, N, W1, W2, D);
+  if (rc != MMS_OK) return rc;
+  if (N == 0) return MMS_OK;
+  if (!q_f16 || !a_f16 || !top) return MMS_ERR_INVALID_ARG;
+  if (dist_mode == 0 && (!norm0 || !norm1)) return MMS_ERR_INVALID_ARG;
+  return simcross_grid_forward_f16(dist_mode, N, W1, W2, D, q_f16, a_f16, top, norm0, norm1, as_stream(stream));
+}
+
+int mms_simcross_backward_f16(int dist_mode, int N, int W1, int W2, int D, const void* q_f16, const void* a_f16,
+                              const float* top, const float* top_diff, const float* norm0, const float* norm1,
+                              void* dq_f16, void* da_f16, void* stream) {
+  const int rc = grid_f16_refusal(dist_mode, N, W1, W2, D);
+  if (rc != MMS_OK) return rc;
+  if (N == 0) return MMS_OK;
+  if (!q_f16 || !a_f16 || !top || !top_diff || !dq_f16 || !da_f16) return MMS_ERR_INVALID_ARG;
+  if (dist_mode == 0 && (!norm0 || !norm1)) return MMS_ERR_INVALID_ARG;
+  return simcross_grid_backward_f16(dist_mode, N, W1, W2, D, q_f16, a_f16, top, top_diff, norm0, norm1, dq_f16, da_f16,
+                                    as_stream(stream));
+}
+
+int mms_simcross_forward_backward_f16(int dist_mode, int N, int W1, int W2, int D, const void* q_f16,
+                                      const void* a_f16, const float* top_diff, float* top, float* norm0,
+                                      float* norm1, void* dq_f16, void* da_f16, void* stream) {
+  const int rc = grid_f16_refusal(dist_mode, N, W1, W2, D);
+  if (rc != MMS_OK) return rc;
+  if (N == 0) return MMS_OK;
+  if (!q_f16 || !a_f16 || !top_diff || !top || !dq_f16 || !da_f16) return MMS_ERR_INVALID_ARG;
+  if (dist_mode == 0 && (!norm0 || !norm1)) return MMS_ERR_INVALID_ARG;
+  return simcross_grid_forward_backward_f16(dist_mode, N, W1, W2, D, q_f16, a_f16, top_diff, top, norm0, norm1, dq_f16,
+                                            da_f16, as_stream(stream));
+}
+
 int mms_embed_simcross_forward_f32(int dist_mode, int N, int W1, int W2, int D, int K,
                                    const float* index_q, const float* index_a, const float* weight,
                                    const float* embed_bias, float* top, float* norm0, float* norm1, void* stream) {

@@ -36,6 +36,15 @@ int simcross_elementwise_forward_backward(int mode, int N, int W1, int W2, int D
 int embed_simcross_forward(int mode, int N, int W1, int W2, int D, int K, const float* index_q, const float* index_a,
                            const float* weight, const float* embed_bias, float* top, float* norm0, float* norm1,
                            hipStream_t s);
+// simcross_cross_f16.hip (fp16 storage, word grids, dist_mode 0 / 1; the caller has checked the arguments)
+int simcross_grid_forward_f16(int mode, int N, int W1, int W2, int D, const void* q, const void* a, float* top,
+                              float* norm0, float* norm1, hipStream_t s);
+int simcross_grid_backward_f16(int mode, int N, int W1, int W2, int D, const void* q, const void* a, const float* top,
+                               const float* top_diff, const float* norm0, const float* norm1, void* dq, void* da,
+                               hipStream_t s);
+int simcross_grid_forward_backward_f16(int mode, int N, int W1, int W2, int D, const void* q, const void* a,
+                                       const float* top_diff, float* top, float* norm0, float* norm1, void* dq,
+                                       void* da, hipStream_t s);
 // bilinear.hip (SimCross dist_mode 2)
 size_t bilinear_workspace_bytes(int N, int W1, int W2, int D, int M);
 int bilinear_forward(int N, int W1, int W2, int D, int M, const float* q, const float* a, const float* W,

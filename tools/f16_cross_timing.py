@@ -1,0 +1,95 @@
+"""tools/f16_cross_timing.py -- dev-only: the fp16-storage word-grid calls against the fp32 entry points on the same shapes, the
+inputs widened.  HIP events around one pass over a ring of operand sets larger than the last-level cache (every call reads its
+operands from HBM), both variants in one process, alternating, REPS passes each; prints median, min and max per call in us.
+
+  python tools/f16_cross_timing.py [--reps 7] [--out FILE]
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from mms_answer_selection_amd import capi
+
+RING_BYTES = 768 << 20          # per variant: three times the 256 MB last-level cache
+
+
+def operand_sets(shape, half, n_sets):
+    N, W1, W2, D = shape
+    g = torch.Generator(device="cuda").manual_seed(7)
+    sets = []
+    for _ in range(n_sets):
+        q = (torch.randn(N, W1, D, device="cuda", generator=g) * 0.4).half()
+        a = (torch.randn(N, W2, D, device="cuda", generator=g) * 0.4).half()
+        if not half:
+            q, a = q.float(), a.float()
+        sets.append(dict(q=q, a=a, dT=torch.randn(N, 1, W1, W2, device="cuda", generator=g), top=torch.empty(N, 1, W1, W2, device="cuda"),
+                         n0=torch.empty(N, W1, device="cuda"), n1=torch.empty(N, W2, device="cuda"), dq=torch.empty_like(q), da=torch.empty_like(a)))
+    return sets
+
+
+def set_bytes(shape, half):
+    N, W1, W2, D = shape
+    e = 2 if half else 4
+    return 2 * N * (W1 + W2) * D * e + 2 * N * W1 * W2 * 4
+
+
+def call(kind, mode, half, s):
+    n = dict(norm0=s["n0"], norm1=s["n1"]) if mode == 0 else {}
+    if kind == "fwd":
+        (capi.simcross_forward_f16 if half else capi.simcross_forward)(mode, s["q"], s["a"], s["top"], **n)
+    elif kind == "bwd":
+        (capi.simcross_backward_f16 if half else capi.simcross_backward)(mode, s["q"], s["a"], s["top"], s["dT"], s["dq"], s["da"], **n)
+    else:
+        (capi.simcross_forward_backward_f16 if half else capi.simcross_forward_backward)(mode, s["q"], s["a"], s["dT"], s["top"], s["dq"], s["da"], **n)
+
+
+def one_pass(kind, mode, half, sets):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for s in sets:
+        call(kind, mode, half, s)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / len(sets)
+
+
+CASES = [("fwd", 1, "fp32", (1517, 40, 40, 50)), ("fwd", 0, "fp32", (1517, 40, 40, 50)), ("bwd", 1, "fp32", (1517, 40, 40, 50)),
+         ("bwd", 1, "reference", (1517, 40, 40, 50)), ("fwdbwd", 1, "fp32", (64, 40, 40, 300)), ("fwdbwd", 0, "fp32", (64, 40, 40, 300))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = ["%s, %d passes per variant, ring of operand sets >= %d MB per variant" % (torch.cuda.get_device_name(0), args.reps, RING_BYTES >> 20)]
+    for kind, mode, bwd_mode, shape in CASES:
+        capi.set_euclid_backward_mode(bwd_mode)
+        sets = {half: operand_sets(shape, half, max(4, min(256, -(-RING_BYTES // set_bytes(shape, half))))) for half in (False, True)}
+        for half in (False, True):                   # the backward reads a forward's top (and norms)
+            for s in sets[half]:
+                call("fwd", mode, half, s)
+            one_pass(kind, mode, half, sets[half])   # warm-up pass
+        ts = {False: [], True: []}
+        for _ in range(args.reps):
+            for half in (False, True):
+                ts[half].append(one_pass(kind, mode, half, sets[half]))
+        what = "%-6s %s %-9s %s" % (kind, ("cosine", "euclid")[mode], bwd_mode if (mode == 1 and kind != "fwd") else "", "x".join(map(str, shape)))
+        for half in (False, True):
+            v = sorted(ts[half])
+            lines.append("%-44s %-4s median %8.2f us   min %8.2f   max %8.2f   (%d sets)" % (what, "f16" if half else "fp32", v[len(v) // 2], v[0], v[-1],
+                                                                                            len(sets[half])))
+        print("\n".join(lines[-2:]), flush=True)
+        del sets
+        torch.cuda.empty_cache()
+    capi.set_euclid_backward_mode("fp32")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
