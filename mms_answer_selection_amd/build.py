@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmms_hip.so")
 LAYER_LIB = os.path.join(HERE, "libmms_caffe.so")
 
-HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "simmatrix.hip", "pairrank.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip"]
+HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip"]
 def _hip_headers():
     """Every header under csrc/ is a dependency of every .hip object (panel_gemm.h is included by simmatrix.hip,
     gemm32.h by three sources, ...): found by glob so that a new header cannot be forgotten."""
@@ -34,9 +34,9 @@ HIPCC_FLAGS = [
     "-fno-fast-math", "-Wall", "-Wno-unused-function",
     "-mllvm", "-amdgpu-kernarg-preload-count=16",
 ]
-# pairrank.hip: the arrival atomics of the fused step are issued by ONE lane and their return values are consumed
+# triplet_steps.hip: the arrival atomics of the fused steps are issued by ONE lane and their return values are consumed
 # after the gradient stores; the atomic optimizer's wave scan + readfirstlane would pull the wait to the issue.
-EXTRA_FLAGS = {"pairrank.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+EXTRA_FLAGS = {"triplet_steps.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
 
 
 def _hipcc():

@@ -233,13 +233,23 @@ __host__ __device__ __forceinline__ int spec_h4(int D4) { return (D4 + 2) / 3; }
 __host__ __device__ __forceinline__ int spec_stride4(int D4) { return 3 * spec_h4(D4); }
 
 // Host-side facts about the kernels built on this scheme (simcross_rows.hip and the fused triplet steps of
-// pairrank.hip route on them; each is written here and nowhere else).
+// triplet_steps.hip route on them; each is written here and nowhere else).
 // Dynamic LDS of a workgroup of `waves` waves that each hold `pairs_per_wave` images of D4 float4.
 inline size_t spec_image_lds(int waves, int pairs_per_wave, int D4) {
   return (size_t)waves * pairs_per_wave * spec_stride4(D4) * sizeof(float4);
 }
 // Widths with a kernel specialised at compile time: 100-d, 200-d and 300-d GloVe (D4 = 25, 50, 75).
 inline bool glove_width(int D) { return D == 300 || D == 200 || D == 100; }
+// f(std::integral_constant<int, D4>{}) for such a width, so that D4 can be a template argument:
+// with_glove_d4(D, [&](auto W) { launch K<decltype(W)::value, ...> }).  Calls nothing for any other D.
+template <class F>
+inline void with_glove_d4(int D, F&& f) {
+  switch (D) {
+    case 100: f(std::integral_constant<int, 25>{}); break;
+    case 200: f(std::integral_constant<int, 50>{}); break;
+    case 300: f(std::integral_constant<int, 75>{}); break;
+  }
+}
 // A wave kernel keeps a pair in registers, at most four 16-byte loads per operand per lane of a whole wave.
 inline bool wave_width_ok(int D) { return D <= 1024; }
 // Two pairs per wave (32 candidate lanes each) only while the narrower windows hold: at D = 1024 the ordered

@@ -80,6 +80,12 @@ int pairrank_forward(int count, float margin, const float* a, const float* b, co
                      float* similar, float* loss, void* ws, size_t ws_bytes, hipStream_t s);
 int pairrank_backward(int count, float top_diff, const float* y, const float* ordered, const float* similar, float* da,
                       float* db, hipStream_t s);
+int triplet_loss_from_terms(const float* terms, int N, float* loss, hipStream_t s);
+int pairrank_hinge_mode();
+void set_pairrank_hinge_mode(int m);
+int loss_sum_mode();
+void set_loss_sum_mode(int m);
+// triplet_steps.hip
 size_t triplet_workspace_bytes(int N);
 int triplet_workspace_init(void* ws, size_t ws_bytes, hipStream_t s);
 int triplet_euclid_step(int N, int D, float margin, float loss_weight, const float* q, const float* ap, const float* an,
@@ -88,13 +94,8 @@ int triplet_euclid_step(int N, int D, float margin, float loss_weight, const flo
 int triplet_cosine_step(int N, int D, float margin, float loss_weight, const float* q, const float* ap, const float* an,
                         const float* y, float* s_pos, float* s_neg, float* norm_q, float* norm_pos, float* norm_neg,
                         float* loss, float* dq, float* dap, float* dan, void* ws, size_t ws_bytes, hipStream_t s);
-int triplet_loss_from_terms(const float* terms, int N, float* loss, hipStream_t s);
-int pairrank_hinge_mode();
-void set_pairrank_hinge_mode(int m);
 int triplet_finish_mode();
 void set_triplet_finish_mode(int m);
-int loss_sum_mode();
-void set_loss_sum_mode(int m);
 // ranking.hip
 // (T = float or double: the folds run in T, the order is that of the scores narrowed to float for both)
 size_t rank_workspace_bytes(int n);

@@ -1,6 +1,7 @@
 // csrc/pairrank_math.h -- PairRankLoss for ONE element, in the reference's operation order
-// (src/caffe/layers/pair_rank_loss_layer.cpp:28-37, 43-44, 72-79).  Shared by pairrank.hip (the layer's kernels and
-// the fused Euclidean triplet step) and by the panel GEMM's epilogue (the fused learned-metric triplet step).
+// (src/caffe/layers/pair_rank_loss_layer.cpp:28-37, 43-44, 72-79).  Shared by pairrank.hip (the layer's kernels),
+// triplet_steps.hip (the fused Euclid and cosine triplet steps) and the panel GEMM's epilogue (the fused
+// learned-metric triplet step).
 #ifndef MMS_PAIRRANK_MATH_H_
 #define MMS_PAIRRANK_MATH_H_
 

@@ -1065,18 +1065,16 @@ static void launch_pair32(const float* q, const float* a, const float* top_in, c
     return FWD ? 0 : 1;
   }();
   const bool shift = same_line_phase(q, a, BWD ? dq : nullptr, BWD ? da : nullptr);
-  with_bool(BWD && exact, [&](auto E) {   // a forward has no backward term: its EXACT is false
-    constexpr bool EXACT = decltype(E)::value;
-#define MMS_P32(d4)                                                                                  \
-  case 4 * d4:                                                                                       \
-    hipLaunchKernelGGL((layout == 0   ? (shift ? euclid_pair32_kernel<d4, FWD, BWD, EXACT, WPB, true> \
-                                               : euclid_pair32_kernel<d4, FWD, BWD, EXACT, WPB>)     \
-                        : layout == 1 ? euclid_block_kernel<d4, FWD, BWD, EXACT, WPB>                \
-                                      : euclid_block_kernel<d4, FWD, BWD, EXACT, WPB, 1>),           \
-                       dim3(grid), dim3(64 * WPB), 0, s, N, q, a, top_in, top_diff, top_out, dq, da); \
-    break;
-    switch (D) { MMS_P32(25) MMS_P32(50) MMS_P32(75) }
-#undef MMS_P32
+  with_glove_d4(D, [&](auto W) {
+    constexpr int D4C = decltype(W)::value;
+    with_bool(BWD && exact, [&](auto E) {   // a forward has no backward term: its EXACT is false
+      constexpr bool EXACT = decltype(E)::value;
+      hipLaunchKernelGGL((layout == 0   ? (shift ? euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB, true>
+                                                 : euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB>)
+                          : layout == 1 ? euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB>
+                                        : euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB, 1>),
+                         dim3(grid), dim3(64 * WPB), 0, s, N, q, a, top_in, top_diff, top_out, dq, da);
+    });
   });
 }
 
@@ -1130,13 +1128,10 @@ void launch_cosine_rows(int N, int D, const float* q, const float* a, const floa
   if (route == CosineRows::kPair32) {
     constexpr int WPB = 8;
     const unsigned grid = (unsigned)((N + 2 * WPB - 1) / (2 * WPB));
-#define MMS_C32(d4)                                                                                 \
-  case 4 * d4:                                                                                      \
-    hipLaunchKernelGGL((cosine_pair32_kernel<d4, FWD, BWD, WPB>), dim3(grid), dim3(64 * WPB), 0, s, \
-                       N, q, a, top_diff, top, norm0, norm1, dq, da);                               \
-    break;
-    switch (D) { MMS_C32(25) MMS_C32(50) MMS_C32(75) }
-#undef MMS_C32
+    with_glove_d4(D, [&](auto W) {
+      hipLaunchKernelGGL((cosine_pair32_kernel<decltype(W)::value, FWD, BWD, WPB>), dim3(grid), dim3(64 * WPB), 0, s,
+                         N, q, a, top_diff, top, norm0, norm1, dq, da);
+    });
   } else {
     hipLaunchKernelGGL((route == CosineRows::kVec4 ? cosine_rows_kernel<true, FWD, BWD> : cosine_rows_kernel<false, FWD, BWD>),
                        dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, q, a, top_diff, top, norm0, norm1, dq, da, N, D);
