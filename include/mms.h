@@ -238,7 +238,7 @@ int mms_simcross_cosine_forward_backward_f16(int N, int D, const void* q_f16, co
  *   Euclid backward: mms_set_euclid_backward_mode is honoured as in mms_simcross_backward_f32 (reference: the fp32
  *       gradient is the reference's bit for bit before its one rounding to half), read once per call.
  *   Any D >= 1 and any 2-byte aligned operands: alignment only selects between kernels, never refuses.
- *   MMS_ERR_UNSUPPORTED: dist_mode 2 (the bilinear mode has no half storage); W1 == 1 && W2 == 1 (use the rows family:
+ *   MMS_ERR_UNSUPPORTED: dist_mode 2 (use mms_simcross_bilinear_*_f16 below); W1 == 1 && W2 == 1 (use the rows family:
  *       mms_simcross_euclid_*_f16 / mms_simcross_cosine_*_f16).  MMS_ERR_INVALID_ARG: bad sizes, a NULL required pointer,
  *       as in the fp32 calls.  N == 0: MMS_OK.  A call that does not return MMS_OK, and N == 0, write nothing.
  *   mms_simcross_forward_backward_f16: the forward, then the backward, on `stream`; the same bits as the two calls. */
@@ -250,6 +250,49 @@ int mms_simcross_backward_f16(int dist_mode, int N, int W1, int W2, int D, const
 int mms_simcross_forward_backward_f16(int dist_mode, int N, int W1, int W2, int D, const void* q_f16,
                                       const void* a_f16, const float* top_diff, float* top, float* norm0,
                                       float* norm1, void* dq_f16, void* da_f16, void* stream);
+
+/* fp16-STORAGE SimCross dist_mode 2 (bilinear, T[n,m] = Q_n W_m A_n^T + bias_m) on W1 x W2 WORD GRIDS, the mode network_v4
+ * scores and trains with (sim_cross_layer.cpp:140-161, 251-305): q (N,W1,D), a (N,W2,D), dq, da IEEE half in HBM; W (M,D,D),
+ * bias and dbias (M,W1,W2), top and top_diff (N,M,W1,W2) and dW (M,D,D) fp32.  bias NULL = no bias term.
+ *   Arithmetic: every half is widened exactly and everything after that is the fp32 arithmetic of mms_simcross_forward_f32 /
+ *       mms_simcross_backward_f32 at dist_mode 2 on the widened inputs (the same kernels, instantiated for half storage, where
+ *       the word grids fit them; otherwise those calls themselves on a widened copy in the workspace).  The sums the
+ *       reference takes in place keep their ascending order: dq, da over m; dW over pairs; dbias over n.  dW is OVERWRITTEN;
+ *       dbias is ACCUMULATED into when bias_term != 0 (the fused call: when bias != NULL) and untouched otherwise.
+ *   Bits: top, dW and dbias carry the bits of the fp32 calls run on 16-byte-aligned fp32 copies of the widened operands; dq
+ *       and da are those calls' dq and da, each element rounded ONCE (RNE) to half when stored; overflow gives +-Inf as RNE
+ *       does.  There are no propagate-down flags: both gradients are always computed.  mms_set_matrix_mode is NOT consulted
+ *       (dist_mode 2 on word grids is fp32 MFMA in the fp32 call too).
+ *   workspace: mms_simcross_bilinear_workspace_bytes_f16 bytes (never 0 for a valid shape; it covers the forward and the
+ *       backward of the shape), no initialisation needed, nothing past that size is written.  A missing or short workspace:
+ *       MMS_ERR_WORKSPACE.
+ *   Any D >= 1 and any 2-byte aligned operands: alignment (and D) only select how wide the staging loads are, never refuse.
+ *   MMS_ERR_UNSUPPORTED: W1 == 1 && W2 == 1 (the rows family of the learned metric: mms_simmatrix_forward_f16,
+ *       mms_simmatrix_forward_train_f16, mms_simmatrix_backward_f16).  MMS_ERR_INVALID_ARG: bad sizes (as
+ *       mms_simcross_forward_f32 at dist_mode 2: N < 0, W1, W2, D or M <= 0, more than 2^31 - 1 elements in q, a or top), a
+ *       NULL required pointer -- q, a, W, top; in the backward also top_diff, dq, da, dW, and dbias with a bias term.
+ *       N == 0: MMS_OK.  A call that does not return MMS_OK, and N == 0, write nothing.
+ *   mms_simcross_bilinear_forward_backward_f16: the forward, then the backward, on `stream`; the same bits as the two calls. */
+size_t mms_simcross_bilinear_workspace_bytes_f16(int N, int W1, int W2, int D, int M);
+int mms_simcross_bilinear_forward_f16(int N, int W1, int W2, int D, int M, const void* q_f16, const void* a_f16,
+                                      const float* W, const float* bias, float* top, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int mms_simcross_bilinear_backward_f16(int N, int W1, int W2, int D, int M, const void* q_f16, const void* a_f16,
+                                       const float* W, int bias_term, const float* top_diff, void* dq_f16, void* da_f16,
+                                       float* dW, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+int mms_simcross_bilinear_forward_backward_f16(int N, int W1, int W2, int D, int M, const void* q_f16, const void* a_f16,
+                                               const float* W, const float* bias, const float* top_diff, float* top,
+                                               void* dq_f16, void* da_f16, float* dW, float* dbias, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+/* The scoring forward of the same family straight from word ids and a HALF embedding table (K,D): the twin of
+ * mms_embed_simcross_bilinear_forward_f32 (below), the gather done by the staging loads, no workspace.  Row value =
+ * embed_bias[d] + widen(table[id][d]) in fp32 (embed_bias: D floats or NULL), ids clamped to [0, K - 1] as there; top
+ * carries the bits of that call on the widened table -- and, with embed_bias NULL, of mms_simcross_bilinear_forward_f16 on
+ * the gathered rows.  K > 0, K * D <= 2^31 - 1, else MMS_ERR_INVALID_ARG; MMS_ERR_UNSUPPORTED outside the geometries the
+ * _f32 twin covers (W1, W2 <= 48, D <= 64, not W1 == W2 == 1, and N >= 512 or N <= 256 with N * M <= 65535). */
+int mms_embed_simcross_bilinear_forward_f16(int N, int W1, int W2, int D, int M, int K, const float* index_q,
+                                            const float* index_a, const void* table_f16, const float* embed_bias,
+                                            const float* W, const float* bias, float* top, void* stream);
 
 /* Device scratch needed by the three fp32 calls above (0 is possible). */
 size_t mms_simcross_workspace_bytes(int dist_mode, int N, int W1, int W2, int D,

@@ -53,6 +53,11 @@ _SIGNATURES = {
     "mms_simcross_forward_f16": (_i, [_i] * 5 + [_vp] * 5 + [_vp]),
     "mms_simcross_backward_f16": (_i, [_i] * 5 + [_vp] * 8 + [_vp]),
     "mms_simcross_forward_backward_f16": (_i, [_i] * 5 + [_vp] * 8 + [_vp]),
+    "mms_simcross_bilinear_workspace_bytes_f16": (_sz, [_i] * 5),
+    "mms_simcross_bilinear_forward_f16": (_i, [_i] * 5 + [_vp] * 6 + [_sz, _vp]),
+    "mms_simcross_bilinear_backward_f16": (_i, [_i] * 5 + [_vp] * 3 + [_i] + [_vp] * 6 + [_sz, _vp]),
+    "mms_simcross_bilinear_forward_backward_f16": (_i, [_i] * 5 + [_vp] * 11 + [_sz, _vp]),
+    "mms_embed_simcross_bilinear_forward_f16": (_i, [_i] * 6 + [_vp] * 8),
     "mms_embed_workspace_bytes": (_sz, [_i, _i]),
     "mms_embed_forward_f32": (_i, [_i, _i, _i] + [_vp] * 5),
     "mms_embed_backward_f32": (_i, [_i, _i, _i] + [_vp] * 5 + [_sz, _vp]),
@@ -594,6 +599,86 @@ def simcross_forward_backward_f16(mode, q, a, top_diff, top, dq, da, norm0=None,
         mode, N, W1, W2, D, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(top_diff, "top_diff"), _ptr(top, "top"),
         _ptr(norm0, "norm0", True), _ptr(norm1, "norm1", True), _ptr(dq, "dq", dtype=h), _ptr(da, "da", dtype=h), _stream()),
         "mms_simcross_forward_backward_f16")
+
+
+def simcross_bilinear_workspace_bytes_f16(N, W1, W2, D, M):
+    return lib().mms_simcross_bilinear_workspace_bytes_f16(N, W1, W2, D, M)
+
+
+def _bilinear_f16_shape(q, a, W, bias, dbias=None):
+    N, W1, W2, D = _grid_f16_shape(q, a)
+    if W is None or W.dim() != 3 or tuple(W.shape[1:]) != (D, D):
+        raise MMSError("W (M, D, D) expected with D = %d, got %s" % (D, None if W is None else tuple(W.shape)))
+    M = W.shape[0]
+    _expect_shape(bias, (M, W1, W2), "bias")
+    _expect_shape(dbias, (M, W1, W2), "dbias")
+    return N, W1, W2, D, M
+
+
+def simcross_bilinear_forward_f16(q, a, W, bias, top, ws=None):
+    """fp16-storage SimCross dist_mode 2 on word grids (include/mms.h: mms_simcross_bilinear_forward_f16): q (N, W1, D), a (N, W2, D)
+    half tensors; W (M, D, D), bias (M, W1, W2) or None and top (N, M, W1, W2) float32."""
+    N, W1, W2, D, M = _bilinear_f16_shape(q, a, W, bias)
+    h = torch.float16
+    _expect_shape(top, (N, M, W1, W2), "top")
+    wsp, wsb = (ws or _default_ws).get(simcross_bilinear_workspace_bytes_f16(N, W1, W2, D, M), q.device)
+    check(lib().mms_simcross_bilinear_forward_f16(
+        N, W1, W2, D, M, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(W, "W"), _ptr(bias, "bias", True), _ptr(top, "top"),
+        wsp, wsb, _stream()), "mms_simcross_bilinear_forward_f16")
+
+
+def simcross_bilinear_backward_f16(q, a, W, top_diff, dq, da, dW, dbias=None, ws=None):
+    """The backward of simcross_bilinear_forward_f16: dq, da half tensors shaped like q, a; dW like W (overwritten); dbias
+    (M, W1, W2) float32 is accumulated into, None = no bias term (mms_simcross_bilinear_backward_f16)."""
+    N, W1, W2, D, M = _bilinear_f16_shape(q, a, W, None, dbias)
+    h = torch.float16
+    _expect_shape(top_diff, (N, M, W1, W2), "top_diff")
+    _expect_shape(dq, q.shape, "dq")
+    _expect_shape(da, a.shape, "da")
+    _expect_shape(dW, W.shape, "dW")
+    wsp, wsb = (ws or _default_ws).get(simcross_bilinear_workspace_bytes_f16(N, W1, W2, D, M), q.device)
+    check(lib().mms_simcross_bilinear_backward_f16(
+        N, W1, W2, D, M, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(W, "W"), int(dbias is not None),
+        _ptr(top_diff, "top_diff"), _ptr(dq, "dq", dtype=h), _ptr(da, "da", dtype=h), _ptr(dW, "dW"), _ptr(dbias, "dbias", True),
+        wsp, wsb, _stream()), "mms_simcross_bilinear_backward_f16")
+
+
+def simcross_bilinear_forward_backward_f16(q, a, W, bias, top_diff, top, dq, da, dW, dbias=None, ws=None):
+    """simcross_bilinear_forward_f16 then simcross_bilinear_backward_f16 in one call; the bias term is `bias is not None`, and
+    then dbias is required (mms_simcross_bilinear_forward_backward_f16)."""
+    N, W1, W2, D, M = _bilinear_f16_shape(q, a, W, bias, dbias)
+    h = torch.float16
+    _expect_shape(top, (N, M, W1, W2), "top")
+    _expect_shape(top_diff, (N, M, W1, W2), "top_diff")
+    _expect_shape(dq, q.shape, "dq")
+    _expect_shape(da, a.shape, "da")
+    _expect_shape(dW, W.shape, "dW")
+    wsp, wsb = (ws or _default_ws).get(simcross_bilinear_workspace_bytes_f16(N, W1, W2, D, M), q.device)
+    check(lib().mms_simcross_bilinear_forward_backward_f16(
+        N, W1, W2, D, M, _ptr(q, "q", dtype=h), _ptr(a, "a", dtype=h), _ptr(W, "W"), _ptr(bias, "bias", True),
+        _ptr(top_diff, "top_diff"), _ptr(top, "top"), _ptr(dq, "dq", dtype=h), _ptr(da, "da", dtype=h), _ptr(dW, "dW"),
+        _ptr(dbias, "dbias", True), wsp, wsb, _stream()), "mms_simcross_bilinear_forward_backward_f16")
+
+
+def embed_simcross_bilinear_forward_f16(index_q, index_a, table, W, bias, top, embed_bias=None):
+    """embed_simcross_bilinear_forward from a half table (K, D): index_q (N, W1), index_a (N, W2) float32 ids, W (M, D, D), bias
+    (M, W1, W2) or None, embed_bias (D) or None, top (N, M, W1, W2) float32 (mms_embed_simcross_bilinear_forward_f16)."""
+    if index_q.dim() != 2 or index_a.dim() != 2 or index_q.shape[0] != index_a.shape[0] or table.dim() != 2:
+        raise MMSError("index_q (N, W1), index_a (N, W2) and table (K, D) expected, got %s, %s and %s"
+                       % (tuple(index_q.shape), tuple(index_a.shape), tuple(table.shape)))
+    N, W1 = index_q.shape
+    W2 = index_a.shape[1]
+    K, D = table.shape
+    if W is None or W.dim() != 3 or tuple(W.shape[1:]) != (D, D):
+        raise MMSError("W (M, D, D) expected with D = %d, got %s" % (D, None if W is None else tuple(W.shape)))
+    M = W.shape[0]
+    _expect_shape(bias, (M, W1, W2), "bias")
+    _expect_shape(embed_bias, (D,), "embed_bias")
+    _expect_shape(top, (N, M, W1, W2), "top")
+    check(lib().mms_embed_simcross_bilinear_forward_f16(
+        N, W1, W2, D, M, K, _ptr(index_q, "index_q"), _ptr(index_a, "index_a"), _ptr(table, "table", dtype=torch.float16),
+        _ptr(embed_bias, "embed_bias", True), _ptr(W, "W"), _ptr(bias, "bias", True), _ptr(top, "top"), _stream()),
+        "mms_embed_simcross_bilinear_forward_f16")
 
 
 def embed_forward(index, weight, top, bias=None):

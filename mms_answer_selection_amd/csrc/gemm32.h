@@ -79,9 +79,12 @@ struct ReduceGroup {
   int accumulate[kGroupMax];     // the sum starts from out[e] (bias.diff += ..., sim_cross_layer.cpp:301-304) instead of 0
   int first[kGroupMax + 1];
   int cnt;
+  int half_out[kGroupMax];       // out holds IEEE halves: the fp32 sum is rounded once (RNE) as it is stored
 };
 // next problem of a grouped reduction: its blocks follow the previous problem's (first[cnt] = blocks so far)
 void reduce_group_add(ReduceGroup& rg, const float* part, float* out, long long n, int splits, int accumulate = 0);
+// the same with half storage of the result (fp16-storage gradients): out[e] = half(0 + part[0*n + e] + part[1*n + e] + ...)
+void reduce_group_add_half(ReduceGroup& rg, const float* part, void* out_f16, long long n, int splits);
 void reduce_group_launch(const ReduceGroup& rg, hipStream_t s);
 
 // ---- one launch each of the element-wise kernels that more than one source uses ----

@@ -494,6 +494,8 @@ bool gemm_launch_group(const GemmArgs* gs, const int* nb0s, int n, hipStream_t s
   return true;
 }
 
+// HALF: some problem of the group stores halves (reduce_group_add_half); the fp32 groups run the <false> instance
+template <bool HALF>
 __global__ __launch_bounds__(256) void splitk_reduce_group_kernel(ReduceGroup rg) {
   int p = 0;
 #pragma unroll
@@ -506,6 +508,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_group_kernel(ReduceGroup rg
   const long long stride = (long long)(rg.first[p + 1] - rg.first[p]) * 256;
   const bool accumulate = rg.accumulate[p] != 0;
   for (long long e = (long long)(blockIdx.x - rg.first[p]) * 256 + threadIdx.x; e < n; e += stride) {
+    if (HALF && rg.half_out[p]) {
+      reinterpret_cast<_Float16*>(out)[e] = (_Float16)ordered_slab_sum(part, n, e, splits, 0.f);
+      continue;
+    }
     out[e] = ordered_slab_sum(part, n, e, splits, accumulate ? out[e] : 0.f);
   }
 }
@@ -585,8 +591,17 @@ void reduce_group_add(ReduceGroup& rg, const float* part, float* out, long long 
   rg.part[i] = part; rg.out[i] = out; rg.n[i] = n; rg.splits[i] = splits; rg.accumulate[i] = accumulate;
   for (int j = i + 1; j <= kGroupMax; ++j) rg.first[j] = rg.first[i] + (int)ew_blocks(n);
 }
+void reduce_group_add_half(ReduceGroup& rg, const float* part, void* out_f16, long long n, int splits) {
+  rg.half_out[rg.cnt] = 1;
+  reduce_group_add(rg, part, static_cast<float*>(out_f16), n, splits, 0);
+}
 void reduce_group_launch(const ReduceGroup& rg, hipStream_t s) {
-  hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(rg.first[rg.cnt]), dim3(256), 0, s, rg);
+  bool half = false;
+  for (int i = 0; i < rg.cnt; ++i) half = half || rg.half_out[i] != 0;
+  if (half)
+    hipLaunchKernelGGL(splitk_reduce_group_kernel<true>, dim3(rg.first[rg.cnt]), dim3(256), 0, s, rg);
+  else
+    hipLaunchKernelGGL(splitk_reduce_group_kernel<false>, dim3(rg.first[rg.cnt]), dim3(256), 0, s, rg);
 }
 
 // Split count for a product with a long K (the dW products: K = pairs).  Workgroups = tiles x batch x

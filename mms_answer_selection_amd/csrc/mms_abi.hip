@@ -256,7 +256,7 @@ int mms_simcross_euclid_forward_backward_f16(int N, int D, const void* q_f16, co
 // The word-grid fp16-storage calls: what all three check before anything else.  MMS_OK: go on.
 static int grid_f16_refusal(int dist_mode, int N, int W1, int W2, int D) {
   if (!dims_ok(dist_mode, N, W1, W2, D, 1)) return MMS_ERR_INVALID_ARG;
-  if (dist_mode == 2) return MMS_ERR_UNSUPPORTED;                 // the bilinear mode has no half-storage kernels
+  if (dist_mode == 2) return MMS_ERR_UNSUPPORTED;                 // the bilinear mode: mms_simcross_bilinear_*_f16
   if (W1 == 1 && W2 == 1) return MMS_ERR_UNSUPPORTED;             // the rows family: mms_simcross_{euclid,cosine}_*_f16
   return MMS_OK;
 }
@@ -293,6 +293,62 @@ int mms_simcross_forward_backward_f16(int dist_mode, int N, int W1, int W2, int 
   if (dist_mode == 0 && (!norm0 || !norm1)) return MMS_ERR_INVALID_ARG;
   return simcross_grid_forward_backward_f16(dist_mode, N, W1, W2, D, q_f16, a_f16, top_diff, top, norm0, norm1, dq_f16,
                                             da_f16, as_stream(stream));
+}
+
+// The word-grid fp16-storage calls of dist_mode 2: what all of them check first.  MMS_OK: go on.
+static int bilinear_f16_refusal(int N, int W1, int W2, int D, int M) {
+  if (!dims_ok(2, N, W1, W2, D, M)) return MMS_ERR_INVALID_ARG;
+  if (W1 == 1 && W2 == 1) return MMS_ERR_UNSUPPORTED;             // the rows family of the learned metric: mms_simmatrix_*_f16
+  return MMS_OK;
+}
+
+size_t mms_simcross_bilinear_workspace_bytes_f16(int N, int W1, int W2, int D, int M) {
+  if (bilinear_f16_refusal(N, W1, W2, D, M) != MMS_OK) return 0;
+  return bilinear_workspace_bytes_f16(N, W1, W2, D, M);
+}
+
+int mms_simcross_bilinear_forward_f16(int N, int W1, int W2, int D, int M, const void* q_f16, const void* a_f16,
+                                      const float* W, const float* bias, float* top, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  const int rc = bilinear_f16_refusal(N, W1, W2, D, M);
+  if (rc != MMS_OK) return rc;
+  if (N == 0) return MMS_OK;
+  if (!q_f16 || !a_f16 || !W || !top) return MMS_ERR_INVALID_ARG;
+  return simcross_bilinear_f16(N, W1, W2, D, M, q_f16, a_f16, W, bias, 0, nullptr, top, nullptr, nullptr, nullptr, nullptr,
+                               workspace, workspace_bytes, true, false, as_stream(stream));
+}
+
+int mms_simcross_bilinear_backward_f16(int N, int W1, int W2, int D, int M, const void* q_f16, const void* a_f16,
+                                       const float* W, int bias_term, const float* top_diff, void* dq_f16, void* da_f16,
+                                       float* dW, float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = bilinear_f16_refusal(N, W1, W2, D, M);
+  if (rc != MMS_OK) return rc;
+  if (N == 0) return MMS_OK;
+  if (!q_f16 || !a_f16 || !W || !top_diff || !dq_f16 || !da_f16 || !dW || (bias_term && !dbias)) return MMS_ERR_INVALID_ARG;
+  return simcross_bilinear_f16(N, W1, W2, D, M, q_f16, a_f16, W, nullptr, bias_term, top_diff, nullptr, dq_f16, da_f16, dW,
+                               dbias, workspace, workspace_bytes, false, true, as_stream(stream));
+}
+
+int mms_simcross_bilinear_forward_backward_f16(int N, int W1, int W2, int D, int M, const void* q_f16, const void* a_f16,
+                                               const float* W, const float* bias, const float* top_diff, float* top,
+                                               void* dq_f16, void* da_f16, float* dW, float* dbias, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+  const int rc = bilinear_f16_refusal(N, W1, W2, D, M);
+  if (rc != MMS_OK) return rc;
+  if (N == 0) return MMS_OK;
+  if (!q_f16 || !a_f16 || !W || !top || !top_diff || !dq_f16 || !da_f16 || !dW || (bias && !dbias)) return MMS_ERR_INVALID_ARG;
+  return simcross_bilinear_f16(N, W1, W2, D, M, q_f16, a_f16, W, bias, bias != nullptr, top_diff, top, dq_f16, da_f16, dW,
+                               dbias, workspace, workspace_bytes, true, true, as_stream(stream));
+}
+
+int mms_embed_simcross_bilinear_forward_f16(int N, int W1, int W2, int D, int M, int K, const float* index_q,
+                                            const float* index_a, const void* table_f16, const float* embed_bias,
+                                            const float* W, const float* bias, float* top, void* stream) {
+  if (!dims_ok(2, N, W1, W2, D, M) || K <= 0 || (long long)K * D > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
+  if (N == 0) return MMS_OK;
+  if (!index_q || !index_a || !table_f16 || !W || !top) return MMS_ERR_INVALID_ARG;
+  return embed_bilinear_forward_f16(N, W1, W2, D, M, K, index_q, index_a, table_f16, embed_bias, W, bias, top,
+                                    as_stream(stream));
 }
 
 int mms_embed_simcross_forward_f32(int dist_mode, int N, int W1, int W2, int D, int K,

@@ -55,6 +55,14 @@ int bilinear_backward(int N, int W1, int W2, int D, int M, const float* q, const
 int embed_bilinear_forward(int N, int W1, int W2, int D, int M, int K, const float* index_q, const float* index_a,
                            const float* table, const float* embed_bias, const float* W, const float* bias, float* top,
                            hipStream_t s);
+// bilinear_f16.hip (fp16 storage, word grids, dist_mode 2; the caller has checked the arguments)
+size_t bilinear_workspace_bytes_f16(int N, int W1, int W2, int D, int M);
+int simcross_bilinear_f16(int N, int W1, int W2, int D, int M, const void* q_f16, const void* a_f16, const float* W,
+                          const float* bias, int bias_term, const float* top_diff, float* top, void* dq_f16, void* da_f16,
+                          float* dW, float* dbias, void* ws, size_t ws_bytes, bool fwd, bool bwd, hipStream_t s);
+int embed_bilinear_forward_f16(int N, int W1, int W2, int D, int M, int K, const float* index_q, const float* index_a,
+                               const void* table_f16, const float* embed_bias, const float* W, const float* bias,
+                               float* top, hipStream_t s);
 // simmatrix.hip
 int set_matrix_mode(int mode);
 int get_matrix_mode();
