@@ -293,6 +293,30 @@ int mms_simcross_bilinear_forward_backward_f16(int N, int W1, int W2, int D, int
 int mms_embed_simcross_bilinear_forward_f16(int N, int W1, int W2, int D, int M, int K, const float* index_q,
                                             const float* index_a, const void* table_f16, const float* embed_bias,
                                             const float* W, const float* bias, float* top, void* stream);
+/* The scoring forward of dist_mode 0 (cosine) and 1 (Euclid) straight from word ids and a HALF embedding table (K,D):
+ * top == SimCross(Embed(index_q), Embed(index_a)), the twin of mms_embed_simcross_forward_f32 (below), the gather done
+ * by the staging loads of the word-grid kernels of mms_simcross_forward_f16.
+ *   Operands: index_q (N,W1), index_a (N,W2) word ids as floats, converted with (int) and clamped to [0, K - 1] as there;
+ *       table_f16 (K,D) IEEE halves; embed_bias D floats or NULL; top (N,1,W1,W2) fp32; norm0 (N,W1), norm1 (N,W2) fp32,
+ *       written in dist_mode 0 (required), ignored in dist_mode 1 (may be NULL).
+ *   Row value: embed_bias[d] + widen(table[id][d]), one fp32 add -- the widened half alone when embed_bias is NULL.
+ *       Everything after that is the fp32 arithmetic of mms_embed_simcross_forward_f32: the forward sums d ascending
+ *       per output, the norms use that call's lane order and wave sum.
+ *   Bits: top, and in dist_mode 0 the norms, carry the bits of mms_embed_simcross_forward_f32 run on the table widened
+ *       to fp32 -- and, with embed_bias NULL, of mms_simcross_forward_f16 on the gathered rows.  Euclid top is therefore
+ *       the reference CPU code's on the widened gathered rows.
+ *   No workspace, no allocation, no host synchronisation; safe to capture in a hipGraph.  One launch in dist_mode 1,
+ *       three in dist_mode 0 (two norm launches, then the forward), as the twin.
+ *   Any D >= 1 and any 2-byte aligned table: alignment and D only select how wide the loads are, never refuse.
+ *       W1 == 1 && W2 == 1 is served (by the word-grid kernels, as in the twin).
+ *   MMS_ERR_UNSUPPORTED: dist_mode 2 (use mms_embed_simcross_bilinear_forward_f16 above), and any other dist_mode that is
+ *       not 0 or 1, answered before the sizes are looked at, as by the twin.  MMS_ERR_INVALID_ARG: whatever
+ *       mms_embed_simcross_forward_f32 rejects -- bad sizes, K <= 0, K * D > 2^31 - 1, a NULL required pointer (index_q,
+ *       index_a, table_f16, top; the norms in dist_mode 0).  N == 0: MMS_OK.  A call that does not return MMS_OK, and
+ *       N == 0, write nothing. */
+int mms_embed_simcross_forward_f16(int dist_mode, int N, int W1, int W2, int D, int K, const float* index_q,
+                                   const float* index_a, const void* table_f16, const float* embed_bias, float* top,
+                                   float* norm0, float* norm1, void* stream);
 
 /* Device scratch needed by the three fp32 calls above (0 is possible). */
 size_t mms_simcross_workspace_bytes(int dist_mode, int N, int W1, int W2, int D,

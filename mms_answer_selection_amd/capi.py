@@ -58,6 +58,7 @@ _SIGNATURES = {
     "mms_simcross_bilinear_backward_f16": (_i, [_i] * 5 + [_vp] * 3 + [_i] + [_vp] * 6 + [_sz, _vp]),
     "mms_simcross_bilinear_forward_backward_f16": (_i, [_i] * 5 + [_vp] * 11 + [_sz, _vp]),
     "mms_embed_simcross_bilinear_forward_f16": (_i, [_i] * 6 + [_vp] * 8),
+    "mms_embed_simcross_forward_f16": (_i, [_i] * 6 + [_vp] * 8),
     "mms_embed_workspace_bytes": (_sz, [_i, _i]),
     "mms_embed_forward_f32": (_i, [_i, _i, _i] + [_vp] * 5),
     "mms_embed_backward_f32": (_i, [_i, _i, _i] + [_vp] * 5 + [_sz, _vp]),
@@ -116,6 +117,10 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 class MMSError(RuntimeError):
     pass
+
+
+class MMSArgumentError(MMSError, ValueError):
+    """A wrapper's own check of a tensor's shape or dtype failed, before any launch."""
 
 
 MMS_VERSION = 212      # include/mms.h
@@ -679,6 +684,28 @@ def embed_simcross_bilinear_forward_f16(index_q, index_a, table, W, bias, top, e
         N, W1, W2, D, M, K, _ptr(index_q, "index_q"), _ptr(index_a, "index_a"), _ptr(table, "table", dtype=torch.float16),
         _ptr(embed_bias, "embed_bias", True), _ptr(W, "W"), _ptr(bias, "bias", True), _ptr(top, "top"), _stream()),
         "mms_embed_simcross_bilinear_forward_f16")
+
+
+def embed_simcross_forward_f16(mode, index_q, index_a, table, top, norm0=None, norm1=None, embed_bias=None):
+    """embed_simcross_forward from a half table (K, D), dist_mode 0 / 1: index_q (N, W1), index_a (N, W2) float32 ids, embed_bias (D)
+    or None, top (N, 1, W1, W2), norm0 (N, W1), norm1 (N, W2) float32, the norms for dist_mode 0 only
+    (mms_embed_simcross_forward_f16).  A table that is not half, or index_q and index_a of different batch sizes: ValueError."""
+    if index_q.dim() != 2 or index_a.dim() != 2 or index_q.shape[0] != index_a.shape[0] or table.dim() != 2:
+        raise MMSArgumentError("index_q (N, W1), index_a (N, W2) and table (K, D) expected, got %s, %s and %s"
+                               % (tuple(index_q.shape), tuple(index_a.shape), tuple(table.shape)))
+    if table.dtype != torch.float16:
+        raise MMSArgumentError("table must be torch.float16 (got %s); an fp32 table goes to embed_simcross_forward" % table.dtype)
+    N, W1 = index_q.shape
+    W2 = index_a.shape[1]
+    K, D = table.shape
+    _expect_shape(embed_bias, (D,), "embed_bias")
+    _expect_shape(top, (N, 1, W1, W2), "top")
+    _expect_shape(norm0, (N, W1), "norm0")
+    _expect_shape(norm1, (N, W2), "norm1")
+    check(lib().mms_embed_simcross_forward_f16(
+        mode, N, W1, W2, D, K, _ptr(index_q, "index_q"), _ptr(index_a, "index_a"), _ptr(table, "table", dtype=torch.float16),
+        _ptr(embed_bias, "embed_bias", True), _ptr(top, "top"), _ptr(norm0, "norm0", True), _ptr(norm1, "norm1", True), _stream()),
+        "mms_embed_simcross_forward_f16")
 
 
 def embed_forward(index, weight, top, bias=None):

@@ -351,17 +351,35 @@ int mms_embed_simcross_bilinear_forward_f16(int N, int W1, int W2, int D, int M,
                                     as_stream(stream));
 }
 
-int mms_embed_simcross_forward_f32(int dist_mode, int N, int W1, int W2, int D, int K,
-                                   const float* index_q, const float* index_a, const float* weight,
-                                   const float* embed_bias, float* top, float* norm0, float* norm1, void* stream) {
-  if (dist_mode != 0 && dist_mode != 1) return MMS_ERR_UNSUPPORTED;   // bilinear: run Embed, then SimCross
+// mms_embed_simcross_forward_f32 / _f16: what both check before anything else.  MMS_OK: go on, unless N == 0.
+static int embed_simcross_refusal(int dist_mode, int N, int W1, int W2, int D, int K, const float* index_q,
+                                  const float* index_a, const void* table, const float* top, const float* norm0,
+                                  const float* norm1) {
+  if (dist_mode != 0 && dist_mode != 1) return MMS_ERR_UNSUPPORTED;   // bilinear: mms_embed_simcross_bilinear_forward_*
   if (!dims_ok(dist_mode, N, W1, W2, D, 1) || K <= 0 || (long long)K * D > 0x7fffffffLL)
     return MMS_ERR_INVALID_ARG;
   if (N == 0) return MMS_OK;
-  if (!index_q || !index_a || !weight || !top) return MMS_ERR_INVALID_ARG;
+  if (!index_q || !index_a || !table || !top) return MMS_ERR_INVALID_ARG;
   if (dist_mode == 0 && (!norm0 || !norm1)) return MMS_ERR_INVALID_ARG;
+  return MMS_OK;
+}
+
+int mms_embed_simcross_forward_f32(int dist_mode, int N, int W1, int W2, int D, int K,
+                                   const float* index_q, const float* index_a, const float* weight,
+                                   const float* embed_bias, float* top, float* norm0, float* norm1, void* stream) {
+  const int rc = embed_simcross_refusal(dist_mode, N, W1, W2, D, K, index_q, index_a, weight, top, norm0, norm1);
+  if (rc != MMS_OK || N == 0) return rc;
   return embed_simcross_forward(dist_mode, N, W1, W2, D, K, index_q, index_a, weight, embed_bias, top, norm0,
                                 norm1, as_stream(stream));
+}
+
+int mms_embed_simcross_forward_f16(int dist_mode, int N, int W1, int W2, int D, int K,
+                                   const float* index_q, const float* index_a, const void* table_f16,
+                                   const float* embed_bias, float* top, float* norm0, float* norm1, void* stream) {
+  const int rc = embed_simcross_refusal(dist_mode, N, W1, W2, D, K, index_q, index_a, table_f16, top, norm0, norm1);
+  if (rc != MMS_OK || N == 0) return rc;
+  return embed_simcross_forward_f16(dist_mode, N, W1, W2, D, K, index_q, index_a, table_f16, embed_bias, top, norm0,
+                                    norm1, as_stream(stream));
 }
 
 int mms_embed_simcross_bilinear_forward_f32(int N, int W1, int W2, int D, int M, int K,

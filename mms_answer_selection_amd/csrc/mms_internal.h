@@ -45,6 +45,9 @@ int simcross_grid_backward_f16(int mode, int N, int W1, int W2, int D, const voi
 int simcross_grid_forward_backward_f16(int mode, int N, int W1, int W2, int D, const void* q, const void* a,
                                        const float* top_diff, float* top, float* norm0, float* norm1, void* dq,
                                        void* da, hipStream_t s);
+int embed_simcross_forward_f16(int mode, int N, int W1, int W2, int D, int K, const float* index_q, const float* index_a,
+                               const void* table_f16, const float* embed_bias, float* top, float* norm0, float* norm1,
+                               hipStream_t s);
 // bilinear.hip (SimCross dist_mode 2)
 size_t bilinear_workspace_bytes(int N, int W1, int W2, int D, int M);
 int bilinear_forward(int N, int W1, int W2, int D, int M, const float* q, const float* a, const float* W,

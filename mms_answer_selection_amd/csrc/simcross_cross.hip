@@ -17,18 +17,13 @@
 // contraction, so mul and add must round separately to match it bitwise.
 #include "cosine_math.h"
 #include "cross_acc.h"
+#include "cross_gather.h"
 #include "euclid_math.h"
 #include "mms_internal.h"
 
 namespace mms {
 
 // L2 norms of `rows` rows of length D: one wave per row (cosine, general W).
-// Word id stored as a float (Caffe feeds ids as Dtype), clamped into the table like embed_fwd_kernel.
-__device__ __forceinline__ int gather_id(float v, int K) {
-  const int i = (int)v;
-  return i < 0 ? 0 : (i >= K ? K - 1 : i);
-}
-
 // index != nullptr: row `row` is table row index[row] of x (K rows) -- the Embed gather fused in.
 __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__ x,
                                                        float* __restrict__ nrm,
@@ -48,17 +43,7 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__
 // Forward for general W1 x W2, MODE 0 (cosine; norms precomputed) or 1.
 // One wave per (pair, j-tile, k-tile); tile = (8*RJ) x (8*RK) outputs,
 // lane (lj = lane>>3, lk = lane&7) owns outputs j = j0+lj+8*rj, k = k0+lk+8*rk: CrossAcc (cross_acc.h).
-
-// Embed fused into the load: with iq != nullptr, q and a are both the embedding
-// TABLE (K x D) and row j of pair n is table row iq[n*W1 + j] (ia likewise) -- the (N, W, D) blobs
-// the Embed layer would write and SimCross read back never exist.
-struct CrossGather {
-  const float* iq;
-  const float* ia;
-  int K;
-  const float* bias;     // the Embed layer's bias (D floats) or nullptr: row value = bias[d] + table[id][d], the
-                         // one rounding of embed_layer.cpp:146-151 (gemm with alpha = beta = 1)
-};
+// The fused Embed gather (a CrossGather with iq != nullptr; gather_id clamps the ids): cross_gather.h.
 
 // Generic staging: q/a are staged DC floats of d at a time in LDS with stride DC+1 (bank =
 // (row + d) mod 32: conflict-free across rows, broadcast within a row).

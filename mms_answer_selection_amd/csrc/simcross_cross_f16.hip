@@ -1,19 +1,24 @@
 // csrc/simcross_cross_f16.hip -- fp16-STORAGE SimCross dist_mode 0 (cosine) and 1 (Euclidean) on W1 x W2 word grids
-// (mms_simcross_forward_f16 / _backward_f16 / _forward_backward_f16): q, a, dq, da are IEEE halves in HBM; top,
-// top_diff and the norms fp32.  The arithmetic is that of simcross_cross.hip on the exactly-widened inputs: a half
+// (mms_simcross_forward_f16 / _backward_f16 / _forward_backward_f16, and mms_embed_simcross_forward_f16, the forward
+// straight from word ids and a half embedding table): q, a, dq, da are IEEE halves in HBM; top, top_diff and the norms fp32.  The arithmetic is that of simcross_cross.hip on the exactly-widened inputs: a half
 // becomes a float when it is written to LDS (forward, tiled backward) or right after its load (plain backward, norms),
 // every sum is fp32 in the reference's order (sim_cross_layer.cpp:96-139, 208-250), and a gradient element is rounded
 // ONCE, RNE, when it is stored (v_cvt_f16_f32: overflow gives +-Inf).  The forward's register tile and T are CrossAcc
 // (cross_acc.h), the backward terms euclid_math.h / cosine_math.h: no arithmetic is defined here.
 //
 // Alignment: halves are loaded and stored one by one unless a wider access has tested its own preconditions -- the
-// pair image copies 16 bytes per lane (launch_cross_fwd_f16: aligned16 of both bases, D = 50), the backward packs
-// 2 or 4 neighbouring d of a row into one store where the address allows (store_halves).  Any D >= 1 and any 2-byte
-// aligned operand is served.
+// pair image copies 16 bytes per lane (cross_fwd_image_ok_f16: aligned16 of both bases, D = 50) or, gathered from a
+// table, 4 bytes (a 4-byte aligned table: its 100-byte rows promise no more), the backward packs 2 or 4 neighbouring d
+// of a row into one store where the address allows (store_halves).  Any D >= 1 and any 2-byte aligned operand is served.
+//
+// The Embed gather (cross_gather.h) is the template option GATHER of the two forward kernels and a run-time one of the
+// norm kernel: q and a are then both the table, row j of pair n is table row gather_id(iq[n*W1 + j]), and a row value
+// is bias[d] + widen(table[id][d]) -- one fp32 add after the widening -- or the widened half alone without a bias.
 //
 // Compiled with -ffp-contract=off like every source of the library.
 #include "cosine_math.h"
 #include "cross_acc.h"
+#include "cross_gather.h"
 #include "euclid_math.h"
 #include "mms_internal.h"
 
@@ -43,14 +48,16 @@ __device__ __forceinline__ void store_halves(_Float16* p, const float* v, int n)
 
 // L2 norms of `rows` half rows of length D: one wave per row, the lane order and the wave sum of row_norm_kernel
 // (simcross_cross.hip), so the norms carry the bits of the fp32 call on the widened rows.
+// index != nullptr: row `row` is table row index[row] of x (K rows), and ebias (or nullptr) is added before squaring.
 __global__ __launch_bounds__(256) void row_norm_f16_kernel(const _Float16* __restrict__ x, float* __restrict__ nrm,
-                                                           long long rows, int D) {
+                                                           long long rows, int D, const float* __restrict__ index, int K,
+                                                           const float* __restrict__ ebias) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const _Float16* r = x + row * D;
+  const _Float16* r = x + (index ? (long long)gather_id(index[row], K) : row) * D;
   float s = 0.f;
-  for (int i = lane; i < D; i += 64) { const float v = (float)r[i]; s += v * v; }
+  for (int i = lane; i < D; i += 64) { const float v = ebias ? ebias[i] + (float)r[i] : (float)r[i]; s += v * v; }
   s = wave_sum(s);
   if (lane == 0) nrm[row] = sqrtf(s);
 }
@@ -59,13 +66,17 @@ __global__ __launch_bounds__(256) void row_norm_f16_kernel(const _Float16* __res
 // (pair, j-tile, k-tile); q / a are staged DC values of d at a time in LDS, as floats, stride DC + 1.  Every load of a
 // chunk is issued (clamped, hence unconditional, addresses) before the first LDS write, and the next chunk's loads
 // right after the writes of the current one -- `ok ? load : 0` costs one memory round trip per row.
-template <int RJ, int RK, int MODE>
+// GATHER: the word ids of the tile's rows become table offsets once per wave, in LDS, as in cross_fwd_kernel; the bias
+// of a chunk's column is loaded with the chunk and added when the half is widened.
+template <int RJ, int RK, int MODE, bool GATHER>
 __global__ __launch_bounds__(256) void cross_fwd_f16_kernel(
     const _Float16* __restrict__ q, const _Float16* __restrict__ a, const float* __restrict__ norm0,
-    const float* __restrict__ norm1, float* __restrict__ top, int N, int W1, int W2, int D, int tilesJ, int tilesK) {
+    const float* __restrict__ norm1, float* __restrict__ top, int N, int W1, int W2, int D, int tilesJ, int tilesK,
+    CrossGather gt) {
   constexpr int TJ = 8 * RJ, TK = 8 * RK, DC = 32, LS = DC + 1;
   __shared__ float qs[4][TJ * LS];
   __shared__ float as[4][TK * LS];
+  __shared__ int rowoff[4][GATHER ? TJ + TK : 1];   // gather: element offset of each tile row in the table
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long long work = (long long)blockIdx.x * 4 + wave;
   const long long total = (long long)N * tilesJ * tilesK;
@@ -83,23 +94,44 @@ __global__ __launch_bounds__(256) void cross_fwd_f16_kernel(
 
   const int lrow = lane >> 5, lcol = lane & 31;
   _Float16 rq[TJ / 2], ra[TK / 2];
+  float bv = 0.f;                                  // gather with a bias: the bias of this lane's column of the chunk
+  const bool biased = GATHER && gt.bias != nullptr;
+  if constexpr (GATHER) {                          // word ids of this tile's rows -> table offsets, once
+    for (int r = lane; r < TJ + TK; r += 64) {
+      const bool isq = r < TJ;
+      const int rr = isq ? min(j0 + r, W1 - 1) : min(k0 + r - TJ, W2 - 1);
+      const float id = isq ? gt.iq[(size_t)n * W1 + rr] : gt.ia[(size_t)n * W2 + rr];
+      rowoff[wave][r] = gather_id(id, gt.K) * D;
+    }
+    wave_lds_sync();
+  }
   auto fetch = [&](int d0) {
     const int col = min(d0 + lcol, D - 1);
+    if constexpr (GATHER) {
 #pragma unroll
-    for (int r = 0; r < TJ; r += 2) rq[r / 2] = qn[(size_t)min(j0 + r + lrow, W1 - 1) * D + col];
+      for (int r = 0; r < TJ; r += 2) rq[r / 2] = q[(size_t)rowoff[wave][r + lrow] + col];
 #pragma unroll
-    for (int r = 0; r < TK; r += 2) ra[r / 2] = an[(size_t)min(k0 + r + lrow, W2 - 1) * D + col];
+      for (int r = 0; r < TK; r += 2) ra[r / 2] = a[(size_t)rowoff[wave][TJ + r + lrow] + col];
+      if (biased) bv = gt.bias[col];
+    } else {
+#pragma unroll
+      for (int r = 0; r < TJ; r += 2) rq[r / 2] = qn[(size_t)min(j0 + r + lrow, W1 - 1) * D + col];
+#pragma unroll
+      for (int r = 0; r < TK; r += 2) ra[r / 2] = an[(size_t)min(k0 + r + lrow, W2 - 1) * D + col];
+    }
   };
+  // a staged value: the widened half, plus the bias where there is one (never 0 + x: -0 keeps its sign without a bias)
+  auto value = [&](_Float16 h) { return biased ? bv + (float)h : (float)h; };
   fetch(0);
   for (int d0 = 0; d0 < D; d0 += DC) {
     const int dn = min(DC, D - d0);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < TJ; r += 2)
-      qs[wave][(r + lrow) * LS + lcol] = (valid && j0 + r + lrow < W1 && lcol < dn) ? (float)rq[r / 2] : 0.f;
+      qs[wave][(r + lrow) * LS + lcol] = (valid && j0 + r + lrow < W1 && lcol < dn) ? value(rq[r / 2]) : 0.f;
 #pragma unroll
     for (int r = 0; r < TK; r += 2)
-      as[wave][(r + lrow) * LS + lcol] = (valid && k0 + r + lrow < W2 && lcol < dn) ? (float)ra[r / 2] : 0.f;
+      as[wave][(r + lrow) * LS + lcol] = (valid && k0 + r + lrow < W2 && lcol < dn) ? value(ra[r / 2]) : 0.f;
     __syncthreads();
     if (d0 + DC < D) fetch(d0 + DC);
     acc.accumulate(&qs[wave][lj * LS], &as[wave][lk * LS], LS, dn);
@@ -112,10 +144,13 @@ __global__ __launch_bounds__(256) void cross_fwd_f16_kernel(
 // W1*D and W2*D halves of the pair are contiguous and a multiple of 16 bytes (W % 8 == 0), so with 16-byte aligned
 // bases they are copied 8 halves per lane per load and widened into the fp32 image (row stride D floats) that
 // accumulate() reads.  All loads of a batch are issued before its first LDS write.  2 waves per workgroup.
-template <int RJ, int RK, int MODE, int D>
+// GATHER: image row r is table row id[r], assembled row by row.  A table row is D halves = 100 bytes, so a 4-byte
+// aligned table promises 4-byte aligned rows and no more: the copy runs in half2, D / 2 per row, widened to the float2
+// of the same image.  Per batch: the ids of 8 + 8 elements, then their 16 loads (and the bias pairs), then the writes.
+template <int RJ, int RK, int MODE, int D, bool GATHER>
 __global__ __launch_bounds__(128) void cross_fwd_image_f16_kernel(
     const _Float16* __restrict__ q, const _Float16* __restrict__ a, const float* __restrict__ norm0,
-    const float* __restrict__ norm1, float* __restrict__ top, int N) {
+    const float* __restrict__ norm1, float* __restrict__ top, int N, CrossGather gt) {
   constexpr int W1 = 8 * RJ, W2 = 8 * RK;
   constexpr int nq8 = W1 * D / 8, na8 = W2 * D / 8;   // exact: W1, W2 multiples of 8
   extern __shared__ float4 img4_f16[];                // [2 waves][(W1 + W2) * D / 4]
@@ -125,25 +160,74 @@ __global__ __launch_bounds__(128) void cross_fwd_image_f16_kernel(
   const int n = valid ? work : N - 1;
   float4* qs4 = img4_f16 + (size_t)wave * 2 * (nq8 + na8);
   float4* as4 = qs4 + 2 * nq8;
-  const half8* q8 = reinterpret_cast<const half8*>(q + (size_t)n * W1 * D);
-  const half8* a8 = reinterpret_cast<const half8*>(a + (size_t)n * W2 * D);
-  auto widen = [](float4* dst, const half8& h) {
-    dst[0] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-    dst[1] = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
-  };
-  for (int i0 = 0; i0 < (nq8 > na8 ? nq8 : na8); i0 += 256) {
-    half8 rq[4], ra[4];
+  if constexpr (GATHER) {
+    static_assert(D % 2 == 0, "the gather copies half2");
+    constexpr int R2 = D / 2;                      // half2 per row
+    constexpr int NQ2 = W1 * R2, NA2 = W2 * R2, NMAX = NQ2 > NA2 ? NQ2 : NA2;
+    float2* qs2 = reinterpret_cast<float2*>(qs4);
+    float2* as2 = reinterpret_cast<float2*>(as4);
+    const half2v* t2 = reinterpret_cast<const half2v*>(q);
+    const float* iq = gt.iq + (size_t)n * W1;
+    const float* ia = gt.ia + (size_t)n * W2;
+    const bool biased = gt.bias != nullptr;
+    for (int e0 = 0; e0 < NMAX; e0 += 512) {
+      float idq[8], ida[8];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + 64 * u + lane;
-      rq[u] = q8[min(i, nq8 - 1)];
-      ra[u] = a8[min(i, na8 - 1)];
+      for (int u = 0; u < 8; ++u) {
+        const int e = e0 + 64 * u + lane;
+        idq[u] = iq[min(e, NQ2 - 1) / R2];
+        ida[u] = ia[min(e, NA2 - 1) / R2];
+      }
+      half2v rq[8], ra[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int e = e0 + 64 * u + lane;
+        rq[u] = t2[(size_t)gather_id(idq[u], gt.K) * R2 + min(e, NQ2 - 1) % R2];
+        ra[u] = t2[(size_t)gather_id(ida[u], gt.K) * R2 + min(e, NA2 - 1) % R2];
+      }
+      float2 vq[8], va[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        vq[u] = make_float2((float)rq[u][0], (float)rq[u][1]);
+        va[u] = make_float2((float)ra[u][0], (float)ra[u][1]);
+      }
+      if (biased) {                                // the bias is floats of its own alignment: two 4-byte loads per pair
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int e = e0 + 64 * u + lane;
+          const int cq = 2 * (min(e, NQ2 - 1) % R2), ca = 2 * (min(e, NA2 - 1) % R2);
+          vq[u].x = gt.bias[cq] + vq[u].x; vq[u].y = gt.bias[cq + 1] + vq[u].y;
+          va[u].x = gt.bias[ca] + va[u].x; va[u].y = gt.bias[ca + 1] + va[u].y;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int e = e0 + 64 * u + lane;
+        if (e < NQ2) qs2[e] = vq[u];
+        if (e < NA2) as2[e] = va[u];
+      }
     }
+  } else {
+    const half8* q8 = reinterpret_cast<const half8*>(q + (size_t)n * W1 * D);
+    const half8* a8 = reinterpret_cast<const half8*>(a + (size_t)n * W2 * D);
+    auto widen = [](float4* dst, const half8& h) {
+      dst[0] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+      dst[1] = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
+    };
+    for (int i0 = 0; i0 < (nq8 > na8 ? nq8 : na8); i0 += 256) {
+      half8 rq[4], ra[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + 64 * u + lane;
-      if (i < nq8) widen(qs4 + 2 * i, rq[u]);
-      if (i < na8) widen(as4 + 2 * i, ra[u]);
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + 64 * u + lane;
+        rq[u] = q8[min(i, nq8 - 1)];
+        ra[u] = a8[min(i, na8 - 1)];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + 64 * u + lane;
+        if (i < nq8) widen(qs4 + 2 * i, rq[u]);
+        if (i < na8) widen(as4 + 2 * i, ra[u]);
+      }
     }
   }
   wave_lds_sync();
@@ -367,16 +451,19 @@ static size_t cross_bwd_tiled_lds_f16(int mode, int W1, int W2) {
 
 constexpr int kImageD16 = 50;   // the driver's default embedding width (do_trec_qa_clean.py -d 50)
 
-// the pair image needs whole 8-row tiles, 16-byte loads from both operands and two images in 64 KB
-static bool cross_fwd_image_ok_f16(int N, int W1, int W2, int D, const void* q, const void* a) {
+// the pair image needs whole 8-row tiles, two images in 64 KB and the alignment of its loads: 16 bytes from both
+// operands, or, gathered (q == a == the table), the 4 bytes that a 4-byte aligned table's 100-byte rows keep
+static bool cross_fwd_image_ok_f16(int N, int W1, int W2, int D, const void* q, const void* a, bool gather) {
   const size_t img = (size_t)(W1 + W2) * D * sizeof(float);
-  return W1 % 8 == 0 && W2 % 8 == 0 && W1 / 8 <= 5 && W2 / 8 <= 5 && N >= 1024 && D == kImageD16 && aligned16(q) &&
-         aligned16(a) && 2 * img <= 64 * 1024;
+  const uintptr_t need = gather ? 3u : 15u;
+  return W1 % 8 == 0 && W2 % 8 == 0 && W1 / 8 <= 5 && W2 / 8 <= 5 && N >= 1024 && D == kImageD16 &&
+         (reinterpret_cast<uintptr_t>(q) & need) == 0 && (reinterpret_cast<uintptr_t>(a) & need) == 0 && 2 * img <= 64 * 1024;
 }
 
-template <int MODE>
+// GATHER: q == a == the table and gt names the ids (embed_simcross_forward_f16)
+template <int MODE, bool GATHER>
 static void launch_cross_fwd_f16(const _Float16* q, const _Float16* a, const float* n0, const float* n1, float* top,
-                                 int N, int W1, int W2, int D, hipStream_t s) {
+                                 int N, int W1, int W2, int D, hipStream_t s, CrossGather gt) {
   // register tile per lane as in launch_cross_fwd: as large as possible while the launch has 1024 waves
   auto r_cap = [](int w, int cap) { int r = (w + 7) / 8; return r > cap ? cap : r; };
   int rj = 1, rk = 1, tilesJ = 1, tilesK = 1;
@@ -385,14 +472,14 @@ static void launch_cross_fwd_f16(const _Float16* q, const _Float16* a, const flo
     tilesJ = (W1 + 8 * rj - 1) / (8 * rj); tilesK = (W2 + 8 * rk - 1) / (8 * rk);
     if ((long long)N * tilesJ * tilesK >= 1024) break;
   }
-  if (cross_fwd_image_ok_f16(N, W1, W2, D, q, a)) {
+  if (cross_fwd_image_ok_f16(N, W1, W2, D, q, a, GATHER)) {
     static_assert(kImageD16 % 2 == 0 && (kImageD16 % 16) != 0, "rows 8 apart in different banks: gcd(D, 64) <= 8");
     const size_t img = (size_t)(W1 + W2) * D * sizeof(float);
     const unsigned g2 = (unsigned)((N + 1) / 2);
 #define MMS_IMG_CASE(J, K)                                                                                    \
   if (W1 == 8 * J && W2 == 8 * K) {                                                                           \
-    hipLaunchKernelGGL((cross_fwd_image_f16_kernel<J, K, MODE, kImageD16>), dim3(g2), dim3(128), 2 * img, s,  \
-                       q, a, n0, n1, top, N);                                                                 \
+    hipLaunchKernelGGL((cross_fwd_image_f16_kernel<J, K, MODE, kImageD16, GATHER>), dim3(g2), dim3(128),      \
+                       2 * img, s, q, a, n0, n1, top, N, gt);                                                 \
     return;                                                                                                   \
   }
 #define MMS_IMG_ROW(J) MMS_IMG_CASE(J, 1) MMS_IMG_CASE(J, 2) MMS_IMG_CASE(J, 3) MMS_IMG_CASE(J, 4) MMS_IMG_CASE(J, 5)
@@ -402,11 +489,11 @@ static void launch_cross_fwd_f16(const _Float16* q, const _Float16* a, const flo
   }
   const long long work = (long long)N * tilesJ * tilesK;
   const unsigned grid = (unsigned)((work + 3) / 4);
-#define MMS_CROSS_CASE(J, K)                                                            \
-  if (rj == J && rk == K) {                                                             \
-    hipLaunchKernelGGL((cross_fwd_f16_kernel<J, K, MODE>), dim3(grid), dim3(256), 0, s, \
-                       q, a, n0, n1, top, N, W1, W2, D, tilesJ, tilesK);                \
-    return;                                                                             \
+#define MMS_CROSS_CASE(J, K)                                                                    \
+  if (rj == J && rk == K) {                                                                     \
+    hipLaunchKernelGGL((cross_fwd_f16_kernel<J, K, MODE, GATHER>), dim3(grid), dim3(256), 0, s, \
+                       q, a, n0, n1, top, N, W1, W2, D, tilesJ, tilesK, gt);                    \
+    return;                                                                                     \
   }
 #define MMS_CROSS_ROW(J) MMS_CROSS_CASE(J, 1) MMS_CROSS_CASE(J, 2) MMS_CROSS_CASE(J, 3) \
                          MMS_CROSS_CASE(J, 4) MMS_CROSS_CASE(J, 5)
@@ -415,16 +502,18 @@ static void launch_cross_fwd_f16(const _Float16* q, const _Float16* a, const flo
 #undef MMS_CROSS_CASE
 }
 
+// The word-grid forward; GATHER: q and a are the embedding table and the Embed gather is fused in.
+template <bool GATHER>
 static void cross_forward_f16(int mode, int N, int W1, int W2, int D, const _Float16* q, const _Float16* a, float* top,
-                              float* norm0, float* norm1, hipStream_t s) {
+                              float* norm0, float* norm1, hipStream_t s, CrossGather gt) {
   if (mode == 1) {
-    launch_cross_fwd_f16<1>(q, a, nullptr, nullptr, top, N, W1, W2, D, s);
+    launch_cross_fwd_f16<1, GATHER>(q, a, nullptr, nullptr, top, N, W1, W2, D, s, gt);
     return;
   }
   const long long r0 = (long long)N * W1, r1 = (long long)N * W2;
-  hipLaunchKernelGGL(row_norm_f16_kernel, dim3((unsigned)((r0 + 3) / 4)), dim3(256), 0, s, q, norm0, r0, D);
-  hipLaunchKernelGGL(row_norm_f16_kernel, dim3((unsigned)((r1 + 3) / 4)), dim3(256), 0, s, a, norm1, r1, D);
-  launch_cross_fwd_f16<0>(q, a, norm0, norm1, top, N, W1, W2, D, s);
+  hipLaunchKernelGGL(row_norm_f16_kernel, dim3((unsigned)((r0 + 3) / 4)), dim3(256), 0, s, q, norm0, r0, D, gt.iq, gt.K, gt.bias);
+  hipLaunchKernelGGL(row_norm_f16_kernel, dim3((unsigned)((r1 + 3) / 4)), dim3(256), 0, s, a, norm1, r1, D, gt.ia, gt.K, gt.bias);
+  launch_cross_fwd_f16<0, GATHER>(q, a, norm0, norm1, top, N, W1, W2, D, s, gt);
 }
 
 // tiled while the tables fit 64 KB of LDS, else plain; `exact`: the Euclid backward mode, read once by the entry point
@@ -449,12 +538,25 @@ static void cross_backward_f16(int mode, int N, int W1, int W2, int D, const _Fl
 }
 
 // =============================== entry points ===============================
-// mms_abi.hip has checked the arguments: mode 0 or 1, not W1 == W2 == 1, N >= 1.
+// mms_abi.hip has checked the arguments: mode 0 or 1, not W1 == W2 == 1 (the gathered forward serves that too), N >= 1.
+
+constexpr CrossGather kNoGather{nullptr, nullptr, 0, nullptr};
 
 int simcross_grid_forward_f16(int mode, int N, int W1, int W2, int D, const void* q, const void* a, float* top,
                               float* norm0, float* norm1, hipStream_t s) {
-  cross_forward_f16(mode, N, W1, W2, D, static_cast<const _Float16*>(q), static_cast<const _Float16*>(a), top, norm0,
-                    norm1, s);
+  cross_forward_f16<false>(mode, N, W1, W2, D, static_cast<const _Float16*>(q), static_cast<const _Float16*>(a), top,
+                           norm0, norm1, s, kNoGather);
+  return launch_status();
+}
+
+// top = SimCross(Embed(index_q), Embed(index_a)) for dist_mode 0 / 1 from a half table (K, D): embed_simcross_forward
+// (simcross_cross.hip) with the table's halves widened by the gathering loads.  No workspace, one launch for Euclid and
+// three for cosine.
+int embed_simcross_forward_f16(int mode, int N, int W1, int W2, int D, int K, const float* index_q, const float* index_a,
+                               const void* table, const float* embed_bias, float* top, float* norm0, float* norm1,
+                               hipStream_t s) {
+  const _Float16* t = static_cast<const _Float16*>(table);
+  cross_forward_f16<true>(mode, N, W1, W2, D, t, t, top, norm0, norm1, s, CrossGather{index_q, index_a, K, embed_bias});
   return launch_status();
 }
 
@@ -473,7 +575,7 @@ int simcross_grid_forward_backward_f16(int mode, int N, int W1, int W2, int D, c
   const bool exact = euclid_backward_mode() == MMS_EUCLID_BWD_REFERENCE;
   const _Float16* qh = static_cast<const _Float16*>(q);
   const _Float16* ah = static_cast<const _Float16*>(a);
-  cross_forward_f16(mode, N, W1, W2, D, qh, ah, top, norm0, norm1, s);
+  cross_forward_f16<false>(mode, N, W1, W2, D, qh, ah, top, norm0, norm1, s, kNoGather);
   cross_backward_f16(mode, N, W1, W2, D, qh, ah, top, top_diff, norm0, norm1, static_cast<_Float16*>(dq),
                      static_cast<_Float16*>(da), exact, s);
   return launch_status();

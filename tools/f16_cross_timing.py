@@ -4,8 +4,10 @@ operands from HBM), both variants in one process, alternating, REPS passes each;
 
 The bilinear rows (dist_mode 2, M = 4 with bias; mms_simcross_bilinear_*_f16, mms_embed_simcross_bilinear_forward_f16) time the scoring
 forward from grids and from word ids (a 100000-row table) at the test split's 1517 candidates, and forward + backward at a training batch.
+The embed rows (dist_mode 1 and 0 from word ids and the same 100000-row table, with the Embed bias) time mms_embed_simcross_forward_f16
+against mms_embed_simcross_forward_f32 at those 1517 candidates.
 
-  python tools/f16_cross_timing.py [--reps 7] [--out FILE] [--only elementwise|bilinear]
+  python tools/f16_cross_timing.py [--reps 7] [--out FILE] [--only elementwise|bilinear|embed]
 """
 import argparse
 import os
@@ -143,14 +145,63 @@ def bilinear_rows(reps, lines):
         torch.cuda.empty_cache()
 
 
+EMBED_CASES = [(1, (1517, 40, 40, 50)), (0, (1517, 40, 40, 50))]
+
+
+def embed_sets(shape, half, n_sets):
+    N, W1, W2, D = shape
+    g = torch.Generator(device="cuda").manual_seed(13)
+    sets = []
+    for _ in range(n_sets):
+        table = (torch.randn(BILINEAR_K, D, device="cuda", generator=g) * 0.4).half()
+        sets.append(dict(table=table if half else table.float(), ebias=torch.randn(D, device="cuda", generator=g) * 0.1,
+                         iq=torch.randint(0, BILINEAR_K, (N, W1), device="cuda", generator=g).float(),
+                         ia=torch.randint(0, BILINEAR_K, (N, W2), device="cuda", generator=g).float(),
+                         top=torch.empty(N, 1, W1, W2, device="cuda"), n0=torch.empty(N, W1, device="cuda"), n1=torch.empty(N, W2, device="cuda")))
+    return sets
+
+
+def embed_pass(mode, half, sets):
+    f = capi.embed_simcross_forward_f16 if half else capi.embed_simcross_forward
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for s in sets:
+        n = dict(norm0=s["n0"], norm1=s["n1"]) if mode == 0 else {}
+        f(mode, s["iq"], s["ia"], s["table"], s["top"], embed_bias=s["ebias"], **n)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / len(sets)
+
+
+def embed_rows(reps, lines):
+    for mode, shape in EMBED_CASES:
+        N, W1, W2, D = shape
+        nbytes = lambda half: BILINEAR_K * D * (2 if half else 4) + N * (W1 + W2) * 4 + N * W1 * W2 * 4
+        sets = {half: embed_sets(shape, half, max(4, min(256, -(-RING_BYTES // nbytes(half))))) for half in (False, True)}
+        for half in (False, True):
+            embed_pass(mode, half, sets[half])      # warm-up pass
+        ts = {False: [], True: []}
+        for _ in range(reps):
+            for half in (False, True):
+                ts[half].append(embed_pass(mode, half, sets[half]))
+        what = "fwd_ids %s embed bias  %s" % (("cosine", "euclid")[mode], "x".join(map(str, shape)))
+        for half in (False, True):
+            v = sorted(ts[half])
+            lines.append("%-44s %-4s median %8.2f us   min %8.2f   max %8.2f   (%d sets)" % (what, "f16" if half else "fp32", v[len(v) // 2], v[0], v[-1],
+                                                                                            len(sets[half])))
+        print("\n".join(lines[-2:]), flush=True)
+        del sets
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", choices=("elementwise", "bilinear"), default=None)
+    ap.add_argument("--only", choices=("elementwise", "bilinear", "embed"), default=None)
     args = ap.parse_args()
     lines = ["%s, %d passes per variant, ring of operand sets >= %d MB per variant" % (torch.cuda.get_device_name(0), args.reps, RING_BYTES >> 20)]
-    for kind, mode, bwd_mode, shape in (CASES if args.only != "bilinear" else []):
+    for kind, mode, bwd_mode, shape in (CASES if args.only in (None, "elementwise") else []):
         capi.set_euclid_backward_mode(bwd_mode)
         sets = {half: operand_sets(shape, half, max(4, min(256, -(-RING_BYTES // set_bytes(shape, half))))) for half in (False, True)}
         for half in (False, True):                   # the backward reads a forward's top (and norms)
@@ -170,8 +221,10 @@ def main():
         del sets
         torch.cuda.empty_cache()
     capi.set_euclid_backward_mode("fp32")
-    if args.only != "elementwise":
+    if args.only in (None, "bilinear"):
         bilinear_rows(args.reps, lines)
+    if args.only in (None, "embed"):
+        embed_rows(args.reps, lines)
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
