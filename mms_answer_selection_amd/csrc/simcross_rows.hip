@@ -329,6 +329,20 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
   }
 }
 
+// p[i] as ONE 16-byte vector load that stays where it is written.  (A float4 is a struct: copying one out of a
+// __restrict__ const array is a memcpy that the optimiser forwards to the first use of each member, i.e. the load is
+// emitted THERE -- behind whatever was meant to run while it is in flight.)
+template <typename I>
+__device__ __forceinline__ float4 load4(const float4* p, I i) {
+  const mms_v4f v = reinterpret_cast<const mms_v4f*>(p)[i];
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// What a backward-only launch of euclid_block_kernel keeps per slot once T and dT of the slot's pair have landed:
+// c = dT*T*T*T and r = fl32(1/den) in the fp32 arithmetic, the reference mode's coefficient set otherwise.
+template <bool EXACT> struct SlotCoef { float c, r; };
+template <> struct SlotCoef<true> { EuclidCoef k; };
+
 // ---- the same algorithm with the global-memory side laid out by WORKGROUP, not by pair ----------
 // Measured (tools/launchbench.hip, profiles/r02_launchbench.txt): HBM-cold, a launch whose waves each read
 // two 512-byte pieces 1200 bytes apart per load instruction (the row-aligned layout above) takes 4.4 us for
@@ -346,12 +360,27 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
 // SPAN = waves that share one dense run: WPB (the whole workgroup, one barrier) or 1 (each wave reads its own two
 // rows as a dense run and synchronises with nobody: the chain phases of a CU's waves then start as their own data
 // arrives instead of all at once).
-template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB, int SPAN = WPB>
+//
+// The BACKWARD-ONLY launch (!FWD && BWD) is one pass at two waves per SIMD with every wave in the same phase, so
+// whatever a wave executes between "its last byte has landed" and "its last store is issued" is exposed once per
+// launch.  Two things keep that stretch short:
+//  * T and dT of a thread's slots are requested BEFORE the operands (vmcnt retires in order: they are usable while
+//    the six 16-byte loads are still in flight) and everything that depends on them alone -- c = dT*T*T*T and the
+//    fp64 reciprocal chain of the divisor, or the reference mode's EuclidCoef -- is formed and pinned in registers
+//    under a counted wait that leaves the operand loads outstanding.  Same expressions on the same values: the
+//    gradients keep their bits.
+//  * FULL: every run of the launch lies inside the batch (the host knows: N a multiple of the pairs per workgroup).
+//    No end-of-batch clamp on any address, no lane mask on any store but the compile-time i < C of the last slot,
+//    32-bit index math off one 64-bit base per run.  With the stores unmasked the compiler counts vmcnt per slot:
+//    slot `it`'s two stores leave as soon as its own operands are in.
+template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB, int SPAN = WPB, bool FULL = false>
 __global__ __launch_bounds__(64 * WPB) void euclid_block_kernel(
     int N, const float* __restrict__ q, const float* __restrict__ a,
     const float* __restrict__ top_in, const float* __restrict__ top_diff,
     float* __restrict__ top_out, float* __restrict__ dq, float* __restrict__ da) {
   static_assert(SPAN == WPB || SPAN == 1, "a dense run belongs to the workgroup or to one wave");
+  constexpr bool BONLY = !FWD && BWD;                        // the backward-only launch
+  static_assert(!FULL || BONLY, "the whole-batch instantiation exists for the backward-only launch");
   constexpr int T = 64 * SPAN, R = 2 * SPAN, C = R * D4C;
   constexpr int NSPAN = WPB / SPAN;                          // runs per workgroup
   constexpr int NIT = (C + T - 1) / T;                       // float4s per operand per thread
@@ -369,37 +398,77 @@ __global__ __launch_bounds__(64 * WPB) void euclid_block_kernel(
   const float4* q4 = reinterpret_cast<const float4*>(q);
   const float4* a4 = reinterpret_cast<const float4*>(a);
 
+  // slot `it` holds float4 i of the run: only the last slot can fall past its end (T * (NIT - 1) < C), so in the
+  // backward-only launch the test folds away for every other slot once the loops are unrolled (the forward
+  // instantiations keep the test they had, and with it their code)
+  auto in_run = [](int it, int i) { return NIT * T == C || (BONLY && it < NIT - 1) || i < C; };
+  // per-float4 pair values (dT; T too in a backward-only launch, which requests them ahead of the operands)
+  float Tg[NIT], gg[NIT];
+  auto request_pair_values = [&] {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = tid + T * it;
+      const int pr = (in_run(it, i) ? i : 0) / D4C;             // pair within the run
+      if constexpr (FULL) {
+        gg[it] = (top_diff + run * R)[pr];
+        Tg[it] = (top_in + run * R)[pr];
+      } else {
+        long long row = run * R + pr;
+        row = row < N ? row : N - 1;
+        gg[it] = top_diff[row];
+        if (!FWD) Tg[it] = top_in[row];
+      }
+    }
+  };
+  if constexpr (BONLY) request_pair_values();
   float4 x[NIT], y[NIT], df[NIT];
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int i = tid + T * it;
-    long long gi = b + ((NIT * T == C || i < C) ? i : 0);     // clamp: keep the load unconditional
-    gi = gi < total4 ? gi : total4 - 1;                       // a run past the end reads the last float4
-    x[it] = q4[gi];
-    y[it] = a4[gi];
-  }
-  // per-float4 pair coefficients of a backward-only launch: requested with the operands
-  float Tg[NIT], gg[NIT];
-  if (BWD) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + T * it;
-      long long row = run * R + ((NIT * T == C || i < C) ? i : 0) / D4C;
-      row = row < N ? row : N - 1;
-      gg[it] = top_diff[row];
-      if (!FWD) Tg[it] = top_in[row];
+    const int ci = in_run(it, i) ? i : 0;                     // clamp: keep the load unconditional
+    if constexpr (FULL) {
+      x[it] = load4(q4 + b, ci);
+      y[it] = load4(a4 + b, ci);
+    } else {
+      long long gi = b + ci;
+      gi = gi < total4 ? gi : total4 - 1;                     // a run past the end reads the last float4
+      // (load4 only where something is meant to run under the loads: the forward instantiations keep their code)
+      x[it] = BONLY ? load4(q4, gi) : q4[gi];
+      y[it] = BONLY ? load4(a4, gi) : a4[gi];
     }
   }
+  if constexpr (BWD && !BONLY) request_pair_values();
+  if constexpr (BONLY) __builtin_amdgcn_sched_barrier(0);    // every request is issued before the first wait
+  // backward-only launch: the per-slot coefficients, formed while the operands are in flight and pinned so that
+  // they cannot sink behind the operand wait
+  SlotCoef<EXACT> coef[BONLY ? NIT : 1];                     // (no other launch has any)
+  if constexpr (BONLY) {
 #pragma unroll
-  for (int it = 0; it < NIT; ++it) {
+    for (int it = 0; it < NIT; ++it) {
+      if constexpr (EXACT) {
+        coef[it].k = euclid_coef(Tg[it], gg[it]);
+        asm volatile("" : "+v"(coef[it].k.c), "+v"(coef[it].k.den), "+v"(coef[it].k.rcp));
+      } else {
+        coef[it].c = gg[it] * Tg[it] * Tg[it] * Tg[it];
+        coef[it].r = (float)rcp_newton((double)(Tg[it] - 1.0f) + 1e-9);
+        asm volatile("" : "+v"(coef[it].c), "+v"(coef[it].r));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);                       // ... and no operand's first use is hoisted into them
+  }
+  auto subtract = [&](int it) {
     df[it].x = x[it].x - y[it].x; df[it].y = x[it].y - y[it].y;
     df[it].z = x[it].z - y[it].z; df[it].w = x[it].w - y[it].w;
+  };
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if constexpr (!FULL) subtract(it);                      // FULL: slot by slot, next to the slot's stores
     if (FWD) {
       const int i = tid + T * it;
       float4 s;
       s.x = df[it].x * df[it].x; s.y = df[it].y * df[it].y;
       s.z = df[it].z * df[it].z; s.w = df[it].w * df[it].w;
-      if (NIT * T == C || i < C) lds4[(ST4 == D4C) ? i : (i / D4C) * ST4 + (i % D4C)] = s;
+      if (in_run(it, i)) lds4[(ST4 == D4C) ? i : (i / D4C) * ST4 + (i % D4C)] = s;
     }
   }
   if (FWD) {
@@ -457,31 +526,46 @@ __global__ __launch_bounds__(64 * WPB) void euclid_block_kernel(
 
   float4* dq4 = reinterpret_cast<float4*>(dq);
   float4* da4 = reinterpret_cast<float4*>(da);
-  if (!FWD) {
+  if constexpr (BONLY && !FULL) {
     // Everything this thread requested is in registers before its first store.  The stores sit under lane masks
     // (the end of the batch), so the compiler cannot count them: a load consumed after a store became
     // s_waitcnt vmcnt(0), i.e. a wait for the ACKNOWLEDGEMENT of the stores already issued -- in the middle of
-    // the store phase of the launch that bounds the headline.
+    // the store phase of the launch that bounds the headline.  (The pair values were consumed above; FULL has no
+    // masked store before its last slot and needs none of this.)
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      asm volatile("" : "+v"(gg[it]), "+v"(Tg[it]));
+    for (int it = 0; it < NIT; ++it)
       asm volatile("" : "+v"(df[it].x), "+v"(df[it].y), "+v"(df[it].z), "+v"(df[it].w));
-    }
   }
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int i = tid + T * it;
-    const bool live = (NIT * T == C || i < C) && (b + i < total4);
-    const float Tp = FWD ? Tl[((NIT * T == C || i < C) ? i : 0) / D4C] : Tg[it];
+    const bool live = in_run(it, i) && (FULL || b + i < total4);
+    if constexpr (FULL) subtract(it);
+    if constexpr (FULL && NIT * T != C) {
+      // the last slot's stores are masked: its operands are waited for (counted: only stores are younger) out here,
+      // so that neither the wait nor the loads can move into the masked block
+      if (it == NIT - 1) asm volatile("" : "+v"(df[it].x), "+v"(df[it].y), "+v"(df[it].z), "+v"(df[it].w));
+    }
     float4 t;
-    if (EXACT) {
-      const EuclidCoef k = euclid_coef(Tp, gg[it]);
-      t = euclid_tt4(k, df[it]);
+    if constexpr (BONLY) {
+      if constexpr (EXACT) {
+        t = euclid_tt4(coef[it].k, df[it]);
+      } else {
+        const float c = coef[it].c, r = coef[it].r;
+        t.x = (c * df[it].x) * r; t.y = (c * df[it].y) * r;
+        t.z = (c * df[it].z) * r; t.w = (c * df[it].w) * r;
+      }
     } else {
-      const float c = gg[it] * Tp * Tp * Tp;
-      const float r = (float)rcp_newton((double)(Tp - 1.0f) + 1e-9);
-      t.x = (c * df[it].x) * r; t.y = (c * df[it].y) * r;
-      t.z = (c * df[it].z) * r; t.w = (c * df[it].w) * r;
+      const float Tp = Tl[(in_run(it, i) ? i : 0) / D4C];
+      if (EXACT) {
+        const EuclidCoef k = euclid_coef(Tp, gg[it]);
+        t = euclid_tt4(k, df[it]);
+      } else {
+        const float c = gg[it] * Tp * Tp * Tp;
+        const float r = (float)rcp_newton((double)(Tp - 1.0f) + 1e-9);
+        t.x = (c * df[it].x) * r; t.y = (c * df[it].y) * r;
+        t.z = (c * df[it].z) * r; t.w = (c * df[it].w) * r;
+      }
     }
     if (live) {
       // dq = 0 + tt ; da = 0 + (-tt)   (:176-177 zero, :219-220 accumulate once)
@@ -491,6 +575,7 @@ __global__ __launch_bounds__(64 * WPB) void euclid_block_kernel(
       stream_store(dq4 + b + i, o0);
       stream_store(da4 + b + i, o1);
     }
+    if constexpr (FULL) __builtin_amdgcn_sched_barrier(0);   // slot `it` is stored before slot it + 1 is waited for
   }
 }
 
@@ -1057,7 +1142,9 @@ static void launch_pair32(const float* q, const float* a, const float* top_in, c
   // 4.13 us, dense 3.59-3.68 us, at the same bytes and the same L1-to-L2 read requests (one per line either
   // way) but 24 % fewer L1 line accesses: a 16-lane quarter that starts mid-line looks up three lines, one
   // that starts on a line two.  The figures above predate the map; with it the Forward launch + dense Backward
-  // launch of bench.py went 7.50 -> 7.22 us per step.
+  // launch of bench.py went 7.50 -> 7.22 us per step, and with the dense Backward's coefficients formed ahead of
+  // its operands and its whole-batch instantiation (euclid_block_kernel's FULL, selected below) 7.28 -> 7.03
+  // (profiles/bwd_coef_first_*).
   // Dev switch for A/B timing: MMS_EUCLID_LAYOUT_{FWD,BWD,FUSED} = pair | block | wave (dense run per wave).
   static const int layout = [] {
     const char* e = std::getenv(FWD && BWD ? "MMS_EUCLID_LAYOUT_FUSED" : FWD ? "MMS_EUCLID_LAYOUT_FWD" : "MMS_EUCLID_LAYOUT_BWD");
@@ -1065,14 +1152,20 @@ static void launch_pair32(const float* q, const float* a, const float* top_in, c
     return FWD ? 0 : 1;
   }();
   const bool shift = same_line_phase(q, a, BWD ? dq : nullptr, BWD ? da : nullptr);
+  // Every workgroup's pairs lie inside the batch: the backward-only dense kernel then runs without end-of-batch
+  // clamps and store masks (euclid_block_kernel's FULL; a workgroup owns 2 * WPB pairs whatever its SPAN).
+  constexpr bool BONLY = !FWD && BWD;
+  const bool full = BONLY && N % (2 * WPB) == 0;
   with_glove_d4(D, [&](auto W) {
     constexpr int D4C = decltype(W)::value;
     with_bool(BWD && exact, [&](auto E) {   // a forward has no backward term: its EXACT is false
       constexpr bool EXACT = decltype(E)::value;
       hipLaunchKernelGGL((layout == 0   ? (shift ? euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB, true>
                                                  : euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB>)
-                          : layout == 1 ? euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB>
-                                        : euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB, 1>),
+                          : layout == 1 ? (full ? euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB, WPB, BONLY>
+                                                : euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB>)
+                                        : (full ? euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB, 1, BONLY>
+                                                : euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB, 1>)),
                          dim3(grid), dim3(64 * WPB), 0, s, N, q, a, top_in, top_diff, top_out, dq, da);
     });
   });
