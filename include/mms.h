@@ -667,6 +667,53 @@ int mms_embed_backward_pair_indexed_f32(int M0, int M1, int N, int K, const floa
 
 size_t mms_embed_workspace_bytes(int M, int N);
 
+/* fp16-STORAGE Embed (no reference instantiation: common.hpp:41-44): the Embed ends of the fp16-storage word-grid family
+ * (mms_simcross_*_f16, mms_simcross_bilinear_*_f16 above).  The forwards gather a HALF table into the half (N,W,D) grids
+ * those calls read; the backwards take the half dq / da those calls leave and add them into the fp32 master gradient of
+ * the table in the reference's order.  Each call is the twin of the _f32 call of the same name, above.
+ *   Operands: index* word ids as floats, converted with (int) and clamped to [0, K - 1] exactly as the twins do;
+ *       table_f16 (K,N), top*_f16 (M,N), top_diff*_f16 (M,N) IEEE halves; bias (N) fp32 or NULL; weight_diff (K,N) and
+ *       bias_diff (N) fp32, accumulated into as in the twin, either may be NULL.
+ *   Forward: with bias NULL, top[n,d] is the table's half copied bit for bit (NaN payloads, +-Inf, subnormals pass
+ *       through).  With a bias, top[n,d] = RNE_half(bias[d] + widen(table[id][d])): the one fp32 add of the twin, then one
+ *       rounding to nearest even (overflow gives +-Inf) -- mms_embed_forward_f32 on the widened table, rounded once.  With
+ *       bias NULL, mms_simcross_forward_f16 on these grids carries the bits of mms_embed_simcross_forward_f16 from the
+ *       same ids.
+ *   Backward: every half of top_diff is widened exactly; everything after that is the fp32 arithmetic of the twin.
+ *       weight_diff[id,:] receives its rows one by one, n ascending, on top of the value already there
+ *       (embed_layer.cpp:155-180); for the pair calls layer 0's rows, then layer 1's.  weight_diff AND bias_diff carry
+ *       the bits of the _f32 twin run on the widened top_diff -- weight_diff therefore the reference CPU code's bits on
+ *       those values.
+ *   Workspace: mms_embed_workspace_bytes(M, N) (M0 + M1 for the pair calls) serves the _f16 calls unchanged: the layout
+ *       holds ids, row numbers and fp32 partial sums, nothing of the storage type.
+ *   Inverted index: it depends on the ids alone.  mms_embed_forward_pair_f16 writes the same workspace contents as
+ *       mms_embed_forward_pair_f32 for the same ids, under the same mms_embed_pair_index_supported rule; an index built by
+ *       either forward serves either indexed backward.
+ *   Any N >= 1 and any 2-byte aligned half operands: alignment and N only select how wide the loads and stores are,
+ *       never refuse.
+ *   No allocation, no host synchronisation; safe to capture in a hipGraph.  No floating-point atomics: the results are
+ *       deterministic.  None of the per-thread arithmetic modes is consulted.
+ *   Errors: argument tuple for argument tuple those of the _f32 twins.  M == 0 (single-layer calls): MMS_OK.
+ *       weight_diff == bias_diff == NULL: MMS_OK.  The indexed call with sizes mms_embed_pair_index_supported refuses:
+ *       MMS_ERR_UNSUPPORTED.  A missing or short workspace: MMS_ERR_WORKSPACE.  Bad sizes (M < 0, M0 or M1 <= 0, N <= 0,
+ *       K <= 0, M * N > 2^31 - 1) or a NULL required pointer: MMS_ERR_INVALID_ARG.  A call that does not return MMS_OK
+ *       writes nothing, and nothing past an output's last element is ever written. */
+int mms_embed_forward_f16(int M, int N, int K, const float* index, const void* table_f16,
+                          const float* bias, void* top_f16, void* stream);
+int mms_embed_forward_pair_f16(int M0, int M1, int N, int K, const float* index0, const float* index1,
+                               const void* table_f16, const float* bias, void* top0_f16, void* top1_f16,
+                               void* index_workspace, size_t index_workspace_bytes, void* stream);
+int mms_embed_backward_f16(int M, int N, int K, const float* index, const void* top_diff_f16,
+                           float* weight_diff, float* bias_diff, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int mms_embed_backward_pair_f16(int M0, int M1, int N, int K, const float* index0, const void* top_diff0_f16,
+                                const float* index1, const void* top_diff1_f16, float* weight_diff,
+                                float* bias_diff, void* workspace, size_t workspace_bytes, void* stream);
+int mms_embed_backward_pair_indexed_f16(int M0, int M1, int N, int K, const float* index0, const void* top_diff0_f16,
+                                        const float* index1, const void* top_diff1_f16, float* weight_diff,
+                                        float* bias_diff, void* index_workspace, size_t index_workspace_bytes,
+                                        void* stream);
+
 /* Embed fused into SimCross's loads (forward / scoring; dist_mode 0 or 1):
  *   top == SimCross(Embed(index_q), Embed(index_a))
  * i.e. embed_layer.cpp:135-152 followed by sim_cross_layer.cpp:96-139, without the (N,W,D) blobs in

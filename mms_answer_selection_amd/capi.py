@@ -66,6 +66,11 @@ _SIGNATURES = {
     "mms_embed_pair_index_supported": (_i, [_i, _i, _i]),
     "mms_embed_forward_pair_f32": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
     "mms_embed_backward_pair_indexed_f32": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
+    "mms_embed_forward_f16": (_i, [_i, _i, _i] + [_vp] * 5),
+    "mms_embed_forward_pair_f16": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
+    "mms_embed_backward_f16": (_i, [_i, _i, _i] + [_vp] * 5 + [_sz, _vp]),
+    "mms_embed_backward_pair_f16": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
+    "mms_embed_backward_pair_indexed_f16": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
     "mms_feed_gather_rows_f32": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "mms_simcross_workspace_bytes_f64": (_sz, [_i] * 6),
     "mms_simcross_forward_f64": (_i, [_i] * 6 + [_vp] * 8 + [_sz, _vp]),
@@ -774,6 +779,68 @@ def embed_backward_pair_indexed(index0, index1, top_diff0, top_diff1, weight_dif
                                                     _ptr(weight_diff, "weight_diff", True), _ptr(bias_diff, "bias_diff", True),
                                                     index.buf.data_ptr(), index.buf.numel(), _stream()),
           "mms_embed_backward_pair_indexed_f32")
+
+
+# ---- fp16-storage Embed: half table / top / top_diff, float32 ids, bias and (master) gradients.  The workspace and the
+# EmbedPairIndex are those of the float32 calls: an index built by either pair forward serves either indexed backward.
+_H = torch.float16
+
+
+def embed_forward_f16(index, table, top, bias=None):
+    """embed_forward from a half table (K, N) into a half top (M, N); bias (N) float32 or None (mms_embed_forward_f16)."""
+    M, (K, N) = index.numel(), table.shape
+    check(lib().mms_embed_forward_f16(M, N, K, _ptr(index, "index"), _ptr(table, "table", dtype=_H),
+                                      _ptr(bias, "bias", True), _ptr(top, "top", dtype=_H), _stream()),
+          "mms_embed_forward_f16")
+
+
+def embed_backward_f16(index, top_diff, weight_diff, bias_diff=None, ws=None, shape=None):
+    """embed_backward of a half top_diff (M, N) into float32 weight_diff / bias_diff (mms_embed_backward_f16)."""
+    M, (K, N) = index.numel(), (shape if shape is not None else weight_diff.shape)
+    wsp, wsb = (ws or _default_ws).get(lib().mms_embed_workspace_bytes(M, N), index.device)
+    check(lib().mms_embed_backward_f16(M, N, K, _ptr(index, "index"), _ptr(top_diff, "top_diff", dtype=_H),
+                                       _ptr(weight_diff, "weight_diff", True),
+                                       _ptr(bias_diff, "bias_diff", True), wsp, wsb, _stream()),
+          "mms_embed_backward_f16")
+
+
+def embed_backward_pair_f16(index0, index1, top_diff0, top_diff1, weight_diff, bias_diff=None, ws=None, shape=None):
+    """embed_backward_pair of two half top_diffs into float32 gradients (mms_embed_backward_pair_f16)."""
+    M0, M1, (K, N) = index0.numel(), index1.numel(), (shape if shape is not None else weight_diff.shape)
+    wsp, wsb = (ws or _default_ws).get(lib().mms_embed_workspace_bytes(M0 + M1, N), index0.device)
+    check(lib().mms_embed_backward_pair_f16(M0, M1, N, K, _ptr(index0, "index0"), _ptr(top_diff0, "top_diff0", dtype=_H),
+                                            _ptr(index1, "index1"), _ptr(top_diff1, "top_diff1", dtype=_H),
+                                            _ptr(weight_diff, "weight_diff", True), _ptr(bias_diff, "bias_diff", True),
+                                            wsp, wsb, _stream()), "mms_embed_backward_pair_f16")
+
+
+def embed_forward_pair_f16(index0, index1, table, top0, top1, bias=None, index=None):
+    """embed_forward_pair from a half table into half tops; `index` (an EmbedPairIndex) as there.  Returns True if the
+    index was built (mms_embed_forward_pair_f16)."""
+    M0, M1, (K, N) = index0.numel(), index1.numel(), table.shape
+    wsp, wsb, built = None, 0, False
+    if index is not None and lib().mms_embed_pair_index_supported(M0, M1, K):
+        wsp, wsb = index.get(lib().mms_embed_workspace_bytes(M0 + M1, N), index0.device)
+        built = True
+    check(lib().mms_embed_forward_pair_f16(M0, M1, N, K, _ptr(index0, "index0"), _ptr(index1, "index1"),
+                                           _ptr(table, "table", dtype=_H), _ptr(bias, "bias", True),
+                                           _ptr(top0, "top0", dtype=_H), _ptr(top1, "top1", dtype=_H), wsp, wsb, _stream()),
+          "mms_embed_forward_pair_f16")
+    return built
+
+
+def embed_backward_pair_indexed_f16(index0, index1, top_diff0, top_diff1, weight_diff, index, bias_diff=None, shape=None):
+    """embed_backward_pair_f16 with the index a pair forward (half or float32) built for (index0, index1)."""
+    M0, M1, (K, N) = index0.numel(), index1.numel(), (shape if shape is not None else weight_diff.shape)
+    if index.buf is None:
+        raise MMSError("embed_backward_pair_indexed_f16: no index was built (the pair forward returned False); use "
+                       "embed_backward_pair_f16")
+    check(lib().mms_embed_backward_pair_indexed_f16(M0, M1, N, K, _ptr(index0, "index0"),
+                                                    _ptr(top_diff0, "top_diff0", dtype=_H), _ptr(index1, "index1"),
+                                                    _ptr(top_diff1, "top_diff1", dtype=_H),
+                                                    _ptr(weight_diff, "weight_diff", True), _ptr(bias_diff, "bias_diff", True),
+                                                    index.buf.data_ptr(), index.buf.numel(), _stream()),
+          "mms_embed_backward_pair_indexed_f16")
 
 
 def feed_gather_rows(src, first, rows, dst, perm=None):

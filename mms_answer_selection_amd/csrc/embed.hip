@@ -15,7 +15,9 @@
 //             in a TREC-QA batch; its chain is long (one dependent add per row
 //             per column) but is a single destination among ~10^3 short ones.
 #include <algorithm>
+#include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include <rocprim/rocprim.hpp>
 
@@ -27,51 +29,64 @@ namespace mms {
 // of two Embed layers that share one table (network_v4's w2v_q / w2v_a, do_trec_qa_clean.py:452-467), whose Backward
 // calls the reference runs one after the other into the same weight diff (embed_layer.cpp:155-180): row n of the
 // concatenation is layer 0's row n, or layer 1's row n - M0.  A single layer is M0 = M, second = null.
-// T: the element type (float or double, the two the reference instantiates); the pair calls are float only.
-template <class T>
+// T: the element type of the arithmetic, of the ids and of the gradients (float or double, the two the reference
+// instantiates); the pair calls are float only.  S: the type top_diff is STORED in -- T, or _Float16 with T = float (the
+// fp16-storage calls, mms_embed_backward*_f16).  A stored element enters the arithmetic through widen() and nowhere
+// else, so an S instantiation carries the bits of the T one run on the widened rows.
+template <class T, class S = T>
 struct EmbedSrc {
-  const T* index0; const T* diff0; int M0;
-  const T* index1; const T* diff1;
+  const T* index0; const S* diff0; int M0;
+  const T* index1; const S* diff1;
   __device__ __forceinline__ T index(int n) const { return n < M0 ? index0[n] : index1[n - M0]; }
-  __device__ __forceinline__ const T* row(unsigned n, int N) const {
+  __device__ __forceinline__ const S* row(unsigned n, int N) const {
     return (int)n < M0 ? diff0 + (size_t)n * N : diff1 + (size_t)(n - M0) * N;
   }
+  static __device__ __forceinline__ T widen(S v) { return (T)v; }                  // exact: every half is a float
+  __host__ __device__ EmbedSrc<T> ids() const { return {index0, nullptr, M0, index1, nullptr}; }   // what the index build reads
 };
 
 // gemm(M,N,1) of the bias term: alpha*(1*bias) + beta*top, one rounded add
 template <class T>
 __device__ __forceinline__ T embed_add_bias(T b, T v) { return (T)1 * ((T)1 * b) + (T)1 * v; }
-// PAIRS (double only): N is even and weight / bias / top are 16-byte aligned, so every row is -- a lane moves two
-// columns per 16-byte access; any other N or base takes the one-column loop.  Same adds, same bits.
-template <class T, bool PAIRS = false>
+// One wave moves one table row to its top row, VW elements of the storage type S per lane and access.  The caller has
+// checked that VW divides N and that both bases are VW * sizeof(S) aligned, so every row is; VW = 1 is the always
+// correct route.  Without a bias the elements are copied bit for bit; with one, each is widened to T, takes the one
+// add of the reference and is rounded back to S (to nearest even; the identity when S is T).  Same adds whatever VW.
+template <class T, class S, int VW>
+__device__ __forceinline__ void embed_move_row(const S* __restrict__ w, const T* __restrict__ bias, S* __restrict__ t,
+                                               int N, int lane) {
+  typedef S vec __attribute__((ext_vector_type(VW)));
+  const vec* wv = reinterpret_cast<const vec*>(w);
+  vec* tv = reinterpret_cast<vec*>(t);
+  for (int d = lane; d < N / VW; d += 64) {
+    vec v = wv[d];
+    if (bias) {
+#pragma unroll
+      for (int e = 0; e < VW; ++e) v[e] = (S)embed_add_bias(bias[d * VW + e], (T)v[e]);
+    }
+    tv[d] = v;
+  }
+}
+// the widest access of embed_move_row (at most `widest` elements, 16 bytes) that N and the bases a, b, c allow
+template <class S>
+static int embed_row_width(int N, const void* a, const void* b, const void* c, int widest) {
+  int vw = widest;
+  auto fits = [&](const void* p) { return reinterpret_cast<uintptr_t>(p) % (vw * sizeof(S)) == 0; };
+  while (vw > 1 && (N % vw != 0 || !fits(a) || !fits(b) || !fits(c))) vw /= 2;
+  return vw;
+}
+template <class T, class S, int VW>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(int M, int N, int K,
                                                         const T* __restrict__ index,
-                                                        const T* __restrict__ weight,
+                                                        const S* __restrict__ weight,
                                                         const T* __restrict__ bias,
-                                                        T* __restrict__ top) {
+                                                        S* __restrict__ top) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);   // one wave per output row
   if (n >= M) return;
   const int lane = threadIdx.x & 63;
   int idx = (int)index[n];
   idx = idx < 0 ? 0 : (idx >= K ? K - 1 : idx);        // the reference only DCHECKs; stay in bounds
-  const T* w = weight + (size_t)idx * N;
-  T* t = top + (size_t)n * N;
-  if constexpr (PAIRS) {
-    const double2* w2 = reinterpret_cast<const double2*>(w);
-    const double2* b2 = reinterpret_cast<const double2*>(bias);
-    double2* t2 = reinterpret_cast<double2*>(t);
-    for (int d = lane; d < N / 2; d += 64) {
-      double2 v = w2[d];
-      if (bias) { const double2 b = b2[d]; v.x = embed_add_bias(b.x, v.x); v.y = embed_add_bias(b.y, v.y); }
-      t2[d] = v;
-    }
-  } else {
-    for (int d = lane; d < N; d += 64) {
-      T v = w[d];
-      if (bias) v = embed_add_bias(bias[d], v);
-      t[d] = v;
-    }
-  }
+  embed_move_row<T, S, VW>(weight + (size_t)idx * N, bias, top + (size_t)n * N, N, lane);
 }
 
 template <class T>
@@ -101,13 +116,13 @@ __global__ __launch_bounds__(256) void embed_head_flags_kernel(int M, const unsi
 // ahead, then CH/8 independent loads per thread, all issued before the first LDS write).  One
 // memory round trip per chunk instead of two per row -- the zero-pad word id owns thousands
 // of rows of a TREC-QA batch.  Short segments (<= CH rows: nearly every id) are one chunk.
-template <int CH, int GW, class T>   // GW gathering waves; block = 64 * (GW + 1) threads
+template <int CH, int GW, class T, class S>   // GW gathering waves; block = 64 * (GW + 1) threads
 __global__ __launch_bounds__(64 * (GW + 1)) void embed_bwd_seg_kernel(
     int M, int N, const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
     const unsigned* __restrict__ heads, const unsigned* __restrict__ nseg,
-    EmbedSrc<T> src, T* __restrict__ weight_diff, int rmin, int rmax) {
+    EmbedSrc<T, S> src, T* __restrict__ weight_diff, int rmin, int rmax) {
   extern __shared__ __align__(16) unsigned char seg_raw[];
-  T* seg_buf = reinterpret_cast<T*>(seg_raw);    // [2][CH][64] elements, then [2][CH] row numbers
+  T* seg_buf = reinterpret_cast<T*>(seg_raw);    // [2][CH][64] elements (widened: the adder reads T), then [2][CH] row numbers
   constexpr int RPT = CH / GW;                   // rows per gathering thread per chunk
   static_assert(CH % GW == 0, "chunk rows must divide evenly over the gathering waves");
   unsigned* vbuf = reinterpret_cast<unsigned*>(seg_buf + 2 * CH * 64);
@@ -127,7 +142,7 @@ __global__ __launch_bounds__(64 * (GW + 1)) void embed_bwd_seg_kernel(
     if (gt < 0) return;
     T x[RPT];
 #pragma unroll
-    for (int u = 0; u < RPT; ++u) x[u] = src.row(vbuf[b * CH + rg + u * GW], N)[gcol];
+    for (int u = 0; u < RPT; ++u) x[u] = src.widen(src.row(vbuf[b * CH + rg + u * GW], N)[gcol]);
 #pragma unroll
     for (int u = 0; u < RPT; ++u) seg_buf[(b * CH + rg + u * GW) * 64 + col] = x[u];
   };
@@ -167,8 +182,8 @@ __global__ __launch_bounds__(64 * (GW + 1)) void embed_bwd_seg_kernel(
 // chip idle anyway: the partial sums in the workgroups NEXT to the one-workgroup inverted-index build, the final sum
 // in workgroups appended to the short-segment launch (3 launches per backward pass instead of 5).
 constexpr int kBiasChunk = 128;
-template <int LANES, class T>                         // blockDim.x == 64 * LANES
-__device__ __forceinline__ void embed_bias_partial_body(int c, int M, int N, const EmbedSrc<T>& src,
+template <int LANES, class T, class S>                // blockDim.x == 64 * LANES
+__device__ __forceinline__ void embed_bias_partial_body(int c, int M, int N, const EmbedSrc<T, S>& src,
                                                         T* __restrict__ partial, T (*red)[64]) {
   const int ry = threadIdx.x >> 6, dl = threadIdx.x & 63;
   const int n0 = c * kBiasChunk, n1 = min(M, n0 + kBiasChunk);
@@ -178,7 +193,7 @@ __device__ __forceinline__ void embed_bias_partial_body(int c, int M, int N, con
     for (int nb = n0 + ry; nb < n1; nb += 8 * LANES) {
       T v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = src.row((unsigned)min(nb + LANES * u, M - 1), N)[d];
+      for (int u = 0; u < 8; ++u) v[u] = src.widen(src.row((unsigned)min(nb + LANES * u, M - 1), N)[d]);
 #pragma unroll
       for (int u = 0; u < 8; ++u) s += (nb + LANES * u < n1) ? v[u] : (T)0;
     }
@@ -207,8 +222,8 @@ __device__ __forceinline__ void embed_bias_finish_body(int d, int chunks, int N,
   }
   bias_diff[d] = (T)1 * s + (T)1 * bias_diff[d];
 }
-template <class T>
-__global__ __launch_bounds__(256) void embed_bias_partial_kernel(int M, int N, EmbedSrc<T> src,
+template <class T, class S>
+__global__ __launch_bounds__(256) void embed_bias_partial_kernel(int M, int N, EmbedSrc<T, S> src,
                                                                  T* __restrict__ partial) {
   __shared__ T red[4][64];
   embed_bias_partial_body<4>((int)blockIdx.x, M, N, src, partial, red);
@@ -268,9 +283,9 @@ __device__ __forceinline__ void embed_prep_body(int M, int K, unsigned bits, con
   }
   if (t == 0) nseg[0] = total;
 }
-template <class T>
+template <class T, class S>
 __global__ __launch_bounds__(kPrepThreads) void embed_prep_small_kernel(
-    int M, int K, unsigned bits, EmbedSrc<T> src, unsigned* __restrict__ keys,
+    int M, int K, unsigned bits, EmbedSrc<T, S> src, unsigned* __restrict__ keys,
     unsigned* __restrict__ vals, unsigned* __restrict__ heads, unsigned* __restrict__ nseg,
     int N, T* __restrict__ bias_partial) {
   if (blockIdx.x > 0) {                          // riders: the bias gradient's partial sums (bias_partial != null)
@@ -278,7 +293,7 @@ __global__ __launch_bounds__(kPrepThreads) void embed_prep_small_kernel(
     embed_bias_partial_body<kPrepThreads / 64>((int)blockIdx.x - 1, M, N, src, bias_partial, red);
     return;
   }
-  embed_prep_body(M, K, bits, src, keys, vals, heads, nseg);
+  embed_prep_body(M, K, bits, src.ids(), keys, vals, heads, nseg);
 }
 
 // Forward of two Embed layers over ONE table in one launch, with the inverted index of their concatenated word ids
@@ -286,9 +301,10 @@ __global__ __launch_bounds__(kPrepThreads) void embed_prep_small_kernel(
 // takes 14 us at a lone workgroup's clock, and in the forward it costs nothing -- the gathers and the layers behind
 // them keep the rest of the chip busy.  The backward pass (embed_backward_pair with index_ready) then starts at the
 // segment kernels.
+template <class S, int VW>              // the table and the tops are stored as S; VW as embed_move_row
 __global__ __launch_bounds__(kPrepThreads) void embed_fwd_pair_kernel(
-    int M0, int M1, int N, int K, EmbedSrc<float> src, const float* __restrict__ weight, const float* __restrict__ bias,
-    float* __restrict__ top0, float* __restrict__ top1, int build, unsigned bits, unsigned* __restrict__ keys,
+    int M0, int M1, int N, int K, EmbedSrc<float> src, const S* __restrict__ weight, const float* __restrict__ bias,
+    S* __restrict__ top0, S* __restrict__ top1, int build, unsigned bits, unsigned* __restrict__ keys,
     unsigned* __restrict__ vals, unsigned* __restrict__ heads, unsigned* __restrict__ nseg) {
   const int M = M0 + M1;
   if (build && blockIdx.x == 0) {
@@ -300,23 +316,18 @@ __global__ __launch_bounds__(kPrepThreads) void embed_fwd_pair_kernel(
   const int lane = threadIdx.x & 63;
   int idx = (int)src.index(n);
   idx = idx < 0 ? 0 : (idx >= K ? K - 1 : idx);
-  const float* w = weight + (size_t)idx * N;
-  float* t = n < M0 ? top0 + (size_t)n * N : top1 + (size_t)(n - M0) * N;
-  for (int d = lane; d < N; d += 64) {
-    float v = w[d];
-    if (bias) v = embed_add_bias(bias[d], v);            // as embed_fwd_kernel
-    t[d] = v;
-  }
+  S* t = n < M0 ? top0 + (size_t)n * N : top1 + (size_t)(n - M0) * N;
+  embed_move_row<float, S, VW>(weight + (size_t)idx * N, bias, t, N, lane);              // as embed_fwd_kernel
 }
 
 // Short segments (nearly every word id: a handful of rows): one WAVE per (id, 64-column slice),
 // four per workgroup, no LDS and no barrier -- the row numbers and then the rows are requested
 // all at once (8 or 32 unconditional loads with clamped addresses), then added in order.
-template <class T>
+template <class T, class S>
 __global__ __launch_bounds__(256) void embed_bwd_short_kernel(
     int M, int N, const unsigned* __restrict__ keys, const unsigned* __restrict__ vals,
     const unsigned* __restrict__ heads, const unsigned* __restrict__ nseg,
-    EmbedSrc<T> src, T* __restrict__ weight_diff, int seg_blocks, int bias_chunks,
+    EmbedSrc<T, S> src, T* __restrict__ weight_diff, int seg_blocks, int bias_chunks,
     const T* __restrict__ bias_partial, T* __restrict__ bias_diff) {
   if ((int)blockIdx.x >= seg_blocks) {           // riders: the bias gradient's final sum (the partials are a launch old)
     if (blockIdx.y == 0)
@@ -336,13 +347,13 @@ __global__ __launch_bounds__(256) void embed_bwd_short_kernel(
   if (R <= 8) {
     T x[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) x[u] = src.row(vals[p + min(u, R - 1)], N)[gc];
+    for (int u = 0; u < 8; ++u) x[u] = src.widen(src.row(vals[p + min(u, R - 1)], N)[gc]);
 #pragma unroll
     for (int u = 0; u < 8; ++u) if (u < R) acc = (T)1 * x[u] + acc;
   } else {
     T x[32];
 #pragma unroll
-    for (int u = 0; u < 32; ++u) x[u] = src.row(vals[p + min(u, R - 1)], N)[gc];
+    for (int u = 0; u < 32; ++u) x[u] = src.widen(src.row(vals[p + min(u, R - 1)], N)[gc]);
 #pragma unroll
     for (int u = 0; u < 32; ++u) if (u < R) acc = (T)1 * x[u] + acc;
   }
@@ -363,29 +374,39 @@ static EmbedWs embed_ws(int M, int N, size_t elem) {   // elem: bytes of the ele
   w.total = o + (size_t)M * 8 + (4u << 20);
   return w;
 }
+// (the layout depends on the ARITHMETIC type alone: the fp16-storage calls use the float one)
 size_t embed_workspace_bytes(int M, int N) { return embed_ws(M, N, sizeof(float)).total; }
 size_t embed_workspace_bytes_f64(int M, int N) { return embed_ws(M, N, sizeof(double)).total; }
 
-template <class T>
-int embed_forward(int M, int N, int K, const T* index, const T* weight, const T* bias,
-                  T* top, hipStream_t s) {
-  if constexpr (sizeof(T) == 8) {
-    if (N % 2 == 0 && aligned16(weight) && aligned16(bias) && aligned16(top)) {
-      hipLaunchKernelGGL((embed_fwd_kernel<T, true>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, M, N, K, index,
-                         weight, bias, top);
-      return launch_status();
-    }
+// Elements per lane and access: float rows one column at a time; double rows two (16 bytes) when N is even and weight /
+// bias / top are 16-byte aligned; half rows 8, 4 or 2 as N and the table's and top's addresses allow (a row of N = 50
+// halves is 100 bytes: 4-byte aligned at best), else one.  Same adds, same bits.
+template <class T, class S>
+int embed_forward(int M, int N, int K, const T* index, const S* weight, const T* bias, S* top, hipStream_t s) {
+  const dim3 grid((unsigned)((M + 3) / 4));
+  auto launch = [&](auto vw) {
+    hipLaunchKernelGGL((embed_fwd_kernel<T, S, decltype(vw)::value>), grid, dim3(256), 0, s, M, N, K, index, weight,
+                       bias, top);
+  };
+  int vw = 1;
+  if constexpr (sizeof(S) == 8) vw = (N % 2 == 0 && aligned16(weight) && aligned16(bias) && aligned16(top)) ? 2 : 1;
+  if constexpr (sizeof(S) == 2) vw = embed_row_width<S>(N, weight, top, top, 8);
+  if (vw == 1) launch(std::integral_constant<int, 1>());
+  if constexpr (sizeof(S) != 4) {
+    if (vw == 2) launch(std::integral_constant<int, 2>());
   }
-  hipLaunchKernelGGL(embed_fwd_kernel<T>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, M, N, K, index,
-                     weight, bias, top);
+  if constexpr (sizeof(S) == 2) {
+    if (vw == 4) launch(std::integral_constant<int, 4>());
+    if (vw == 8) launch(std::integral_constant<int, 8>());
+  }
   return launch_status();
 }
 
 // rows per chunk of the long-segment kernel: two chunks of 64 columns (+ row numbers) in the CU's 160 KB of LDS
 template <class T> constexpr int kSegChunk = sizeof(T) == 4 ? 256 : 128;
 
-template <class T>
-static int embed_backward_src(int M, int N, int K, const EmbedSrc<T>& src,
+template <class T, class S>
+static int embed_backward_src(int M, int N, int K, const EmbedSrc<T, S>& src,
                               T* weight_diff, T* bias_diff, void* ws, size_t ws_bytes, hipStream_t s,
                               bool index_ready = false) {
   const EmbedWs lay = embed_ws(M, N, sizeof(T));
@@ -404,16 +425,16 @@ static int embed_backward_src(int M, int N, int K, const EmbedSrc<T>& src,
     if (index_ready && M <= kPrepMax && bits < 32) {
       // keys / vals / heads / nseg of this workspace were written by embed_forward_pair for these very ids
       if (bias_diff) {
-        hipLaunchKernelGGL(embed_bias_partial_kernel<T>, dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N, src,
+        hipLaunchKernelGGL((embed_bias_partial_kernel<T, S>), dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N, src,
                            reinterpret_cast<T*>(base + lay.partial));
         bias_rides = true;                          // (the final sum still rides with the short-segment launch)
       }
     } else if (M <= kPrepMax && bits < 32) {
       bias_rides = bias_diff != nullptr;
-      hipLaunchKernelGGL(embed_prep_small_kernel<T>, dim3(1u + (bias_rides ? (unsigned)lay.chunks : 0u)), dim3(kPrepThreads), 0,
+      hipLaunchKernelGGL((embed_prep_small_kernel<T, S>), dim3(1u + (bias_rides ? (unsigned)lay.chunks : 0u)), dim3(kPrepThreads), 0,
                          s, M, K, bits, src, k1, v1, heads, nseg, N, reinterpret_cast<T*>(base + lay.partial));
     } else {
-      hipLaunchKernelGGL(embed_keys_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, M, K, src,
+      hipLaunchKernelGGL(embed_keys_kernel<T>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, M, K, src.ids(),
                          k0, v0);
       size_t need = 0;
       if (rocprim::radix_sort_pairs(nullptr, need, k0, k1, v0, v1, (size_t)M, 0u, bits, s) != hipSuccess)
@@ -435,19 +456,19 @@ static int embed_backward_src(int M, int N, int K, const EmbedSrc<T>& src,
     constexpr int CH = kSegChunk<T>;
     constexpr size_t kLongLds = 2 * CH * (64 * sizeof(T) + sizeof(unsigned));   // 130 KB of the CU's 160 KB
     static const hipError_t once = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&embed_bwd_seg_kernel<CH, 8, T>),
+        reinterpret_cast<const void*>(&embed_bwd_seg_kernel<CH, 8, T, S>),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLds);
     (void)once;
     const unsigned seg_blocks = (grid.x + 3) / 4, fin_blocks = bias_rides ? (unsigned)((N + 255) / 256) : 0u;
-    hipLaunchKernelGGL(embed_bwd_short_kernel<T>, dim3(seg_blocks + fin_blocks, grid.y), dim3(256), 0, s, M, N, k1, v1,
+    hipLaunchKernelGGL((embed_bwd_short_kernel<T, S>), dim3(seg_blocks + fin_blocks, grid.y), dim3(256), 0, s, M, N, k1, v1,
                        heads, nseg, src, weight_diff, (int)seg_blocks, lay.chunks,
                        reinterpret_cast<const T*>(base + lay.partial), bias_diff);
-    hipLaunchKernelGGL((embed_bwd_seg_kernel<CH, 8, T>), grid, dim3(576), kLongLds, s, M, N, k1, v1, heads, nseg,
+    hipLaunchKernelGGL((embed_bwd_seg_kernel<CH, 8, T, S>), grid, dim3(576), kLongLds, s, M, N, k1, v1, heads, nseg,
                        src, weight_diff, 33, 0x7fffffff);
   }
   if (bias_diff && !bias_rides) {
     T* partial = reinterpret_cast<T*>(base + lay.partial);
-    hipLaunchKernelGGL(embed_bias_partial_kernel<T>, dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N,
+    hipLaunchKernelGGL((embed_bias_partial_kernel<T, S>), dim3((unsigned)lay.chunks), dim3(256), 0, s, M, N,
                        src, partial);
     hipLaunchKernelGGL(embed_bias_finish_kernel<T>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s,
                        lay.chunks, N, partial, bias_diff);
@@ -455,28 +476,40 @@ static int embed_backward_src(int M, int N, int K, const EmbedSrc<T>& src,
   return launch_status();
 }
 
-template <class T>
-int embed_backward(int M, int N, int K, const T* index, const T* top_diff,
+template <class T, class S>
+int embed_backward(int M, int N, int K, const T* index, const S* top_diff,
                    T* weight_diff, T* bias_diff, void* ws, size_t ws_bytes, hipStream_t s) {
-  const EmbedSrc<T> src{index, top_diff, M, nullptr, nullptr};
+  const EmbedSrc<T, S> src{index, top_diff, M, nullptr, nullptr};
   return embed_backward_src(M, N, K, src, weight_diff, bias_diff, ws, ws_bytes, s);
 }
-// Layer<float> and Layer<double>: the two instantiations the reference makes (INSTANTIATE_CLASS, common.hpp:41-44)
-template int embed_forward<float>(int, int, int, const float*, const float*, const float*, float*, hipStream_t);
-template int embed_forward<double>(int, int, int, const double*, const double*, const double*, double*, hipStream_t);
-template int embed_backward<float>(int, int, int, const float*, const float*, float*, float*, void*, size_t, hipStream_t);
-template int embed_backward<double>(int, int, int, const double*, const double*, double*, double*, void*, size_t,
-                                    hipStream_t);
+// Layer<float> and Layer<double>: the two instantiations the reference makes (INSTANTIATE_CLASS, common.hpp:41-44);
+// <float, _Float16>: the fp16-storage calls (half table / top / top_diff, fp32 bias and gradients)
+template int embed_forward<float, float>(int, int, int, const float*, const float*, const float*, float*, hipStream_t);
+template int embed_forward<double, double>(int, int, int, const double*, const double*, const double*, double*,
+                                           hipStream_t);
+template int embed_forward<float, _Float16>(int, int, int, const float*, const _Float16*, const float*, _Float16*,
+                                            hipStream_t);
+template int embed_backward<float, float>(int, int, int, const float*, const float*, float*, float*, void*, size_t,
+                                          hipStream_t);
+template int embed_backward<double, double>(int, int, int, const double*, const double*, double*, double*, void*, size_t,
+                                            hipStream_t);
+template int embed_backward<float, _Float16>(int, int, int, const float*, const _Float16*, float*, float*, void*, size_t,
+                                             hipStream_t);
 
 // Two Embed layers over ONE table: layer 0's Backward, then layer 1's, as one pass over the concatenation of their
 // rows (the inverted index is built once, every table row is read and written once, the bias gradient is one sum).
 // Same bits as the two calls: a table row's additions keep the order "layer 0's rows ascending, then layer 1's".
-int embed_backward_pair(int M0, int M1, int N, int K, const float* index0, const float* top_diff0, const float* index1,
-                        const float* top_diff1, float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes,
+template <class S>
+int embed_backward_pair(int M0, int M1, int N, int K, const float* index0, const S* top_diff0, const float* index1,
+                        const S* top_diff1, float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes,
                         hipStream_t s, int index_ready) {
-  const EmbedSrc<float> src{index0, top_diff0, M0, index1, top_diff1};
+  const EmbedSrc<float, S> src{index0, top_diff0, M0, index1, top_diff1};
   return embed_backward_src(M0 + M1, N, K, src, weight_diff, bias_diff, ws, ws_bytes, s, index_ready != 0);
 }
+template int embed_backward_pair<float>(int, int, int, int, const float*, const float*, const float*, const float*, float*,
+                                        float*, void*, size_t, hipStream_t, int);
+template int embed_backward_pair<_Float16>(int, int, int, int, const float*, const _Float16*, const float*, const _Float16*,
+                                           float*, float*, void*, size_t, hipStream_t, int);
 
 // can embed_forward_pair build the index for these sizes?  (the one-workgroup sort: up to 4,096 ids)
 bool embed_pair_index_supported(int M0, int M1, int K) {
@@ -487,9 +520,10 @@ bool embed_pair_index_supported(int M0, int M1, int K) {
 
 // top0 = Embed(index0), top1 = Embed(index1), one launch; index_ws (optional, embed_workspace_bytes(M0 + M1, N)): the
 // inverted index of the ids in the order (index0, index1) -- hand the SAME workspace and the same order to
-// embed_backward_pair with index_ready = 1
-int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const float* index1, const float* weight,
-                       const float* bias, float* top0, float* top1, void* index_ws, size_t index_ws_bytes, hipStream_t s) {
+// embed_backward_pair with index_ready = 1.  The index depends on the ids alone: whatever S, the same words.
+template <class S>
+int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const float* index1, const S* weight,
+                       const float* bias, S* top0, S* top1, void* index_ws, size_t index_ws_bytes, hipStream_t s) {
   const int M = M0 + M1;
   const EmbedWs lay = embed_ws(M, N, sizeof(float));
   const bool build = index_ws != nullptr && embed_pair_index_supported(M0, M1, K);
@@ -499,14 +533,28 @@ int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const 
   while (bits < 32 && (1ull << bits) < (unsigned long long)K) ++bits;
   const EmbedSrc<float> src{index0, nullptr, M0, index1, nullptr};
   const unsigned rows_per_wg = kPrepThreads / 64;
-  hipLaunchKernelGGL(embed_fwd_pair_kernel, dim3((unsigned)((M + rows_per_wg - 1) / rows_per_wg) + (build ? 1u : 0u)),
-                     dim3(kPrepThreads), 0, s, M0, M1, N, K, src, weight, bias, top0, top1, build ? 1 : 0, bits,
-                     build ? reinterpret_cast<unsigned*>(base + lay.k1) : nullptr,
-                     build ? reinterpret_cast<unsigned*>(base + lay.v1) : nullptr,
-                     build ? reinterpret_cast<unsigned*>(base + lay.heads) : nullptr,
-                     build ? reinterpret_cast<unsigned*>(base + lay.nseg) : nullptr);
+  auto launch = [&](auto vw) {
+    hipLaunchKernelGGL((embed_fwd_pair_kernel<S, decltype(vw)::value>),
+                       dim3((unsigned)((M + rows_per_wg - 1) / rows_per_wg) + (build ? 1u : 0u)), dim3(kPrepThreads), 0, s,
+                       M0, M1, N, K, src, weight, bias, top0, top1, build ? 1 : 0, bits,
+                       build ? reinterpret_cast<unsigned*>(base + lay.k1) : nullptr,
+                       build ? reinterpret_cast<unsigned*>(base + lay.v1) : nullptr,
+                       build ? reinterpret_cast<unsigned*>(base + lay.heads) : nullptr,
+                       build ? reinterpret_cast<unsigned*>(base + lay.nseg) : nullptr);
+  };
+  const int vw = sizeof(S) == 2 ? embed_row_width<S>(N, weight, top0, top1, 8) : 1;   // as embed_forward
+  if (vw == 1) launch(std::integral_constant<int, 1>());
+  if constexpr (sizeof(S) == 2) {
+    if (vw == 2) launch(std::integral_constant<int, 2>());
+    if (vw == 4) launch(std::integral_constant<int, 4>());
+    if (vw == 8) launch(std::integral_constant<int, 8>());
+  }
   return launch_status();
 }
+template int embed_forward_pair<float>(int, int, int, int, const float*, const float*, const float*, const float*, float*,
+                                       float*, void*, size_t, hipStream_t);
+template int embed_forward_pair<_Float16>(int, int, int, int, const float*, const float*, const _Float16*, const float*,
+                                          _Float16*, _Float16*, void*, size_t, hipStream_t);
 
 // ---- batch feed: rows of a device-resident dataset -> one top blob -----------------
 // Replaces the per-row caffe_copy loop of HDF5DataLayer::Forward_cpu/_gpu

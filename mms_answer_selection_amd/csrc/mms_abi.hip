@@ -101,21 +101,43 @@ int rank_accuracy_abi(int count, const T* a, const T* b, const T* label, T* acc_
   if (!a || !b || !label || !acc_out) return MMS_ERR_INVALID_ARG;
   return rank_accuracy(count, a, b, label, acc_out, workspace, workspace_bytes, as_stream(stream));
 }
-template <class T>
-int embed_forward_abi(int M, int N, int K, const T* index, const T* weight, const T* bias, T* top, void* stream) {
+// (S: how table / top / top_diff are stored -- T, or _Float16 for the _f16 calls: one set of checks for every twin)
+template <class T, class S>
+int embed_forward_abi(int M, int N, int K, const T* index, const S* weight, const T* bias, S* top, void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || (long long)M * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
   if (M == 0) return MMS_OK;
   if (!index || !weight || !top) return MMS_ERR_INVALID_ARG;
   return embed_forward(M, N, K, index, weight, bias, top, as_stream(stream));
 }
-template <class T>
-int embed_backward_abi(int M, int N, int K, const T* index, const T* top_diff, T* weight_diff, T* bias_diff,
+template <class T, class S>
+int embed_backward_abi(int M, int N, int K, const T* index, const S* top_diff, T* weight_diff, T* bias_diff,
                        void* workspace, size_t workspace_bytes, void* stream) {
   if (M < 0 || N <= 0 || K <= 0 || (long long)M * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
   if (M == 0 || (!weight_diff && !bias_diff)) return MMS_OK;
   if (!index || !top_diff) return MMS_ERR_INVALID_ARG;
   return embed_backward(M, N, K, index, top_diff, weight_diff, bias_diff, workspace, workspace_bytes,
                         as_stream(stream));
+}
+// indexed: the workspace holds the inverted index the pair forward built for these ids (mms_embed_backward_pair_indexed_*)
+template <class S>
+int embed_backward_pair_abi(int M0, int M1, int N, int K, const float* index0, const S* top_diff0, const float* index1,
+                            const S* top_diff1, float* weight_diff, float* bias_diff, void* workspace,
+                            size_t workspace_bytes, void* stream, bool indexed) {
+  if (M0 <= 0 || M1 <= 0 || N <= 0 || K <= 0 || !index0 || !top_diff0 || !index1 || !top_diff1) return MMS_ERR_INVALID_ARG;
+  if (((long long)M0 + M1) * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;    // N >= 1: M0 + M1 is an int as well
+  if (indexed && !embed_pair_index_supported(M0, M1, K)) return MMS_ERR_UNSUPPORTED;   // no index was built for these sizes
+  if (!weight_diff && !bias_diff) return MMS_OK;
+  return embed_backward_pair(M0, M1, N, K, index0, top_diff0, index1, top_diff1, weight_diff, bias_diff, workspace,
+                             workspace_bytes, as_stream(stream), indexed ? 1 : 0);
+}
+template <class S>
+int embed_forward_pair_abi(int M0, int M1, int N, int K, const float* index0, const float* index1, const S* weight,
+                           const float* bias, S* top0, S* top1, void* index_workspace, size_t index_workspace_bytes,
+                           void* stream) {
+  if (M0 <= 0 || M1 <= 0 || N <= 0 || K <= 0 || !index0 || !index1 || !weight || !top0 || !top1) return MMS_ERR_INVALID_ARG;
+  if (((long long)M0 + M1) * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
+  return embed_forward_pair(M0, M1, N, K, index0, index1, weight, bias, top0, top1, index_workspace,
+                            index_workspace_bytes, as_stream(stream));
 }
 }  // namespace
 
@@ -578,11 +600,8 @@ int mms_rank_accuracy_f32(int count, const float* a, const float* b, const float
 int mms_embed_backward_pair_f32(int M0, int M1, int N, int K, const float* index0, const float* top_diff0,
                                 const float* index1, const float* top_diff1, float* weight_diff, float* bias_diff,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (M0 <= 0 || M1 <= 0 || N <= 0 || K <= 0 || !index0 || !top_diff0 || !index1 || !top_diff1) return MMS_ERR_INVALID_ARG;
-  if ((long long)M0 + M1 > 0x7fffffffLL || ((long long)M0 + M1) * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
-  if (!weight_diff && !bias_diff) return MMS_OK;
-  return embed_backward_pair(M0, M1, N, K, index0, top_diff0, index1, top_diff1, weight_diff, bias_diff, workspace,
-                             workspace_bytes, as_stream(stream), 0);
+  return embed_backward_pair_abi(M0, M1, N, K, index0, top_diff0, index1, top_diff1, weight_diff, bias_diff, workspace,
+                                 workspace_bytes, stream, false);
 }
 
 int mms_embed_pair_index_supported(int M0, int M1, int K) {
@@ -592,21 +611,15 @@ int mms_embed_pair_index_supported(int M0, int M1, int K) {
 int mms_embed_forward_pair_f32(int M0, int M1, int N, int K, const float* index0, const float* index1,
                                const float* weight, const float* bias, float* top0, float* top1, void* index_workspace,
                                size_t index_workspace_bytes, void* stream) {
-  if (M0 <= 0 || M1 <= 0 || N <= 0 || K <= 0 || !index0 || !index1 || !weight || !top0 || !top1) return MMS_ERR_INVALID_ARG;
-  if (((long long)M0 + M1) * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
-  return embed_forward_pair(M0, M1, N, K, index0, index1, weight, bias, top0, top1, index_workspace,
-                            index_workspace_bytes, as_stream(stream));
+  return embed_forward_pair_abi(M0, M1, N, K, index0, index1, weight, bias, top0, top1, index_workspace,
+                                index_workspace_bytes, stream);
 }
 
 int mms_embed_backward_pair_indexed_f32(int M0, int M1, int N, int K, const float* index0, const float* top_diff0,
                                         const float* index1, const float* top_diff1, float* weight_diff, float* bias_diff,
                                         void* index_workspace, size_t index_workspace_bytes, void* stream) {
-  if (M0 <= 0 || M1 <= 0 || N <= 0 || K <= 0 || !index0 || !top_diff0 || !index1 || !top_diff1) return MMS_ERR_INVALID_ARG;
-  if (((long long)M0 + M1) * N > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;
-  if (!embed_pair_index_supported(M0, M1, K)) return MMS_ERR_UNSUPPORTED;     // no index was built for these sizes
-  if (!weight_diff && !bias_diff) return MMS_OK;
-  return embed_backward_pair(M0, M1, N, K, index0, top_diff0, index1, top_diff1, weight_diff, bias_diff, index_workspace,
-                             index_workspace_bytes, as_stream(stream), 1);
+  return embed_backward_pair_abi(M0, M1, N, K, index0, top_diff0, index1, top_diff1, weight_diff, bias_diff,
+                                 index_workspace, index_workspace_bytes, stream, true);
 }
 
 size_t mms_embed_workspace_bytes(int M, int N) { return (M > 0 && N > 0) ? embed_workspace_bytes(M, N) : 0; }
@@ -620,6 +633,44 @@ int mms_embed_backward_f32(int M, int N, int K, const float* index, const float*
                            float* weight_diff, float* bias_diff, void* workspace,
                            size_t workspace_bytes, void* stream) {
   return embed_backward_abi(M, N, K, index, top_diff, weight_diff, bias_diff, workspace, workspace_bytes, stream);
+}
+
+// fp16 storage: half table / top / top_diff, fp32 ids, bias and gradients; the checks and the workspace of the _f32 twins
+int mms_embed_forward_f16(int M, int N, int K, const float* index, const void* table_f16, const float* bias,
+                          void* top_f16, void* stream) {
+  return embed_forward_abi(M, N, K, index, static_cast<const _Float16*>(table_f16), bias, static_cast<_Float16*>(top_f16),
+                           stream);
+}
+
+int mms_embed_forward_pair_f16(int M0, int M1, int N, int K, const float* index0, const float* index1,
+                               const void* table_f16, const float* bias, void* top0_f16, void* top1_f16,
+                               void* index_workspace, size_t index_workspace_bytes, void* stream) {
+  return embed_forward_pair_abi(M0, M1, N, K, index0, index1, static_cast<const _Float16*>(table_f16), bias,
+                                static_cast<_Float16*>(top0_f16), static_cast<_Float16*>(top1_f16), index_workspace,
+                                index_workspace_bytes, stream);
+}
+
+int mms_embed_backward_f16(int M, int N, int K, const float* index, const void* top_diff_f16, float* weight_diff,
+                           float* bias_diff, void* workspace, size_t workspace_bytes, void* stream) {
+  return embed_backward_abi(M, N, K, index, static_cast<const _Float16*>(top_diff_f16), weight_diff, bias_diff, workspace,
+                            workspace_bytes, stream);
+}
+
+int mms_embed_backward_pair_f16(int M0, int M1, int N, int K, const float* index0, const void* top_diff0_f16,
+                                const float* index1, const void* top_diff1_f16, float* weight_diff, float* bias_diff,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  return embed_backward_pair_abi(M0, M1, N, K, index0, static_cast<const _Float16*>(top_diff0_f16), index1,
+                                 static_cast<const _Float16*>(top_diff1_f16), weight_diff, bias_diff, workspace,
+                                 workspace_bytes, stream, false);
+}
+
+int mms_embed_backward_pair_indexed_f16(int M0, int M1, int N, int K, const float* index0, const void* top_diff0_f16,
+                                        const float* index1, const void* top_diff1_f16, float* weight_diff,
+                                        float* bias_diff, void* index_workspace, size_t index_workspace_bytes,
+                                        void* stream) {
+  return embed_backward_pair_abi(M0, M1, N, K, index0, static_cast<const _Float16*>(top_diff0_f16), index1,
+                                 static_cast<const _Float16*>(top_diff1_f16), weight_diff, bias_diff, index_workspace,
+                                 index_workspace_bytes, stream, true);
 }
 
 int mms_feed_gather_rows_f32(int rows, int row_elems, int src_rows, const float* src, const int* perm,

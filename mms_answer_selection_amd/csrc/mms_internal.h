@@ -124,17 +124,22 @@ void set_rank_tie_mode(int m);
 // embed.hip
 size_t embed_workspace_bytes(int M, int N);
 size_t embed_workspace_bytes_f64(int M, int N);
-template <class T>
-int embed_forward(int M, int N, int K, const T* index, const T* weight, const T* bias, T* top, hipStream_t s);
-template <class T>
-int embed_backward(int M, int N, int K, const T* index, const T* top_diff, T* weight_diff, T* bias_diff, void* ws,
+// (T: ids, bias, gradients and all arithmetic; S: how table / top / top_diff are stored -- T itself, or _Float16 with
+// T = float, whose workspace is embed_workspace_bytes too.  Instantiated: <float, float>, <double, double>,
+// <float, _Float16>; the pair calls for S = float and _Float16.)
+template <class T, class S>
+int embed_forward(int M, int N, int K, const T* index, const S* weight, const T* bias, S* top, hipStream_t s);
+template <class T, class S>
+int embed_backward(int M, int N, int K, const T* index, const S* top_diff, T* weight_diff, T* bias_diff, void* ws,
                    size_t ws_bytes, hipStream_t s);
-int embed_backward_pair(int M0, int M1, int N, int K, const float* index0, const float* top_diff0, const float* index1,
-                        const float* top_diff1, float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes,
+template <class S>
+int embed_backward_pair(int M0, int M1, int N, int K, const float* index0, const S* top_diff0, const float* index1,
+                        const S* top_diff1, float* weight_diff, float* bias_diff, void* ws, size_t ws_bytes,
                         hipStream_t s, int index_ready);
 bool embed_pair_index_supported(int M0, int M1, int K);
-int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const float* index1, const float* weight,
-                       const float* bias, float* top0, float* top1, void* index_ws, size_t index_ws_bytes, hipStream_t s);
+template <class S>
+int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const float* index1, const S* weight,
+                       const float* bias, S* top0, S* top1, void* index_ws, size_t index_ws_bytes, hipStream_t s);
 int feed_gather_rows(int rows, int row_elems, int src_rows, const float* src, const int* perm, int first, float* dst,
                      hipStream_t s);
 // mms_abi.hip
