@@ -311,6 +311,17 @@ __device__ __forceinline__ float chain_sum_speculative(const float4* img4, int D
 //    ds_bpermute round trips;
 //  * a miss anywhere (never observed on real data; forced by the adversarial
 //    tests) sends the whole wave to ONE exact re-walk of the full image.
+// Byte address of `p` within the workgroup's LDS, and the 16-byte read of float4 `u` behind such an address (one
+// ds_read_b128 with an immediate offset, issued where it is written).
+typedef __attribute__((address_space(3))) const mms_v4f lds_v4f;
+__device__ __forceinline__ unsigned lds_address(const void* p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
+}
+__device__ __forceinline__ float4 lds_read4(unsigned addr, int u) {
+  const mms_v4f t = ((lds_v4f*)(size_t)addr)[u];
+  return make_float4(t.x, t.y, t.z, t.w);
+}
+
 template <int H4>
 struct SpecSegment {
   float4 v[H4];
@@ -326,6 +337,37 @@ struct SpecSegment {
       s = s + __builtin_shufflevector(lo, lo, 1, 1);
       s = s + __builtin_shufflevector(hi, hi, 0, 0);
       s = s + __builtin_shufflevector(hi, hi, 1, 1);
+    }
+    return s;
+  }
+
+  // The same reads and the same adds with the chain started on its FIRST read.  lgkmcnt counts to 15: behind all H4
+  // reads of load() the wait in front of step 0 can only say "at most 14 outstanding", i.e. H4 - 14 reads back,
+  // while step 0 needs read 0.  So load_first() issues AHEAD <= 15 reads, and chain_streamed() issues read u + AHEAD
+  // right after the four adds of step u, as counter room appears: every wait in the chain is then the exact count
+  // of the read it needs (AHEAD - 1 outstanding behind it).  Whatever the caller puts between the two calls runs
+  // while read 0 is on its way.  `seg` is the segment's LDS byte address (lds_address below), which the caller can
+  // form and pin long before the reads.  The empty asm makes the address of read u + AHEAD depend on the sum after
+  // step u -- no instruction, but the read cannot be hoisted back to the front -- and one scheduling fence per step
+  // keeps it from drifting behind the next step.
+  static constexpr int AHEAD = H4 < 15 ? H4 : 15;
+  __device__ __forceinline__ void load_first(unsigned seg) {
+#pragma unroll
+    for (int u = 0; u < AHEAD; ++u) v[u] = lds_read4(seg, u);
+  }
+  __device__ __forceinline__ float2v chain_streamed(unsigned seg, float2v s) {
+#pragma unroll
+    for (int u = 0; u < H4; ++u) {
+      const float2v lo = {v[u].x, v[u].y}, hi = {v[u].z, v[u].w};
+      s = __builtin_shufflevector(lo, lo, 0, 0) + s;
+      s = __builtin_shufflevector(lo, lo, 1, 1) + s;
+      s = __builtin_shufflevector(hi, hi, 0, 0) + s;
+      s = __builtin_shufflevector(hi, hi, 1, 1) + s;
+      if (u + AHEAD < H4) {
+        asm volatile("" : "+v"(seg) : "v"(s));
+        v[u + AHEAD] = lds_read4(seg, u + AHEAD);
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
     return s;
   }

@@ -171,6 +171,130 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
   }
 }
 
+// p[i] as ONE 16-byte vector load that stays where it is written.  (A float4 is a struct: copying one out of a
+// __restrict__ const array is a memcpy that the optimiser forwards to the first use of each member, i.e. the load is
+// emitted THERE -- behind whatever was meant to run while it is in flight.)
+template <typename I>
+__device__ __forceinline__ float4 load4(const float4* p, I i) {
+  const mms_v4f v = reinterpret_cast<const mms_v4f*>(p)[i];
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// ---- the forward-only launch of euclid_pair32_kernel (below; its comment describes the algorithm) ----------
+// One pass at two waves per SIMD with every wave in the same phase: whatever a wave executes between "its last byte
+// has landed" and "T is stored" is exposed once per launch.  Same algorithm, same LDS image, same windows, same
+// expressions on the same values as the kernel's shared body, so T keeps its bits; what differs is the order of
+// issue, the waits and the predicates:
+//  * all 2 * NIT operand loads leave first, in row order (slot 0 first), as unconditional vector loads of a clamped
+//    column: a lane without a column in a slot reads column 0 of its row and neither writes nor sums the result
+//    (left to the compiler, slot 0's loads sank into the lane-masked block of its LDS write, behind the other
+//    slots' loads, with a wait for ALL loads inside the mask);
+//  * slot `it` is subtracted, squared, written to the image and added to the window centres under a counted wait
+//    that leaves the later slots in flight (vmcnt(4), (2), (0) at NIT = 3).  The squares are pinned in registers
+//    ahead of the lane mask of the LDS write: the masked block then holds a DS write and no wait;
+//  * a window centre is reduced across the half-wave as soon as the last slot that contributes to it is in
+//    (D = 300: p1 after slot 0, p2 and with it the chain's start value after slot 1), under the loads still in
+//    flight, instead of after the image is complete;
+//  * the zero pad of the image is written while the loads are in flight, and the priority is raised before the
+//    chain's reads, not after them;
+//  * the chain starts on its first LDS read (SpecSegment::load_first / chain_streamed in euclid_math.h);
+//  * FULL: every pair of the launch lies inside the batch and q and a span less than 4 GiB each (the host knows).
+//    No clamp of the row, no `have` on the store of T, one 32-bit byte offset per slot off the two kernel
+//    arguments (which arrive in SGPRs) instead of a 64-bit row pointer per operand.
+template <int D4C, int WPB, bool SHIFT, bool FULL>
+__device__ __forceinline__ void euclid_pair32_forward(int N, const float* __restrict__ q, const float* __restrict__ a,
+                                                      float* __restrict__ top_out, float4* lds4) {
+  constexpr int NIT = (D4C + 31) / 32;
+  constexpr int H4 = (D4C + 2) / 3, ST4 = 3 * H4;
+  constexpr int MAXU = SHIFT ? 7 : 0;            // largest peel at the start of a row
+  // slot `it` holds columns [32*it - MAXU, 32*it + 31]: the last slot with a column of segment 0 / of segments 0-1
+  constexpr int P1_LAST = (H4 + MAXU - 1) / 32 < NIT - 1 ? (H4 + MAXU - 1) / 32 : NIT - 1;
+  constexpr int P2_LAST = (2 * H4 + MAXU - 1) / 32 < NIT - 1 ? (2 * H4 + MAXU - 1) / 32 : NIT - 1;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int grp = lane >> 5, j = lane & 31;
+  const int want = (blockIdx.x * WPB + wave) * 2 + grp;
+  const bool have = FULL || want < N;            // (a wave past the end works on the last pair and stores nothing)
+  const int row = have ? want : N - 1;
+  const unsigned r0 = (unsigned)row * D4C;       // FULL: the row's first float4, as a 32-bit index
+  const float4* q4 = reinterpret_cast<const float4*>(q) + (FULL ? 0 : (size_t)row * D4C);
+  const float4* a4 = reinterpret_cast<const float4*>(a) + (FULL ? 0 : (size_t)row * D4C);
+  const int u = !SHIFT ? 0
+                : FULL ? (int)(((unsigned)(reinterpret_cast<size_t>(q) >> 4) + r0) & 7)
+                       : (int)((reinterpret_cast<size_t>(q4) >> 4) & 7);
+  const int j0 = j - u;
+  const bool first_ok = !SHIFT || j0 >= 0;
+  const bool last_ok = j0 + 32 * (NIT - 1) < D4C;
+  auto valid_slot = [&](int it) { return (it > 0 || first_ok) && (it < NIT - 1 || last_ok); };
+
+  float4 x[NIT], y[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = valid_slot(it) ? j0 + 32 * it : 0;   // clamp: the load is unconditional
+    if constexpr (FULL) {
+      const unsigned off = (r0 + (unsigned)i) * 16u;
+      const char* qb = reinterpret_cast<const char*>(q4) + off;
+      const char* ab = reinterpret_cast<const char*>(a4) + off;
+      x[it] = load4(reinterpret_cast<const float4*>(qb), 0);
+      y[it] = load4(reinterpret_cast<const float4*>(ab), 0);
+    } else {
+      x[it] = load4(q4, i);
+      y[it] = load4(a4, i);
+    }
+    __builtin_amdgcn_sched_barrier(0);           // in row order, and every request before anything else
+  }
+
+  float4* img = lds4 + (wave * 2 + grp) * ST4;
+  unsigned seg = lds_address(img + spec_seg32(j) * H4);   // this lane's segment of the chain,
+  asm volatile("" : "+v"(seg));                            // addressed before the first wait
+  if (ST4 > D4C && j < ST4 - D4C) img[D4C + j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float p1 = 0.f, p2 = 0.f;
+  float2v start = {0.f, 0.f};
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const bool valid = valid_slot(it);
+    float4 s;
+    s.x = x[it].x - y[it].x; s.y = x[it].y - y[it].y;
+    s.z = x[it].z - y[it].z; s.w = x[it].w - y[it].w;
+    s.x = s.x * s.x; s.y = s.y * s.y; s.z = s.z * s.z; s.w = s.w * s.w;
+    asm volatile("" : "+v"(s.x), "+v"(s.y), "+v"(s.z), "+v"(s.w));   // in registers before the lane mask
+    const int i = j0 + 32 * it;
+    if (valid) img[i] = s;
+    const float s4 = valid ? (s.x + s.y) + (s.z + s.w) : 0.f;
+    // tree-sum contributions to the two window centres, as in the shared body
+    if (32 * it + 31 < H4) p1 += s4;
+    else if (32 * it - MAXU < H4) p1 += (i < H4) ? s4 : 0.f;
+    if (32 * it + 31 < 2 * H4) p2 += s4;
+    else if (32 * it - MAXU < 2 * H4) p2 += (i < 2 * H4) ? s4 : 0.f;
+    if (it < NIT - 1) {                          // a centre that is complete is reduced under the loads in flight
+      if (it == P1_LAST) p1 = half_wave_sum(p1);
+      if (it == P2_LAST) {
+        p2 = half_wave_sum(p2);
+        start = spec_start32(p1, p2, j);
+        asm volatile("" : "+v"(start));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);           // slot `it` is done before slot it + 1 is waited for
+  }
+  wave_lds_sync();
+  __builtin_amdgcn_s_setprio(3);
+  SpecSegment<H4> sg;
+  sg.load_first(seg);                            // in flight while whatever is left of the centres is reduced
+  if (P1_LAST == NIT - 1) p1 = half_wave_sum(p1);
+  if (P2_LAST == NIT - 1) {
+    p2 = half_wave_sum(p2);
+    start = spec_start32(p1, p2, j);
+  }
+  const float2v end = sg.chain_streamed(seg, start);
+  bool hit;
+  float dist = spec_resolve_halves(start, end, j, &hit);
+  if (!hit) {                                    // uniform per half; exact re-walk of this lane's pair
+    dist = chain_sum_lds(img, ST4, 0.0f);
+  }
+  __builtin_amdgcn_s_setprio(0);
+  const float T = 1.0f / (1.0f + sqrtf(dist));   // :106-107
+  if (j == 0 && have) top_out[row] = T;
+}
+
 // ---- width-specialised wave-pair kernel (the headline configuration) ----------
 // Same algorithm as euclid_rows_wave_kernel<.., RW = 2, ..> for D/4 = D4C known at
 // compile time, with the layout made ROW-ALIGNED: lanes 0-31 own pair 2w, lanes
@@ -197,7 +321,10 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
 // and the tree sums p1 / p2 merely centre the windows, so T has the same bits.  The lane must hold the same
 // column of every array it touches, so the host asks for SHIFT only when they are congruent mod 128
 // (same_line_phase below); u is taken from q.
-template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB, bool SHIFT = false>
+//
+// The forward-only launch (FWD && !BWD) runs euclid_pair32_forward above; FULL is its whole-batch form.  The FWD
+// parts of the body below serve the fused launch.
+template <int D4C, bool FWD, bool BWD, bool EXACT, int WPB, bool SHIFT = false, bool FULL = false>
 __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     int N, const float* __restrict__ q, const float* __restrict__ a,
     const float* __restrict__ top_in, const float* __restrict__ top_diff,
@@ -209,6 +336,11 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
   constexpr int MAXU = SHIFT ? 7 : 0;            // largest peel at the start of a row
   static_assert(32 * NIT - MAXU >= D4C, "the shifted slots must still cover the row");
   __shared__ float4 lds4[FWD ? WPB * 2 * ST4 : 1];
+  static_assert(!FULL || (FWD && !BWD), "the whole-batch instantiation exists for the forward-only launch");
+  if constexpr (FWD && !BWD) {
+    euclid_pair32_forward<D4C, WPB, SHIFT, FULL>(N, q, a, top_out, lds4);
+    return;
+  }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int grp = lane >> 5, j = lane & 31;
   // No early exit: a wave past the end works on the last pair and stores nothing, so that no
@@ -327,15 +459,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_pair32_kernel(
     stream_store(da4 + j0 + 32 * it, o1);
   }
   }
-}
-
-// p[i] as ONE 16-byte vector load that stays where it is written.  (A float4 is a struct: copying one out of a
-// __restrict__ const array is a memcpy that the optimiser forwards to the first use of each member, i.e. the load is
-// emitted THERE -- behind whatever was meant to run while it is in flight.)
-template <typename I>
-__device__ __forceinline__ float4 load4(const float4* p, I i) {
-  const mms_v4f v = reinterpret_cast<const mms_v4f*>(p)[i];
-  return make_float4(v.x, v.y, v.z, v.w);
 }
 
 // What a backward-only launch of euclid_block_kernel keeps per slot once T and dT of the slot's pair have landed:
@@ -1144,7 +1267,9 @@ static void launch_pair32(const float* q, const float* a, const float* top_in, c
   // that starts on a line two.  The figures above predate the map; with it the Forward launch + dense Backward
   // launch of bench.py went 7.50 -> 7.22 us per step, and with the dense Backward's coefficients formed ahead of
   // its operands and its whole-batch instantiation (euclid_block_kernel's FULL, selected below) 7.28 -> 7.03
-  // (profiles/bwd_coef_first_*).
+  // (profiles/bwd_coef_first_*); with the forward-only launch's own body (euclid_pair32_forward: loads first in row
+  // order, counted waits per slot, window centres reduced under the loads, the chain started on its first LDS read,
+  // whole-batch instantiation) 7.06 / 7.01 -> 6.94 (profiles/fwd_tail_*).
   // Dev switch for A/B timing: MMS_EUCLID_LAYOUT_{FWD,BWD,FUSED} = pair | block | wave (dense run per wave).
   static const int layout = [] {
     const char* e = std::getenv(FWD && BWD ? "MMS_EUCLID_LAYOUT_FUSED" : FWD ? "MMS_EUCLID_LAYOUT_FWD" : "MMS_EUCLID_LAYOUT_BWD");
@@ -1156,12 +1281,18 @@ static void launch_pair32(const float* q, const float* a, const float* top_in, c
   // clamps and store masks (euclid_block_kernel's FULL; a workgroup owns 2 * WPB pairs whatever its SPAN).
   constexpr bool BONLY = !FWD && BWD;
   const bool full = BONLY && N % (2 * WPB) == 0;
+  // The same promise to the forward-only row-aligned kernel (euclid_pair32_forward's FULL), which also forms its
+  // addresses from 32-bit byte offsets: q and a span less than 4 GiB each.
+  constexpr bool FONLY = FWD && !BWD;
+  const bool full_fwd = FONLY && N % (2 * WPB) == 0 && (unsigned long long)N * D * sizeof(float) <= 0xffffffffull;
   with_glove_d4(D, [&](auto W) {
     constexpr int D4C = decltype(W)::value;
     with_bool(BWD && exact, [&](auto E) {   // a forward has no backward term: its EXACT is false
       constexpr bool EXACT = decltype(E)::value;
-      hipLaunchKernelGGL((layout == 0   ? (shift ? euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB, true>
-                                                 : euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB>)
+      hipLaunchKernelGGL((layout == 0   ? (full_fwd ? (shift ? euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB, true, FONLY>
+                                                             : euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB, false, FONLY>)
+                                                    : (shift ? euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB, true>
+                                                             : euclid_pair32_kernel<D4C, FWD, BWD, EXACT, WPB>))
                           : layout == 1 ? (full ? euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB, WPB, BONLY>
                                                 : euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB>)
                                         : (full ? euclid_block_kernel<D4C, FWD, BWD, EXACT, WPB, 1, BONLY>
