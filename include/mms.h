@@ -782,6 +782,63 @@ int mms_fm_forward_backward_f32(int N, int C, int dim, const float* x, const flo
                                 float* top, float* bottom_diff, float* bias_diff, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * BN: the fork's batch normalisation (include/caffe/layers/batch_norm_v0_layer.hpp,
+ * src/caffe/layers/bn_layer.cpp / .cu, bn_param { scale_filler shift_filler
+ * bn_memory = 0.9 }, caffe.proto:484-488).  x and top are contiguous (N, C, S)
+ * with S = H*W: element (n, c, s) at (n*C + c)*S + s.  Per channel c, over its
+ * N*S elements:
+ *   TRAIN (phase 0)  mean = (1/N)(1/S) sum x;  var = (1/N)(1/S) sum x*x - mean*mean
+ *                    running_mean = (1 - bn_memory)*mean + bn_memory*running_mean
+ *                    running_var  = (1 - bn_memory)*var  + bn_memory*running_var
+ *   TEST  (phase 1)  mean = running_mean, var = running_var (both only read)
+ *   std = sqrt(var + 1e-9);  xn = (x + (-mean)) / std;  top = xn*scale + shift
+ *   backward: shift_diff = sum dy;  scale_diff = sum xn*dy;  g = dy*scale;
+ *             bottom_diff = (g - (xn * sum xn*g + sum g) / (N*S)) / std
+ * scale, shift, running_mean, running_var are the layer's blobs_[0..3], C
+ * elements each; save_mean / save_std (C each) are its batch_mean_ /
+ * batch_variance_ after Forward (the latter holds the standard deviation), which
+ * Backward reads -- whichever phase the last forward ran in.  xn is not stored:
+ * backward recomputes it from x with the forward's two operations.  var is not
+ * clamped (as in the reference, a channel whose var rounds below -1e-9 is NaN).
+ * The reference's sums are BLAS gemv's (1e-5 class); the order
+ * here is fixed: no atomics, the same words on every run, on either side of the
+ * routing threshold and whether or not the arrays allow 16-byte accesses.
+ *
+ * Any S >= 1, C >= 1, N >= 0 and any element-aligned arrays.  Host-side, before
+ * anything is enqueued: MMS_ERR_INVALID_ARG for N < 0, C <= 0, S <= 0,
+ * N*C*S > INT_MAX, a phase other than 0 / 1 or, with N > 0, a NULL required array
+ * or top == x (the reference's CHECK_NE: no in-place); N == 0 launches nothing;
+ * MMS_ERR_WORKSPACE when the workspace is NULL or smaller than the query and the
+ * call needs it (TRAIN forward and backward; TEST forward never does).
+ *
+ * workspace: mms_bn_workspace_bytes(N, C, S), 0 where one workgroup per channel
+ * serves (one launch per pass).  Otherwise a channel's 16-byte groups are cut
+ * into K = bytes / (C * 4 * sizeof(element)) chunks; launch 1 leaves the sums of
+ * chunk k of channel c in words (c*K + k)*4 + {0..3} of the workspace (forward:
+ * sum x, sum x*x; backward: sum dy, sum xn*dy, sum g, sum xn*g) and launch 2 adds
+ * them in ascending k, starting from chunk 0's.
+ * ------------------------------------------------------------------------- */
+size_t mms_bn_workspace_bytes(int N, int C, int S);
+
+/* Replaces BNLayer<float>::Forward_cpu / Forward_gpu
+ *   src/caffe/layers/bn_layer.cpp:122-257, bn_layer.cu.
+ * All arrays are required; top must not be x.  TRAIN updates running_mean and
+ * running_var in place; TEST reads them. */
+int mms_bn_forward_f32(int phase, int N, int C, int S, float bn_memory, const float* x, const float* scale,
+                       const float* shift, float* running_mean, float* running_var, float* top, float* save_mean,
+                       float* save_std, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Replaces BNLayer<float>::Backward_cpu / Backward_gpu
+ *   src/caffe/layers/bn_layer.cpp:262-383, bn_layer.cu.
+ * bottom_diff (N*C*S), scale_diff (C) and shift_diff (C) may each be NULL, which
+ * skips that output; at least one must be given.  Each one given is OVERWRITTEN
+ * -- the reference's gemv's run with beta = 0, so the two parameter diffs are not
+ * accumulated into.  bottom_diff must not alias x or top_diff. */
+int mms_bn_backward_f32(int N, int C, int S, const float* x, const float* top_diff, const float* scale,
+                        const float* save_mean, const float* save_std, float* bottom_diff, float* scale_diff,
+                        float* shift_diff, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Batch feed: dst[i,:] = src[perm[first+i],:], i < rows,
  * for a dataset (src_rows, row_elems) resident in HBM; perm (src_rows ints on
  * the device) or NULL for the identity; first + rows <= src_rows.
@@ -829,6 +886,15 @@ int mms_pairrank_backward_f64(int count, double top_diff, const double* y, const
 int mms_fm_forward_f64(int N, int C, int dim, const double* x, const double* bias, double* top, void* stream);
 int mms_fm_backward_f64(int N, int C, int dim, const double* x, const double* top_diff, double* bottom_diff,
                         double* bias_diff, void* stream);
+/* BNLayer<double>: the arguments, errors, routes and fixed order of mms_bn_forward_f32 / mms_bn_backward_f32 with
+ * every float a double (16-byte groups are 2 elements; var_eps_ is the double 1e-9); ~1e-12 vs the reference. */
+size_t mms_bn_workspace_bytes_f64(int N, int C, int S);
+int mms_bn_forward_f64(int phase, int N, int C, int S, double bn_memory, const double* x, const double* scale,
+                       const double* shift, double* running_mean, double* running_var, double* top,
+                       double* save_mean, double* save_std, void* workspace, size_t workspace_bytes, void* stream);
+int mms_bn_backward_f64(int N, int C, int S, const double* x, const double* top_diff, const double* scale,
+                        const double* save_mean, const double* save_std, double* bottom_diff, double* scale_diff,
+                        double* shift_diff, void* workspace, size_t workspace_bytes, void* stream);
 
 /* EmbedLayer<double> (embed_layer.cpp:135-180): the arguments, errors and M == 0 behaviour of mms_embed_forward_f32 /
  * mms_embed_backward_f32 with every float* a double* (word ids are doubles: Caffe feeds them as Dtype).  top and

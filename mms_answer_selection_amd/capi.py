@@ -84,6 +84,12 @@ _SIGNATURES = {
     "mms_fm_forward_backward_f32": (_i, [_i] * 3 + [_vp] * 7),
     "mms_fm_forward_f64": (_i, [_i] * 3 + [_vp] * 4),
     "mms_fm_backward_f64": (_i, [_i] * 3 + [_vp] * 5),
+    "mms_bn_workspace_bytes": (_sz, [_i] * 3),
+    "mms_bn_forward_f32": (_i, [_i] * 4 + [_f] + [_vp] * 9 + [_sz, _vp]),
+    "mms_bn_backward_f32": (_i, [_i] * 3 + [_vp] * 9 + [_sz, _vp]),
+    "mms_bn_workspace_bytes_f64": (_sz, [_i] * 3),
+    "mms_bn_forward_f64": (_i, [_i] * 4 + [C.c_double] + [_vp] * 9 + [_sz, _vp]),
+    "mms_bn_backward_f64": (_i, [_i] * 3 + [_vp] * 9 + [_sz, _vp]),
     "mms_set_euclid_backward_mode": (_i, [_i]),
     "mms_get_euclid_backward_mode": (_i, []),
     "mms_null_launch": (_i, [_i, _vp]),
@@ -381,6 +387,62 @@ def fm_forward_backward(x, top_diff, top, bottom_diff, bias=None, bias_diff=None
         N, C, dim, _ptr(x, "x"), _ptr(bias, "bias", True), _ptr(top_diff, "top_diff"), _ptr(top, "top"),
         _ptr(bottom_diff, "bottom_diff"), _ptr(bias_diff, "bias_diff", True), _stream()),
         "mms_fm_forward_backward_f32")
+
+
+def _bn_shape(x):
+    """(N, C, S) of a blob (N, C, S) or (N, C, H, W): S is everything after the channel axis."""
+    if x.dim() < 2:
+        raise MMSArgumentError("BN: x must be (N, C, ...), got %s" % (tuple(x.shape),))
+    S = 1
+    for d in x.shape[2:]:
+        S *= int(d)
+    return int(x.shape[0]), int(x.shape[1]), S
+
+
+def bn_workspace_bytes(N, C, S):
+    """0 where one workgroup per channel serves (include/mms.h: mms_bn_workspace_bytes)."""
+    return lib().mms_bn_workspace_bytes(N, C, S)
+
+
+def bn_workspace_bytes_f64(N, C, S):
+    return lib().mms_bn_workspace_bytes_f64(N, C, S)
+
+
+def _bn_forward(suffix, dt, query, x, scale, shift, running_mean, running_var, top, save_mean, save_std, phase,
+                bn_memory, ws):
+    N, C, S = _bn_shape(x)
+    wsp, wsb = (ws or _default_ws).get(query(N, C, S), x.device)
+    name = "mms_bn_forward_" + suffix
+    check(getattr(lib(), name)(
+        int(phase), N, C, S, float(bn_memory), _ptr(x, "x", dtype=dt), _ptr(scale, "scale", dtype=dt),
+        _ptr(shift, "shift", dtype=dt), _ptr(running_mean, "running_mean", dtype=dt),
+        _ptr(running_var, "running_var", dtype=dt), _ptr(top, "top", dtype=dt), _ptr(save_mean, "save_mean", dtype=dt),
+        _ptr(save_std, "save_std", dtype=dt), wsp, wsb, _stream()), name)
+
+
+def _bn_backward(suffix, dt, query, x, top_diff, scale, save_mean, save_std, bottom_diff, scale_diff, shift_diff, ws):
+    N, C, S = _bn_shape(x)
+    wsp, wsb = (ws or _default_ws).get(query(N, C, S), x.device)
+    name = "mms_bn_backward_" + suffix
+    check(getattr(lib(), name)(
+        N, C, S, _ptr(x, "x", dtype=dt), _ptr(top_diff, "top_diff", dtype=dt), _ptr(scale, "scale", dtype=dt),
+        _ptr(save_mean, "save_mean", dtype=dt), _ptr(save_std, "save_std", dtype=dt),
+        _ptr(bottom_diff, "bottom_diff", True, dt), _ptr(scale_diff, "scale_diff", True, dt),
+        _ptr(shift_diff, "shift_diff", True, dt), wsp, wsb, _stream()), name)
+
+
+def bn_forward(x, scale, shift, running_mean, running_var, top, save_mean, save_std, phase=0, bn_memory=0.9, ws=None):
+    """BN forward (include/mms.h: mms_bn_forward_f32).  x, top (N, C, S) or (N, C, H, W); the other six C floats.
+    phase 0 = TRAIN (batch statistics; the running blobs are updated in place), 1 = TEST (running statistics, read
+    only).  save_mean / save_std are what bn_backward needs."""
+    _bn_forward("f32", torch.float32, bn_workspace_bytes, x, scale, shift, running_mean, running_var, top, save_mean,
+                save_std, phase, bn_memory, ws)
+
+
+def bn_backward(x, top_diff, scale, save_mean, save_std, bottom_diff=None, scale_diff=None, shift_diff=None, ws=None):
+    """Each of bottom_diff, scale_diff, shift_diff may be None (skipped); those given are overwritten."""
+    _bn_backward("f32", torch.float32, bn_workspace_bytes, x, top_diff, scale, save_mean, save_std, bottom_diff,
+                 scale_diff, shift_diff, ws)
 
 
 class TripletWorkspace:
@@ -996,6 +1058,18 @@ def fm_backward_f64(x, top_diff, bottom_diff=None, bias_diff=None):
         N, C, dim, _ptr(x, "x", dtype=_D), _ptr(top_diff, "top_diff", dtype=_D),
         _ptr(bottom_diff, "bottom_diff", True, _D), _ptr(bias_diff, "bias_diff", True, _D), _stream()),
         "mms_fm_backward_f64")
+
+
+def bn_forward_f64(x, scale, shift, running_mean, running_var, top, save_mean, save_std, phase=0, bn_memory=0.9,
+                   ws=None):
+    _bn_forward("f64", _D, bn_workspace_bytes_f64, x, scale, shift, running_mean, running_var, top, save_mean,
+                save_std, phase, bn_memory, ws)
+
+
+def bn_backward_f64(x, top_diff, scale, save_mean, save_std, bottom_diff=None, scale_diff=None, shift_diff=None,
+                    ws=None):
+    _bn_backward("f64", _D, bn_workspace_bytes_f64, x, top_diff, scale, save_mean, save_std, bottom_diff, scale_diff,
+                 shift_diff, ws)
 
 
 def embed_forward_f64(index, weight, top, bias=None):
