@@ -839,6 +839,53 @@ int mms_bn_backward_f32(int N, int C, int S, const float* x, const float* top_di
                         float* shift_diff, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * BN -> AvePool -> TanH in one call: what network_v4 does with both of its BN
+ * outputs (do_trec_qa_clean.py:472-477).  Replaces, in sequence,
+ *   BNLayer (bn_layer.cpp), PoolingLayer AVE (pooling_layer.cpp:197-212,
+ *   :291-317) and the in-place TanHLayer (tanh_layer.cpp:13-33)
+ * for poolings whose windows TILE the map: kernel (kh, kw) with H % kh == 0 and
+ * W % kw == 0, stride == kernel, no padding -- or ONE window that is the whole
+ * map, whatever stride it declares.  Every window then has pool_size = kh*kw.
+ * Any other pooling is MMS_ERR_INVALID_ARG here: call mms_bn_forward and pool in
+ * the host.  x and bottom_diff are (N, C, H, W); top, top_diff and save_pool
+ * are (N, C, H/kh, W/kw); every other array has C elements.
+ *   mean, var, std = sqrt(var + 1e-9), running blobs: as mms_bn_forward
+ *   m = window_mean(x): the window's elements added in (h, w) order, / (kh*kw)
+ *   save_pool = (m + (-mean)) / std        (the pooled normalised map)
+ *   top = tanh(save_pool*scale + shift)    (the TanH's blob: it runs in place)
+ *   backward: gp = top_diff*(1 - top*top);  shift_diff = sum gp;
+ *             scale_diff = sum gp*save_pool;  a = scale*scale_diff;
+ *             b = scale*shift_diff;  xn = (x + (-mean)) / std;
+ *             bottom_diff = (gp/(kh*kw)*scale + (-1/(N*H*W))*(xn*a + b)) / std
+ * The BN output itself is never formed: a host that needs it calls
+ * mms_bn_forward.  x is read once per pass and bottom_diff written once; the
+ * rest of the traffic is pooled-size.  Sums have a fixed order (no atomics;
+ * DESIGN.md 4.12a): the same words on every run, on either route, whatever the
+ * arrays' alignment and whatever the workspace held.
+ *
+ * Host-side, before anything is enqueued: MMS_ERR_INVALID_ARG for N < 0, C, H, W,
+ * kh or kw below 1, windows that do not tile the map, N*C*H*W > INT_MAX, a
+ * phase other than 0 / 1 or, with N > 0, a NULL required array, top or save_pool
+ * equal to an input or to each other, bottom_diff equal to an input; N == 0
+ * launches nothing; then MMS_ERR_WORKSPACE when the workspace is NULL or
+ * smaller than the query and the call needs it (TRAIN forward and backward).
+ *
+ * workspace: 0 where one workgroup per channel serves (at most 64 KB of x per
+ * channel: one launch per pass); otherwise two launches per pass (TEST forward:
+ * always one).  Backward: bottom_diff, scale_diff, shift_diff may each be NULL
+ * (skipped), at least one is required; those given are overwritten.
+ * ------------------------------------------------------------------------- */
+size_t mms_bn_pool_tanh_workspace_bytes(int N, int C, int H, int W, int kh, int kw);
+int mms_bn_pool_tanh_forward_f32(int phase, int N, int C, int H, int W, int kh, int kw, float bn_memory,
+                                 const float* x, const float* scale, const float* shift, float* running_mean,
+                                 float* running_var, float* top, float* save_pool, float* save_mean, float* save_std,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int mms_bn_pool_tanh_backward_f32(int N, int C, int H, int W, int kh, int kw, const float* x, const float* top,
+                                  const float* top_diff, const float* save_pool, const float* scale,
+                                  const float* save_mean, const float* save_std, float* bottom_diff, float* scale_diff,
+                                  float* shift_diff, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Batch feed: dst[i,:] = src[perm[first+i],:], i < rows,
  * for a dataset (src_rows, row_elems) resident in HBM; perm (src_rows ints on
  * the device) or NULL for the identity; first + rows <= src_rows.
@@ -895,6 +942,18 @@ int mms_bn_forward_f64(int phase, int N, int C, int S, double bn_memory, const d
 int mms_bn_backward_f64(int N, int C, int S, const double* x, const double* top_diff, const double* scale,
                         const double* save_mean, const double* save_std, double* bottom_diff, double* scale_diff,
                         double* shift_diff, void* workspace, size_t workspace_bytes, void* stream);
+/* mms_bn_pool_tanh_* with every float a double: the same arguments, errors, routes and fixed order (a 16-byte access
+ * is 2 elements); ~1e-12 vs the three reference layers in sequence. */
+size_t mms_bn_pool_tanh_workspace_bytes_f64(int N, int C, int H, int W, int kh, int kw);
+int mms_bn_pool_tanh_forward_f64(int phase, int N, int C, int H, int W, int kh, int kw, double bn_memory,
+                                 const double* x, const double* scale, const double* shift, double* running_mean,
+                                 double* running_var, double* top, double* save_pool, double* save_mean,
+                                 double* save_std, void* workspace, size_t workspace_bytes, void* stream);
+int mms_bn_pool_tanh_backward_f64(int N, int C, int H, int W, int kh, int kw, const double* x, const double* top,
+                                  const double* top_diff, const double* save_pool, const double* scale,
+                                  const double* save_mean, const double* save_std, double* bottom_diff,
+                                  double* scale_diff, double* shift_diff, void* workspace, size_t workspace_bytes,
+                                  void* stream);
 
 /* EmbedLayer<double> (embed_layer.cpp:135-180): the arguments, errors and M == 0 behaviour of mms_embed_forward_f32 /
  * mms_embed_backward_f32 with every float* a double* (word ids are doubles: Caffe feeds them as Dtype).  top and

@@ -90,6 +90,12 @@ _SIGNATURES = {
     "mms_bn_workspace_bytes_f64": (_sz, [_i] * 3),
     "mms_bn_forward_f64": (_i, [_i] * 4 + [C.c_double] + [_vp] * 9 + [_sz, _vp]),
     "mms_bn_backward_f64": (_i, [_i] * 3 + [_vp] * 9 + [_sz, _vp]),
+    "mms_bn_pool_tanh_workspace_bytes": (_sz, [_i] * 6),
+    "mms_bn_pool_tanh_forward_f32": (_i, [_i] * 7 + [_f] + [_vp] * 10 + [_sz, _vp]),
+    "mms_bn_pool_tanh_backward_f32": (_i, [_i] * 6 + [_vp] * 11 + [_sz, _vp]),
+    "mms_bn_pool_tanh_workspace_bytes_f64": (_sz, [_i] * 6),
+    "mms_bn_pool_tanh_forward_f64": (_i, [_i] * 7 + [C.c_double] + [_vp] * 10 + [_sz, _vp]),
+    "mms_bn_pool_tanh_backward_f64": (_i, [_i] * 6 + [_vp] * 11 + [_sz, _vp]),
     "mms_set_euclid_backward_mode": (_i, [_i]),
     "mms_get_euclid_backward_mode": (_i, []),
     "mms_null_launch": (_i, [_i, _vp]),
@@ -443,6 +449,64 @@ def bn_backward(x, top_diff, scale, save_mean, save_std, bottom_diff=None, scale
     """Each of bottom_diff, scale_diff, shift_diff may be None (skipped); those given are overwritten."""
     _bn_backward("f32", torch.float32, bn_workspace_bytes, x, top_diff, scale, save_mean, save_std, bottom_diff,
                  scale_diff, shift_diff, ws)
+
+
+def _bn_pool_shape(x, kernel):
+    """(N, C, H, W, kh, kw) of a 4-D blob and a pooling kernel (k or (kh, kw))."""
+    if x.dim() != 4:
+        raise MMSArgumentError("BN + pooling: x must be (N, C, H, W), got %s" % (tuple(x.shape),))
+    kh, kw = (kernel, kernel) if isinstance(kernel, int) else kernel
+    return tuple(int(d) for d in x.shape) + (int(kh), int(kw))
+
+
+def bn_pool_tanh_workspace_bytes(N, C, H, W, kh, kw):
+    """0 where one workgroup per channel serves (include/mms.h: mms_bn_pool_tanh_workspace_bytes)."""
+    return lib().mms_bn_pool_tanh_workspace_bytes(N, C, H, W, kh, kw)
+
+
+def bn_pool_tanh_workspace_bytes_f64(N, C, H, W, kh, kw):
+    return lib().mms_bn_pool_tanh_workspace_bytes_f64(N, C, H, W, kh, kw)
+
+
+def _bn_pool_tanh_forward(suffix, dt, query, x, kernel, scale, shift, running_mean, running_var, top, save_pool,
+                          save_mean, save_std, phase, bn_memory, ws):
+    dims = _bn_pool_shape(x, kernel)
+    wsp, wsb = (ws or _default_ws).get(query(*dims), x.device)
+    name = "mms_bn_pool_tanh_forward_" + suffix
+    check(getattr(lib(), name)(
+        int(phase), *dims, float(bn_memory), _ptr(x, "x", dtype=dt), _ptr(scale, "scale", dtype=dt),
+        _ptr(shift, "shift", dtype=dt), _ptr(running_mean, "running_mean", dtype=dt),
+        _ptr(running_var, "running_var", dtype=dt), _ptr(top, "top", dtype=dt), _ptr(save_pool, "save_pool", dtype=dt),
+        _ptr(save_mean, "save_mean", dtype=dt), _ptr(save_std, "save_std", dtype=dt), wsp, wsb, _stream()), name)
+
+
+def _bn_pool_tanh_backward(suffix, dt, query, x, kernel, top, top_diff, save_pool, scale, save_mean, save_std,
+                           bottom_diff, scale_diff, shift_diff, ws):
+    dims = _bn_pool_shape(x, kernel)
+    wsp, wsb = (ws or _default_ws).get(query(*dims), x.device)
+    name = "mms_bn_pool_tanh_backward_" + suffix
+    check(getattr(lib(), name)(
+        *dims, _ptr(x, "x", dtype=dt), _ptr(top, "top", dtype=dt), _ptr(top_diff, "top_diff", dtype=dt),
+        _ptr(save_pool, "save_pool", dtype=dt), _ptr(scale, "scale", dtype=dt), _ptr(save_mean, "save_mean", dtype=dt),
+        _ptr(save_std, "save_std", dtype=dt), _ptr(bottom_diff, "bottom_diff", True, dt),
+        _ptr(scale_diff, "scale_diff", True, dt), _ptr(shift_diff, "shift_diff", True, dt), wsp, wsb, _stream()), name)
+
+
+def bn_pool_tanh_forward(x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
+                         phase=0, bn_memory=0.9, ws=None):
+    """BN -> AvePool(kernel = stride, windows tile the map) -> TanH (include/mms.h: mms_bn_pool_tanh_forward_f32).
+    x (N, C, H, W); kernel k or (kh, kw); top, save_pool (N, C, H/kh, W/kw); the other six C floats.  phase as in
+    bn_forward.  save_pool, save_mean, save_std and top are what bn_pool_tanh_backward needs."""
+    _bn_pool_tanh_forward("f32", torch.float32, bn_pool_tanh_workspace_bytes, x, kernel, scale, shift, running_mean,
+                          running_var, top, save_pool, save_mean, save_std, phase, bn_memory, ws)
+
+
+def bn_pool_tanh_backward(x, kernel, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff=None,
+                          scale_diff=None, shift_diff=None, ws=None):
+    """Each of bottom_diff (N, C, H, W), scale_diff, shift_diff (C) may be None (skipped); those given are
+    overwritten."""
+    _bn_pool_tanh_backward("f32", torch.float32, bn_pool_tanh_workspace_bytes, x, kernel, top, top_diff, save_pool,
+                           scale, save_mean, save_std, bottom_diff, scale_diff, shift_diff, ws)
 
 
 class TripletWorkspace:
@@ -1070,6 +1134,18 @@ def bn_backward_f64(x, top_diff, scale, save_mean, save_std, bottom_diff=None, s
                     ws=None):
     _bn_backward("f64", _D, bn_workspace_bytes_f64, x, top_diff, scale, save_mean, save_std, bottom_diff, scale_diff,
                  shift_diff, ws)
+
+
+def bn_pool_tanh_forward_f64(x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
+                             phase=0, bn_memory=0.9, ws=None):
+    _bn_pool_tanh_forward("f64", _D, bn_pool_tanh_workspace_bytes_f64, x, kernel, scale, shift, running_mean,
+                          running_var, top, save_pool, save_mean, save_std, phase, bn_memory, ws)
+
+
+def bn_pool_tanh_backward_f64(x, kernel, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff=None,
+                              scale_diff=None, shift_diff=None, ws=None):
+    _bn_pool_tanh_backward("f64", _D, bn_pool_tanh_workspace_bytes_f64, x, kernel, top, top_diff, save_pool, scale,
+                           save_mean, save_std, bottom_diff, scale_diff, shift_diff, ws)
 
 
 def embed_forward_f64(index, weight, top, bias=None):

@@ -31,21 +31,11 @@
 // TEST-phase forward is launch 2 alone on either route.
 #include <limits.h>
 
+#include "bn_common.h"        // the routes' sizes, bn_block_sum, bn_fold: shared with csrc/bn_pool.hip
 #include "mms_internal.h"
 
 namespace mms {
 namespace {
-
-constexpr int kBnThreads = 256;             // a (channel, chunk) workgroup of the large route
-constexpr int kBnSmallThreads = 1024;       // the one workgroup of a channel on the small route
-constexpr int kBnBatch = 4;                 // groups a thread has in flight before it uses the first
-// The routing threshold, in 16-byte groups per channel (16384 floats, 8192 doubles: 64 KB).  Up to here the one
-// workgroup of 1024 threads covers its channel with ONE batch of kBnBatch loads per thread and pass, i.e. in about one
-// memory round trip, which is what the second launch of the large route would cost on its own.
-constexpr unsigned kBnSmallGroups = kBnSmallThreads * kBnBatch;
-constexpr unsigned kBnChunkGroups = 2048;   // smallest chunk: 32 KB, two batches per thread of 256
-constexpr int kBnMaxChunks = 64;            // longest fold every workgroup of launch 2 repeats in its prologue
-constexpr int kBnSlots = 4;                 // workspace words per (channel, chunk): forward uses 2, backward 4
 
 struct BnRoute {
   bool small;
@@ -79,9 +69,6 @@ size_t bn_workspace_bytes(int N, int C, int S) {
   return r.small ? 0 : (size_t)C * r.chunks * kBnSlots * sizeof(T);
 }
 
-template <typename T>
-using bn_vec = T __attribute__((ext_vector_type(16 / sizeof(T))));
-
 struct BnGeom {
   unsigned S;        // elements per run
   unsigned total;    // N * S, the elements of one channel
@@ -91,36 +78,6 @@ struct BnGeom {
 struct BnPos {       // a group's first element: index in the channel, run, offset in the run
   unsigned i, n, s;
 };
-
-__device__ __forceinline__ float bn_sqrt(float v) { return sqrtf(v); }
-__device__ __forceinline__ double bn_sqrt(double v) { return sqrt(v); }
-
-__device__ __forceinline__ float bn_wave_sum(float v) { return wave_sum(v); }
-__device__ __forceinline__ double bn_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-// NQ sums across a workgroup at once; every thread ends with the totals.  red: NQ * THREADS / 64 words of LDS.
-template <int THREADS, int NQ, typename T>
-__device__ __forceinline__ void bn_block_sum(T (&v)[NQ], T* red) {
-  constexpr int W = THREADS / kWave;
-  const int wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) v[q] = bn_wave_sum(v[q]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) red[q * W + wid] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    T t = red[q * W];
-    for (int w = 1; w < W; ++w) t += red[q * W + w];
-    v[q] = t;
-  }
-}
 
 // The group at p of each of NIN arrays (pointers to the channel's first run).  Elements past the channel's end read 0.
 template <typename T, bool VEC, int NIN>
@@ -258,18 +215,6 @@ __device__ __forceinline__ void bn_backward_sums(const T* __restrict__ x, const 
 __device__ __forceinline__ void bn_chunk(unsigned groups, unsigned gpc, unsigned k, unsigned* g0, unsigned* g1) {
   *g0 = k * gpc;                                  // k < chunks: k * gpc < groups
   *g1 = groups - *g0 < gpc ? groups : *g0 + gpc;
-}
-
-// The channel's NQ sums from its chunks' workspace slots, ascending: ((chunk 0 + chunk 1) + chunk 2) + ...
-template <int NQ, typename T>
-__device__ __forceinline__ void bn_fold(const T* __restrict__ ws, int c, int chunks, T (&tot)[NQ]) {
-  const T* p = ws + (size_t)c * chunks * kBnSlots;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) tot[q] = p[q];
-  for (int j = 1; j < chunks; ++j) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) tot[q] += p[j * kBnSlots + q];
-  }
 }
 
 // Large route, launch 1.  BWD false: slots 0, 1 = sum x, sum x*x.  BWD true: slots 0..3 = the four backward sums.

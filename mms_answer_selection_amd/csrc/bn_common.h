@@ -1,0 +1,67 @@
+// csrc/bn_common.h -- what csrc/bn.hip (BN) and csrc/bn_pool.hip (BN -> AvePool -> TanH) share: the sizes of the two
+// routes, the workgroup sum with its fixed order, and the ascending fold of a channel's chunk sums.
+#ifndef MMS_BN_COMMON_H_
+#define MMS_BN_COMMON_H_
+
+#include "mms_common.h"
+
+namespace mms {
+
+constexpr int kBnThreads = 256;             // a (channel, chunk) workgroup of the large route
+constexpr int kBnSmallThreads = 1024;       // the one workgroup of a channel on the small route
+constexpr int kBnBatch = 4;                 // groups a thread has in flight before it uses the first
+// The routing threshold, in 16-byte groups per channel (16384 floats, 8192 doubles: 64 KB).  Up to here the one
+// workgroup of 1024 threads covers its channel with ONE batch of kBnBatch loads per thread and pass, i.e. in about one
+// memory round trip, which is what the second launch of the large route would cost on its own.
+constexpr unsigned kBnSmallGroups = kBnSmallThreads * kBnBatch;
+constexpr unsigned kBnChunkGroups = 2048;   // smallest chunk: 32 KB, two batches per thread of 256
+constexpr int kBnMaxChunks = 64;            // longest fold every workgroup of launch 2 repeats in its prologue
+constexpr int kBnSlots = 4;                 // workspace words per (channel, chunk): forward uses 2, backward 4
+
+template <typename T>
+using bn_vec = T __attribute__((ext_vector_type(16 / sizeof(T))));
+
+__device__ __forceinline__ float bn_sqrt(float v) { return sqrtf(v); }
+__device__ __forceinline__ double bn_sqrt(double v) { return sqrt(v); }
+
+__device__ __forceinline__ float bn_wave_sum(float v) { return wave_sum(v); }
+__device__ __forceinline__ double bn_wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// NQ sums across a workgroup at once; every thread ends with the totals.  red: NQ * THREADS / 64 words of LDS.
+template <int THREADS, int NQ, typename T>
+__device__ __forceinline__ void bn_block_sum(T (&v)[NQ], T* red) {
+  constexpr int W = THREADS / kWave;
+  const int wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) v[q] = bn_wave_sum(v[q]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) red[q * W + wid] = v[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    T t = red[q * W];
+    for (int w = 1; w < W; ++w) t += red[q * W + w];
+    v[q] = t;
+  }
+}
+
+// The channel's NQ sums from its chunks' workspace slots, ascending: ((chunk 0 + chunk 1) + chunk 2) + ...
+template <int NQ, typename T>
+__device__ __forceinline__ void bn_fold(const T* __restrict__ ws, int c, int chunks, T (&tot)[NQ]) {
+  const T* p = ws + (size_t)c * chunks * kBnSlots;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) tot[q] = p[q];
+  for (int j = 1; j < chunks; ++j) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) tot[q] += p[j * kBnSlots + q];
+  }
+}
+
+}  // namespace mms
+#endif  // MMS_BN_COMMON_H_
