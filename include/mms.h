@@ -889,6 +889,7 @@ int mms_bn_pool_tanh_backward_f32(int N, int C, int H, int W, int kh, int kw, co
  * Batch feed: dst[i,:] = src[perm[first+i],:], i < rows,
  * for a dataset (src_rows, row_elems) resident in HBM; perm (src_rows ints on
  * the device) or NULL for the identity; first + rows <= src_rows.
+ * A perm entry outside [0, src_rows) reads the nearest valid row (0 or src_rows - 1).
  * Replaces the per-row caffe_copy loop of HDF5DataLayer<float>::Forward_cpu/_gpu
  *   src/caffe/layers/hdf5_data_layer.cpp:124-151, hdf5_data_layer.cu:19-51.
  * ------------------------------------------------------------------------- */
