@@ -544,7 +544,8 @@ int mms_triplet_cosine_step_f32(int N, int D, float margin, float loss_weight,
  * then dq = B W^T and dW += Q^T B.  Neither Q W nor the (N, 1) score gradients reach HBM.  Scores, loss terms and
  * hinge decisions follow the reference's operation order given the scores; everything that passes through a product
  * agrees with the layer-by-layer result to 1e-5 (the reference's own products go through CBLAS).
- * Shapes the panel kernel does not serve (K2 > 304, sizes not multiples of 4, small N) run the layers one by one
+ * Shapes the panel kernel does not serve (K1 or K2 > 304, K1 or K2 not a multiple of 4, fewer than 6081 triplets --
+ * 96 panels of 64 rows -- or N not a multiple of 4) run the layers one by one
  * inside the call: same results, no fusion.  `loss` may be NULL.  dW is accumulated into (zero it like
  * Net::ClearParamDiffs does).  workspace: mms_triplet_simmatrix_workspace_bytes(N, K1, K2), no initialisation needed.
  * ------------------------------------------------------------------------- */

@@ -219,3 +219,39 @@ def reference(A, B):
     """(C64, D): the fp64 product and the fp64 product of absolute values."""
     A64, B64 = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
     return A64 @ B64, np.abs(A64) @ np.abs(B64)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the probe check (tests/test_gpu_matrix_pipe_accuracy.py, tests/test_gpu_triplet_simmatrix_fused.py)
+# ----------------------------------------------------------------------------------------------------------------------
+def check_probe(what, got, A, B, rowscale=None, extra=None, single=None, a_half=False, half_out=False):
+    """got ~ rowscale * (A . B) + extra at the probe bar.  single = (x, y): the two factors of each output element (arrays that
+    broadcast to got's shape), used to NAME the plane product a failure has lost."""
+    C64, D = reference(A, B)
+    rs = None if rowscale is None else np.asarray(rowscale, dtype=np.float64).reshape(-1, 1)
+    if rs is not None:
+        C64, D = C64 * rs, D * np.abs(rs)
+    if extra is not None:
+        C64 = C64 + np.asarray(extra, dtype=np.float64)
+    allow = half_ulp_of_half(C64) if half_out else None
+    e, idx = componentwise_error(got, C64, D, what, allow)
+    print("%s: e = %.3g (bar %.3g), worst at %s" % (what, e, BAR, idx))
+    if e > BAR:
+        hint = ""
+        if single is not None and not half_out:
+            g = np.asarray(got, dtype=np.float64)
+            if extra is not None:
+                g = g - np.asarray(extra, dtype=np.float64)
+            if rs is not None:
+                g = g / rs
+            x, y = np.broadcast_arrays(*single)
+            bad = (np.abs(np.asarray(got, dtype=np.float64) - C64) > BAR * D)
+            hint = "; %d of %d elements over the bar, first at %s; %s" % (
+                int(bad.sum()), bad.size, tuple(int(v) for v in np.argwhere(bad)[0]), name_lost_term(x[bad], y[bad], g[bad], a_half))
+        raise AssertionError("%s: componentwise error %.3g > %.3g at %s%s" % (what, e, BAR, idx, hint))
+    return e
+
+
+def diag_of(A, K, offset=0):
+    i = np.arange(A.shape[0])
+    return A[i, (i + offset) % K]

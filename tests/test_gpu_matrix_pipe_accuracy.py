@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import matrix_pipe_model as mp
+from matrix_pipe_model import check_probe, diag_of
 from util import assert_bitexact, rng
 
 pytestmark = pytest.mark.gpu
@@ -53,39 +54,6 @@ def matrix_mode(request, hiplib):
     capi.set_matrix_mode(request.param)
     yield request.param
     capi.set_matrix_mode("bf16x3")
-
-
-def check_probe(what, got, A, B, rowscale=None, extra=None, single=None, a_half=False, half_out=False):
-    """got ~ rowscale * (A . B) + extra at the probe bar.  single = (x, y): the two factors of each output element (arrays that
-    broadcast to got's shape), used to NAME the plane product a failure has lost."""
-    C64, D = mp.reference(A, B)
-    rs = None if rowscale is None else np.asarray(rowscale, dtype=np.float64).reshape(-1, 1)
-    if rs is not None:
-        C64, D = C64 * rs, D * np.abs(rs)
-    if extra is not None:
-        C64 = C64 + np.asarray(extra, dtype=np.float64)
-    allow = mp.half_ulp_of_half(C64) if half_out else None
-    e, idx = mp.componentwise_error(got, C64, D, what, allow)
-    print("%s: e = %.3g (bar %.3g), worst at %s" % (what, e, mp.BAR, idx))
-    if e > mp.BAR:
-        hint = ""
-        if single is not None and not half_out:
-            g = np.asarray(got, dtype=np.float64)
-            if extra is not None:
-                g = g - np.asarray(extra, dtype=np.float64)
-            if rs is not None:
-                g = g / rs
-            x, y = np.broadcast_arrays(*single)
-            bad = (np.abs(np.asarray(got, dtype=np.float64) - C64) > mp.BAR * D)
-            hint = "; %d of %d elements over the bar, first at %s; %s" % (
-                int(bad.sum()), bad.size, tuple(int(v) for v in np.argwhere(bad)[0]), mp.name_lost_term(x[bad], y[bad], g[bad], a_half))
-        raise AssertionError("%s: componentwise error %.3g > %.3g at %s%s" % (what, e, mp.BAR, idx, hint))
-    return e
-
-
-def diag_of(A, K, offset=0):
-    i = np.arange(A.shape[0])
-    return A[i, (i + offset) % K]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -156,12 +124,16 @@ def test_probe_simmatrix_backward(shape, cached, matrix_mode, hiplib):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# plane probes: the fused triplet step (its backward half is on the bf16 pipe)
+# plane probes: the triplet step at shapes its fused route refuses -- the layers one by one, inside the call
 # ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(2125, 300, 300), (2049, 64, 160)])
 def test_probe_triplet_simmatrix_step(shape, matrix_mode, oracle, hiplib):
-    """dq = B W^T and dW += Q^T B with B = g+ a+ + g- a-.  a- = 0, loss_weight = N and a margin no score reaches make
-    B = g+ a+ with g+ = +-1 (asserted from PairRankLoss evaluated at the GPU's own scores), so the probes apply as they are."""
+    """Both shapes have fewer than 6081 triplets (and odd N): tripsim_fused refuses them and mms_triplet_simmatrix_step_f32 runs
+    SimMatrix x 2 -> PairRankLoss -> SimMatrix backward x 2 -> Split sum (profiles/learned_metric_routes.txt).  This holds THAT
+    route's backward to the bar; the fused route has its own module, tests/test_gpu_triplet_simmatrix_fused.py.
+    dq = dq+ + dq- and dW += both branches' terms.  a- = 0, loss_weight = N and a margin no score reaches make them g+ a+ W^T
+    and Q^T (g+ a+) with g+ = +-1 (asserted from PairRankLoss evaluated at the GPU's own scores), so the probes apply as they
+    are."""
     from mms_answer_selection_amd import capi
     N, K1, K2 = shape
     r = rng(5 * N + K1 + K2)

@@ -1094,8 +1094,11 @@ def test_triplet_workspaces_are_independent_and_recoverable(hiplib):
 # --------------------------------------------------------------------------- #
 # Fused learned-metric (q, a+, a-) step == SimMatrix x 2 -> PairRankLoss chain of the oracle
 # --------------------------------------------------------------------------- #
-@pytest.mark.parametrize("cfg", [(4096, 300, 300), (6145, 300, 300), (8192, 100, 200),   # the panel kernel's fast path
-                                 (333, 300, 300), (64, 7, 5), (2048, 302, 300)])          # the layers, one by one
+# (the fused route needs N >= 6081 and N % 4 == 0: tests/test_gpu_triplet_simmatrix_fused.py; the order keeps the case ids)
+@pytest.mark.parametrize("cfg", [(4096, 300, 300), (6145, 300, 300),                     # the layers, one by one: 64 row blocks; odd N
+                                 (8192, 100, 200),                                       # the fused route
+                                 (333, 300, 300), (64, 7, 5), (2048, 302, 300),          # the layers, one by one
+                                 (6148, 300, 300)])                                      # the fused route, ragged last panel
 def test_triplet_simmatrix_step(cfg, oracle, hiplib):
     """mms_triplet_simmatrix_step_f32 against the layer-by-layer chain (sim_matrix_layer.cpp:53-95 twice with W shared,
     pair_rank_loss_layer.cpp:26-84, Split sum of dq): scores / loss / gradients at 1e-5, and -- given the GPU's own

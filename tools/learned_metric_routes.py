@@ -10,9 +10,9 @@ Driven and listed exactly like tools/elementwise_routes.py, whose command line, 
       python3 tools/learned_metric_routes.py --listing OUT --labels LABELS > profiles/learned_metric_routes.txt
 
 Shapes are those of the tests that hold these routes to their bars: the route table of
-tests/test_gpu_bilinear_grid_accuracy.py (every row), the shape lists of tests/test_gpu_matrix_pipe_accuracy.py and
-tests/test_gpu_simmatrix_flags.py, the Embed-fused cases of tests/test_gpu_embed.py.  Calls that clear a buffer with
-hipMemsetAsync (the SimMatrix alias's dW, the fused step's ones) make the runtime launch its fill kernel between the
+tests/test_gpu_bilinear_grid_accuracy.py (every row), the shape lists of tests/test_gpu_matrix_pipe_accuracy.py,
+tests/test_gpu_simmatrix_flags.py and tests/test_gpu_triplet_simmatrix_fused.py, the Embed-fused cases of
+tests/test_gpu_embed.py.  Calls that clear a buffer with hipMemsetAsync (the SimMatrix alias's dW, the fused step's ones) make the runtime launch its fill kernel between the
 library's own; the listing leaves it out."""
 import elementwise_routes as er          # parses the command line: the two scripts share it
 
@@ -33,7 +33,11 @@ EMBED = [(1517, 40, 40, 50, 4, 20000, 1), (600, 16, 24, 64, 2, 300, 0), (50, 40,
 PIPE = [(2049, 300, 300), (2125, 52, 304), (2049, 64, 160), (2048, 24, 8), (2125, 96, 128), (2085, 200, 72)]
 FLAGS = [(130, 33, 18), (700, 64, 48), (2048, 24, 8), (2049, 33, 18), (6144, 64, 48)]
 HALF = [(2049, 304, 304), (2125, 64, 160), (2048, 24, 8), (2125, 96, 128), (2085, 200, 72)]
-TRIPLET = [(2125, 300, 300), (2049, 64, 160), (6144, 64, 48), (130, 33, 18)]     # the last one: the layers one by one
+# The fused route needs N >= 6081 (96 panels of 64 rows) and N % 4 == 0: (2125, 300, 300), (2049, 64, 160), (130, 33, 18) and
+# (6080, 300, 300) run the layers one by one; the others are the shapes of tests/test_gpu_triplet_simmatrix_fused.py
+TRIPLET = [(2125, 300, 300), (2049, 64, 160), (6144, 64, 48), (130, 33, 18),
+           (6084, 4, 4), (6084, 36, 68), (6084, 112, 64), (6148, 116, 112), (6144, 100, 200), (6084, 208, 212),
+           (6084, 300, 300), (6148, 304, 304), (6080, 300, 300)]
 MODES = ("bf16x3", "fp32")
 
 
