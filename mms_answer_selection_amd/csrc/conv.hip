@@ -1,0 +1,677 @@
+// csrc/conv.hip -- Convolution, the reference's 2-d ConvolutionLayer (conv_layer.cpp:25-73, base_conv_layer.cpp:257-321),
+// and its extern "C" entry points (include/mms_conv.h: mms_conv_*).  The reference forms an im2col buffer and calls BLAS
+// per image; nothing here writes such a buffer.  With Cg = C / group, Kg = K / group and g = k / Kg:
+//
+//   forward      top[n,k,oy,ox]  = sum_{c<Cg, i<kh, j<kw} w[k,c,i,j] * x[n, g Cg + c, oy sh - ph + i, ox sw - pw + j] + bias[k]
+//   bottom_diff  dx[n,c,y,x]     = sum_{k in group of c, i, j : (y + ph - i) = oy sh, (x + pw - j) = ox sw} w[k,c,i,j] * dy[n,k,oy,ox]
+//   weight_diff  dw[k,c,i,j]    += sum_{n,oy,ox} dy[n,k,oy,ox] * x[n, g Cg + c, oy sh - ph + i, ox sw - pw + j]
+//   bias_diff    db[k]          += sum_{n,oy,ox} dy[n,k,oy,ox]
+//
+// Two routes (mms_conv_route, the one place that decides; conv_prod_plan / conv_wdiff_plan say what the fast one takes):
+//
+//   generic  direct kernels <T>, one thread per output element, sums in ascending (c, i, j) (forward), (k, i, j)
+//            (bottom_diff, gather form: no col2im scatter) and (n, oy, ox) (parameter diffs) order.  Every accepted
+//            shape; all of double; float where the fast route does not reach.
+//   fast     float, stride 1, pad 0, group 1, C and K <= 64: an implicit GEMM on v_mfma_f32_16x16x4_f32.
+//            PRODUCT kernel (forward, and bottom_diff as the same product on top_diff with C and K swapped, the taps
+//            flipped and a border of kh-1 / kw-1 zeros, which the staging writes by predication): a workgroup of four
+//            waves owns up to 256 output pixels -- a band of whole rows of one image, or several whole small images
+//            -- and all output channels.  Per chunk of input channels it stages the chunk's input band
+//            [image][channel][row][col] and the chunk's weights [k][m] in LDS; the im2col operand B[k][pixel] is
+//            band[koff[k] + pix[pixel]], two offsets added.  MFMA rows are output channels and columns are 16
+//            consecutive pixels of the band, so a store instruction writes runs along OW.  Wave w owns pixel tiles
+//            w, w+4, w+8, w+12 x all MT channel tiles.  Order of a sum: channels ascending in chunks, (c, i, j)
+//            ascending inside a chunk in steps of four, the four of a step as the MFMA adds them.
+//            PARAMETER-DIFF kernel: rows are output channels, columns 16 consecutive (c, i, j), the sum runs over
+//            pixels.  The (image group, row band) units of the batch are dealt in ascending runs to at most 64 slabs
+//            (blockIdx.y); a workgroup owns four column tiles x all MT channel tiles, walks its slab's units in
+//            ascending order -- staging the unit's x band and top_diff tile in LDS -- and writes its partial sums to
+//            slab s of the workspace.  The workgroups of column group 0 also add each channel's top_diff from the
+//            staged tile, pixel by pixel: bias_diff comes from the same sweep.
+//   both     conv_reduce_kernel adds the slabs in ascending order, first to last, and then into weight_diff / bias_diff.
+//
+// Nothing is read 16 bytes at a time, so alignment cannot change an order; every workspace word that is read has been
+// written by this call.
+#include <limits.h>
+
+#include "mms_conv.h"
+#include "mms_internal.h"
+
+namespace mms {
+namespace {
+
+typedef float conv_v4f __attribute__((ext_vector_type(4)));
+
+constexpr int kConvThreads = 256;
+constexpr int kConvMaxSlabs = 64;          // partial sums of the parameter diffs per element, at most
+constexpr int kConvTilePixels = 256;       // output pixels of a fast workgroup: 16 tiles of 16
+constexpr int kConvLdsFloats = 16384;      // 64 KB: the dynamic LDS a launch gets without asking for more
+constexpr int kConvMaxChannels = 64;       // fast route: MT <= 4 channel tiles of 16
+
+struct ConvDims {
+  int N, C, H, W, K, kh, kw, sh, sw, ph, pw, G, OH, OW, Cg, Kg;
+};
+
+// the shape's refusal, else MMS_OK and *d
+int conv_check(const mms_conv_shape* s, ConvDims* d) {
+  if (!s) return MMS_ERR_INVALID_ARG;
+  if (s->N < 0 || s->C <= 0 || s->H <= 0 || s->W <= 0 || s->K <= 0 || s->kh <= 0 || s->kw <= 0 || s->stride_h <= 0 ||
+      s->stride_w <= 0 || s->pad_h < 0 || s->pad_w < 0 || s->dilation_h <= 0 || s->dilation_w <= 0 || s->group <= 0)
+    return MMS_ERR_INVALID_ARG;
+  if (s->C % s->group || s->K % s->group) return MMS_ERR_INVALID_ARG;
+  if (s->dilation_h != 1 || s->dilation_w != 1) return MMS_ERR_UNSUPPORTED;
+  const long long eh = (long long)s->H + 2LL * s->pad_h - s->kh, ew = (long long)s->W + 2LL * s->pad_w - s->kw;
+  if (eh < 0 || ew < 0) return MMS_ERR_INVALID_ARG;
+  const long long OH = eh / s->stride_h + 1, OW = ew / s->stride_w + 1;
+  const long long nx = (long long)s->N * s->C, nt = (long long)s->N * s->K;
+  const long long nw = (long long)s->K * (s->C / s->group);
+  if (OH > INT_MAX || OW > INT_MAX || (long long)s->H * s->W > INT_MAX || OH * OW > INT_MAX ||
+      (long long)s->kh * s->kw > INT_MAX)
+    return MMS_ERR_INVALID_ARG;
+  if (nx > INT_MAX || nt > INT_MAX || nw > INT_MAX || nx * ((long long)s->H * s->W) > INT_MAX ||
+      nt * (OH * OW) > INT_MAX || nw * ((long long)s->kh * s->kw) > INT_MAX)
+    return MMS_ERR_INVALID_ARG;
+  *d = {s->N,     s->C,     s->H,     s->W,    s->K,    s->kh,           s->kw,          s->stride_h, s->stride_w,
+        s->pad_h, s->pad_w, s->group, (int)OH, (int)OW, s->C / s->group, s->K / s->group};
+  return MMS_OK;
+}
+
+inline int round4(int v) { return (v + 3) & ~3; }
+
+// ---- generic route ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kConvThreads) void conv_forward_direct_kernel(ConvDims d, const T* __restrict__ x,
+                                                                           const T* __restrict__ w,
+                                                                           const T* __restrict__ bias,
+                                                                           T* __restrict__ top, int total) {
+  const int idx = blockIdx.x * kConvThreads + threadIdx.x;
+  if (idx >= total) return;
+  const int ox = idx % d.OW;
+  int t = idx / d.OW;
+  const int oy = t % d.OH;
+  t /= d.OH;
+  const int k = t % d.K, n = t / d.K;
+  const int g = k / d.Kg;
+  const int y0 = oy * d.sh - d.ph, x0 = ox * d.sw - d.pw;
+  T acc = T(0);
+  for (int c = 0; c < d.Cg; ++c) {
+    const T* xc = x + ((size_t)n * d.C + g * d.Cg + c) * d.H * d.W;
+    const T* wc = w + ((size_t)k * d.Cg + c) * d.kh * d.kw;
+    for (int i = 0; i < d.kh; ++i) {
+      const int iy = y0 + i;
+      if (iy < 0 || iy >= d.H) continue;
+      for (int j = 0; j < d.kw; ++j) {
+        const int ix = x0 + j;
+        if (ix < 0 || ix >= d.W) continue;
+        acc += wc[i * d.kw + j] * xc[(size_t)iy * d.W + ix];
+      }
+    }
+  }
+  top[idx] = bias ? acc + bias[k] : acc;
+}
+
+// gather form: the (k, i, j) whose forward term read this bottom element
+template <typename T>
+__global__ __launch_bounds__(kConvThreads) void conv_bottom_direct_kernel(ConvDims d, const T* __restrict__ w,
+                                                                          const T* __restrict__ dy,
+                                                                          T* __restrict__ dx, int total) {
+  const int idx = blockIdx.x * kConvThreads + threadIdx.x;
+  if (idx >= total) return;
+  const int xx = idx % d.W;
+  int t = idx / d.W;
+  const int yy = t % d.H;
+  t /= d.H;
+  const int c = t % d.C, n = t / d.C;
+  const int g = c / d.Cg, cl = c - g * d.Cg;
+  T acc = T(0);
+  for (int kk = 0; kk < d.Kg; ++kk) {
+    const int k = g * d.Kg + kk;
+    const T* wk = w + ((size_t)k * d.Cg + cl) * d.kh * d.kw;
+    const T* dk = dy + ((size_t)n * d.K + k) * d.OH * d.OW;
+    for (int i = 0; i < d.kh; ++i) {
+      const int ty = yy + d.ph - i;
+      if (ty < 0 || ty % d.sh) continue;
+      const int oy = ty / d.sh;
+      if (oy >= d.OH) continue;
+      for (int j = 0; j < d.kw; ++j) {
+        const int tx = xx + d.pw - j;
+        if (tx < 0 || tx % d.sw) continue;
+        const int ox = tx / d.sw;
+        if (ox >= d.OW) continue;
+        acc += wk[i * d.kw + j] * dk[(size_t)oy * d.OW + ox];
+      }
+    }
+  }
+  dx[idx] = acc;
+}
+
+// Slab blockIdx.y sums rows [y * rps, (y + 1) * rps) of the N * OH (n, oy) rows; element e < nW is a weight, e - nW a bias.
+template <typename T>
+__global__ __launch_bounds__(kConvThreads) void conv_param_direct_kernel(ConvDims d, const T* __restrict__ x,
+                                                                         const T* __restrict__ dy,
+                                                                         T* __restrict__ part, int nW, int want_w,
+                                                                         int want_b, int rps) {
+  const int e = blockIdx.x * kConvThreads + threadIdx.x;
+  if (e >= nW + d.K) return;
+  if (e < nW ? !want_w : !want_b) return;
+  const int rows = d.N * d.OH;
+  const int r0 = blockIdx.y * rps, r1 = min(rows, r0 + rps);
+  T acc = T(0);
+  if (e < nW) {
+    const int j = e % d.kw;
+    int t = e / d.kw;
+    const int i = t % d.kh;
+    t /= d.kh;
+    const int c = t % d.Cg, k = t / d.Cg;
+    const int g = k / d.Kg;
+    for (int r = r0; r < r1; ++r) {
+      const int n = r / d.OH, oy = r - n * d.OH;
+      const int iy = oy * d.sh - d.ph + i;
+      if (iy < 0 || iy >= d.H) continue;
+      const T* dr = dy + (((size_t)n * d.K + k) * d.OH + oy) * d.OW;
+      const T* xr = x + (((size_t)n * d.C + g * d.Cg + c) * d.H + iy) * d.W;
+      for (int ox = 0; ox < d.OW; ++ox) {
+        const int ix = ox * d.sw - d.pw + j;
+        if (ix < 0 || ix >= d.W) continue;
+        acc += dr[ox] * xr[ix];
+      }
+    }
+  } else {
+    const int k = e - nW;
+    for (int r = r0; r < r1; ++r) {
+      const int n = r / d.OH, oy = r - n * d.OH;
+      const T* dr = dy + (((size_t)n * d.K + k) * d.OH + oy) * d.OW;
+      for (int ox = 0; ox < d.OW; ++ox) acc += dr[ox];
+    }
+  }
+  part[(size_t)blockIdx.y * (nW + d.K) + e] = acc;
+}
+
+// diff[e] = diff[e] + (part[0][e] + part[1][e] + ... ), slabs ascending; both routes
+template <typename T>
+__global__ __launch_bounds__(kConvThreads) void conv_reduce_kernel(const T* __restrict__ part, int slabs, int nW, int K,
+                                                                   T* __restrict__ weight_diff,
+                                                                   T* __restrict__ bias_diff) {
+  const int e = blockIdx.x * kConvThreads + threadIdx.x;
+  if (e >= nW + K) return;
+  T* out = e < nW ? (weight_diff ? weight_diff + e : nullptr) : (bias_diff ? bias_diff + (e - nW) : nullptr);
+  if (!out) return;
+  const size_t stride = (size_t)nW + K;
+  T s = part[e];
+  for (int k = 1; k < slabs; ++k) s += part[k * stride + e];
+  *out = *out + s;
+}
+
+int conv_generic_slabs(const ConvDims& d, int* rps) {
+  const int rows = d.N * d.OH;
+  const int want = rows < kConvMaxSlabs ? rows : kConvMaxSlabs;
+  *rps = (rows + want - 1) / want;
+  return (rows + *rps - 1) / *rps;
+}
+
+// ---- fast route ---------------------------------------------------------------------------------------------------
+// The pixels of a workgroup: `G` whole images where an image has at most kConvTilePixels / 2 pixels, else `R` whole
+// rows of one image, `bands` bands per image.
+bool conv_tile_geometry(int OHt, int OWt, int* G, int* R, int* bands) {
+  if (OWt > kConvTilePixels) return false;
+  const int PI = OHt * OWt;
+  if (PI <= kConvTilePixels / 2) {
+    *G = kConvTilePixels / PI;
+    *R = OHt;
+    *bands = 1;
+  } else {
+    const int rmax = kConvTilePixels / OWt;
+    const int nb = (OHt + rmax - 1) / rmax;
+    *G = 1;
+    *R = (OHt + nb - 1) / nb;
+    *bands = (OHt + *R - 1) / *R;
+  }
+  return true;
+}
+
+struct ConvProdArgs {
+  const float* in;       // (N, Cin, IH, IW)
+  const float* w;        // W'(m, ci, t) = w[m * w_ms + ci * w_cs + (flip ? kh kw - 1 - t : t)]
+  const float* bias;     // per output channel, or NULL
+  float* out;            // (N, Cout, OHt, OWt)
+  int N, Cin, Cout, IH, IW, OHt, OWt, kh, kw;
+  int vph, vpw;          // rows / columns of zeros before the input (bottom_diff: kh - 1, kw - 1)
+  int G, R, bands;       // conv_tile_geometry
+  int BW, plane;         // band: row length IW + 2 vpw, BR * BW elements per channel with BR = R + kh - 1
+  int CC, Kpad;          // input channels per chunk; round4(CC * kh * kw)
+  int MT;                // channel tiles of 16
+  int w_ms, w_cs, flip;
+  bool ok;
+  size_t lds_bytes;
+};
+
+// pass 0: forward.  pass 1: bottom_diff, the forward product on top_diff with C and K swapped and the taps flipped.
+ConvProdArgs conv_prod_plan(const ConvDims& d, int pass) {
+  ConvProdArgs a = {};
+  if (d.sh != 1 || d.sw != 1 || d.ph != 0 || d.pw != 0 || d.G != 1 || d.C > kConvMaxChannels || d.K > kConvMaxChannels)
+    return a;
+  const int khkw = d.kh * d.kw;
+  a.N = d.N; a.kh = d.kh; a.kw = d.kw;
+  if (pass == 0) {
+    a.Cin = d.C; a.Cout = d.K; a.IH = d.H; a.IW = d.W; a.OHt = d.OH; a.OWt = d.OW;
+    a.vph = a.vpw = 0;
+    a.w_ms = d.C * khkw; a.w_cs = khkw; a.flip = 0;
+  } else {
+    a.Cin = d.K; a.Cout = d.C; a.IH = d.OH; a.IW = d.OW; a.OHt = d.H; a.OWt = d.W;
+    a.vph = d.kh - 1; a.vpw = d.kw - 1;
+    a.w_ms = khkw; a.w_cs = d.C * khkw; a.flip = 1;
+  }
+  if (!conv_tile_geometry(a.OHt, a.OWt, &a.G, &a.R, &a.bands)) return a;
+  a.BW = a.IW + 2 * a.vpw;
+  a.MT = a.Cout <= 16 ? 1 : a.Cout <= 32 ? 2 : 4;
+  const int Mpad = 16 * a.MT;
+  for (;;) {
+    a.plane = (a.R + d.kh - 1) * a.BW;
+    a.CC = 0;
+    for (int cc = a.Cin; cc >= 1; --cc) {
+      const long long kp = round4(cc * khkw);
+      if ((long long)a.G * cc * a.plane + (long long)Mpad * kp + kp <= kConvLdsFloats) { a.CC = cc; break; }
+    }
+    if (a.CC >= (a.Cin < 4 ? a.Cin : 4)) break;
+    if (a.G > 1) { a.G = (a.G + 1) / 2; continue; }       // fewer images, then fewer rows, per workgroup
+    if (a.R > 1) { a.R = (a.R + 1) / 2; a.bands = (a.OHt + a.R - 1) / a.R; continue; }
+    if (a.CC >= 1) break;
+    return a;
+  }
+  a.Kpad = round4(a.CC * khkw);
+  a.lds_bytes = ((size_t)a.G * a.CC * a.plane + (size_t)Mpad * a.Kpad + a.Kpad) * sizeof(float);
+  a.ok = true;
+  return a;
+}
+
+template <int MT>
+__global__ __launch_bounds__(kConvThreads) void conv_prod_kernel(ConvProdArgs a) {
+  constexpr int NT = 4, Mpad = 16 * MT;
+  extern __shared__ float conv_lds[];
+  float* band = conv_lds;                               // [G][CC][BR][BW]
+  float* wsm = band + a.G * a.CC * a.plane;             // [Kpad][Mpad]
+  int* koff = reinterpret_cast<int*>(wsm + a.Kpad * Mpad);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, grp = lane >> 4;
+  const int khkw = a.kh * a.kw;
+  const int n0 = blockIdx.x * a.G, gc = min(a.G, a.N - n0);
+  const int oy0 = blockIdx.y * a.R, rb = min(a.R, a.OHt - oy0);
+  const int per = rb * a.OWt, P = gc * per, bru = rb + a.kh - 1;
+  const size_t PI = (size_t)a.OHt * a.OWt;
+
+  for (int k = tid; k < a.Kpad; k += kConvThreads) {
+    const int cl = k / khkw, t = k - cl * khkw, i = t / a.kw, j = t - i * a.kw;
+    koff[k] = cl * a.plane + i * a.BW + j;
+  }
+  int pix[NT];
+  size_t outoff[NT];
+  bool pvalid[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int p = (wave + 4 * nt) * 16 + l16;
+    pvalid[nt] = p < P;
+    const int pp = pvalid[nt] ? p : 0;
+    const int img = pp / per, q = pp - img * per, r = q / a.OWt, c = q - r * a.OWt;
+    pix[nt] = img * a.CC * a.plane + r * a.BW + c;
+    outoff[nt] = (size_t)(n0 + img) * a.Cout * PI + (size_t)(oy0 + r) * a.OWt + c;
+  }
+  conv_v4f acc[MT][NT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (conv_v4f){0.f, 0.f, 0.f, 0.f};
+
+  for (int ci0 = 0; ci0 < a.Cin; ci0 += a.CC) {
+    const int cc = min(a.CC, a.Cin - ci0), klen = cc * khkw, ksteps = (klen + 3) >> 2, k4 = ksteps * 4;
+    __syncthreads();                                    // the previous chunk has been consumed
+    for (int e = tid; e < Mpad * k4; e += kConvThreads) {
+      const int m = e / k4, kk = e - m * k4;
+      float v = 0.f;
+      if (m < a.Cout && kk < klen) {
+        const int cl = kk / khkw, t = kk - cl * khkw;
+        v = a.w[(size_t)m * a.w_ms + (size_t)(ci0 + cl) * a.w_cs + (a.flip ? khkw - 1 - t : t)];
+      }
+      wsm[kk * Mpad + m] = v;
+    }
+    for (int e = tid; e < gc * cc * bru * a.BW; e += kConvThreads) {
+      const int bc = e % a.BW;
+      int t = e / a.BW;
+      const int br = t % bru;
+      t /= bru;
+      const int cl = t % cc, img = t / cc;
+      const int iy = oy0 + br - a.vph, ix = bc - a.vpw;
+      float v = 0.f;
+      if (iy >= 0 && iy < a.IH && ix >= 0 && ix < a.IW)
+        v = a.in[(((size_t)(n0 + img) * a.Cin + ci0 + cl) * a.IH + iy) * a.IW + ix];
+      band[(img * a.CC + cl) * a.plane + br * a.BW + bc] = v;
+    }
+    __syncthreads();
+    for (int s = 0; s < ksteps; ++s) {
+      const int k = 4 * s + grp;
+      const bool kvalid = k < klen;                     // the weights of k >= klen are zeros; the band's are not staged
+      const int off = kvalid ? koff[k] : 0;
+      float av[MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) av[mt] = wsm[k * Mpad + 16 * mt + l16];
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        if ((wave + 4 * nt) * 16 >= P) continue;        // wave-uniform: the tile holds no pixel
+        const float t = band[off + pix[nt]];
+        const float bv = kvalid ? t : 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv, acc[mt][nt], 0, 0, 0);
+      }
+    }
+  }
+  // lane: pixel column l16, output channels 16 mt + 4 grp + r
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = 16 * mt + 4 * grp + r;
+      if (m >= a.Cout) continue;
+      const float b = a.bias ? a.bias[m] : 0.f;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+        if (pvalid[nt]) a.out[outoff[nt] + (size_t)m * PI] = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];
+    }
+}
+
+struct ConvWdiffArgs {
+  const float* x;        // (N, C, H, W)
+  const float* dy;       // (N, K, OH, OW)
+  float* part;           // [slab][nW + K]
+  int N, C, K, H, W, OH, OW, kh, kw;
+  int G, R, bands;       // conv_tile_geometry of the top pixels, shrunk to the LDS
+  int plane;             // (R + kh - 1) * W
+  int PP;                // row length of the staged top_diff tile: round4(G * R * OW) + 1
+  int MT;
+  int units, ups, slabs; // (image group, band) units; units per slab; slabs
+  int want_w, want_b;
+  bool ok;
+  size_t lds_bytes;
+};
+
+ConvWdiffArgs conv_wdiff_plan(const ConvDims& d) {
+  ConvWdiffArgs a = {};
+  if (d.sh != 1 || d.sw != 1 || d.ph != 0 || d.pw != 0 || d.G != 1 || d.C > kConvMaxChannels || d.K > kConvMaxChannels)
+    return a;
+  a.N = d.N; a.C = d.C; a.K = d.K; a.H = d.H; a.W = d.W; a.OH = d.OH; a.OW = d.OW; a.kh = d.kh; a.kw = d.kw;
+  if (!conv_tile_geometry(d.OH, d.OW, &a.G, &a.R, &a.bands)) return a;
+  a.MT = d.K <= 16 ? 1 : d.K <= 32 ? 2 : 4;
+  for (;;) {
+    a.plane = (a.R + d.kh - 1) * d.W;
+    a.PP = round4(a.G * a.R * d.OW) + 1;
+    const long long need = (long long)a.G * d.C * a.plane + (long long)16 * a.MT * a.PP + a.PP;
+    if (need <= kConvLdsFloats) break;
+    if (a.G > 1) { --a.G; continue; }
+    if (a.R > 1) { --a.R; a.bands = (d.OH + a.R - 1) / a.R; continue; }
+    return a;
+  }
+  a.lds_bytes = ((size_t)a.G * d.C * a.plane + (size_t)16 * a.MT * a.PP + a.PP) * sizeof(float);
+  a.units = d.N ? ((d.N + a.G - 1) / a.G) * a.bands : 0;
+  const int want = a.units < kConvMaxSlabs ? a.units : kConvMaxSlabs;
+  a.ups = want ? (a.units + want - 1) / want : 1;
+  a.slabs = (a.units + a.ups - 1) / a.ups;
+  a.ok = true;
+  return a;
+}
+
+template <int MT>
+__global__ __launch_bounds__(kConvThreads) void conv_wdiff_kernel(ConvWdiffArgs a) {
+  constexpr int Mpad = 16 * MT;
+  extern __shared__ float conv_lds[];
+  float* band = conv_lds;                               // [G][C][BR][W]
+  float* tds = band + a.G * a.C * a.plane;              // [Mpad][PP]: top_diff, channel x pixel of the unit
+  int* pixoff = reinterpret_cast<int*>(tds + Mpad * a.PP);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, grp = lane >> 4;
+  const int khkw = a.kh * a.kw, ncols = a.C * khkw, nW = a.K * ncols;
+  const int ct = blockIdx.x * 4 + wave;
+  const bool tile_on = a.want_w && ct * 16 < ncols;     // wave-uniform
+  const int ncol = ct * 16 + l16;
+  int ncoff = 0;
+  if (ncol < ncols) {
+    const int c = ncol / khkw, t = ncol - c * khkw, i = t / a.kw, j = t - i * a.kw;
+    ncoff = c * a.plane + i * a.W + j;
+  }
+  const bool bias_on = a.want_b && blockIdx.x == 0 && tid < a.K;
+  const size_t PI = (size_t)a.OH * a.OW;
+  float bsum = 0.f;
+  conv_v4f acc[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) acc[mt] = (conv_v4f){0.f, 0.f, 0.f, 0.f};
+
+  const int u0 = blockIdx.y * a.ups, u1 = min(a.units, u0 + a.ups);
+  for (int u = u0; u < u1; ++u) {
+    const int ig = u / a.bands, bnd = u - ig * a.bands;
+    const int n0 = ig * a.G, gc = min(a.G, a.N - n0);
+    const int oy0 = bnd * a.R, rb = min(a.R, a.OH - oy0);
+    const int per = rb * a.OW, P = gc * per, steps = (P + 3) >> 2, p4 = steps * 4, bru = rb + a.kh - 1;
+    __syncthreads();                                    // the previous unit has been consumed
+    if (a.want_w) {                                     // every wave stages, with or without a tile of its own
+      for (int e = tid; e < gc * a.C * bru * a.W; e += kConvThreads) {
+        const int bc = e % a.W;
+        int t = e / a.W;
+        const int br = t % bru;
+        t /= bru;                                       // t = img * C + c
+        band[t * a.plane + br * a.W + bc] = a.x[((size_t)(n0 * a.C + t) * a.H + oy0 + br) * a.W + bc];
+      }
+    }
+    for (int e = tid; e < Mpad * p4; e += kConvThreads) {
+      const int m = e / p4, p = e - m * p4;
+      float v = 0.f;
+      if (m < a.K && p < P) {
+        const int img = p / per, q = p - img * per, r = q / a.OW, c = q - r * a.OW;
+        v = a.dy[((size_t)(n0 + img) * a.K + m) * PI + (size_t)(oy0 + r) * a.OW + c];
+      }
+      tds[m * a.PP + p] = v;
+    }
+    for (int p = tid; p < p4; p += kConvThreads) {
+      int o = -1;
+      if (p < P) {
+        const int img = p / per, q = p - img * per, r = q / a.OW, c = q - r * a.OW;
+        o = img * a.C * a.plane + r * a.W + c;
+      }
+      pixoff[p] = o;
+    }
+    __syncthreads();
+    if (bias_on)
+      for (int p = 0; p < P; ++p) bsum += tds[tid * a.PP + p];
+    if (tile_on) {
+      for (int s = 0; s < steps; ++s) {
+        const int p = 4 * s + grp;
+        const int po = pixoff[p];
+        const float t = band[ncoff + (po < 0 ? 0 : po)];
+        const float bv = po < 0 ? 0.f : t;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(tds[(16 * mt + l16) * a.PP + p], bv, acc[mt], 0, 0, 0);
+      }
+    }
+  }
+  float* slab = a.part + (size_t)blockIdx.y * (nW + a.K);
+  if (tile_on && ncol < ncols) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = 16 * mt + 4 * grp + r;
+        if (m < a.K) slab[(size_t)m * ncols + ncol] = acc[mt][r];
+      }
+  }
+  if (bias_on) slab[nW + tid] = bsum;
+}
+
+template <class F>
+inline void with_mt(int MT, F&& f) {
+  if (MT == 1) f(std::integral_constant<int, 1>{});
+  else if (MT == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
+void conv_prod_launch(ConvProdArgs a, const float* in, const float* w, const float* bias, float* out, hipStream_t s) {
+  a.in = in; a.w = w; a.bias = bias; a.out = out;
+  const dim3 grid((unsigned)((a.N + a.G - 1) / a.G), (unsigned)a.bands);
+  with_mt(a.MT, [&](auto M) {
+    hipLaunchKernelGGL((conv_prod_kernel<decltype(M)::value>), grid, dim3(kConvThreads), a.lds_bytes, s, a);
+  });
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------
+int conv_route(const ConvDims& d, int pass) {
+  if (pass == MMS_CONV_PASS_FORWARD || pass == MMS_CONV_PASS_BOTTOM_DIFF)
+    return conv_prod_plan(d, pass).ok ? MMS_CONV_ROUTE_FAST : MMS_CONV_ROUTE_GENERIC;
+  if (pass == MMS_CONV_PASS_PARAM_DIFF) return conv_wdiff_plan(d).ok ? MMS_CONV_ROUTE_FAST : MMS_CONV_ROUTE_GENERIC;
+  return MMS_CONV_ROUTE_NONE;
+}
+
+template <typename T>
+size_t conv_workspace_bytes(const mms_conv_shape* shape) {
+  ConvDims d;
+  if (conv_check(shape, &d) != MMS_OK || d.N == 0) return 0;
+  int rps;
+  int slabs = conv_generic_slabs(d, &rps);
+  if (std::is_same<T, float>::value) {
+    const ConvWdiffArgs f = conv_wdiff_plan(d);
+    if (f.ok && f.slabs > slabs) slabs = f.slabs;
+  }
+  return (size_t)slabs * ((size_t)d.K * d.Cg * d.kh * d.kw + d.K) * sizeof(T);
+}
+
+template <typename T>
+int conv_forward(const mms_conv_shape* shape, const T* x, const T* w, const T* bias, T* top, bool generic,
+                 hipStream_t s) {
+  ConvDims d;
+  const int rc = conv_check(shape, &d);
+  if (rc != MMS_OK) return rc;
+  if (d.N == 0) return MMS_OK;
+  if (!x || !w || !top || (const T*)top == x) return MMS_ERR_INVALID_ARG;
+  if constexpr (std::is_same<T, float>::value) {
+    if (!generic && conv_route(d, MMS_CONV_PASS_FORWARD) == MMS_CONV_ROUTE_FAST) {
+      conv_prod_launch(conv_prod_plan(d, MMS_CONV_PASS_FORWARD), x, w, bias, top, s);
+      return launch_status();
+    }
+  }
+  const int total = d.N * d.K * d.OH * d.OW;
+  hipLaunchKernelGGL((conv_forward_direct_kernel<T>), dim3((total + kConvThreads - 1) / kConvThreads),
+                     dim3(kConvThreads), 0, s, d, x, w, bias, top, total);
+  return launch_status();
+}
+
+template <typename T>
+int conv_backward(const mms_conv_shape* shape, const T* x, const T* w, const T* dy, T* dx, T* dw, T* db, void* workspace,
+                  size_t workspace_bytes, bool generic, hipStream_t s) {
+  ConvDims d;
+  int rc = conv_check(shape, &d);
+  if (rc != MMS_OK) return rc;
+  if (d.N == 0) return MMS_OK;
+  if (!x || !w || !dy || (!dx && !dw && !db)) return MMS_ERR_INVALID_ARG;
+  if (dx && ((const T*)dx == x || (const T*)dx == dy)) return MMS_ERR_INVALID_ARG;
+  if ((dw || db) && (!workspace || workspace_bytes < conv_workspace_bytes<T>(shape))) return MMS_ERR_WORKSPACE;
+  constexpr bool kFloat = std::is_same<T, float>::value;
+  if (dx) {
+    bool done = false;
+    if constexpr (kFloat) {
+      if (!generic && conv_route(d, MMS_CONV_PASS_BOTTOM_DIFF) == MMS_CONV_ROUTE_FAST) {
+        conv_prod_launch(conv_prod_plan(d, MMS_CONV_PASS_BOTTOM_DIFF), dy, w, nullptr, dx, s);
+        done = true;
+      }
+    }
+    if (!done) {
+      const int total = d.N * d.C * d.H * d.W;
+      hipLaunchKernelGGL((conv_bottom_direct_kernel<T>), dim3((total + kConvThreads - 1) / kConvThreads),
+                         dim3(kConvThreads), 0, s, d, w, dy, dx, total);
+    }
+    if ((rc = launch_status()) != MMS_OK) return rc;
+  }
+  if (!dw && !db) return MMS_OK;
+  const int nW = d.K * d.Cg * d.kh * d.kw;
+  T* part = static_cast<T*>(workspace);
+  int slabs = 0;
+  if constexpr (kFloat) {
+    if (!generic && conv_route(d, MMS_CONV_PASS_PARAM_DIFF) == MMS_CONV_ROUTE_FAST) {
+      ConvWdiffArgs a = conv_wdiff_plan(d);
+      a.x = x; a.dy = dy; a.part = part; a.want_w = dw != nullptr; a.want_b = db != nullptr;
+      const int groups = dw ? (d.C * d.kh * d.kw + 63) / 64 : 1;     // four column tiles of 16 per workgroup
+      with_mt(a.MT, [&](auto M) {
+        hipLaunchKernelGGL((conv_wdiff_kernel<decltype(M)::value>), dim3((unsigned)groups, (unsigned)a.slabs),
+                           dim3(kConvThreads), a.lds_bytes, s, a);
+      });
+      slabs = a.slabs;
+    }
+  }
+  if (!slabs) {
+    int rps;
+    slabs = conv_generic_slabs(d, &rps);
+    hipLaunchKernelGGL((conv_param_direct_kernel<T>), dim3((nW + d.K + kConvThreads - 1) / kConvThreads, slabs),
+                       dim3(kConvThreads), 0, s, d, x, dy, part, nW, dw != nullptr, db != nullptr, rps);
+  }
+  if ((rc = launch_status()) != MMS_OK) return rc;
+  hipLaunchKernelGGL((conv_reduce_kernel<T>), dim3((nW + d.K + kConvThreads - 1) / kConvThreads), dim3(kConvThreads),
+                     0, s, (const T*)part, slabs, nW, d.K, dw, db);
+  return launch_status();
+}
+
+}  // namespace
+}  // namespace mms
+
+using namespace mms;
+
+extern "C" {
+
+int mms_conv_output_dims(const mms_conv_shape* shape, int* OH, int* OW) {
+  ConvDims d;
+  const int rc = conv_check(shape, &d);
+  if (rc != MMS_OK) return rc;
+  if (!OH || !OW) return MMS_ERR_INVALID_ARG;
+  *OH = d.OH;
+  *OW = d.OW;
+  return MMS_OK;
+}
+
+size_t mms_conv_workspace_bytes(const mms_conv_shape* shape) { return conv_workspace_bytes<float>(shape); }
+size_t mms_conv_workspace_bytes_f64(const mms_conv_shape* shape) { return conv_workspace_bytes<double>(shape); }
+
+int mms_conv_route(const mms_conv_shape* shape, int pass) {
+  ConvDims d;
+  if (conv_check(shape, &d) != MMS_OK) return MMS_CONV_ROUTE_NONE;
+  return conv_route(d, pass);
+}
+
+int mms_conv_forward_f32(const mms_conv_shape* shape, const float* x, const float* weight, const float* bias,
+                         float* top, void*, size_t, void* stream) {
+  return conv_forward<float>(shape, x, weight, bias, top, false, static_cast<hipStream_t>(stream));
+}
+
+int mms_conv_backward_f32(const mms_conv_shape* shape, const float* x, const float* weight, const float* top_diff,
+                          float* bottom_diff, float* weight_diff, float* bias_diff, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  return conv_backward<float>(shape, x, weight, top_diff, bottom_diff, weight_diff, bias_diff, workspace,
+                              workspace_bytes, false, static_cast<hipStream_t>(stream));
+}
+
+int mms_conv_forward_f64(const mms_conv_shape* shape, const double* x, const double* weight, const double* bias,
+                         double* top, void*, size_t, void* stream) {
+  return conv_forward<double>(shape, x, weight, bias, top, true, static_cast<hipStream_t>(stream));
+}
+
+int mms_conv_backward_f64(const mms_conv_shape* shape, const double* x, const double* weight, const double* top_diff,
+                          double* bottom_diff, double* weight_diff, double* bias_diff, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  return conv_backward<double>(shape, x, weight, top_diff, bottom_diff, weight_diff, bias_diff, workspace,
+                               workspace_bytes, true, static_cast<hipStream_t>(stream));
+}
+
+int mms_conv_forward_generic_f32(const mms_conv_shape* shape, const float* x, const float* weight, const float* bias,
+                                 float* top, void*, size_t, void* stream) {
+  return conv_forward<float>(shape, x, weight, bias, top, true, static_cast<hipStream_t>(stream));
+}
+
+int mms_conv_backward_generic_f32(const mms_conv_shape* shape, const float* x, const float* weight,
+                                  const float* top_diff, float* bottom_diff, float* weight_diff, float* bias_diff,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  return conv_backward<float>(shape, x, weight, top_diff, bottom_diff, weight_diff, bias_diff, workspace,
+                              workspace_bytes, true, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
