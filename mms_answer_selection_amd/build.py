@@ -21,11 +21,13 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmms_hip.so")
 LAYER_LIB = os.path.join(HERE, "libmms_caffe.so")
 
-HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip"]
+HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "head.hip"]
 def _hip_headers():
-    """Every header under csrc/ is a dependency of every .hip object (panel_gemm.h is included by simmatrix.hip,
-    gemm32.h by four sources, ...): found by glob so that a new header cannot be forgotten."""
-    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")))
+    """Every header under csrc/ and under include/ is a dependency of every .hip object (panel_gemm.h is included by
+    simmatrix.hip, gemm32.h by four sources, mms_conv.h and mms_head.h by one each, ...): found by glob so that a new
+    header cannot be forgotten."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")) +
+                  glob.glob(os.path.join(ROOT, "include", "*.h")))
 
 
 HIPCC_FLAGS = [
@@ -63,7 +65,7 @@ def _compile_one(args):
 def build_hip(force=False, verbose=False):
     """One object per .hip source (compiled in parallel, rebuilt only when stale), then one link."""
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = _hip_headers() + [os.path.join(ROOT, "include", "mms.h"), os.path.abspath(__file__)]
+    hdrs = _hip_headers() + [os.path.abspath(__file__)]
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"]
