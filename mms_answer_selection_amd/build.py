@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmms_hip.so")
 LAYER_LIB = os.path.join(HERE, "libmms_caffe.so")
 
-HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "head.hip"]
+HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "head.hip", "solver.hip"]
 def _hip_headers():
     """Every header under csrc/ and under include/ is a dependency of every .hip object (panel_gemm.h is included by
     simmatrix.hip, gemm32.h by four sources, mms_conv.h and mms_head.h by one each, ...): found by glob so that a new
