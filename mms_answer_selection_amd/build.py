@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmms_hip.so")
 LAYER_LIB = os.path.join(HERE, "libmms_caffe.so")
 
-HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "head.hip", "solver.hip"]
+HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_rows_cosine.hip", "simcross_rows_f16.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "head.hip", "solver.hip"]
 def _hip_headers():
     """Every header under csrc/ and under include/ is a dependency of every .hip object (panel_gemm.h is included by
     simmatrix.hip, gemm32.h by four sources, mms_conv.h and mms_head.h by one each, ...): found by glob so that a new
@@ -78,7 +78,9 @@ def build_hip(force=False, verbose=False):
             jobs.append(([_hipcc()] + cflags + EXTRA_FLAGS.get(f, []) + ["-c", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
                                                 src, "-o", obj], verbose))
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), max(1, (os.cpu_count() or 2) // 2))) as ex:
+        # os.cpu_count() is the whole host's, whatever share of it this process may use: MAX_JOBS, else 16, caps the pool
+        cap = int(os.environ.get("MAX_JOBS") or 16)
+        with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), cap, (os.cpu_count() or 2) // 2))) as ex:
             list(ex.map(_compile_one, jobs))
     if jobs or force or _stale(LIB, objs):
         cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB]

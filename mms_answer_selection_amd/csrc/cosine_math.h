@@ -1,6 +1,6 @@
 // csrc/cosine_math.h -- SimCross dist_mode 0 (cosine) for ONE pair, W1 = W2 = 1: the per-lane accumulation
 // order, the score and the two forms of the backward (src/caffe/layers/sim_cross_layer.cpp:112-139, 226-250).
-// Shared by simcross_rows.hip (cosine_pair32_kernel, cosine_rows_kernel) and by the fused cosine triplet
+// Shared by simcross_rows_cosine.hip (cosine_pair32_kernel, cosine_rows_kernel) and by the fused cosine triplet
 // step in triplet_steps.hip, whose scores, norms and gradients must carry the bits of those kernels: one definition
 // of every expression, built with -ffp-contract=off, so the same operands give the same bits wherever it is
 // inlined.

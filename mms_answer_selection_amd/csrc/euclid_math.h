@@ -42,6 +42,14 @@ __device__ __forceinline__ EuclidCoef euclid_coef(float T, float g) {
   return k;
 }
 
+// Lane `src`'s den or rcp in every lane; `src` is a compile-time lane once the caller's loop is unrolled: two v_readlane.
+__device__ __forceinline__ double readlane_f64(double v, int src) {
+  const long long b = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)b, src);
+  const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), src);
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // The reference expression, literally.
 __device__ __forceinline__ float euclid_tt_exact(float c, double den, float diff) {
   return (float)((double)(c * diff) / den);
@@ -231,9 +239,16 @@ __device__ __forceinline__ float2v chain_sum_lds_pk(const float4* r4, int n4, fl
 // non-negative running sum is exact, so every lane runs the same h4 steps.
 __host__ __device__ __forceinline__ int spec_h4(int D4) { return (D4 + 2) / 3; }
 __host__ __device__ __forceinline__ int spec_stride4(int D4) { return 3 * spec_h4(D4); }
+// What float4 `i4` (tree sum `s4`) of a pair's image adds to (pred1, pred2) of its pair; `r1`: the wave's second pair.
+template <int RW>
+__device__ __forceinline__ void spec_pred_add(float2v (&pred)[RW], bool r1, int i4, int h4, float s4) {
+  const float2v c = {(i4 < h4) ? s4 : 0.f, (i4 < 2 * h4) ? s4 : 0.f}, z2 = {0.f, 0.f};
+  pred[0] += r1 ? z2 : c;
+  if (RW == 2) pred[RW - 1] += r1 ? c : z2;
+}
 
-// Host-side facts about the kernels built on this scheme (simcross_rows.hip and the fused triplet steps of
-// triplet_steps.hip route on them; each is written here and nowhere else).
+// Host-side facts about the kernels built on this scheme (the three simcross_rows*.hip and the fused triplet steps
+// of triplet_steps.hip route on them; each is written here and nowhere else).
 // Dynamic LDS of a workgroup of `waves` waves that each hold `pairs_per_wave` images of D4 float4.
 inline size_t spec_image_lds(int waves, int pairs_per_wave, int D4) {
   return (size_t)waves * pairs_per_wave * spec_stride4(D4) * sizeof(float4);

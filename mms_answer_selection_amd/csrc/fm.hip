@@ -11,7 +11,7 @@
 //
 // t2_j is a C-long chain, independent across j: one thread per (sample, column).  t1 is ONE ordered chain of
 // (dim-1)(C+1) + C + 1 dependent adds per sample: it is walked by one lane from an LDS image of its addends, in the
-// form of euclid_rows_lanechain_f16_kernel (simcross_rows.hip) -- exact by construction, no speculation.
+// form of euclid_rows_lanechain_f16_kernel (simcross_rows_f16.hip) -- exact by construction, no speculation.
 #include <limits.h>
 
 #include "mms_internal.h"

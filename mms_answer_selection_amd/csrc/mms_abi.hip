@@ -239,6 +239,7 @@ int mms_simcross_forward_backward_f32(int dist_mode, int N, int W1, int W2, int 
                                                norm1, dq, da, as_stream(stream));
 }
 
+// fp16-storage sentence-vector pairs (W1 == W2 == 1): the kernels and their routing are simcross_rows_f16.hip's
 int mms_simcross_euclid_forward_f16(int N, int D, const void* q_f16, const void* a_f16, float* top,
                                     void* stream) {
   if (N < 0 || D <= 0 || (long long)N * D > 0x7fffffffLL) return MMS_ERR_INVALID_ARG;

@@ -18,6 +18,10 @@ inline int launch_status() {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// every array a launch touches (p2, p3: the gradients, null in a forward) takes 16-byte accesses of rows of D floats
+inline bool vec4_ok(int D, const void* p0, const void* p1, const void* p2, const void* p3) {
+  return (D % 4 == 0) && aligned16(p0) && aligned16(p1) && (!p2 || aligned16(p2)) && (!p3 || aligned16(p3));
+}
 
 inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 

@@ -6,22 +6,24 @@
 #include "mms_common.h"
 
 namespace mms {
-// simcross_rows.hip (W1 == W2 == 1)
+// simcross_rows.hip (W1 == W2 == 1, Euclid)
 // false: no rows kernel serves this Euclid forward or fused launch, and the word-grid kernels take it.  `exact`:
 // euclid_backward_mode() == MMS_EUCLID_BWD_REFERENCE, read once by the entry point.  Instantiated for
 // <true, false>, <false, true> and <true, true>.
 template <bool FWD, bool BWD>
 bool launch_euclid_rows(int N, int D, const float* q, const float* a, const float* top_in, const float* top_diff,
                         float* top_out, float* dq, float* da, bool exact, hipStream_t s);
+int euclid_backward_mode();
+void set_euclid_backward_mode(int m);
+// simcross_rows_cosine.hip (W1 == W2 == 1, cosine; the same three instantiations)
 template <bool FWD, bool BWD>
 void launch_cosine_rows(int N, int D, const float* q, const float* a, const float* top_diff, float* top, float* norm0,
                         float* norm1, float* dq, float* da, hipStream_t s);
+// simcross_rows_f16.hip (W1 == W2 == 1, fp16 storage)
 int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top, void* dq,
                              void* da, bool bwd, hipStream_t s);
 int simcross_cosine_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top, float* norm0,
                              float* norm1, void* dq, void* da, bool bwd, hipStream_t s);
-int euclid_backward_mode();
-void set_euclid_backward_mode(int m);
 int f16_distance_mode();
 void set_f16_distance_mode(int m);
 // simcross_cross.hip

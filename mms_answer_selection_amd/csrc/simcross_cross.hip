@@ -10,8 +10,9 @@
 //   Cosine bwd  :226-250.
 //
 // Forward: one wave per (pair, j-tile, k-tile), q/a d-chunks staged in LDS, an RJ x RK register tile per lane, d
-// ascending per output.  W1 == W2 == 1 (sentence-vector pairs) has kernels of its own in simcross_rows.hip; the
-// entry points at the end of this file try those first and fall through to the grid kernels.
+// ascending per output.  W1 == W2 == 1 (sentence-vector pairs) has kernels of its own in simcross_rows.hip
+// (Euclid) and simcross_rows_cosine.hip; the entry points at the end of this file try those first and fall through to
+// the grid kernels.
 //
 // Compiled with -ffp-contract=off: the reference CPU build has no FMA
 // contraction, so mul and add must round separately to match it bitwise.
@@ -665,7 +666,8 @@ static void launch_cross_fwd(const float* q, const float* a, const float* n0,
 }
 
 // =============================== entry points ===============================
-// DESIGN.md 4.4b is the table this section is read against.  W1 == W2 == 1 tries simcross_rows.hip first.
+// DESIGN.md 4.4b is the table this section is read against.  W1 == W2 == 1 tries simcross_rows.hip (Euclid) or
+// simcross_rows_cosine.hip first.
 
 // The word-grid forward; gt.iq != nullptr: q and a are the embedding table and the Embed gather is fused in.
 static void cross_forward(int mode, int N, int W1, int W2, int D, const float* q, const float* a, float* top,

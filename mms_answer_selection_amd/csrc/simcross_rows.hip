@@ -1,12 +1,11 @@
-// csrc/simcross_rows.hip -- SimCross dist_mode 0 (cosine) and 1 (Euclidean) for W1 == W2 == 1 (sentence-vector
-// pairs; BASELINE cfg 2/5), fp32 and fp16 storage, for gfx950.  HBM-bound: no MFMA here.  The word-grid kernels
-// and the three fp32 entry points, which try this side first, are in simcross_cross.hip.
+// csrc/simcross_rows.hip -- SimCross dist_mode 1 (Euclidean) for W1 == W2 == 1 (sentence-vector pairs; BASELINE
+// cfg 2), fp32, for gfx950: the kernels, their routing and the per-thread backward mode.  HBM-bound: no MFMA here.
+// The word-grid kernels and the three fp32 entry points, which try this side first, are in simcross_cross.hip; the
+// rows kernels of dist_mode 0 and of half storage in the two other simcross_rows_*.hip.
 //
 // Reference semantics (all file:line in src/caffe/layers/sim_cross_layer.cpp):
 //   Euclid fwd  :96-111   T = 1/(1+sqrt(sum_d (q-a)^2)), d ascending, fp32.
 //   Euclid bwd  :208-225  tt = dT*T*T*T*(q-a)/(T-1+1e-9) (double divide); dq[d] = tt, da[d] = -tt.
-//   Cosine fwd  :112-139  n0,n1 = sqrt(dot) cached; T = dot/n0/n1.
-//   Cosine bwd  :226-250.
 //
 // A workgroup owns ROWS consecutive pairs, streams them with 16-byte loads into LDS, and ONE lane per pair walks d
 // ascending so the sum has the reference's order bit for bit.  The forward+backward fusion keeps q-a in LDS (or in
@@ -18,7 +17,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "cosine_math.h"
 #include "euclid_math.h"
 #include "mms_internal.h"
 
@@ -93,12 +91,7 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
       const int ir = r1 ? i - D4 : i;
       if (i < n4) sq4[r1 ? i + (st4 - D4) : i] = s;
       const float s4 = (i < n4) ? (s.x + s.y) + (s.z + s.w) : 0.f;
-      float2v c;                                   // (segment-0 part, segments-0-1 part)
-      c.x = (ir < h4) ? s4 : 0.f;
-      c.y = (ir < 2 * h4) ? s4 : 0.f;
-      const float2v z2 = {0.f, 0.f};
-      pred[0] += r1 ? z2 : c;
-      if (RW == 2) pred[RW - 1] += r1 ? c : z2;
+      spec_pred_add<RW>(pred, r1, ir, h4, s4);
     }
   }
   if (FWD) {
@@ -123,19 +116,9 @@ __global__ __launch_bounds__(256) void euclid_rows_wave_kernel(
   const EuclidCoef mine = euclid_coef(T, g);
   EuclidCoef kr[RW];
 #pragma unroll
-  for (int r = 0; r < RW; ++r) {
-    // lane r*LPR is a compile-time lane: v_readlane (no LDS round trip as with ds_bpermute)
-    kr[r].c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.c), r * LPR));
-    {
-      const long long dn = __double_as_longlong(mine.den), rc = __double_as_longlong(mine.rcp);
-      const unsigned dlo = __builtin_amdgcn_readlane((int)(unsigned)dn, r * LPR);
-      const unsigned dhi = __builtin_amdgcn_readlane((int)(unsigned)(dn >> 32), r * LPR);
-      const unsigned rlo = __builtin_amdgcn_readlane((int)(unsigned)rc, r * LPR);
-      const unsigned rhi = __builtin_amdgcn_readlane((int)(unsigned)(rc >> 32), r * LPR);
-      kr[r].den = __longlong_as_double((long long)(((unsigned long long)dhi << 32) | dlo));
-      kr[r].rcp = __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
-    }
-  }
+  for (int r = 0; r < RW; ++r)                   // lane r*LPR leads pair r's lane group
+    kr[r] = EuclidCoef{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.c), r * LPR)),
+                       readlane_f64(mine.den, r * LPR), readlane_f64(mine.rcp, r * LPR)};
   float4* dq4 = reinterpret_cast<float4*>(dq) + base4;
   float4* da4 = reinterpret_cast<float4*>(da) + base4;
   // all NIT float4s as ONE straight-line block (their instruction chains interleave),
@@ -702,300 +685,6 @@ __global__ __launch_bounds__(64 * WPB) void euclid_block_kernel(
   }
 }
 
-// ---- fp16 storage, fp32 arithmetic (BASELINE cfg 5) --------------------------
-// Same wave-centric structure with one pair per wave (cfg 5 is D = 1024): q, a,
-// dq, da live in HBM as IEEE half (half the bytes per pair: s = 2 in SURVEY
-// 8d's formulas); every half is widened exactly to fp32 on load, ALL arithmetic
-// is the fp32 reference arithmetic in the reference order, and only the final
-// dq / da are rounded (RNE) to half.  The scores stay fp32.  Hence:
-//   top == oracle(fp32(q_half), fp32(a_half)) bit for bit, and
-//   dq  == half(oracle dq) bit for bit.
-// The reference has no fp16 instantiation (common.hpp:41-44); this is an
-// MI355X-side storage format, not a change of the layer's numerics.
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-// RW pairs per wave (64 / RW lanes each).  The ordered sum runs with RW == 2 (D <= 400: beyond that its
-// speculation windows of 32 lanes miss too often, see simcross_euclid_rows_f16, and the lane-chain kernel
-// below takes over); a miss re-walks one segment exactly, so results never change, only time.
-// TREE (RW == 1 only): the distance is the TREE sum of the squares that the ordered variants use only to centre
-// their speculation windows -- no ordered chain, 8.3 instead of 19 us at cfg 5's shard.  The reference has no
-// fp16 instantiation, so there is no reference rounding to reproduce; SURVEY 8(d) holds cfg 5 to 1e-3 relative
-// against the fp32 oracle on the fp16-rounded inputs, and this sum is within ~1e-6 of it.  Opt-in
-// (mms_set_f16_distance_mode): the default stays the ordered sum, bit-identical to the fp32 layer's.
-template <int NIT, int RW, bool BWD, bool TREE = false>
-__global__ __launch_bounds__(256) void euclid_rows_wave_f16_kernel(
-    const _Float16* __restrict__ q, const _Float16* __restrict__ a,
-    const float* __restrict__ top_diff, float* __restrict__ top_out,
-    _Float16* __restrict__ dq, _Float16* __restrict__ da, int N, int D8) {
-  constexpr int LPR = 64 / RW;
-  extern __shared__ float4 lds4[];               // [4 waves][RW images] (euclid_math.h)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int row0 = (blockIdx.x * 4 + wave) * RW;
-  if (row0 >= N) return;
-  const int rows = min(RW, N - row0);
-  const int n8 = rows * D8;
-  const int D4 = 2 * D8;
-  const size_t base8 = (size_t)row0 * D8;
-  const half8* q8 = reinterpret_cast<const half8*>(q) + base8;
-  const half8* a8 = reinterpret_cast<const half8*>(a) + base8;
-  const int h4 = spec_h4(D4), st4 = 3 * h4;
-  float4* sq4 = lds4 + (size_t)wave * RW * st4;
-
-  half8 x[NIT], y[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it;
-    const int ii = i < n8 ? i : 0;
-    x[it] = q8[ii];
-    y[it] = a8[ii];
-  }
-  const int grp = lane / LPR, j = lane % LPR;
-  const int grow = min(grp, rows - 1);           // a missing 2nd pair mirrors the 1st (results unused)
-  float g = 0.f;
-  if (BWD) g = top_diff[row0 + grow];
-
-  float4 df[2 * NIT];
-  float tree_total = 0.f;
-  float2v pred[RW];                              // per pair: (pred1, pred2) partial sums
-#pragma unroll
-  for (int r = 0; r < RW; ++r) pred[r] = (float2v){0.f, 0.f};
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it;
-    const bool r1 = (RW == 2) && (i >= D8);
-    const int ir = r1 ? i - D8 : i;              // half8 index inside its pair
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      float4 d;
-      d.x = (float)x[it][4 * hh + 0] - (float)y[it][4 * hh + 0];
-      d.y = (float)x[it][4 * hh + 1] - (float)y[it][4 * hh + 1];
-      d.z = (float)x[it][4 * hh + 2] - (float)y[it][4 * hh + 2];
-      d.w = (float)x[it][4 * hh + 3] - (float)y[it][4 * hh + 3];
-      df[2 * it + hh] = d;
-      float4 s;
-      s.x = d.x * d.x; s.y = d.y * d.y; s.z = d.z * d.z; s.w = d.w * d.w;
-      const int i4 = 2 * ir + hh;                // float4 index inside the pair's image
-      if constexpr (!TREE) {
-        if (i < n8) sq4[(r1 ? st4 : 0) + i4] = s;
-      }
-      const float s4 = (i < n8) ? (s.x + s.y) + (s.z + s.w) : 0.f;
-      if (TREE) tree_total += s4;
-      float2v c;
-      c.x = (i4 < h4) ? s4 : 0.f;
-      c.y = (i4 < 2 * h4) ? s4 : 0.f;
-      const float2v z2 = {0.f, 0.f};
-      pred[0] += r1 ? z2 : c;
-      if (RW == 2) pred[RW - 1] += r1 ? c : z2;
-    }
-  }
-  if constexpr (!TREE) {                         // the tree sum reads no image: its launch has no LDS to pad
-    const int npad = st4 - D4;
-    if (lane < RW * npad) sq4[(lane / npad) * st4 + D4 + (lane % npad)] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  float my1 = 0.f, my2 = 0.f;
-#pragma unroll
-  for (int r = 0; r < RW; ++r) {
-    const float p1 = wave_sum(pred[r].x), p2 = wave_sum(pred[r].y);
-    if (r == grow) { my1 = p1; my2 = p2; }
-  }
-  float dist;
-  if constexpr (TREE) {
-    dist = wave_sum(tree_total);
-  } else {
-    wave_lds_sync();
-    dist = chain_sum_speculative<LPR>(sq4 + grow * st4, D4, my1, my2, j, grp * LPR);
-  }
-  const float T = 1.0f / (1.0f + sqrtf(dist));
-  if (BWD) asm volatile("" : "+v"(g));          // in a register before the store of T (see euclid_pair32_kernel)
-  if (j == 0 && grp < rows) top_out[row0 + grp] = T;
-  if (!BWD) return;
-
-  const EuclidCoef mine = euclid_coef(T, g);
-  EuclidCoef kr[RW];
-#pragma unroll
-  for (int r = 0; r < RW; ++r) {                 // lane r*LPR is a compile-time lane: v_readlane
-    kr[r].c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine.c), r * LPR));
-    const long long dn = __double_as_longlong(mine.den), rc = __double_as_longlong(mine.rcp);
-    const unsigned dlo = __builtin_amdgcn_readlane((int)(unsigned)dn, r * LPR);
-    const unsigned dhi = __builtin_amdgcn_readlane((int)(unsigned)(dn >> 32), r * LPR);
-    const unsigned rlo = __builtin_amdgcn_readlane((int)(unsigned)rc, r * LPR);
-    const unsigned rhi = __builtin_amdgcn_readlane((int)(unsigned)(rc >> 32), r * LPR);
-    kr[r].den = __longlong_as_double((long long)(((unsigned long long)dhi << 32) | dlo));
-    kr[r].rcp = __longlong_as_double((long long)(((unsigned long long)rhi << 32) | rlo));
-  }
-  half8* dq8 = reinterpret_cast<half8*>(dq) + base8;
-  half8* da8 = reinterpret_cast<half8*>(da) + base8;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it;
-    if (i >= n8) break;
-    const EuclidCoef& k = (RW == 2 && i >= D8) ? kr[RW - 1] : kr[0];
-    half8 o0, o1;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const float4 t = euclid_tt4(k, df[2 * it + hh]);
-      o0[4 * hh + 0] = (_Float16)(0.f + t.x); o0[4 * hh + 1] = (_Float16)(0.f + t.y);
-      o0[4 * hh + 2] = (_Float16)(0.f + t.z); o0[4 * hh + 3] = (_Float16)(0.f + t.w);
-      o1[4 * hh + 0] = (_Float16)(0.f + (-t.x)); o1[4 * hh + 1] = (_Float16)(0.f + (-t.y));
-      o1[4 * hh + 2] = (_Float16)(0.f + (-t.z)); o1[4 * hh + 3] = (_Float16)(0.f + (-t.w));
-    }
-    stream_store_vec(dq8 + i, o0);
-    stream_store_vec(da8 + i, o1);
-  }
-}
-
-// The ORDERED distance at large D without speculation (round 3; D > 400, where a speculative chain with one pair per
-// wave was 55 % of the launch: 20.2 us at cfg 5's shard against 13.2 here, profiles/r03_f16_lanewalk.txt).  One wave per pair loads,
-// squares and later differentiates its pair exactly as above; the squares go to LDS as the pair's image, and after one
-// workgroup barrier LANE p of wave 0 walks pair p's image front to back -- the reference's d-ascending fp32 sum
-// (sim_cross_layer.cpp:100-106) as 4 D4 dependent adds fed by D4 ds_read_b128, about 2.4 us for D = 1024 whatever the
-// number of lanes walking.  Eight pairs per workgroup, several workgroups per CU: one workgroup's walk hides behind the
-// others' loads and stores (the launch is HBM-bound: 67 MB).  No windows, no misses, no re-walks; bit-identical by
-// construction.
-template <int NIT, bool BWD, int WPB = 8>
-__global__ __launch_bounds__(64 * WPB) void euclid_rows_lanechain_f16_kernel(
-    const _Float16* __restrict__ q, const _Float16* __restrict__ a, const float* __restrict__ top_diff,
-    float* __restrict__ top_out, _Float16* __restrict__ dq, _Float16* __restrict__ da, int N, int D8) {
-  extern __shared__ float4 lc_lds[];             // [WPB pairs][D4 + 1] float4, then WPB floats (the distances)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int row = blockIdx.x * WPB + wave;
-  const int rowc = row < N ? row : N - 1;        // a missing pair mirrors the last one (results unused)
-  const int D4 = 2 * D8, st4 = D4 + 1;
-  const half8* q8 = reinterpret_cast<const half8*>(q) + (size_t)rowc * D8;
-  const half8* a8 = reinterpret_cast<const half8*>(a) + (size_t)rowc * D8;
-  float4* img = lc_lds + (size_t)wave * st4;
-  float* dist_lds = reinterpret_cast<float*>(lc_lds + (size_t)WPB * st4);
-
-  half8 x[NIT], y[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it, ii = i < D8 ? i : 0;
-    x[it] = q8[ii];
-    y[it] = a8[ii];
-  }
-  float g = 0.f;
-  if (BWD) g = top_diff[rowc];
-  float4 df[2 * NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      float4 d;
-      d.x = (float)x[it][4 * hh + 0] - (float)y[it][4 * hh + 0];
-      d.y = (float)x[it][4 * hh + 1] - (float)y[it][4 * hh + 1];
-      d.z = (float)x[it][4 * hh + 2] - (float)y[it][4 * hh + 2];
-      d.w = (float)x[it][4 * hh + 3] - (float)y[it][4 * hh + 3];
-      df[2 * it + hh] = d;
-      float4 sq;
-      sq.x = d.x * d.x; sq.y = d.y * d.y; sq.z = d.z * d.z; sq.w = d.w * d.w;
-      if (i < D8) img[2 * i + hh] = sq;
-    }
-  }
-  __syncthreads();
-  if (wave == 0 && lane < WPB) {
-    const float4* mine = lc_lds + (size_t)lane * st4;
-    float acc = 0.f;
-#pragma unroll 8
-    for (int i4 = 0; i4 < D4; ++i4) {
-      const float4 v = mine[i4];
-      acc += v.x; acc += v.y; acc += v.z; acc += v.w;
-    }
-    dist_lds[lane] = acc;
-  }
-  __syncthreads();
-  if (row >= N) return;
-  const float dist = dist_lds[wave];
-  const float T = 1.0f / (1.0f + sqrtf(dist));
-  if (BWD) asm volatile("" : "+v"(g));          // in a register before the store of T (see euclid_pair32_kernel)
-  if (lane == 0) top_out[row] = T;
-  if (!BWD) return;
-  const EuclidCoef k = euclid_coef(T, g);
-  half8* dq8 = reinterpret_cast<half8*>(dq) + (size_t)row * D8;
-  half8* da8 = reinterpret_cast<half8*>(da) + (size_t)row * D8;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it;
-    if (i >= D8) break;
-    half8 o0, o1;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const float4 t = euclid_tt4(k, df[2 * it + hh]);
-      o0[4 * hh + 0] = (_Float16)(0.f + t.x); o0[4 * hh + 1] = (_Float16)(0.f + t.y);
-      o0[4 * hh + 2] = (_Float16)(0.f + t.z); o0[4 * hh + 3] = (_Float16)(0.f + t.w);
-      o1[4 * hh + 0] = (_Float16)(0.f + (-t.x)); o1[4 * hh + 1] = (_Float16)(0.f + (-t.y));
-      o1[4 * hh + 2] = (_Float16)(0.f + (-t.z)); o1[4 * hh + 3] = (_Float16)(0.f + (-t.w));
-    }
-    stream_store_vec(dq8 + i, o0);
-    stream_store_vec(da8 + i, o1);
-  }
-}
-
-// fp16-STORAGE cosine, W1 = W2 = 1 (round 3; cfg 5's "multi-modal concat embeddings, fp16" with dist_mode 0): one
-// wave per pair, a lane holds NIT half8 of q and of a (all 16-byte loads up front, kept for the backward), fp32
-// arithmetic on the exactly-widened inputs: three tree sums (the reference's cblas_sdot has no defined order), the
-// reference's T = q.a / nq / na with its two successive divisions (sim_cross_layer.cpp:135) and its cached NORMS
-// (:118); backward through per-pair factors as cosine_pair32_kernel (c1 = g / n0 / n1, c2 = g T / n0^2, c3 = g T / n1^2,
-// IEEE divisions once per pair), gradients stored as RNE halves.  Bytes per pair: reads 2 D s + 4, writes 2 D s + 12.
-template <int NIT, bool BWD>
-__global__ __launch_bounds__(256) void cosine_rows_wave_f16_kernel(
-    const _Float16* __restrict__ q, const _Float16* __restrict__ a, const float* __restrict__ top_diff,
-    float* __restrict__ top, float* __restrict__ norm0, float* __restrict__ norm1,
-    _Float16* __restrict__ dq, _Float16* __restrict__ da, int N, int D8) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  const half8* q8 = reinterpret_cast<const half8*>(q) + (size_t)row * D8;
-  const half8* a8 = reinterpret_cast<const half8*>(a) + (size_t)row * D8;
-  half8 x[NIT], y[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it, ic = i < D8 ? i : D8 - 1;
-    x[it] = q8[ic];
-    y[it] = a8[ic];
-  }
-  float g = BWD ? top_diff[row] : 0.f;
-  float sqq = 0.f, saa = 0.f, sqa = 0.f;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    if (lane + 64 * it < D8) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float xf = (float)x[it][e], yf = (float)y[it][e];
-        sqq += xf * xf; saa += yf * yf; sqa += xf * yf;
-      }
-    }
-  }
-  sqq = wave_sum(sqq); saa = wave_sum(saa); sqa = wave_sum(sqa);
-  const float n0 = sqrtf(sqq), n1 = sqrtf(saa);
-  const float T = sqa / n0 / n1;                       // two successive divisions (:135)
-  if (BWD) asm volatile("" : "+v"(g));
-  if (lane == 0) {
-    top[row] = T;
-    if (norm0) norm0[row] = n0;
-    if (norm1) norm1[row] = n1;
-  }
-  if (!BWD) return;
-  const float c1 = g / n0 / n1, c2 = g * T / (n0 * n0), c3 = g * T / (n1 * n1);
-  half8* dq8 = reinterpret_cast<half8*>(dq) + (size_t)row * D8;
-  half8* da8 = reinterpret_cast<half8*>(da) + (size_t)row * D8;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = lane + 64 * it;
-    if (i < D8) {
-      half8 o0, o1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float xf = (float)x[it][e], yf = (float)y[it][e];
-        o0[e] = (_Float16)(0.f + (c1 * yf - c2 * xf));   // dq = g (a / n0 / n1 - q T / n0^2)   (:239-241)
-        o1[e] = (_Float16)(0.f + (c1 * xf - c3 * yf));   // da = g (q / n0 / n1 - a T / n1^2)   (:243-245)
-      }
-      __builtin_nontemporal_store(o0, dq8 + i);
-      __builtin_nontemporal_store(o1, da8 + i);
-    }
-  }
-}
-
 // ---- generic fallback (any D, any alignment): workgroup of ROWS pairs --------
 // Forward (BWD=false) or forward+backward (BWD=true) for W1=W2=1, Euclidean.
 // LDS: diff[ROWS*D] floats (dynamic) + per-row coefficient slots.
@@ -1056,141 +745,8 @@ __global__ __launch_bounds__(256) void euclid_rows_bwd_kernel(
   }
 }
 
-// Cosine, W1=W2=1: one wave per pair; three dot products reduced with a fixed
-// butterfly (the reference's order here is whatever its BLAS does).
-// BWD fuses the backward with a known top_diff.
-template <bool VEC4, bool FWD, bool BWD>
-__global__ __launch_bounds__(256) void cosine_rows_kernel(
-    const float* __restrict__ q, const float* __restrict__ a,
-    const float* __restrict__ top_diff, float* __restrict__ top,
-    float* __restrict__ norm0, float* __restrict__ norm1,
-    float* __restrict__ dq, float* __restrict__ da, int N, int D) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  const float* qr = q + (size_t)row * D;
-  const float* ar = a + (size_t)row * D;
-  float g = 0.f;
-  if (BWD) g = top_diff[row];                    // requested up front; pinned before the stores of the forward
-  float T, n0, n1;
-  if (FWD) {
-    float sqq = 0.f, saa = 0.f, sqa = 0.f;
-    if (VEC4) {
-      const float4* q4 = reinterpret_cast<const float4*>(qr);
-      const float4* a4 = reinterpret_cast<const float4*>(ar);
-      for (int i = lane; i < (D >> 2); i += 64) {
-        const float4 x = q4[i], y = a4[i];
-        cosine_acc4(sqq, x, x); cosine_acc4(saa, y, y); cosine_acc4(sqa, x, y);
-      }
-    } else {
-      for (int i = lane; i < D; i += 64) {
-        const float x = qr[i], y = ar[i];
-        cosine_acc1(sqq, x, x); cosine_acc1(saa, y, y); cosine_acc1(sqa, x, y);
-      }
-    }
-    sqq = wave_sum(sqq); saa = wave_sum(saa); sqa = wave_sum(sqa);
-    const CosineScore c = cosine_score(sqq, saa, sqa);
-    T = c.T; n0 = c.n0; n1 = c.n1;
-    if (BWD) asm volatile("" : "+v"(g));
-    if (lane == 0) { top[row] = T; norm0[row] = n0; norm1[row] = n1; }
-  } else {
-    T = top[row]; n0 = norm0[row]; n1 = norm1[row];
-  }
-  if (!BWD) return;
-  float* dqr = dq + (size_t)row * D;
-  float* dar = da + (size_t)row * D;
-  // :239-245   dq += g*(a/n0/n1 - q*T/(n0*n0)) ; da += g*(q/n0/n1 - a*T/(n1*n1))
-  const float n00 = n0 * n0, n11 = n1 * n1;
-  if (VEC4) {
-    const float4* q4 = reinterpret_cast<const float4*>(qr);
-    const float4* a4 = reinterpret_cast<const float4*>(ar);
-    float4* dq4 = reinterpret_cast<float4*>(dqr);
-    float4* da4 = reinterpret_cast<float4*>(dar);
-    for (int i = lane; i < (D >> 2); i += 64) {
-      const float4 x = q4[i], y = a4[i];
-      const float4 o0 = cosine_grad4_div(g, n0, n1, T, n00, y, x);
-      const float4 o1 = cosine_grad4_div(g, n0, n1, T, n11, x, y);
-      stream_store(dq4 + i, o0);
-      stream_store(da4 + i, o1);
-    }
-  } else {
-    for (int i = lane; i < D; i += 64) {
-      const float x = qr[i], y = ar[i];
-      dqr[i] = cosine_grad_div(g, n0, n1, T, n00, y, x);
-      dar[i] = cosine_grad_div(g, n0, n1, T, n11, x, y);
-    }
-  }
-}
-
-// Cosine, W1=W2=1, the GloVe widths (D = 100 / 200 / 300): the data movement of
-// euclid_pair32_kernel -- 32 lanes per pair, two pairs per wave, every 16-byte load of q and a issued
-// up front and kept in registers for the backward, half-wave DPP reductions, streaming stores --
-// without the ordered chain (the reference's dot products are cblas_sdot: no defined order, 1e-5
-// contract).  The backward multiplies by per-pair factors 1/n0/n1, T/n0^2, T/n1^2 computed once
-// (IEEE divisions) instead of dividing per element (:239-245 written out costs six divisions per
-// (q_d, a_d)): a few ulp from the reference's expression, inside the same 1e-5.
-template <int D4C, bool FWD, bool BWD, int WPB>
-__global__ __launch_bounds__(64 * WPB) void cosine_pair32_kernel(
-    int N, const float* __restrict__ q, const float* __restrict__ a,
-    const float* __restrict__ top_diff, float* __restrict__ top, float* __restrict__ norm0,
-    float* __restrict__ norm1, float* __restrict__ dq, float* __restrict__ da) {
-  constexpr int NIT = (D4C + 31) / 32;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane >> 5, j = lane & 31;
-  const int want = (blockIdx.x * WPB + wave) * 2 + grp;
-  const bool have = want < N;
-  const int row = have ? want : N - 1;
-  const float4* q4 = reinterpret_cast<const float4*>(q) + (size_t)row * D4C;
-  const float4* a4 = reinterpret_cast<const float4*>(a) + (size_t)row * D4C;
-  float4 x[NIT], y[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = j + 32 * it;
-    const int ii = i < D4C ? i : 0;              // clamp: keep the load unconditional
-    x[it] = q4[ii];
-    y[it] = a4[ii];
-  }
-  float T, n0, n1;
-  if (FWD) {
-    float sqq = 0.f, saa = 0.f, sqa = 0.f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      if (j + 32 * it < D4C) {
-        const float4 u = x[it], v = y[it];
-        cosine_acc4(sqq, u, u); cosine_acc4(saa, v, v); cosine_acc4(sqa, u, v);
-      }
-    }
-    sqq = half_wave_sum(sqq); saa = half_wave_sum(saa); sqa = half_wave_sum(sqa);
-    const CosineScore c = cosine_score(sqq, saa, sqa);
-    T = c.T; n0 = c.n0; n1 = c.n1;
-    if (j == 0 && have) { top[row] = T; norm0[row] = n0; norm1[row] = n1; }
-  } else {
-    T = top[row]; n0 = norm0[row]; n1 = norm1[row];
-  }
-  if (!BWD) return;
-  const float g = top_diff[row];
-  const CosineFactors f = cosine_factors(T, n0, n1);
-  float4* dq4 = reinterpret_cast<float4*>(dq) + (size_t)row * D4C;
-  float4* da4 = reinterpret_cast<float4*>(da) + (size_t)row * D4C;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = j + 32 * it;
-    if (i < D4C && have) {
-      const float4 u = x[it], v = y[it];
-      const float4 o0 = cosine_grad4_fac(g, f.inv01, f.cq, v, u);
-      const float4 o1 = cosine_grad4_fac(g, f.inv01, f.ca, u, v);
-      stream_store(dq4 + i, o0);
-      stream_store(da4 + i, o1);
-    }
-  }
-}
-
 // ================================= dispatch =================================
 // DESIGN.md 4.4b is the table this section is read against.
-
-// How the fp16-storage kernels sum a pair's squares (include/mms.h: mms_set_f16_distance_mode); per calling thread.
-static thread_local int t_f16_distance_mode = MMS_F16_DISTANCE_ORDERED;
-int f16_distance_mode() { return t_f16_distance_mode; }
-void set_f16_distance_mode(int m) { t_f16_distance_mode = m; }
 
 // Backward arithmetic of the Euclidean term (include/mms.h: mms_set_euclid_backward_mode).  The mode
 // belongs to the calling thread (Caffe drives each GPU from its own thread); a thread that never set it
@@ -1213,11 +769,6 @@ void set_euclid_backward_mode(int m) { t_euclid_bwd_mode = m; }
 constexpr int kRows = 8;       // pairs per workgroup in the generic rows kernels
 constexpr int kRowsThreads = 256;
 
-// every array the launch touches (p2, p3: the gradients, null in a forward) takes 16-byte accesses
-static bool vec4_ok(int D, const void* p0, const void* p1, const void* p2, const void* p3) {
-  return (D % 4 == 0) && aligned16(p0) && aligned16(p1) && (!p2 || aligned16(p2)) && (!p3 || aligned16(p3));
-}
-
 // The line-aligned lane map of euclid_pair32_kernel (SHIFT) gives a lane the column that sits at the same place
 // of a 128-byte line in every array, so it serves a launch only when all the arrays it touches (as in vec4_ok)
 // start at the same offset within a line.  Allocator-aligned blobs do; views carved at unrelated offsets get
@@ -1236,11 +787,6 @@ enum class EuclidRows { kPair32, kWave, kGeneric, kNone };
 static EuclidRows euclid_rows_route(int D, const void* q, const void* a, const void* dq, const void* da) {
   if (vec4_ok(D, q, a, dq, da) && wave_width_ok(D)) return glove_width(D) ? EuclidRows::kPair32 : EuclidRows::kWave;
   return rows_fit(D) ? EuclidRows::kGeneric : EuclidRows::kNone;
-}
-enum class CosineRows { kPair32, kVec4, kScalar };
-static CosineRows cosine_rows_route(int D, const void* q, const void* a, const void* dq, const void* da) {
-  if (!vec4_ok(D, q, a, dq, da)) return CosineRows::kScalar;
-  return glove_width(D) ? CosineRows::kPair32 : CosineRows::kVec4;
 }
 
 // Eight waves (16 pairs) per workgroup: N = 4096 is then 256 workgroups, one per CU, two waves
@@ -1343,98 +889,10 @@ bool launch_euclid_rows(int N, int D, const float* q, const float* a, const floa
   return true;
 }
 
-// Cosine, W1 = W2 = 1: always served.  A backward alone reads top / norm0 / norm1 through the same parameters the
-// forward writes them through.
-template <bool FWD, bool BWD>
-void launch_cosine_rows(int N, int D, const float* q, const float* a, const float* top_diff, float* top,
-                        float* norm0, float* norm1, float* dq, float* da, hipStream_t s) {
-  const CosineRows route = cosine_rows_route(D, q, a, dq, da);
-  if (route == CosineRows::kPair32) {
-    constexpr int WPB = 8;
-    const unsigned grid = (unsigned)((N + 2 * WPB - 1) / (2 * WPB));
-    with_glove_d4(D, [&](auto W) {
-      hipLaunchKernelGGL((cosine_pair32_kernel<decltype(W)::value, FWD, BWD, WPB>), dim3(grid), dim3(64 * WPB), 0, s,
-                         N, q, a, top_diff, top, norm0, norm1, dq, da);
-    });
-  } else {
-    hipLaunchKernelGGL((route == CosineRows::kVec4 ? cosine_rows_kernel<true, FWD, BWD> : cosine_rows_kernel<false, FWD, BWD>),
-                       dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, q, a, top_diff, top, norm0, norm1, dq, da, N, D);
-  }
-}
-
 #define MMS_ROWS_INSTANCE(F, B)                                                                                   \
   template bool launch_euclid_rows<F, B>(int, int, const float*, const float*, const float*, const float*, float*, \
-                                         float*, float*, bool, hipStream_t);                                      \
-  template void launch_cosine_rows<F, B>(int, int, const float*, const float*, const float*, float*, float*,      \
-                                         float*, float*, float*, hipStream_t);
+                                         float*, float*, bool, hipStream_t);
 MMS_ROWS_INSTANCE(true, false) MMS_ROWS_INSTANCE(false, true) MMS_ROWS_INSTANCE(true, true)
 #undef MMS_ROWS_INSTANCE
-
-// ---- fp16 storage ------------------------------------------------------------
-// half8 accesses of every array touched, at most four per operand per lane of a wave
-static bool f16_rows_ok(int D, const void* q, const void* a, const void* dq, const void* da, bool bwd) {
-  return D % 8 == 0 && D <= 2048 && aligned16(q) && aligned16(a) && (!bwd || (aligned16(dq) && aligned16(da)));
-}
-
-int simcross_cosine_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff, float* top,
-                             float* norm0, float* norm1, void* dq, void* da, bool bwd, hipStream_t s) {
-  if (N == 0) return MMS_OK;
-  if (!f16_rows_ok(D, q, a, dq, da, bwd)) return MMS_ERR_UNSUPPORTED;
-  const int D8 = D / 8, nit = (D8 + 63) / 64;
-  static constexpr decltype(&cosine_rows_wave_f16_kernel<1, true>) kernels[2][4] = {
-      MMS_NIT4(cosine_rows_wave_f16_kernel, false), MMS_NIT4(cosine_rows_wave_f16_kernel, true)};
-  hipLaunchKernelGGL(kernels[bwd][nit - 1], dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s,
-                     static_cast<const _Float16*>(q), static_cast<const _Float16*>(a), top_diff, top, norm0, norm1,
-                     static_cast<_Float16*>(dq), static_cast<_Float16*>(da), N, D8);
-  return launch_status();
-}
-
-int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const float* top_diff,
-                             float* top, void* dq, void* da, bool bwd, hipStream_t s) {
-  if (N == 0) return MMS_OK;
-  if (!f16_rows_ok(D, q, a, dq, da, bwd)) return MMS_ERR_UNSUPPORTED;
-  const int D8 = D / 8;
-  const bool tree = f16_distance_mode() == MMS_F16_DISTANCE_TREE;
-  const int rw = tree ? 1 : wave_pairs(D);        // tree sum: one pair per wave whatever D, no speculation windows to fit
-  const int nit = (rw * D8 + 63) / 64;
-  using Kernel = decltype(&euclid_rows_wave_f16_kernel<1, 1, true>);   // the three families share one signature
-  Kernel k;
-  unsigned grid, threads = 256;
-  size_t lds;
-  if (tree) {
-    static constexpr Kernel kernels[2][4] = {MMS_NIT4(euclid_rows_wave_f16_kernel, 1, false, true),
-                                             MMS_NIT4(euclid_rows_wave_f16_kernel, 1, true, true)};
-    k = kernels[bwd][nit - 1];
-    grid = (unsigned)((N + 3) / 4);
-    lds = 0;                                          // no image: the tree instantiations touch no LDS
-  } else if (rw == 2) {
-    static constexpr Kernel kernels[2][4] = {MMS_NIT4(euclid_rows_wave_f16_kernel, 2, false),
-                                             MMS_NIT4(euclid_rows_wave_f16_kernel, 2, true)};
-    k = kernels[bwd][nit - 1];
-    grid = (unsigned)((N + 4 * rw - 1) / (4 * rw));
-    lds = spec_image_lds(4, rw, 2 * D8);
-  } else {
-    // ordered beyond two pairs per wave: lane p of wave 0 walks pair p's image
-    constexpr int wpb = 8;                            // 4 / 8 / 16 waves measured alike (profiles/r03_f16_lanewalk.txt)
-    static constexpr Kernel kernels[2][4] = {MMS_NIT4(euclid_rows_lanechain_f16_kernel, false, wpb),
-                                             MMS_NIT4(euclid_rows_lanechain_f16_kernel, true, wpb)};
-    static const bool once = [] {
-      for (const auto& row : kernels)
-        for (const Kernel f : row)
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024);
-      return true;
-    }();
-    (void)once;
-    k = kernels[bwd][nit - 1];
-    grid = (unsigned)((N + wpb - 1) / wpb);
-    threads = 64 * wpb;
-    lds = ((size_t)wpb * (2 * D8 + 1) + 4) * sizeof(float4);
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, s, static_cast<const _Float16*>(q),
-                     static_cast<const _Float16*>(a), top_diff, top, static_cast<_Float16*>(dq),
-                     static_cast<_Float16*>(da), N, D8);
-  return launch_status();
-}
 
 }  // namespace mms

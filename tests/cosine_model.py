@@ -1,4 +1,4 @@
-"""Inputs, references and error bars for the cosine SimCross layer (csrc/simcross_rows.hip, csrc/simcross_cross.hip, csrc/cosine_math.h,
+"""Inputs, references and error bars for the cosine SimCross layer (csrc/simcross_rows_cosine.hip,csrc/simcross_cross.hip, csrc/cosine_math.h,
 dist_mode 0): q (N, W1, D), a (N, W2, D), top / dT (N, 1, W1, W2), norm0 (N, W1), norm1 (N, W2).
 
   n0_j = sqrt(q_j . q_j)   n1_k = sqrt(a_k . a_k)   T_jk = (q_j . a_k) / n0_j / n1_k          (sim_cross_layer.cpp:112-139)

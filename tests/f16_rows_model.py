@@ -1,4 +1,4 @@
-"""The fp16-storage sentence-vector family (csrc/simcross_rows.hip: euclid_rows_wave_f16_kernel, euclid_rows_lanechain_f16_kernel,
+"""The fp16-storage sentence-vector family (csrc/simcross_rows_f16.hip: euclid_rows_wave_f16_kernel, euclid_rows_lanechain_f16_kernel,
 cosine_rows_wave_f16_kernel behind mms_simcross_{euclid,cosine}_forward[_backward]_f16): the host routing restated in Python, the
 shapes that reach every kernel instantiation, the references and the bars.  q, a, dq, da (N, 1, D) halves; top, norms, top_diff fp32.
 
@@ -53,7 +53,7 @@ SPEC_WINDOW_32 = 12          # euclid_math.h: SpecPlan<32>::H1, ulps either side
 # routing
 # ----------------------------------------------------------------------------------------------------------------------
 def f16_rows_ok(D, q=0, a=0, dq=0, da=0, bwd=False):
-    """simcross_rows.hip: f16_rows_ok; q, a, dq, da are addresses."""
+    """simcross_rows_f16.hip: f16_rows_ok; q, a, dq, da are addresses."""
     return D % 8 == 0 and D <= MAX_D and q % 16 == 0 and a % 16 == 0 and (not bwd or (dq % 16 == 0 and da % 16 == 0))
 
 

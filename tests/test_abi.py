@@ -58,6 +58,14 @@ def test_code_object_is_gfx950_only():
     assert targets == {b"gfx950"}, targets
 
 
+def test_every_hip_source_is_built_once():
+    """build.HIP_SOURCES is the csrc/*.hip files, each named once: a new source cannot be forgotten or listed twice."""
+    from mms_answer_selection_amd import build
+    on_disk = {f for f in os.listdir(build.CSRC) if f.endswith(".hip")}
+    assert set(build.HIP_SOURCES) == on_disk, sorted(on_disk.symmetric_difference(build.HIP_SOURCES))
+    assert len(build.HIP_SOURCES) == len(set(build.HIP_SOURCES)), sorted(build.HIP_SOURCES)
+
+
 def test_product_does_not_touch_the_oracle():
     """The product package must not import or link oracle/ (tier rule 3)."""
     pkg = os.path.join(ROOT, "mms_answer_selection_amd")

@@ -1,4 +1,4 @@
-"""Cosine SimCross (dist_mode 0: csrc/simcross_rows.hip, csrc/simcross_cross.hip, csrc/cosine_math.h) on every kernel route: exact-sum probes
+"""Cosine SimCross (dist_mode 0: csrc/simcross_rows_cosine.hip,csrc/simcross_cross.hip, csrc/cosine_math.h) on every kernel route: exact-sum probes
 bit for bit, gradients at bars counted from the roundings, dense data against fp64, and the edge rows.
 
 tests/test_gpu_parity.py holds cosine to 1e-5 max(1, max |ref|) on ten shapes, all with N <= 4 on grids: a score wrong by 2^-14

@@ -1,5 +1,5 @@
 """The fp16-storage sentence-vector calls (mms_simcross_euclid_forward[_backward]_f16, mms_simcross_cosine_forward[_backward]_f16;
-csrc/simcross_rows.hip) on every kernel instantiation: the ordered Euclid kernels bit for bit, the tree sum and the cosine kernel
+csrc/simcross_rows_f16.hip) on every kernel instantiation: the ordered Euclid kernels bit for bit, the tree sum and the cosine kernel
 against fp64 with gradients held to the half bracket, exact-sum probes, edge rows, guard bands and refusals.
 
 tests/test_gpu_parity.py runs these calls at D = 8, 304, 408, 512, 520, 1024, 2048: NIT 1, 2 and 4 of the MMS_NIT4 tables, never
