@@ -1,6 +1,6 @@
 /*
  * include/mms_layer.h -- C handle API over the C++ mirror of the Caffe
- * Layer/Blob interface (libmms_caffe.so, csrc/caffe_api.hpp + caffe_layers.cpp).
+ * Layer/Blob interface (libmms_caffe.so, csrc/caffe_api.hpp + layer_handles.cpp).
  *
  * The C++ classes are what a Caffe build would use directly;
  * this handle API exists so that non-C++ hosts -- the pytest suite, a pycaffe

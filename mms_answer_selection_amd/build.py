@@ -1,4 +1,4 @@
-"""Build libmms_hip.so (HIP kernels + C ABI) for gfx950 with hipcc, in-tree.
+"""Build libmms_hip.so (HIP kernels + C ABI) and libmms_caffe.so (the Caffe-API mirror) for gfx950 with hipcc, in-tree.
 
 hipcc cross-compiles without a GPU.  Flags that matter for parity:
   -ffp-contract=off   the reference CPU build has no FMA contraction; mul and
@@ -22,8 +22,13 @@ LIB = os.path.join(HERE, "libmms_hip.so")
 LAYER_LIB = os.path.join(HERE, "libmms_caffe.so")
 
 HIP_SOURCES = ["mms_abi.hip", "simcross_rows.hip", "simcross_rows_cosine.hip", "simcross_rows_f16.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "head.hip", "solver.hip"]
+# libmms_caffe.so: the Caffe-API mirror, host code compiled as HIP sources (caffe_api.hpp includes the HIP runtime header)
+LAYER_SOURCES = ["caffe_runtime.cpp", "prototxt_reader.cpp", "layers_scoring.cpp", "layers_embed.cpp", "layers_metrics.cpp",
+                 "layers_hdf5data.cpp", "path_net.cpp", "layer_handles.cpp", "caffemodel_io.cpp", "hdf5_io.cpp"]
+
+
 def _hip_headers():
-    """Every header under csrc/ and under include/ is a dependency of every .hip object (panel_gemm.h is included by
+    """Every header under csrc/ and under include/ is a dependency of every object (panel_gemm.h is included by
     simmatrix.hip, gemm32.h by four sources, mms_conv.h and mms_head.h by one each, ...): found by glob so that a new
     header cannot be forgotten."""
     return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")) +
@@ -39,6 +44,7 @@ HIPCC_FLAGS = [
 # triplet_steps.hip: the arrival atomics of the fused steps are issued by ONE lane and their return values are consumed
 # after the gradient stores; the atomic optimizer's wave scan + readfirstlane would pull the wait to the issue.
 EXTRA_FLAGS = {"triplet_steps.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+LAYER_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-x", "hip", "--offload-arch=gfx950", "-Wall"]
 
 
 def _hipcc():
@@ -62,61 +68,56 @@ def _compile_one(args):
     subprocess.check_call(cmd)
 
 
-def build_hip(force=False, verbose=False):
-    """One object per .hip source (compiled in parallel, rebuilt only when stale), then one link."""
+def _compile_objects(sources, flags_for, force, verbose):
+    """One object under build/ per source of csrc/ (compiled in parallel, rebuilt only when the source, a header or this
+    file is newer).  flags_for(name) gives the compile flags of one source.  Returns (objects, whether any was compiled)."""
     from concurrent.futures import ThreadPoolExecutor
     hdrs = _hip_headers() + [os.path.abspath(__file__)]
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    cflags = [f for f in HIPCC_FLAGS if f != "-shared"]
     jobs, objs = [], []
-    for f in HIP_SOURCES:
+    for f in sources:
         src = os.path.join(CSRC, f)
-        obj = os.path.join(objdir, f.replace(".hip", ".o"))
+        obj = os.path.join(objdir, os.path.splitext(f)[0] + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
-            jobs.append(([_hipcc()] + cflags + EXTRA_FLAGS.get(f, []) + ["-c", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                                                src, "-o", obj], verbose))
+            jobs.append(([_hipcc()] + flags_for(f) + ["-c", "-I", os.path.join(ROOT, "include"), "-I", CSRC, src, "-o", obj],
+                         verbose))
     if jobs:
         # os.cpu_count() is the whole host's, whatever share of it this process may use: MAX_JOBS, else 16, caps the pool
         cap = int(os.environ.get("MAX_JOBS") or 16)
         with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), cap, (os.cpu_count() or 2) // 2))) as ex:
             list(ex.map(_compile_one, jobs))
-    if jobs or force or _stale(LIB, objs):
-        cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
+    return objs, bool(jobs)
+
+
+def _link(lib, objs, libs, verbose):
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", lib] + libs
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+
+
+def build_hip(force=False, verbose=False):
+    """libmms_hip.so: one object per .hip source, then one link."""
+    cflags = [f for f in HIPCC_FLAGS if f != "-shared"]
+    objs, compiled = _compile_objects(HIP_SOURCES, lambda f: cflags + EXTRA_FLAGS.get(f, []), force, verbose)
+    if compiled or force or _stale(LIB, objs):
+        _link(LIB, objs, [], verbose)
     return LIB
 
 
 def build_layers(force=False, verbose=False):
-    """C++ mirror of the Caffe Layer/Blob API on top of the C ABI."""
-    src = os.path.join(CSRC, "caffe_layers.cpp")
-    io_src = os.path.join(CSRC, "caffemodel_io.cpp")
-    h5_src = os.path.join(CSRC, "hdf5_io.cpp")
-    if not os.path.exists(src):
-        return None
-    deps = [src, io_src, h5_src, os.path.join(CSRC, "hdf5_io.hpp"), os.path.join(CSRC, "caffe_api.hpp"), os.path.join(ROOT, "include", "mms.h"),
-            os.path.join(ROOT, "include", "mms_layer.h"), LIB, os.path.abspath(__file__)]
-    deps = [d for d in deps if os.path.exists(d)]
-    if not force and not _stale(LAYER_LIB, deps):
-        return LAYER_LIB
-    cmd = [_hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "--offload-arch=gfx950",
-           "-Wall", "-I", os.path.join(ROOT, "include"), "-I", CSRC, src, io_src, h5_src, "-o", LAYER_LIB,
-           "-L", HERE, "-lmms_hip", "-lz", "-Wl,-rpath,$ORIGIN"]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
+    """libmms_caffe.so, the C++ mirror of the Caffe Layer/Blob API on top of the C ABI: one object per layer source,
+    then one link against libmms_hip.so."""
+    objs, compiled = _compile_objects(LAYER_SOURCES, lambda f: LAYER_FLAGS, force, verbose)
+    if compiled or force or _stale(LAYER_LIB, objs + [LIB]):
+        _link(LAYER_LIB, objs, ["-L", HERE, "-lmms_hip", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
     return LAYER_LIB
 
 
 def build_all(force=False, verbose=False):
-    out = [build_hip(force, verbose)]
-    l = build_layers(force, verbose)
-    if l:
-        out.append(l)
-    return out
+    return [build_hip(force, verbose), build_layers(force, verbose)]
 
 
 if __name__ == "__main__":

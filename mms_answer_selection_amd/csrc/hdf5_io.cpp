@@ -2,6 +2,7 @@
 // Specification Version 2.0" (the published spec of libhdf5 1.8); section numbers
 // below are that document's.  Pinned by tests/test_hdf5.py against the h5py-written
 // fixtures the reference's own tests hold (tests/golden/ref_sample_data*.h5).
+// The mms_h5_* C calls of include/mms_layer.h are at the end.
 #include "hdf5_io.hpp"
 
 #include <zlib.h>
@@ -9,6 +10,10 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <memory>
+
+#include "capi_err.hpp"
+#include "mms_layer.h"
 
 namespace mms_h5 {
 namespace {
@@ -599,3 +604,59 @@ bool WriteContiguous(const std::string& path, const std::vector<WriteDataset>& s
 }
 
 }  // namespace mms_h5
+
+// ---- the mms_h5_* calls of include/mms_layer.h (host only) ----
+struct mms_h5_file { mms_h5::File f; std::vector<std::string> names; };
+struct mms_h5_writer { std::vector<mms_h5::WriteDataset> sets; };
+
+extern "C" {
+
+mms_h5_file_t* mms_h5_open(const char* path, char* err, int err_len) {
+  std::unique_ptr<mms_h5_file> h(new mms_h5_file);
+  std::string e;
+  if (!path || !h->f.Open(path, &e)) { set_err(err, err_len, e.empty() ? "null path" : e); return nullptr; }
+  h->names = h->f.DatasetNames();
+  return h.release();
+}
+void mms_h5_close(mms_h5_file_t* h) { delete h; }
+int mms_h5_num_datasets(const mms_h5_file_t* h) { return (int)h->names.size(); }
+const char* mms_h5_dataset_name(const mms_h5_file_t* h, int i) { return h->names[i].c_str(); }
+int mms_h5_dataset_info(const mms_h5_file_t* h, const char* name, long long* dims, int max_axes,
+                        int* type_class, int* elem_size, char* err, int err_len) {
+  mms_h5::DatasetInfo info;
+  std::string e;
+  if (!h->f.Info(name, &info, &e)) { set_err(err, err_len, e); return -1; }
+  for (int a = 0; a < (int)info.dims.size() && a < max_axes; ++a) dims[a] = info.dims[a];
+  if (type_class) *type_class = info.type_class;
+  if (elem_size) *elem_size = info.elem_size;
+  return (int)info.dims.size();
+}
+int mms_h5_read_float(const mms_h5_file_t* h, const char* name, float* out, long long capacity,
+                      char* err, int err_len) {
+  mms_h5::DatasetInfo info;
+  std::vector<float> v;
+  std::string e;
+  if (!h->f.ReadFloat(name, &info, &v, &e)) { set_err(err, err_len, e); return 1; }
+  if ((long long)v.size() > capacity) { set_err(err, err_len, "output buffer too small"); return 2; }
+  std::memcpy(out, v.data(), v.size() * sizeof(float));
+  return 0;
+}
+mms_h5_writer_t* mms_h5_writer_create(void) { return new mms_h5_writer; }
+void mms_h5_writer_destroy(mms_h5_writer_t* w) { delete w; }
+void mms_h5_writer_add(mms_h5_writer_t* w, const char* name, const long long* dims, int num_axes,
+                       int elem_size, const double* values) {
+  mms_h5::WriteDataset d;
+  d.name = name;
+  d.elem_size = elem_size;
+  long long c = 1;
+  for (int a = 0; a < num_axes; ++a) { d.dims.push_back(dims[a]); c *= dims[a]; }
+  d.values.assign(values, values + c);
+  w->sets.push_back(std::move(d));
+}
+int mms_h5_writer_save(const mms_h5_writer_t* w, const char* path, char* err, int err_len) {
+  std::string e;
+  if (!mms_h5::WriteContiguous(path, w->sets, &e)) { set_err(err, err_len, e); return 1; }
+  return 0;
+}
+
+}  // extern "C"

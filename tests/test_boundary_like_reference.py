@@ -7,7 +7,7 @@ exercise them -- each case names the gtest it restates:
     src/caffe/test/test_layer_factory.cpp   LayerFactoryTest.TestCreateLayer
     src/caffe/test/test_embed_layer.cpp     EmbedLayerTest TestSetUp / TestForward / TestForwardWithBias
 
-against the C++ mirror in csrc/caffe_api.hpp / caffe_layers.cpp (handle API of include/mms_layer.h)."""
+against the C++ mirror in csrc/caffe_api.hpp / layers_*.cpp, layer_handles.cpp (handle API of include/mms_layer.h)."""
 import ctypes
 
 import numpy as np
