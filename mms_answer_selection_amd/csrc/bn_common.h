@@ -24,6 +24,20 @@ using bn_vec = T __attribute__((ext_vector_type(16 / sizeof(T))));
 __device__ __forceinline__ float bn_sqrt(float v) { return sqrtf(v); }
 __device__ __forceinline__ double bn_sqrt(double v) { return sqrt(v); }
 
+__device__ __forceinline__ float bn_tanh(float v) { return tanhf(v); }
+__device__ __forceinline__ double bn_tanh(double v) { return tanh(v); }
+
+// The TEST-phase finish of one pooling window of BN -> AvePool -> TanH, from the window's sum s (its ke elements added
+// in (h, w) order, starting from 0), nmean = -mean and std = sqrt(var + 1e-9) of its channel: *save_pool and the return
+// value, top.  csrc/bn_pool.hip's sweep and csrc/conv_stage.hip's epilogue both finish with it.
+template <typename T>
+__device__ __forceinline__ T bn_pool_test_finish(T s, T ke, T nmean, T std, T sc, T sh, T* save_pool) {
+  const T m = s / ke;
+  const T sp = (m + nmean) / std;
+  *save_pool = sp;
+  return bn_tanh(sp * sc + sh);
+}
+
 __device__ __forceinline__ float bn_wave_sum(float v) { return wave_sum(v); }
 __device__ __forceinline__ double bn_wave_sum(double v) {
 #pragma unroll

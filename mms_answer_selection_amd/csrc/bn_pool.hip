@@ -89,9 +89,6 @@ size_t bp_workspace_bytes(int N, int C, int H, int W, int kh, int kw) {
   return (size_t)C * bound * kBnSlots * sizeof(T);
 }
 
-__device__ __forceinline__ float bp_tanh(float v) { return tanhf(v); }
-__device__ __forceinline__ double bp_tanh(double v) { return tanh(v); }
-
 // Chunk k's share of the channel's windows.
 __device__ __forceinline__ void bp_chunk(unsigned windows, unsigned wpc, unsigned k, unsigned* w0, unsigned* w1) {
   *w0 = k * wpc;                                  // k < chunks: k * wpc < windows
@@ -194,7 +191,7 @@ __device__ __forceinline__ void bp_finish(const BpGeom& g, unsigned c, unsigned 
     const size_t p = bp_pooled_index(g, c, w);
     const T sp = (save_pool[p] + nmean) / std;
     save_pool[p] = sp;
-    top[p] = bp_tanh(sp * sc + sh);
+    top[p] = bn_tanh(sp * sc + sh);
   }
 }
 
@@ -236,13 +233,13 @@ __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_forwa
         acc[1] += v[e] * v[e];
       }
     });
-    const T m = s / ke;
     if (test) {
-      const T sp = (m + nmean) / std;
+      T sp;
+      const T t = bn_pool_test_finish(s, ke, nmean, std, sc, sh, &sp);
       save_pool[at.p] = sp;
-      top[at.p] = bp_tanh(sp * sc + sh);
+      top[at.p] = t;
     } else {
-      save_pool[at.p] = m;
+      save_pool[at.p] = s / ke;
     }
   }
   if (test) return;

@@ -32,51 +32,14 @@
 //
 // Nothing is read 16 bytes at a time, so alignment cannot change an order; every workspace word that is read has been
 // written by this call.
-#include <limits.h>
-
+#include "conv_tile.h"
 #include "mms_conv.h"
 #include "mms_internal.h"
 
 namespace mms {
 namespace {
 
-typedef float conv_v4f __attribute__((ext_vector_type(4)));
-
-constexpr int kConvThreads = 256;
 constexpr int kConvMaxSlabs = 64;          // partial sums of the parameter diffs per element, at most
-constexpr int kConvTilePixels = 256;       // output pixels of a fast workgroup: 16 tiles of 16
-constexpr int kConvLdsFloats = 16384;      // 64 KB: the dynamic LDS a launch gets without asking for more
-constexpr int kConvMaxChannels = 64;       // fast route: MT <= 4 channel tiles of 16
-
-struct ConvDims {
-  int N, C, H, W, K, kh, kw, sh, sw, ph, pw, G, OH, OW, Cg, Kg;
-};
-
-// the shape's refusal, else MMS_OK and *d
-int conv_check(const mms_conv_shape* s, ConvDims* d) {
-  if (!s) return MMS_ERR_INVALID_ARG;
-  if (s->N < 0 || s->C <= 0 || s->H <= 0 || s->W <= 0 || s->K <= 0 || s->kh <= 0 || s->kw <= 0 || s->stride_h <= 0 ||
-      s->stride_w <= 0 || s->pad_h < 0 || s->pad_w < 0 || s->dilation_h <= 0 || s->dilation_w <= 0 || s->group <= 0)
-    return MMS_ERR_INVALID_ARG;
-  if (s->C % s->group || s->K % s->group) return MMS_ERR_INVALID_ARG;
-  if (s->dilation_h != 1 || s->dilation_w != 1) return MMS_ERR_UNSUPPORTED;
-  const long long eh = (long long)s->H + 2LL * s->pad_h - s->kh, ew = (long long)s->W + 2LL * s->pad_w - s->kw;
-  if (eh < 0 || ew < 0) return MMS_ERR_INVALID_ARG;
-  const long long OH = eh / s->stride_h + 1, OW = ew / s->stride_w + 1;
-  const long long nx = (long long)s->N * s->C, nt = (long long)s->N * s->K;
-  const long long nw = (long long)s->K * (s->C / s->group);
-  if (OH > INT_MAX || OW > INT_MAX || (long long)s->H * s->W > INT_MAX || OH * OW > INT_MAX ||
-      (long long)s->kh * s->kw > INT_MAX)
-    return MMS_ERR_INVALID_ARG;
-  if (nx > INT_MAX || nt > INT_MAX || nw > INT_MAX || nx * ((long long)s->H * s->W) > INT_MAX ||
-      nt * (OH * OW) > INT_MAX || nw * ((long long)s->kh * s->kw) > INT_MAX)
-    return MMS_ERR_INVALID_ARG;
-  *d = {s->N,     s->C,     s->H,     s->W,    s->K,    s->kh,           s->kw,          s->stride_h, s->stride_w,
-        s->pad_h, s->pad_w, s->group, (int)OH, (int)OW, s->C / s->group, s->K / s->group};
-  return MMS_OK;
-}
-
-inline int round4(int v) { return (v + 3) & ~3; }
 
 // ---- generic route ------------------------------------------------------------------------------------------------
 template <typename T>
@@ -210,171 +173,38 @@ int conv_generic_slabs(const ConvDims& d, int* rps) {
 }
 
 // ---- fast route ---------------------------------------------------------------------------------------------------
-// The pixels of a workgroup: `G` whole images where an image has at most kConvTilePixels / 2 pixels, else `R` whole
-// rows of one image, `bands` bands per image.
-bool conv_tile_geometry(int OHt, int OWt, int* G, int* R, int* bands) {
-  if (OWt > kConvTilePixels) return false;
-  const int PI = OHt * OWt;
-  if (PI <= kConvTilePixels / 2) {
-    *G = kConvTilePixels / PI;
-    *R = OHt;
-    *bands = 1;
-  } else {
-    const int rmax = kConvTilePixels / OWt;
-    const int nb = (OHt + rmax - 1) / rmax;
-    *G = 1;
-    *R = (OHt + nb - 1) / nb;
-    *bands = (OHt + *R - 1) / *R;
+// The product's tile, plan and loop are csrc/conv_tile.h's; this epilogue stores the map.
+struct ConvStoreEpilogue {
+  size_t outoff[kConvNT];
+  size_t PI;
+  __device__ __forceinline__ void pixel(const ConvProdArgs& a, const ConvTile& t, int nt, int img, int r, int c) {
+    outoff[nt] = (size_t)(t.n0 + img) * a.Cout * PI + (size_t)(t.oy0 + r) * a.OWt + c;
   }
-  return true;
-}
-
-struct ConvProdArgs {
-  const float* in;       // (N, Cin, IH, IW)
-  const float* w;        // W'(m, ci, t) = w[m * w_ms + ci * w_cs + (flip ? kh kw - 1 - t : t)]
-  const float* bias;     // per output channel, or NULL
-  float* out;            // (N, Cout, OHt, OWt)
-  int N, Cin, Cout, IH, IW, OHt, OWt, kh, kw;
-  int vph, vpw;          // rows / columns of zeros before the input (bottom_diff: kh - 1, kw - 1)
-  int G, R, bands;       // conv_tile_geometry
-  int BW, plane;         // band: row length IW + 2 vpw, BR * BW elements per channel with BR = R + kh - 1
-  int CC, Kpad;          // input channels per chunk; round4(CC * kh * kw)
-  int MT;                // channel tiles of 16
-  int w_ms, w_cs, flip;
-  bool ok;
-  size_t lds_bytes;
+  // lane: pixel column l16, output channels 16 mt + 4 grp + r
+  template <int MT>
+  __device__ __forceinline__ void finish(const ConvProdArgs& a, const ConvTile&, const conv_v4f (&acc)[MT][kConvNT],
+                                         const bool (&pvalid)[kConvNT]) {
+    const int grp = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = 16 * mt + 4 * grp + r;
+        if (m >= a.Cout) continue;
+        const float b = a.bias ? a.bias[m] : 0.f;
+#pragma unroll
+        for (int nt = 0; nt < kConvNT; ++nt)
+          if (pvalid[nt]) a.out[outoff[nt] + (size_t)m * PI] = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];
+      }
+  }
 };
-
-// pass 0: forward.  pass 1: bottom_diff, the forward product on top_diff with C and K swapped and the taps flipped.
-ConvProdArgs conv_prod_plan(const ConvDims& d, int pass) {
-  ConvProdArgs a = {};
-  if (d.sh != 1 || d.sw != 1 || d.ph != 0 || d.pw != 0 || d.G != 1 || d.C > kConvMaxChannels || d.K > kConvMaxChannels)
-    return a;
-  const int khkw = d.kh * d.kw;
-  a.N = d.N; a.kh = d.kh; a.kw = d.kw;
-  if (pass == 0) {
-    a.Cin = d.C; a.Cout = d.K; a.IH = d.H; a.IW = d.W; a.OHt = d.OH; a.OWt = d.OW;
-    a.vph = a.vpw = 0;
-    a.w_ms = d.C * khkw; a.w_cs = khkw; a.flip = 0;
-  } else {
-    a.Cin = d.K; a.Cout = d.C; a.IH = d.OH; a.IW = d.OW; a.OHt = d.H; a.OWt = d.W;
-    a.vph = d.kh - 1; a.vpw = d.kw - 1;
-    a.w_ms = khkw; a.w_cs = d.C * khkw; a.flip = 1;
-  }
-  if (!conv_tile_geometry(a.OHt, a.OWt, &a.G, &a.R, &a.bands)) return a;
-  a.BW = a.IW + 2 * a.vpw;
-  a.MT = a.Cout <= 16 ? 1 : a.Cout <= 32 ? 2 : 4;
-  const int Mpad = 16 * a.MT;
-  for (;;) {
-    a.plane = (a.R + d.kh - 1) * a.BW;
-    a.CC = 0;
-    for (int cc = a.Cin; cc >= 1; --cc) {
-      const long long kp = round4(cc * khkw);
-      if ((long long)a.G * cc * a.plane + (long long)Mpad * kp + kp <= kConvLdsFloats) { a.CC = cc; break; }
-    }
-    if (a.CC >= (a.Cin < 4 ? a.Cin : 4)) break;
-    if (a.G > 1) { a.G = (a.G + 1) / 2; continue; }       // fewer images, then fewer rows, per workgroup
-    if (a.R > 1) { a.R = (a.R + 1) / 2; a.bands = (a.OHt + a.R - 1) / a.R; continue; }
-    if (a.CC >= 1) break;
-    return a;
-  }
-  a.Kpad = round4(a.CC * khkw);
-  a.lds_bytes = ((size_t)a.G * a.CC * a.plane + (size_t)Mpad * a.Kpad + a.Kpad) * sizeof(float);
-  a.ok = true;
-  return a;
-}
 
 template <int MT>
 __global__ __launch_bounds__(kConvThreads) void conv_prod_kernel(ConvProdArgs a) {
-  constexpr int NT = 4, Mpad = 16 * MT;
   extern __shared__ float conv_lds[];
-  float* band = conv_lds;                               // [G][CC][BR][BW]
-  float* wsm = band + a.G * a.CC * a.plane;             // [Kpad][Mpad]
-  int* koff = reinterpret_cast<int*>(wsm + a.Kpad * Mpad);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, grp = lane >> 4;
-  const int khkw = a.kh * a.kw;
-  const int n0 = blockIdx.x * a.G, gc = min(a.G, a.N - n0);
-  const int oy0 = blockIdx.y * a.R, rb = min(a.R, a.OHt - oy0);
-  const int per = rb * a.OWt, P = gc * per, bru = rb + a.kh - 1;
-  const size_t PI = (size_t)a.OHt * a.OWt;
-
-  for (int k = tid; k < a.Kpad; k += kConvThreads) {
-    const int cl = k / khkw, t = k - cl * khkw, i = t / a.kw, j = t - i * a.kw;
-    koff[k] = cl * a.plane + i * a.BW + j;
-  }
-  int pix[NT];
-  size_t outoff[NT];
-  bool pvalid[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int p = (wave + 4 * nt) * 16 + l16;
-    pvalid[nt] = p < P;
-    const int pp = pvalid[nt] ? p : 0;
-    const int img = pp / per, q = pp - img * per, r = q / a.OWt, c = q - r * a.OWt;
-    pix[nt] = img * a.CC * a.plane + r * a.BW + c;
-    outoff[nt] = (size_t)(n0 + img) * a.Cout * PI + (size_t)(oy0 + r) * a.OWt + c;
-  }
-  conv_v4f acc[MT][NT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (conv_v4f){0.f, 0.f, 0.f, 0.f};
-
-  for (int ci0 = 0; ci0 < a.Cin; ci0 += a.CC) {
-    const int cc = min(a.CC, a.Cin - ci0), klen = cc * khkw, ksteps = (klen + 3) >> 2, k4 = ksteps * 4;
-    __syncthreads();                                    // the previous chunk has been consumed
-    for (int e = tid; e < Mpad * k4; e += kConvThreads) {
-      const int m = e / k4, kk = e - m * k4;
-      float v = 0.f;
-      if (m < a.Cout && kk < klen) {
-        const int cl = kk / khkw, t = kk - cl * khkw;
-        v = a.w[(size_t)m * a.w_ms + (size_t)(ci0 + cl) * a.w_cs + (a.flip ? khkw - 1 - t : t)];
-      }
-      wsm[kk * Mpad + m] = v;
-    }
-    for (int e = tid; e < gc * cc * bru * a.BW; e += kConvThreads) {
-      const int bc = e % a.BW;
-      int t = e / a.BW;
-      const int br = t % bru;
-      t /= bru;
-      const int cl = t % cc, img = t / cc;
-      const int iy = oy0 + br - a.vph, ix = bc - a.vpw;
-      float v = 0.f;
-      if (iy >= 0 && iy < a.IH && ix >= 0 && ix < a.IW)
-        v = a.in[(((size_t)(n0 + img) * a.Cin + ci0 + cl) * a.IH + iy) * a.IW + ix];
-      band[(img * a.CC + cl) * a.plane + br * a.BW + bc] = v;
-    }
-    __syncthreads();
-    for (int s = 0; s < ksteps; ++s) {
-      const int k = 4 * s + grp;
-      const bool kvalid = k < klen;                     // the weights of k >= klen are zeros; the band's are not staged
-      const int off = kvalid ? koff[k] : 0;
-      float av[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) av[mt] = wsm[k * Mpad + 16 * mt + l16];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        if ((wave + 4 * nt) * 16 >= P) continue;        // wave-uniform: the tile holds no pixel
-        const float t = band[off + pix[nt]];
-        const float bv = kvalid ? t : 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv, acc[mt][nt], 0, 0, 0);
-      }
-    }
-  }
-  // lane: pixel column l16, output channels 16 mt + 4 grp + r
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = 16 * mt + 4 * grp + r;
-      if (m >= a.Cout) continue;
-      const float b = a.bias ? a.bias[m] : 0.f;
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-        if (pvalid[nt]) a.out[outoff[nt] + (size_t)m * PI] = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];
-    }
+  ConvStoreEpilogue epi;
+  epi.PI = (size_t)a.OHt * a.OWt;
+  conv_tile_product<MT>(a, conv_lds, epi);
 }
 
 struct ConvWdiffArgs {
@@ -384,7 +214,7 @@ struct ConvWdiffArgs {
   int N, C, K, H, W, OH, OW, kh, kw;
   int G, R, bands;       // conv_tile_geometry of the top pixels, shrunk to the LDS
   int plane;             // (R + kh - 1) * W
-  int PP;                // row length of the staged top_diff tile: round4(G * R * OW) + 1
+  int PP;                // row length of the staged top_diff tile: conv_round4(G * R * OW) + 1
   int MT;
   int units, ups, slabs; // (image group, band) units; units per slab; slabs
   int want_w, want_b;
@@ -397,11 +227,11 @@ ConvWdiffArgs conv_wdiff_plan(const ConvDims& d) {
   if (d.sh != 1 || d.sw != 1 || d.ph != 0 || d.pw != 0 || d.G != 1 || d.C > kConvMaxChannels || d.K > kConvMaxChannels)
     return a;
   a.N = d.N; a.C = d.C; a.K = d.K; a.H = d.H; a.W = d.W; a.OH = d.OH; a.OW = d.OW; a.kh = d.kh; a.kw = d.kw;
-  if (!conv_tile_geometry(d.OH, d.OW, &a.G, &a.R, &a.bands)) return a;
+  if (!conv_tile_geometry(d.OH, d.OW, 1, &a.G, &a.R, &a.bands)) return a;
   a.MT = d.K <= 16 ? 1 : d.K <= 32 ? 2 : 4;
   for (;;) {
     a.plane = (a.R + d.kh - 1) * d.W;
-    a.PP = round4(a.G * a.R * d.OW) + 1;
+    a.PP = conv_round4(a.G * a.R * d.OW) + 1;
     const long long need = (long long)a.G * d.C * a.plane + (long long)16 * a.MT * a.PP + a.PP;
     if (need <= kConvLdsFloats) break;
     if (a.G > 1) { --a.G; continue; }
@@ -502,17 +332,10 @@ __global__ __launch_bounds__(kConvThreads) void conv_wdiff_kernel(ConvWdiffArgs 
   if (bias_on) slab[nW + tid] = bsum;
 }
 
-template <class F>
-inline void with_mt(int MT, F&& f) {
-  if (MT == 1) f(std::integral_constant<int, 1>{});
-  else if (MT == 2) f(std::integral_constant<int, 2>{});
-  else f(std::integral_constant<int, 4>{});
-}
-
 void conv_prod_launch(ConvProdArgs a, const float* in, const float* w, const float* bias, float* out, hipStream_t s) {
   a.in = in; a.w = w; a.bias = bias; a.out = out;
   const dim3 grid((unsigned)((a.N + a.G - 1) / a.G), (unsigned)a.bands);
-  with_mt(a.MT, [&](auto M) {
+  conv_with_mt(a.MT, [&](auto M) {
     hipLaunchKernelGGL((conv_prod_kernel<decltype(M)::value>), grid, dim3(kConvThreads), a.lds_bytes, s, a);
   });
 }
@@ -520,7 +343,7 @@ void conv_prod_launch(ConvProdArgs a, const float* in, const float* w, const flo
 // ---- host -----------------------------------------------------------------------------------------------------------
 int conv_route(const ConvDims& d, int pass) {
   if (pass == MMS_CONV_PASS_FORWARD || pass == MMS_CONV_PASS_BOTTOM_DIFF)
-    return conv_prod_plan(d, pass).ok ? MMS_CONV_ROUTE_FAST : MMS_CONV_ROUTE_GENERIC;
+    return conv_prod_plan(d, pass, 1).ok ? MMS_CONV_ROUTE_FAST : MMS_CONV_ROUTE_GENERIC;
   if (pass == MMS_CONV_PASS_PARAM_DIFF) return conv_wdiff_plan(d).ok ? MMS_CONV_ROUTE_FAST : MMS_CONV_ROUTE_GENERIC;
   return MMS_CONV_ROUTE_NONE;
 }
@@ -548,7 +371,7 @@ int conv_forward(const mms_conv_shape* shape, const T* x, const T* w, const T* b
   if (!x || !w || !top || (const T*)top == x) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (!generic && conv_route(d, MMS_CONV_PASS_FORWARD) == MMS_CONV_ROUTE_FAST) {
-      conv_prod_launch(conv_prod_plan(d, MMS_CONV_PASS_FORWARD), x, w, bias, top, s);
+      conv_prod_launch(conv_prod_plan(d, MMS_CONV_PASS_FORWARD, 1), x, w, bias, top, s);
       return launch_status();
     }
   }
@@ -573,7 +396,7 @@ int conv_backward(const mms_conv_shape* shape, const T* x, const T* w, const T* 
     bool done = false;
     if constexpr (kFloat) {
       if (!generic && conv_route(d, MMS_CONV_PASS_BOTTOM_DIFF) == MMS_CONV_ROUTE_FAST) {
-        conv_prod_launch(conv_prod_plan(d, MMS_CONV_PASS_BOTTOM_DIFF), dy, w, nullptr, dx, s);
+        conv_prod_launch(conv_prod_plan(d, MMS_CONV_PASS_BOTTOM_DIFF, 1), dy, w, nullptr, dx, s);
         done = true;
       }
     }
@@ -593,7 +416,7 @@ int conv_backward(const mms_conv_shape* shape, const T* x, const T* w, const T* 
       ConvWdiffArgs a = conv_wdiff_plan(d);
       a.x = x; a.dy = dy; a.part = part; a.want_w = dw != nullptr; a.want_b = db != nullptr;
       const int groups = dw ? (d.C * d.kh * d.kw + 63) / 64 : 1;     // four column tiles of 16 per workgroup
-      with_mt(a.MT, [&](auto M) {
+      conv_with_mt(a.MT, [&](auto M) {
         hipLaunchKernelGGL((conv_wdiff_kernel<decltype(M)::value>), dim3((unsigned)groups, (unsigned)a.slabs),
                            dim3(kConvThreads), a.lds_bytes, s, a);
       });
