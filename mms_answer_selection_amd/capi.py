@@ -144,6 +144,15 @@ class MMSArgumentError(MMSError, ValueError):
 MMS_VERSION = 212      # include/mms.h
 
 
+def _bind(handle, signatures):
+    """Apply a table {symbol: (restype, argtypes)} to a loaded library; AttributeError if a header and it diverge."""
+    for name, (res, args) in signatures.items():
+        fn = getattr(handle, name)
+        fn.restype = res
+        fn.argtypes = args
+    return handle
+
+
 def lib():
     """The loaded C-ABI library; raises (never falls back) if it is not built."""
     global _lib
@@ -152,16 +161,24 @@ def lib():
             raise MMSError(
                 "libmms_hip.so is not built (%s). Run `python -m mms_answer_selection_amd.build` "
                 "or __graft_entry__.build(); there is no CPU fallback." % LIB_PATH)
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)  # AttributeError if the header and library diverge
-            fn.restype = res
-            fn.argtypes = args
+        l = _bind(C.CDLL(LIB_PATH), _SIGNATURES)
         if l.mms_version() != MMS_VERSION:            # include/mms.h: a host built against another header must refuse
             raise MMSError("libmms_hip.so reports ABI version %d, this binding was written for %d: rebuild "
                            "(python -m mms_answer_selection_amd.build --force)" % (l.mms_version(), MMS_VERSION))
         _lib = l
     return _lib
+
+
+_bound = {}            # id of a family's signature table -> the handle it was last applied to
+
+
+def _bound_lib(signatures):
+    """lib() with the signature table of a family that has a header of its own applied to it: once per handle, and
+    again when the handle is replaced."""
+    l = lib()
+    if _bound.get(id(signatures)) is not l:
+        _bound[id(signatures)] = _bind(l, signatures)
+    return l
 
 
 def check(rc, what):
@@ -182,6 +199,22 @@ def _ptr(t, name, allow_none=False, dtype=torch.float32):
     if not t.is_contiguous():
         raise MMSError("%s must be contiguous" % name)
     return t.data_ptr()
+
+
+def _expect(label, t, shape, name):
+    """A wrapper's own shape check, under its family's label: tensor `t`, when given, has `shape`."""
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise MMSArgumentError("%s: %s must be %s, got %s" % (label, name, tuple(shape), tuple(t.shape)))
+
+
+def _route_symbol(label, family, stem, e, route):
+    """mms_<family>_<stem>_<f32|f64>, or the float call's _generic_ twin: the entry point of a family with two routes."""
+    if route == "auto":
+        return "mms_%s_%s_%s" % (family, stem, e.suffix)
+    if route == "generic":
+        # double has the generic route only, and no entry point of that name
+        return "mms_%s_%s_%s" % (family, stem, "generic_f32" if e.suffix == "f32" else e.suffix)
+    raise MMSArgumentError("%s: route must be 'auto' or 'generic', got %r" % (label, route))
 
 
 def _stream():

@@ -5,6 +5,7 @@ added to `capi`.  Errors are capi's: a refusal of this module's own checks raise
 library is called, a library error code goes through `capi.check`.  The stream is torch's current one.
 """
 import ctypes as C
+import functools
 
 import torch
 
@@ -39,20 +40,10 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_bound = None
-
 
 def lib():
     """capi.lib(), with the mms_conv_* signatures applied to it (once)."""
-    global _bound
-    l = capi.lib()
-    if _bound is not l:
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)  # AttributeError if mms_conv.h and the library diverge
-            fn.restype = res
-            fn.argtypes = args
-        _bound = l
-    return l
+    return capi._bound_lib(_SIGNATURES)
 
 
 def _pair(v, name):
@@ -120,21 +111,11 @@ def _shape_of(x, weight, stride, pad, group):
     return shape, (N, K, oh.value, ow.value)
 
 
-def _expect(t, shape, name):
-    if t is not None and tuple(t.shape) != tuple(shape):
-        raise capi.MMSArgumentError("Convolution: %s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+_expect = functools.partial(capi._expect, "Convolution")
+_symbol = functools.partial(capi._route_symbol, "Convolution", "conv")
 
 
-def _symbol(stem, e, route):
-    if route == "auto":
-        return "mms_conv_%s_%s" % (stem, e.suffix)
-    if route == "generic":
-        # double has the generic route only, and no entry point of that name
-        return "mms_conv_%s_%s" % (stem, "generic_f32" if e.suffix == "f32" else e.suffix)
-    raise capi.MMSArgumentError("Convolution: route must be 'auto' or 'generic', got %r" % (route,))
-
-
-def _conv_forward(e, x, weight, bias, top, stride, pad, group, ws, route):
+def _conv_forward(e, x, weight, bias, top, stride, pad, group, route):
     shape, top_shape = _shape_of(x, weight, stride, pad, group)
     if top is None:
         top = torch.empty(top_shape, dtype=e.dtype, device=x.device)
@@ -171,11 +152,11 @@ def conv_forward(x, weight, bias=None, top=None, *, stride=1, pad=0, group=1, ws
     bias (K) or None (bias_term false); top (N, K, OH, OW) is written and returned (allocated when None).  stride and
     pad: one int or (h, w).  route: "auto" (mms_conv_route decides) or "generic" (the direct kernels at every shape,
     mms_conv_forward_generic_f32).  The forward needs no workspace; `ws` is accepted for symmetry."""
-    return _conv_forward(capi._F32, x, weight, bias, top, stride, pad, group, ws, route)
+    return _conv_forward(capi._F32, x, weight, bias, top, stride, pad, group, route)
 
 
 def conv_forward_f64(x, weight, bias=None, top=None, *, stride=1, pad=0, group=1, ws=None, route="auto"):
-    return _conv_forward(capi._F64, x, weight, bias, top, stride, pad, group, ws, route)
+    return _conv_forward(capi._F64, x, weight, bias, top, stride, pad, group, route)
 
 
 def conv_backward(x, weight, top_diff, bottom_diff=None, weight_diff=None, bias_diff=None, *, stride=1, pad=0, group=1,

@@ -31,20 +31,10 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_bound = None
-
 
 def lib():
     """capi.lib(), with the mms_conv_stage_* signatures applied to it (once)."""
-    global _bound
-    l = capi.lib()
-    if _bound is not l:
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)  # AttributeError if mms_conv_stage.h and the library diverge
-            fn.restype = res
-            fn.argtypes = args
-        _bound = l
-    return l
+    return capi._bound_lib(_SIGNATURES)
 
 
 def _window(pool):

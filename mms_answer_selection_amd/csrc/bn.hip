@@ -421,28 +421,28 @@ int mms_bn_forward_f32(int phase, int N, int C, int S, float bn_memory, const fl
                        const float* shift, float* running_mean, float* running_var, float* top, float* save_mean,
                        float* save_std, void* workspace, size_t workspace_bytes, void* stream) {
   return bn_forward<float>(phase, N, C, S, bn_memory, x, scale, shift, running_mean, running_var, top, save_mean,
-                           save_std, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+                           save_std, workspace, workspace_bytes, as_stream(stream));
 }
 
 int mms_bn_backward_f32(int N, int C, int S, const float* x, const float* top_diff, const float* scale,
                         const float* save_mean, const float* save_std, float* bottom_diff, float* scale_diff,
                         float* shift_diff, void* workspace, size_t workspace_bytes, void* stream) {
   return bn_backward<float>(N, C, S, x, top_diff, scale, save_mean, save_std, bottom_diff, scale_diff, shift_diff,
-                            workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+                            workspace, workspace_bytes, as_stream(stream));
 }
 
 int mms_bn_forward_f64(int phase, int N, int C, int S, double bn_memory, const double* x, const double* scale,
                        const double* shift, double* running_mean, double* running_var, double* top, double* save_mean,
                        double* save_std, void* workspace, size_t workspace_bytes, void* stream) {
   return bn_forward<double>(phase, N, C, S, bn_memory, x, scale, shift, running_mean, running_var, top, save_mean,
-                            save_std, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+                            save_std, workspace, workspace_bytes, as_stream(stream));
 }
 
 int mms_bn_backward_f64(int N, int C, int S, const double* x, const double* top_diff, const double* scale,
                         const double* save_mean, const double* save_std, double* bottom_diff, double* scale_diff,
                         double* shift_diff, void* workspace, size_t workspace_bytes, void* stream) {
   return bn_backward<double>(N, C, S, x, top_diff, scale, save_mean, save_std, bottom_diff, scale_diff, shift_diff,
-                             workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+                             workspace, workspace_bytes, as_stream(stream));
 }
 
 }  // extern "C"

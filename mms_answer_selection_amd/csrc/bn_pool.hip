@@ -478,7 +478,7 @@ int mms_bn_pool_tanh_forward_f32(int phase, int N, int C, int H, int W, int kh, 
                                  void* workspace, size_t workspace_bytes, void* stream) {
   return bp_forward<float>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
                            save_pool, save_mean, save_std, workspace, workspace_bytes,
-                           static_cast<hipStream_t>(stream));
+                           as_stream(stream));
 }
 
 int mms_bn_pool_tanh_backward_f32(int N, int C, int H, int W, int kh, int kw, const float* x, const float* top,
@@ -486,7 +486,7 @@ int mms_bn_pool_tanh_backward_f32(int N, int C, int H, int W, int kh, int kw, co
                                   const float* save_mean, const float* save_std, float* bottom_diff, float* scale_diff,
                                   float* shift_diff, void* workspace, size_t workspace_bytes, void* stream) {
   return bp_backward<float>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                            scale_diff, shift_diff, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+                            scale_diff, shift_diff, workspace, workspace_bytes, as_stream(stream));
 }
 
 int mms_bn_pool_tanh_forward_f64(int phase, int N, int C, int H, int W, int kh, int kw, double bn_memory,
@@ -495,7 +495,7 @@ int mms_bn_pool_tanh_forward_f64(int phase, int N, int C, int H, int W, int kh, 
                                  double* save_std, void* workspace, size_t workspace_bytes, void* stream) {
   return bp_forward<double>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
                             save_pool, save_mean, save_std, workspace, workspace_bytes,
-                            static_cast<hipStream_t>(stream));
+                            as_stream(stream));
 }
 
 int mms_bn_pool_tanh_backward_f64(int N, int C, int H, int W, int kh, int kw, const double* x, const double* top,
@@ -504,7 +504,7 @@ int mms_bn_pool_tanh_backward_f64(int N, int C, int H, int W, int kh, int kw, co
                                   double* scale_diff, double* shift_diff, void* workspace, size_t workspace_bytes,
                                   void* stream) {
   return bp_backward<double>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                             scale_diff, shift_diff, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+                             scale_diff, shift_diff, workspace, workspace_bytes, as_stream(stream));
 }
 
 }  // extern "C"

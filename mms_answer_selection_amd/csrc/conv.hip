@@ -463,38 +463,38 @@ int mms_conv_route(const mms_conv_shape* shape, int pass) {
 
 int mms_conv_forward_f32(const mms_conv_shape* shape, const float* x, const float* weight, const float* bias,
                          float* top, void*, size_t, void* stream) {
-  return conv_forward<float>(shape, x, weight, bias, top, false, static_cast<hipStream_t>(stream));
+  return conv_forward<float>(shape, x, weight, bias, top, false, as_stream(stream));
 }
 
 int mms_conv_backward_f32(const mms_conv_shape* shape, const float* x, const float* weight, const float* top_diff,
                           float* bottom_diff, float* weight_diff, float* bias_diff, void* workspace,
                           size_t workspace_bytes, void* stream) {
   return conv_backward<float>(shape, x, weight, top_diff, bottom_diff, weight_diff, bias_diff, workspace,
-                              workspace_bytes, false, static_cast<hipStream_t>(stream));
+                              workspace_bytes, false, as_stream(stream));
 }
 
 int mms_conv_forward_f64(const mms_conv_shape* shape, const double* x, const double* weight, const double* bias,
                          double* top, void*, size_t, void* stream) {
-  return conv_forward<double>(shape, x, weight, bias, top, true, static_cast<hipStream_t>(stream));
+  return conv_forward<double>(shape, x, weight, bias, top, true, as_stream(stream));
 }
 
 int mms_conv_backward_f64(const mms_conv_shape* shape, const double* x, const double* weight, const double* top_diff,
                           double* bottom_diff, double* weight_diff, double* bias_diff, void* workspace,
                           size_t workspace_bytes, void* stream) {
   return conv_backward<double>(shape, x, weight, top_diff, bottom_diff, weight_diff, bias_diff, workspace,
-                               workspace_bytes, true, static_cast<hipStream_t>(stream));
+                               workspace_bytes, true, as_stream(stream));
 }
 
 int mms_conv_forward_generic_f32(const mms_conv_shape* shape, const float* x, const float* weight, const float* bias,
                                  float* top, void*, size_t, void* stream) {
-  return conv_forward<float>(shape, x, weight, bias, top, true, static_cast<hipStream_t>(stream));
+  return conv_forward<float>(shape, x, weight, bias, top, true, as_stream(stream));
 }
 
 int mms_conv_backward_generic_f32(const mms_conv_shape* shape, const float* x, const float* weight,
                                   const float* top_diff, float* bottom_diff, float* weight_diff, float* bias_diff,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   return conv_backward<float>(shape, x, weight, top_diff, bottom_diff, weight_diff, bias_diff, workspace,
-                              workspace_bytes, true, static_cast<hipStream_t>(stream));
+                              workspace_bytes, true, as_stream(stream));
 }
 
 }  // extern "C"

@@ -250,7 +250,7 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
       conv_with_mt(a.p.MT, [&](auto M) {
         stage_dispatch(ph, pw, [&](auto PH, auto PW) {
           hipLaunchKernelGGL((conv_stage_kernel<decltype(M)::value, decltype(PH)::value, decltype(PW)::value>), grid,
-                             dim3(kConvThreads), a.lds_bytes, static_cast<hipStream_t>(stream), a);
+                             dim3(kConvThreads), a.lds_bytes, as_stream(stream), a);
         });
       });
       return launch_status();

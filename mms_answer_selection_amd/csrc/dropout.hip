@@ -291,35 +291,35 @@ int mms_dropout_threshold_f64(double ratio, unsigned int* thr, double* scale) {
 
 int mms_dropout_forward_f32(const float* x, float* y, long long count, float ratio, int phase, unsigned long long seed,
                             unsigned long long sequence, unsigned long long offset, void* stream) {
-  return dropout_apply<float>(x, y, count, ratio, phase, seed, sequence, offset, static_cast<hipStream_t>(stream));
+  return dropout_apply<float>(x, y, count, ratio, phase, seed, sequence, offset, as_stream(stream));
 }
 
 int mms_dropout_forward_f64(const double* x, double* y, long long count, double ratio, int phase,
                             unsigned long long seed, unsigned long long sequence, unsigned long long offset,
                             void* stream) {
-  return dropout_apply<double>(x, y, count, ratio, phase, seed, sequence, offset, static_cast<hipStream_t>(stream));
+  return dropout_apply<double>(x, y, count, ratio, phase, seed, sequence, offset, as_stream(stream));
 }
 
 int mms_dropout_backward_f32(const float* dy, float* dx, long long count, float ratio, int phase,
                              unsigned long long seed, unsigned long long sequence, unsigned long long offset,
                              void* stream) {
-  return dropout_apply<float>(dy, dx, count, ratio, phase, seed, sequence, offset, static_cast<hipStream_t>(stream));
+  return dropout_apply<float>(dy, dx, count, ratio, phase, seed, sequence, offset, as_stream(stream));
 }
 
 int mms_dropout_backward_f64(const double* dy, double* dx, long long count, double ratio, int phase,
                              unsigned long long seed, unsigned long long sequence, unsigned long long offset,
                              void* stream) {
-  return dropout_apply<double>(dy, dx, count, ratio, phase, seed, sequence, offset, static_cast<hipStream_t>(stream));
+  return dropout_apply<double>(dy, dx, count, ratio, phase, seed, sequence, offset, as_stream(stream));
 }
 
 int mms_dropout_mask_u32(unsigned int* mask, long long count, float ratio, unsigned long long seed,
                          unsigned long long sequence, unsigned long long offset, void* stream) {
-  return dropout_mask<float>(mask, count, ratio, seed, sequence, offset, static_cast<hipStream_t>(stream));
+  return dropout_mask<float>(mask, count, ratio, seed, sequence, offset, as_stream(stream));
 }
 
 int mms_dropout_mask_u32_f64(unsigned int* mask, long long count, double ratio, unsigned long long seed,
                              unsigned long long sequence, unsigned long long offset, void* stream) {
-  return dropout_mask<double>(mask, count, ratio, seed, sequence, offset, static_cast<hipStream_t>(stream));
+  return dropout_mask<double>(mask, count, ratio, seed, sequence, offset, as_stream(stream));
 }
 
 }  // extern "C"

@@ -282,7 +282,7 @@ int mms_fm_forward_f32(int N, int C, int dim, const float* x, const float* bias,
   if (fm_bad_shape(N, C, dim)) return MMS_ERR_INVALID_ARG;
   if (N == 0) return MMS_OK;
   if (!x || !top) return MMS_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = as_stream(stream);
   FmPlan p;
   if (fm_plan(N, C, dim, &p)) {
     hipLaunchKernelGGL((fm_lanewalk_f32_kernel<false>), dim3((unsigned)((N + p.S - 1) / p.S)), dim3(kFmThreads),
@@ -300,7 +300,7 @@ int mms_fm_backward_f32(int N, int C, int dim, const float* x, const float* top_
   if (fm_bad_shape(N, C, dim)) return MMS_ERR_INVALID_ARG;
   if (N == 0) return MMS_OK;
   if (!x || !top_diff) return MMS_ERR_INVALID_ARG;
-  return fm_backward_launch<float>(N, C, dim, x, top_diff, bottom_diff, bias_diff, static_cast<hipStream_t>(stream));
+  return fm_backward_launch<float>(N, C, dim, x, top_diff, bottom_diff, bias_diff, as_stream(stream));
 }
 
 int mms_fm_forward_backward_f32(int N, int C, int dim, const float* x, const float* bias, const float* top_diff,
@@ -308,7 +308,7 @@ int mms_fm_forward_backward_f32(int N, int C, int dim, const float* x, const flo
   if (fm_bad_shape(N, C, dim)) return MMS_ERR_INVALID_ARG;
   if (N == 0) return MMS_OK;
   if (!x || !top_diff || !top || !bottom_diff) return MMS_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStream_t s = as_stream(stream);
   FmPlan p;
   if (fm_plan(N, C, dim, &p)) {
     const unsigned grid = (unsigned)((N + p.S - 1) / p.S) + (bias_diff ? 1u : 0u);
@@ -327,7 +327,7 @@ int mms_fm_forward_f64(int N, int C, int dim, const double* x, const double* bia
   if (N == 0) return MMS_OK;
   if (!x || !top) return MMS_ERR_INVALID_ARG;
   hipLaunchKernelGGL((fm_forward_thread_kernel<double>), dim3(fm_blocks(N)), dim3(kFmThreads), 0,
-                     static_cast<hipStream_t>(stream), x, bias, top, N, C, dim);
+                     as_stream(stream), x, bias, top, N, C, dim);
   return launch_status();
 }
 
@@ -336,7 +336,7 @@ int mms_fm_backward_f64(int N, int C, int dim, const double* x, const double* to
   if (fm_bad_shape(N, C, dim)) return MMS_ERR_INVALID_ARG;
   if (N == 0) return MMS_OK;
   if (!x || !top_diff) return MMS_ERR_INVALID_ARG;
-  return fm_backward_launch<double>(N, C, dim, x, top_diff, bottom_diff, bias_diff, static_cast<hipStream_t>(stream));
+  return fm_backward_launch<double>(N, C, dim, x, top_diff, bottom_diff, bias_diff, as_stream(stream));
 }
 
 }  // extern "C"

@@ -829,7 +829,7 @@ int mms_head_forward_f32(const mms_head_shape* shape, const float* x0, const flo
                          const unsigned int* mask, const float* w2, const float* b2, const float* label, float* h,
                          float* prob, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
   return head_forward<float>(shape, x0, x1, w1, b1, mask, w2, b2, label, h, prob, loss, workspace, workspace_bytes, false,
-                             static_cast<hipStream_t>(stream));
+                             as_stream(stream));
 }
 
 int mms_head_backward_f32(const mms_head_shape* shape, const float* x0, const float* x1, const float* w1,
@@ -838,7 +838,7 @@ int mms_head_backward_f32(const mms_head_shape* shape, const float* x0, const fl
                           float* b1_diff, float* w2_diff, float* b2_diff, void* workspace, size_t workspace_bytes,
                           void* stream) {
   return head_backward<float>(shape, x0, x1, w1, w2, mask, h, prob, label, loss_weight, x0_diff, x1_diff, w1_diff, b1_diff,
-                              w2_diff, b2_diff, workspace, workspace_bytes, false, static_cast<hipStream_t>(stream));
+                              w2_diff, b2_diff, workspace, workspace_bytes, false, as_stream(stream));
 }
 
 int mms_head_forward_f64(const mms_head_shape* shape, const double* x0, const double* x1, const double* w1,
@@ -846,7 +846,7 @@ int mms_head_forward_f64(const mms_head_shape* shape, const double* x0, const do
                          const double* label, double* h, double* prob, double* loss, void* workspace,
                          size_t workspace_bytes, void* stream) {
   return head_forward<double>(shape, x0, x1, w1, b1, mask, w2, b2, label, h, prob, loss, workspace, workspace_bytes, true,
-                              static_cast<hipStream_t>(stream));
+                              as_stream(stream));
 }
 
 int mms_head_backward_f64(const mms_head_shape* shape, const double* x0, const double* x1, const double* w1,
@@ -856,7 +856,7 @@ int mms_head_backward_f64(const mms_head_shape* shape, const double* x0, const d
                           void* stream) {
   return head_backward<double>(shape, x0, x1, w1, w2, mask, h, prob, label, loss_weight, x0_diff, x1_diff, w1_diff,
                                b1_diff, w2_diff, b2_diff, workspace, workspace_bytes, true,
-                               static_cast<hipStream_t>(stream));
+                               as_stream(stream));
 }
 
 int mms_head_forward_generic_f32(const mms_head_shape* shape, const float* x0, const float* x1, const float* w1,
@@ -864,7 +864,7 @@ int mms_head_forward_generic_f32(const mms_head_shape* shape, const float* x0, c
                                  const float* label, float* h, float* prob, float* loss, void* workspace,
                                  size_t workspace_bytes, void* stream) {
   return head_forward<float>(shape, x0, x1, w1, b1, mask, w2, b2, label, h, prob, loss, workspace, workspace_bytes, true,
-                             static_cast<hipStream_t>(stream));
+                             as_stream(stream));
 }
 
 int mms_head_backward_generic_f32(const mms_head_shape* shape, const float* x0, const float* x1, const float* w1,
@@ -873,7 +873,7 @@ int mms_head_backward_generic_f32(const mms_head_shape* shape, const float* x0, 
                                   float* w1_diff, float* b1_diff, float* w2_diff, float* b2_diff, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   return head_backward<float>(shape, x0, x1, w1, w2, mask, h, prob, label, loss_weight, x0_diff, x1_diff, w1_diff, b1_diff,
-                              w2_diff, b2_diff, workspace, workspace_bytes, true, static_cast<hipStream_t>(stream));
+                              w2_diff, b2_diff, workspace, workspace_bytes, true, as_stream(stream));
 }
 
 }  // extern "C"

@@ -17,6 +17,9 @@ inline int launch_status() {
   return hipGetLastError() == hipSuccess ? MMS_OK : MMS_ERR_LAUNCH;
 }
 
+// the `void* stream` of every C entry point
+inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // every array a launch touches (p2, p3: the gradients, null in a forward) takes 16-byte accesses of rows of D floats
 inline bool vec4_ok(int D, const void* p0, const void* p1, const void* p2, const void* p3) {

@@ -144,7 +144,10 @@ int embed_forward_pair(int M0, int M1, int N, int K, const float* index0, const 
                        const float* bias, S* top0, S* top1, void* index_ws, size_t index_ws_bytes, hipStream_t s);
 int feed_gather_rows(int rows, int row_elems, int src_rows, const float* src, const int* perm, int first, float* dst,
                      hipStream_t s);
-// mms_abi.hip
+// net_glue.hip
+int null_launch(int workgroups, hipStream_t s);
+template <class T>
+int dot(int n, const T* x, const T* y, T* out, hipStream_t s);
 int split_sum(int count, int ntop, const float* const* top_diffs, float* bottom_diff, hipStream_t s);
 // f64_paths.hip
 size_t simcross_workspace_bytes_f64(int mode, int N, int W1, int W2, int D, int M);

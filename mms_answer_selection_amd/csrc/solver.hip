@@ -454,13 +454,13 @@ size_t mms_solver_workspace_bytes_f64(const mms_solver_param* param, const mms_s
 int mms_solver_step_f32(const mms_solver_param* param, const mms_solver_blob* blobs, int nblobs, float rate,
                         float* clip_info, void* workspace, size_t workspace_bytes, void* stream) {
   return solver_step<float>(param, blobs, nblobs, rate, clip_info, workspace, workspace_bytes,
-                            static_cast<hipStream_t>(stream));
+                            as_stream(stream));
 }
 
 int mms_solver_step_f64(const mms_solver_param* param, const mms_solver_blob* blobs, int nblobs, double rate,
                         double* clip_info, void* workspace, size_t workspace_bytes, void* stream) {
   return solver_step<double>(param, blobs, nblobs, rate, clip_info, workspace, workspace_bytes,
-                             static_cast<hipStream_t>(stream));
+                             as_stream(stream));
 }
 
 }  // extern "C"

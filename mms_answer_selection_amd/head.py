@@ -5,6 +5,7 @@ added to `capi`.  Errors are capi's: a refusal of this module's own checks raise
 library is called, a library error code goes through `capi.check`.  The stream is torch's current one.
 """
 import ctypes as C
+import functools
 
 import torch
 
@@ -48,20 +49,10 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_bound = None
-
 
 def lib():
     """capi.lib(), with the mms_head_* signatures applied to it (once)."""
-    global _bound
-    l = capi.lib()
-    if _bound is not l:
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)  # AttributeError if mms_head.h and the library diverge
-            fn.restype = res
-            fn.argtypes = args
-        _bound = l
-    return l
+    return capi._bound_lib(_SIGNATURES)
 
 
 def head_shape(N, F0, F1, H, C_, phase=TRAIN, dropout_ratio=0.5, normalization=NORM_VALID, ignore_label=None):
@@ -90,9 +81,8 @@ def head_route_f64(shape, pass_):
     return ROUTE_NONE if head_route(shape, pass_) == ROUTE_NONE else ROUTE_GENERIC
 
 
-def _expect(t, shape, name):
-    if t is not None and tuple(t.shape) != tuple(shape):
-        raise capi.MMSArgumentError("Head: %s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+_expect = functools.partial(capi._expect, "Head")
+_symbol = functools.partial(capi._route_symbol, "Head", "head")
 
 
 def _shape_of(x0, x1, w1, w2, phase, dropout_ratio, normalization, ignore_label):
@@ -109,15 +99,6 @@ def _shape_of(x0, x1, w1, w2, phase, dropout_ratio, normalization, ignore_label)
     if phase not in (TRAIN, TEST):
         raise capi.MMSArgumentError("Head: phase must be TRAIN or TEST, got %r" % (phase,))
     return head_shape(N, F0, F1, H, C_, phase, dropout_ratio, normalization, ignore_label)
-
-
-def _symbol(stem, e, route):
-    if route == "auto":
-        return "mms_head_%s_%s" % (stem, e.suffix)
-    if route == "generic":
-        # double has the generic route only, and no entry point of that name
-        return "mms_head_%s_%s" % (stem, "generic_f32" if e.suffix == "f32" else e.suffix)
-    raise capi.MMSArgumentError("Head: route must be 'auto' or 'generic', got %r" % (route,))
 
 
 def _head_forward(e, x0, x1, w1, b1, mask, w2, b2, label, h, prob, loss, phase, dropout_ratio, normalization,

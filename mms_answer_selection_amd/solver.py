@@ -45,20 +45,10 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-_bound = None
-
 
 def lib():
     """capi.lib(), with the mms_solver_* signatures applied to it (once)."""
-    global _bound
-    l = capi.lib()
-    if _bound is not l:
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)  # AttributeError if mms_solver.h and the library diverge
-            fn.restype = res
-            fn.argtypes = args
-        _bound = l
-    return l
+    return capi._bound_lib(_SIGNATURES)
 
 
 def solver_param(type=ADADELTA, regularization=L2, iter_size=1, diff_out=DIFF_UPDATE, momentum=0.0, delta=1e-8,
