@@ -109,7 +109,7 @@ int triplet_cosine_step(int N, int D, float margin, float loss_weight, const flo
                         float* loss, float* dq, float* dap, float* dan, void* ws, size_t ws_bytes, hipStream_t s);
 int triplet_finish_mode();
 void set_triplet_finish_mode(int m);
-// ranking.hip
+// ranking.hip (host entry points, radix path; device pieces shared with rank_onewg.hip: rank_common.h)
 // (T = float or double: the folds run in T, the order is that of the scores narrowed to float for both)
 size_t rank_workspace_bytes(int n);
 size_t rank_workspace_bytes_f64(int n);
@@ -123,6 +123,13 @@ template <class T>
 int rank_accuracy(int count, const T* a, const T* b, const T* label, T* out, void* ws, size_t ws_bytes, hipStream_t s);
 int rank_tie_mode();
 void set_rank_tie_mode(int m);
+// rank_onewg.hip: the whole metric in one workgroup and one launch, for the sizes it is the fastest at
+enum class RankRoute { kOneWgSmall, kOneWgMid, kRadix };
+RankRoute rank_route(int n, bool libstd);              // libstd: MMS_RANK_TIES_LIBSTDCXX (the radix path emulates it)
+// route: one of the two kOneWg; auc: AUC into out0 (group, out1 and effective unused), otherwise MAP / MRR / effective
+template <class T>
+int rank_onewg(RankRoute route, bool auc, int n, int stride, int offset, int inner, const T* prob, const T* label,
+               const T* group, int has_ignore, int ignore_label, T* out0, T* out1, int* effective, hipStream_t s);
 // embed.hip
 size_t embed_workspace_bytes(int M, int N);
 size_t embed_workspace_bytes_f64(int M, int N);

@@ -1,4 +1,5 @@
-"""Edge-case parity for the ranking metrics (csrc/ranking.hip) on all three size paths:
+"""Edge-case parity for the ranking metrics (csrc/ranking.hip, csrc/rank_onewg.hip, csrc/rank_common.h) on all three size
+paths:
 
     n <= 512         rank_small_kernel   (LDS bitonic sort, one thread per position)
     513 <= n <= 2048 rank_mid_kernel     (register sort, buckets walked by 1,024 threads)
@@ -397,6 +398,87 @@ def test_signed_zero_ties_libstdcxx_mode(n, oracle, hiplib):
     assert same_bits(m, m_ref), (m, m_ref)
     assert same_bits(rr, rr_ref), (rr, rr_ref)
     assert same_bits(auc, auc_ref), (auc, auc_ref)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every instantiation: the double twins at the ends of each size path, libstdc++ mode at its 16 / 17 threshold
+
+
+def same_words(x, y):
+    return np.float64(x).view(np.uint64) == np.float64(y).view(np.uint64) or (np.isnan(x) and np.isnan(y))
+
+
+def auc_f64(score, label):
+    """auc_layer.cpp:119-134 for Dtype = double, distinct float scores, labels 0 / 1: every running sum is an integer
+    below 2^53, so the double sum is the integer sum."""
+    lab = label[np.argsort(-score.astype(np.float32), kind="stable")].astype(np.int64)
+    high = np.cumsum(lab)
+    total, H = int((high * (1 - lab)).sum()), int(high[-1])
+    return np.float64(0) if H <= 0 else np.float64(total) / np.float64(H) / np.float64(lab.size - H)
+
+
+@pytest.mark.parametrize("n,name", [(65, "rand13"), (512, "one"), (513, "rand13"), (2048, "one"), (2048, "singletons"),
+                                    (2049, "rand13")])
+def test_f64_at_the_ends_of_each_size_path(n, name, oracle, hiplib):
+    """rank_small_kernel<0 / 1, double> at a padded size of 128 and at its largest input, rank_mid_kernel<0 / 1, double>
+    at both ends (2,048 singleton groups fill the bucket-head array), the radix kernels in double at their smallest."""
+    from mms_answer_selection_amd import capi
+    r = rng(20 * n + len(name))
+    group, label = layout(r, n, name)
+    score = distinct_scores(r, n)
+    prob, label, group = make_prob(r, score).astype(np.float64), label.astype(np.float64), group.astype(np.float64)
+    m_ref, eff_ref = oracle.map_score(prob, label, group)
+    rr_ref, _ = oracle.mrr_score(prob, label, group)
+    m, rr, eff = capi.rank_map_mrr_f64(dev(prob), dev(label), dev(group))
+    assert eff == eff_ref == int(bucket_counts(label, group)[0].sum())
+    assert same_words(m, m_ref), (m, m_ref)
+    assert same_words(rr, rr_ref), (rr, rr_ref)
+    auc_ref = auc_f64(score, label)
+    auc = capi.rank_auc_f64(dev(prob), dev(label))
+    assert same_words(auc, auc_ref), (auc, auc_ref)
+    if name == "rand13":       # the double front of libstdc++ mode, AUC's tail included: nothing ties, nothing changes
+        capi.set_rank_tie_mode("libstdcxx")
+        try:
+            again = capi.rank_map_mrr_f64(dev(prob), dev(label), dev(group))
+            auc_again = capi.rank_auc_f64(dev(prob), dev(label))
+        finally:
+            capi.set_rank_tie_mode("input")
+        assert again[2] == eff and same_words(again[0], m) and same_words(again[1], rr) and same_words(auc_again, auc)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("m", [16, 17])
+def test_libstdcxx_mode_at_the_insertion_sort_threshold(m, dtype, oracle, hiplib):
+    """Buckets of exactly m items, two score levels, labels mixed: at 16 std::sort is the stable insertion sort, at 17
+    it is introsort, and a cross-label tie is re-sorted by rank_ties_emulate_kernel (the `m > 16` of the detect kernel)."""
+    from mms_answer_selection_amd import capi
+    r = rng(900 + m)
+    group, label = items_from_sizes(r, [m] * 9, lambda s: r.permutation((np.arange(s) % 3 == 0).astype(np.float32)))
+    score = r.choice(np.float32([0.25, 0.75]), group.size)
+    prob, label, group = make_prob(r, score).astype(dtype), label.astype(dtype), group.astype(dtype)
+    same = same_bits if dtype is np.float32 else same_words
+    m_ref, eff_ref = oracle.map_score(prob, label, group)
+    rr_ref, _ = oracle.mrr_score(prob, label, group)
+    one = group == group[0]                                     # AUC's one bucket: the m items of one group
+    p1, l1 = prob[one], label[one]
+    auc_ref = oracle.auc_score(p1, l1)                          # (the oracle's AUC is float only)
+    capi.set_rank_tie_mode("libstdcxx")
+    try:
+        got = (capi.rank_map_mrr if dtype is np.float32 else capi.rank_map_mrr_f64)(dev(prob), dev(label), dev(group))
+        auc = (capi.rank_auc if dtype is np.float32 else capi.rank_auc_f64)(dev(p1), dev(l1))
+    finally:
+        capi.set_rank_tie_mode("input")
+    assert got[2] == eff_ref == 9
+    assert same(got[0], m_ref), (got[0], m_ref)
+    assert same(got[1], rr_ref), (got[1], rr_ref)
+    if dtype is np.float64:
+        # auc = total / high / (count - high) with an integer total: the float oracle's value pins that integer (a
+        # step of 1 in `total` moves the quotient by far more than a float ulp at m <= 17), and with it the double
+        H, F = int(l1.sum()), np.float32
+        totals = [t for t in range(H * (m - H) + 1) if same_bits(F(t) / F(H) / F(m - H), auc_ref)]
+        assert len(totals) == 1
+        auc_ref = np.float64(totals[0]) / np.float64(H) / np.float64(m - H)
+    assert same(auc, auc_ref), (auc, auc_ref)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
