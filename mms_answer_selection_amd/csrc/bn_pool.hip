@@ -1,7 +1,8 @@
 // csrc/bn_pool.hip -- BN -> average pooling over windows that tile the map -> TanH as one call, and its extern "C" entry
-// points (include/mms.h: mms_bn_pool_tanh_*).  The three layers restated are src/caffe/layers/bn_layer.cpp (csrc/bn.hip
-// has the formulas), pooling_layer.cpp:197-212 / :291-317 (AVE; every window here has pool_size = kh*kw) and
-// tanh_layer.cpp:13-33.  Pooling over disjoint windows is linear and BN is affine per channel, so with
+// points (include/mms.h: mms_bn_pool_tanh_*), and the MAX form beside it (at the end of this comment).  The three layers
+// restated are src/caffe/layers/bn_layer.cpp (csrc/bn.hip has the formulas), pooling_layer.cpp:197-212 / :291-317 (AVE;
+// every window here has pool_size = kh*kw) and tanh_layer.cpp:13-33.  Pooling over disjoint windows is linear and BN
+// is affine per channel, so with
 // m = window_mean(x) (the window's elements added in (h, w) order, divided once by kh*kw), per channel c:
 //
 //   forward   mean, var, std, running blobs: as mms_bn_forward, from sum x and sum x*x over the channel
@@ -31,9 +32,22 @@
 //          leaves window means in save_pool and chunk sums in the workspace; launch 2 (pooled-size only) folds and
 //          finishes save_pool and top.  Backward: launch 1 sums over the pooled tensors, launch 2 folds and sweeps.
 // TEST-phase forward knows mean and var beforehand: the sweep finishes each window itself, one launch on either route.
+//
+// The MAX form (include/mms_bn_maxpool.h: mms_bn_maxpool_tanh_*; pooling_layer.cpp:149-170 / :269-287) is the same
+// geometry, routes, walk, statistics and pooled-size sums with another thing kept per window.  Per channel BN's output
+// bn_out(x) = ((x + (-mean)) / std)*scale + shift (bp_normalised, then bp_bn_out: the one place that forms it) is a
+// chain of correctly rounded monotone operations, non-decreasing for scale >= 0 and non-increasing for scale < 0, so the
+// largest BN output of a window is, word for word, bn_out(e) with e = the window's largest x (smallest for scale < 0;
+// for scale == 0 every BN output is shift, and e is the window's first element, where the reference's mask is): the
+// forward sweep keeps e where AVE keeps the sum (bp_keep), and everything after the sweep is AVE's with e in place
+// of the mean.  The reference's mask -- the first element in (h, w) order whose BN output is strictly greater than
+// every earlier one, i.e. the first that attains the maximum -- is not stored: the backward finds e again, then gives
+// gp*scale to the first element whose bn_out equals bn_out(e), which is not arg-ext x where rounding made distinct x
+// collapse.  The backward therefore reads shift, which AVE's does not.
 #include <limits.h>
 
 #include "bn_common.h"
+#include "mms_bn_maxpool.h"
 #include "mms_internal.h"
 
 namespace mms {
@@ -131,9 +145,36 @@ __device__ __forceinline__ void bp_store(T* p, const T (&v)[VEC ? 16 / sizeof(T)
 
 // f(offset from xw, values[E]) for each piece of the window at xw, in (h, w) order; a piece is E elements of one row:
 // 16 bytes (VEC) or one element.  KH, KW > 0: the window's size at compile time (== g.kh, g.kw), every load of the
-// window issued before the first value is used.  KH == KW == 0: any window, piece by piece.
+// window issued before the first value is used.  KH == KW == 0: any window, piece by piece.  With a second f the window
+// is passed over again after the first pass is complete: from the registers that hold it the first way, read again
+// the second.
+template <typename T, bool VEC>
+constexpr int bp_piece = VEC ? 16 / sizeof(T) : 1;
+
+// One pass: over the held window v[KH][KW / E][E], or loading a run-time window (v unused).
 template <typename T, bool VEC, int KH, int KW, class F>
-__device__ __forceinline__ void bp_walk(const T* xw, const BpGeom& g, F&& f) {
+__device__ __forceinline__ void bp_pass(const T* xw, const BpGeom& g,
+                                        const T (*v)[KH ? KW / bp_piece<T, VEC> : 1][bp_piece<T, VEC>], F&& f) {
+  constexpr int E = bp_piece<T, VEC>;
+  if constexpr (KH > 0) {
+#pragma unroll
+    for (int i = 0; i < KH; ++i) {
+#pragma unroll
+      for (int j = 0; j < KW / E; ++j) f((size_t)i * g.W + j * E, v[i][j]);
+    }
+  } else {
+    for (unsigned i = 0; i < g.kh; ++i) {
+      for (unsigned j = 0; j < g.kw; j += E) {
+        T w[E];
+        bp_load<T, VEC>(xw + (size_t)i * g.W + j, w);
+        f((size_t)i * g.W + j, w);
+      }
+    }
+  }
+}
+
+template <typename T, bool VEC, int KH, int KW, class... F>
+__device__ __forceinline__ void bp_walk(const T* xw, const BpGeom& g, F&&... f) {
   constexpr int E = VEC ? 16 / sizeof(T) : 1;
   if constexpr (KH > 0) {
     static_assert(KW % E == 0, "a row is whole pieces");
@@ -143,20 +184,37 @@ __device__ __forceinline__ void bp_walk(const T* xw, const BpGeom& g, F&& f) {
 #pragma unroll
       for (int j = 0; j < KW / E; ++j) bp_load<T, VEC>(xw + (size_t)i * g.W + j * E, v[i][j]);
     }
-#pragma unroll
-    for (int i = 0; i < KH; ++i) {
-#pragma unroll
-      for (int j = 0; j < KW / E; ++j) f((size_t)i * g.W + j * E, v[i][j]);
-    }
+    (bp_pass<T, VEC, KH, KW>(xw, g, v, f), ...);
   } else {
-    for (unsigned i = 0; i < g.kh; ++i) {
-      for (unsigned j = 0; j < g.kw; j += E) {
-        T v[E];
-        bp_load<T, VEC>(xw + (size_t)i * g.W + j, v);
-        f((size_t)i * g.W + j, v);
-      }
-    }
+    (bp_pass<T, VEC, KH, KW>(xw, g, nullptr, f), ...);
   }
+}
+
+// BN for one element, from nmean = -mean, std, scale and shift of its channel, in its two steps: bn_out(x) is
+// bp_bn_out(bp_normalised(x, ...), ...).  The only place that forms them: the forward's finish and the MAX backward's
+// search for the mask compare their words.
+template <typename T>
+__device__ __forceinline__ T bp_normalised(T x, T nmean, T std) {
+  return (x + nmean) / std;
+}
+template <typename T>
+__device__ __forceinline__ T bp_bn_out(T xn, T sc, T sh) {
+  return xn * sc + sh;
+}
+
+// MAX: one step of the scan for a window's extremum, in (h, w) order.  The first element starts it; a later one
+// replaces *e where it is strictly larger (dir > 0: the channel's scale is positive) or smaller (dir < 0: negative); a
+// NaN never does, and with dir == 0 (scale == 0: every BN output is shift, the mask is the first element) nothing does.
+template <typename T>
+__device__ __forceinline__ void bp_keep(bool first, T v, int dir, T* e) {
+  const bool less = v < *e, more = v > *e;           // both formed, then selected: no branch per element
+  *e = first || (dir < 0 ? less : dir > 0 && more) ? v : *e;
+}
+
+// dir of bp_keep for a channel's scale
+template <typename T>
+__device__ __forceinline__ int bp_dir(T sc) {
+  return sc < T(0) ? -1 : sc > T(0) ? 1 : 0;
 }
 
 // TRAIN: mean, var, std of channel c from its two sums, as bn_forward_kernel does; the writer updates the blobs.
@@ -183,21 +241,23 @@ __device__ __forceinline__ size_t bp_pooled_index(const BpGeom& g, unsigned c, u
   return ((size_t)n * g.C + c) * g.P + r;
 }
 
-// TRAIN, after the sweep: windows [w0, w1) of channel c, whose means are in save_pool, become save_pool and top.
+// TRAIN, after the sweep: windows [w0, w1) of channel c, whose means (MAX: extrema) are in save_pool, become save_pool
+// and top.
 template <typename T, int THREADS>
 __device__ __forceinline__ void bp_finish(const BpGeom& g, unsigned c, unsigned w0, unsigned w1, T nmean, T std, T sc,
                                           T sh, T* save_pool, T* __restrict__ top) {
   for (unsigned w = w0 + threadIdx.x; w < w1; w += THREADS) {
     const size_t p = bp_pooled_index(g, c, w);
-    const T sp = (save_pool[p] + nmean) / std;
+    const T sp = bp_normalised(save_pool[p], nmean, std);
     save_pool[p] = sp;
-    top[p] = bn_tanh(sp * sc + sh);
+    top[p] = bn_tanh(bp_bn_out(sp, sc, sh));
   }
 }
 
 // Forward sweep: the only launch of the small route and of the TEST phase, launch 1 of the large route's TRAIN phase.
-// SMALL: grid (C, 1), 1024 threads; otherwise grid (C, chunks), 256 threads.
-template <typename T, bool VEC, int KH, int KW, bool SMALL>
+// SMALL: grid (C, 1), 1024 threads; otherwise grid (C, chunks), 256 threads.  MAX: the window's extremum where AVE has
+// its mean.
+template <typename T, bool VEC, int KH, int KW, bool SMALL, bool MAX>
 __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_forward_kernel(
     const T* __restrict__ x, const T* __restrict__ scale, const T* __restrict__ shift, T* running_mean,
     T* running_var, T* __restrict__ top, T* save_pool, T* save_mean, T* save_std, T* __restrict__ ws, BpGeom g,
@@ -211,6 +271,7 @@ __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_forwa
   const bool writer = blockIdx.y == 0 && threadIdx.x == 0;
   const bool test = phase != 0;
   const T sc = scale[c], sh = shift[c], ke = T(g.kh * g.kw);
+  const int dir = bp_dir(sc);
   T nmean = T(0), std = T(1);
   if (test) {
     const T mean = running_mean[c];
@@ -224,22 +285,24 @@ __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_forwa
   T acc[2] = {T(0), T(0)};
   for (unsigned w = w0 + threadIdx.x; w < w1; w += THREADS) {
     const BpWin at = bp_window(g, c, w);
-    T s = T(0);
-    bp_walk<T, VEC, KH, KW>(x + at.x0, g, [&](size_t, const T(&v)[E]) {
+    T s = T(0);                                    // AVE: the window's sum; MAX: its extremum
+    bp_walk<T, VEC, KH, KW>(x + at.x0, g, [&](size_t off, const T(&v)[E]) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        s += v[e];
+        if constexpr (MAX) bp_keep(off == 0 && e == 0, v[e], dir, &s);
+        else s += v[e];
         acc[0] += v[e];
         acc[1] += v[e] * v[e];
       }
     });
     if (test) {
       T sp;
-      const T t = bn_pool_test_finish(s, ke, nmean, std, sc, sh, &sp);
+      if constexpr (MAX) sp = bp_normalised(s, nmean, std);
+      const T t = MAX ? bn_tanh(bp_bn_out(sp, sc, sh)) : bn_pool_test_finish(s, ke, nmean, std, sc, sh, &sp);
       save_pool[at.p] = sp;
       top[at.p] = t;
     } else {
-      save_pool[at.p] = s / ke;
+      save_pool[at.p] = MAX ? s : s / ke;
     }
   }
   if (test) return;
@@ -310,12 +373,14 @@ __global__ __launch_bounds__(kBnThreads) void bp_backward_partial_kernel(const T
 // Backward: the only launch of the small route (grid (C, 1), 1024 threads, the workgroup sums its own channel) and
 // launch 2 of the large route (grid (C, chunks), 256 threads, the sums come from the workspace).  scale_diff, shift_diff
 // and dx may each be NULL; with dx NULL the large route launches one workgroup per channel, which only folds.
-template <typename T, bool VEC, int KH, int KW, bool SMALL>
-__global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_backward_kernel(
+// The body of both pooling methods' kernels; shift is read by MAX only.
+template <typename T, bool VEC, int KH, int KW, bool SMALL, bool MAX>
+__device__ __forceinline__ void bp_backward_sweep(
     const T* __restrict__ x, const T* __restrict__ top, const T* __restrict__ top_diff,
-    const T* __restrict__ save_pool, const T* __restrict__ scale, const T* __restrict__ save_mean,
-    const T* __restrict__ save_std, T* __restrict__ dx, T* __restrict__ scale_diff, T* __restrict__ shift_diff,
-    const T* __restrict__ ws, BpGeom g, unsigned wpc, int chunks, T minus_inv_count) {
+    const T* __restrict__ save_pool, const T* __restrict__ scale, const T* __restrict__ shift,
+    const T* __restrict__ save_mean, const T* __restrict__ save_std, T* __restrict__ dx, T* __restrict__ scale_diff,
+    T* __restrict__ shift_diff, const T* __restrict__ ws, const BpGeom& g, unsigned wpc, int chunks,
+    T minus_inv_count) {
   constexpr int THREADS = SMALL ? kBnSmallThreads : kBnThreads;
   constexpr int E = VEC ? 16 / sizeof(T) : 1;
   __shared__ T red[2 * THREADS / kWave];
@@ -323,6 +388,9 @@ __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_backw
   unsigned w0, w1;
   bp_chunk(g.windows, wpc, blockIdx.y, &w0, &w1);
   const T nmean = -save_mean[c], std = save_std[c], sc = scale[c], ke = T(g.kh * g.kw);
+  T sh = T(0);
+  if constexpr (MAX) sh = shift[c];
+  const int dir = bp_dir(sc);
   T tot[2];
   if constexpr (SMALL) bp_backward_sums<T, THREADS>(top, top_diff, save_pool, g, c, w0, w1, tot, red);
   else bn_fold<2>(ws, (int)c, chunks, tot);
@@ -336,18 +404,65 @@ __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_backw
     const BpWin at = bp_window(g, c, w);
     const T t = top[at.p];
     const T gp = top_diff[at.p] * (T(1) - t * t);
-    const T gs = gp / ke * sc;                   // the pooling's top_diff / pool_size, then BN's dy * scale
-    T* out = dx + at.x0;
-    bp_walk<T, VEC, KH, KW>(x + at.x0, g, [&](size_t off, const T(&v)[E]) {
-      T o[E];
+    if constexpr (MAX) {
+      // The mask again: the window's extremum as the forward kept it, its BN output, then the first element whose BN
+      // output is that word receives the pooling's top_diff (BN's dy * scale of it); every other element has dy == 0.
+      const T gs = gp * sc;
+      T* out = dx + at.x0;
+      T ext = T(0), ymax = T(0);
+      bool open = true;                            // no element of the window has had ymax yet
+      bp_walk<T, VEC, KH, KW>(
+          x + at.x0, g,
+          [&](size_t off, const T(&v)[E]) {
 #pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const T xn = (v[e] + nmean) / std;
-        o[e] = (gs + minus_inv_count * (xn * a + b)) / std;
-      }
-      bp_store<T, VEC>(out + off, o);
-    });
+            for (int e = 0; e < E; ++e) bp_keep(off == 0 && e == 0, v[e], dir, &ext);
+          },
+          [&](size_t off, const T(&v)[E]) {
+            if (off == 0) ymax = bp_bn_out(bp_normalised(ext, nmean, std), sc, sh);
+            T o[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+              const T xn = bp_normalised(v[e], nmean, std);
+              const bool same = bp_bn_out(xn, sc, sh) == ymax, hit = open & same;
+              open = open & !same;
+              o[e] = ((hit ? gs : T(0)) + minus_inv_count * (xn * a + b)) / std;
+            }
+            bp_store<T, VEC>(out + off, o);
+          });
+    } else {
+      const T gs = gp / ke * sc;                 // the pooling's top_diff / pool_size, then BN's dy * scale
+      T* out = dx + at.x0;
+      bp_walk<T, VEC, KH, KW>(x + at.x0, g, [&](size_t off, const T(&v)[E]) {
+        T o[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const T xn = (v[e] + nmean) / std;
+          o[e] = (gs + minus_inv_count * (xn * a + b)) / std;
+        }
+        bp_store<T, VEC>(out + off, o);
+      });
+    }
   }
+}
+
+template <typename T, bool VEC, int KH, int KW, bool SMALL>
+__global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_backward_kernel(
+    const T* __restrict__ x, const T* __restrict__ top, const T* __restrict__ top_diff,
+    const T* __restrict__ save_pool, const T* __restrict__ scale, const T* __restrict__ save_mean,
+    const T* __restrict__ save_std, T* __restrict__ dx, T* __restrict__ scale_diff, T* __restrict__ shift_diff,
+    const T* __restrict__ ws, BpGeom g, unsigned wpc, int chunks, T minus_inv_count) {
+  bp_backward_sweep<T, VEC, KH, KW, SMALL, false>(x, top, top_diff, save_pool, scale, nullptr, save_mean, save_std, dx,
+                                                  scale_diff, shift_diff, ws, g, wpc, chunks, minus_inv_count);
+}
+
+template <typename T, bool VEC, int KH, int KW, bool SMALL>
+__global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_max_backward_kernel(
+    const T* __restrict__ x, const T* __restrict__ top, const T* __restrict__ top_diff,
+    const T* __restrict__ save_pool, const T* __restrict__ scale, const T* __restrict__ shift,
+    const T* __restrict__ save_mean, const T* __restrict__ save_std, T* __restrict__ dx, T* __restrict__ scale_diff,
+    T* __restrict__ shift_diff, const T* __restrict__ ws, BpGeom g, unsigned wpc, int chunks, T minus_inv_count) {
+  bp_backward_sweep<T, VEC, KH, KW, SMALL, true>(x, top, top_diff, save_pool, scale, shift, save_mean, save_std, dx,
+                                                 scale_diff, shift_diff, ws, g, wpc, chunks, minus_inv_count);
 }
 
 // A window row is whole 16-byte accesses: kw elements are, every row starts on a 16-byte boundary (W elements are, and
@@ -362,12 +477,24 @@ template <int K>
 using bp_int = std::integral_constant<int, K>;
 
 // f(VEC, KH, KW) as types: network_v4's two windows at compile time (4 x 4 where its rows are 16-byte accesses; 5 x 5's
-// 100-byte rows never are), any other window at run time.
-template <class F>
+// 100-byte rows never are), any other window at run time.  They are network_v3's too; MAX adds network_v5's 2 x 2 and
+// 6 x 6, whose rows are 16-byte accesses in double only.
+template <typename T, bool MAX, class F>
 void bp_dispatch(bool vec, int kh, int kw, F&& f) {
-  if (vec && kh == 4 && kw == 4) f(std::true_type{}, bp_int<4>{}, bp_int<4>{});
-  else if (!vec && kh == 5 && kw == 5) f(std::false_type{}, bp_int<5>{}, bp_int<5>{});
-  else with_bool(vec, [&](auto VEC) { f(VEC, bp_int<0>{}, bp_int<0>{}); });
+  if (vec && kh == 4 && kw == 4) return f(std::true_type{}, bp_int<4>{}, bp_int<4>{});
+  if (!vec && kh == 5 && kw == 5) return f(std::false_type{}, bp_int<5>{}, bp_int<5>{});
+  if constexpr (MAX) {
+    if (kh == kw && (kh == 2 || kh == 6)) {
+      auto square = [&](auto K) {
+        if constexpr (decltype(K)::value * sizeof(T) % 16 == 0) {      // bp_vector_ok: vec is false everywhere else
+          if (vec) return f(std::true_type{}, K, K);
+        }
+        f(std::false_type{}, K, K);
+      };
+      return kh == 2 ? square(bp_int<2>{}) : square(bp_int<6>{});
+    }
+  }
+  with_bool(vec, [&](auto VEC) { f(VEC, bp_int<0>{}, bp_int<0>{}); });
 }
 
 BpGeom bp_geom(int N, int C, int H, int W, int kh, int kw) {
@@ -375,7 +502,8 @@ BpGeom bp_geom(int N, int C, int H, int W, int kh, int kw) {
   return {(unsigned)C, (unsigned)H, (unsigned)W, (unsigned)kh, (unsigned)kw, PW, P, (unsigned)N * P};
 }
 
-template <typename T>
+// MAX: the pooling method, here and in bp_backward; the argument rules are one list for both.
+template <typename T, bool MAX>
 int bp_forward(int phase, int N, int C, int H, int W, int kh, int kw, T bn_memory, const T* x, const T* scale,
                const T* shift, T* running_mean, T* running_var, T* top, T* save_pool, T* save_mean, T* save_std,
                void* workspace, size_t workspace_bytes, hipStream_t s) {
@@ -396,16 +524,16 @@ int bp_forward(int phase, int N, int C, int H, int W, int kh, int kw, T bn_memor
   const T inv_S = T(1. / ((double)H * W)), inv_N = T(1. / N);
   const dim3 grid((unsigned)C, (unsigned)r.chunks);
   int rc = MMS_OK;
-  bp_dispatch(bp_vector_ok<T>(W, kw, x, nullptr), kh, kw, [&](auto VEC, auto KH, auto KW) {
+  bp_dispatch<T, MAX>(bp_vector_ok<T>(W, kw, x, nullptr), kh, kw, [&](auto VEC, auto KH, auto KW) {
     constexpr bool V = decltype(VEC)::value;
     constexpr int kH = decltype(KH)::value, kW = decltype(KW)::value;
     if (r.small) {
-      hipLaunchKernelGGL((bp_forward_kernel<T, V, kH, kW, true>), grid, dim3(kBnSmallThreads), 0, s, x, scale, shift,
+      hipLaunchKernelGGL((bp_forward_kernel<T, V, kH, kW, true, MAX>), grid, dim3(kBnSmallThreads), 0, s, x, scale, shift,
                          running_mean, running_var, top, save_pool, save_mean, save_std, (T*)nullptr, g,
                          r.windows_per_chunk, phase, bn_memory, inv_S, inv_N);
       return;
     }
-    hipLaunchKernelGGL((bp_forward_kernel<T, V, kH, kW, false>), grid, dim3(kBnThreads), 0, s, x, scale, shift,
+    hipLaunchKernelGGL((bp_forward_kernel<T, V, kH, kW, false, MAX>), grid, dim3(kBnThreads), 0, s, x, scale, shift,
                        running_mean, running_var, top, save_pool, save_mean, save_std, ws, g, r.windows_per_chunk,
                        phase, bn_memory, inv_S, inv_N);
   });
@@ -416,16 +544,17 @@ int bp_forward(int phase, int N, int C, int H, int W, int kh, int kw, T bn_memor
   return launch_status();
 }
 
-template <typename T>
+// shift: an input of the MAX form only (the mask is found from BN's output); AVE passes none.
+template <typename T, bool MAX>
 int bp_backward(int N, int C, int H, int W, int kh, int kw, const T* x, const T* top, const T* top_diff,
-                const T* save_pool, const T* scale, const T* save_mean, const T* save_std, T* bottom_diff,
-                T* scale_diff, T* shift_diff, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                const T* save_pool, const T* scale, const T* shift, const T* save_mean, const T* save_std,
+                T* bottom_diff, T* scale_diff, T* shift_diff, void* workspace, size_t workspace_bytes, hipStream_t s) {
   if (bp_bad_shape(N, C, H, W, kh, kw)) return MMS_ERR_INVALID_ARG;
   if (N == 0) return MMS_OK;
-  if (!x || !top || !top_diff || !save_pool || !scale || !save_mean || !save_std ||
+  if (!x || !top || !top_diff || !save_pool || !scale || (MAX && !shift) || !save_mean || !save_std ||
       (!bottom_diff && !scale_diff && !shift_diff))
     return MMS_ERR_INVALID_ARG;
-  const void* const inputs[] = {x, top, top_diff, save_pool, scale, save_mean, save_std};
+  const void* const inputs[] = {x, top, top_diff, save_pool, scale, save_mean, save_std, MAX ? shift : x};   // AVE: x twice
   for (const void* in : inputs) {
     if (bottom_diff == in) return MMS_ERR_INVALID_ARG;
   }
@@ -442,18 +571,23 @@ int bp_backward(int N, int C, int H, int W, int kh, int kw, const T* x, const T*
     const int rc = launch_status();
     if (rc != MMS_OK) return rc;
   }
-  bp_dispatch(bp_vector_ok<T>(W, kw, x, bottom_diff), kh, kw, [&](auto VEC, auto KH, auto KW) {
+  bp_dispatch<T, MAX>(bp_vector_ok<T>(W, kw, x, bottom_diff), kh, kw, [&](auto VEC, auto KH, auto KW) {
     constexpr bool V = decltype(VEC)::value;
     constexpr int kH = decltype(KH)::value, kW = decltype(KW)::value;
-    if (r.small) {
-      hipLaunchKernelGGL((bp_backward_kernel<T, V, kH, kW, true>), grid, dim3(kBnSmallThreads), 0, s, x, top, top_diff,
-                         save_pool, scale, save_mean, save_std, bottom_diff, scale_diff, shift_diff, (const T*)nullptr,
-                         g, r.windows_per_chunk, 1, minus_inv_count);
-      return;
-    }
-    hipLaunchKernelGGL((bp_backward_kernel<T, V, kH, kW, false>), bottom_diff ? grid : dim3((unsigned)C),
-                       dim3(kBnThreads), 0, s, x, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                       scale_diff, shift_diff, (const T*)ws, g, r.windows_per_chunk, r.chunks, minus_inv_count);
+    with_bool(r.small, [&](auto SMALL) {
+      constexpr bool S = decltype(SMALL)::value;
+      const dim3 gr = S || bottom_diff ? grid : dim3((unsigned)C), threads(S ? kBnSmallThreads : kBnThreads);
+      const T* sums = S ? nullptr : ws;
+      if constexpr (MAX) {
+        hipLaunchKernelGGL((bp_max_backward_kernel<T, V, kH, kW, S>), gr, threads, 0, s, x, top, top_diff, save_pool,
+                           scale, shift, save_mean, save_std, bottom_diff, scale_diff, shift_diff, sums, g,
+                           r.windows_per_chunk, r.chunks, minus_inv_count);
+      } else {
+        hipLaunchKernelGGL((bp_backward_kernel<T, V, kH, kW, S>), gr, threads, 0, s, x, top, top_diff, save_pool, scale,
+                           save_mean, save_std, bottom_diff, scale_diff, shift_diff, sums, g, r.windows_per_chunk,
+                           r.chunks, minus_inv_count);
+      }
+    });
   });
   return launch_status();
 }
@@ -476,7 +610,7 @@ int mms_bn_pool_tanh_forward_f32(int phase, int N, int C, int H, int W, int kh, 
                                  const float* x, const float* scale, const float* shift, float* running_mean,
                                  float* running_var, float* top, float* save_pool, float* save_mean, float* save_std,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-  return bp_forward<float>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
+  return bp_forward<float, false>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
                            save_pool, save_mean, save_std, workspace, workspace_bytes,
                            as_stream(stream));
 }
@@ -485,15 +619,15 @@ int mms_bn_pool_tanh_backward_f32(int N, int C, int H, int W, int kh, int kw, co
                                   const float* top_diff, const float* save_pool, const float* scale,
                                   const float* save_mean, const float* save_std, float* bottom_diff, float* scale_diff,
                                   float* shift_diff, void* workspace, size_t workspace_bytes, void* stream) {
-  return bp_backward<float>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                            scale_diff, shift_diff, workspace, workspace_bytes, as_stream(stream));
+  return bp_backward<float, false>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, nullptr, save_mean, save_std,
+                                   bottom_diff, scale_diff, shift_diff, workspace, workspace_bytes, as_stream(stream));
 }
 
 int mms_bn_pool_tanh_forward_f64(int phase, int N, int C, int H, int W, int kh, int kw, double bn_memory,
                                  const double* x, const double* scale, const double* shift, double* running_mean,
                                  double* running_var, double* top, double* save_pool, double* save_mean,
                                  double* save_std, void* workspace, size_t workspace_bytes, void* stream) {
-  return bp_forward<double>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
+  return bp_forward<double, false>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
                             save_pool, save_mean, save_std, workspace, workspace_bytes,
                             as_stream(stream));
 }
@@ -503,8 +637,51 @@ int mms_bn_pool_tanh_backward_f64(int N, int C, int H, int W, int kh, int kw, co
                                   const double* save_mean, const double* save_std, double* bottom_diff,
                                   double* scale_diff, double* shift_diff, void* workspace, size_t workspace_bytes,
                                   void* stream) {
-  return bp_backward<double>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                             scale_diff, shift_diff, workspace, workspace_bytes, as_stream(stream));
+  return bp_backward<double, false>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, nullptr, save_mean,
+                                    save_std, bottom_diff, scale_diff, shift_diff, workspace, workspace_bytes,
+                                    as_stream(stream));
+}
+
+// include/mms_bn_maxpool.h: the MAX form.  The workspace is AVE's: the route and the chunk sums are.
+size_t mms_bn_maxpool_tanh_workspace_bytes(int N, int C, int H, int W, int kh, int kw) {
+  return bp_workspace_bytes<float>(N, C, H, W, kh, kw);
+}
+size_t mms_bn_maxpool_tanh_workspace_bytes_f64(int N, int C, int H, int W, int kh, int kw) {
+  return bp_workspace_bytes<double>(N, C, H, W, kh, kw);
+}
+
+int mms_bn_maxpool_tanh_forward_f32(int phase, int N, int C, int H, int W, int kh, int kw, float bn_memory,
+                                    const float* x, const float* scale, const float* shift, float* running_mean,
+                                    float* running_var, float* top, float* save_pool, float* save_mean,
+                                    float* save_std, void* workspace, size_t workspace_bytes, void* stream) {
+  return bp_forward<float, true>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
+                                 save_pool, save_mean, save_std, workspace, workspace_bytes, as_stream(stream));
+}
+
+int mms_bn_maxpool_tanh_backward_f32(int N, int C, int H, int W, int kh, int kw, const float* x, const float* top,
+                                     const float* top_diff, const float* save_pool, const float* scale,
+                                     const float* shift, const float* save_mean, const float* save_std,
+                                     float* bottom_diff, float* scale_diff, float* shift_diff, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  return bp_backward<float, true>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, shift, save_mean, save_std,
+                                  bottom_diff, scale_diff, shift_diff, workspace, workspace_bytes, as_stream(stream));
+}
+
+int mms_bn_maxpool_tanh_forward_f64(int phase, int N, int C, int H, int W, int kh, int kw, double bn_memory,
+                                    const double* x, const double* scale, const double* shift, double* running_mean,
+                                    double* running_var, double* top, double* save_pool, double* save_mean,
+                                    double* save_std, void* workspace, size_t workspace_bytes, void* stream) {
+  return bp_forward<double, true>(phase, N, C, H, W, kh, kw, bn_memory, x, scale, shift, running_mean, running_var, top,
+                                  save_pool, save_mean, save_std, workspace, workspace_bytes, as_stream(stream));
+}
+
+int mms_bn_maxpool_tanh_backward_f64(int N, int C, int H, int W, int kh, int kw, const double* x, const double* top,
+                                     const double* top_diff, const double* save_pool, const double* scale,
+                                     const double* shift, const double* save_mean, const double* save_std,
+                                     double* bottom_diff, double* scale_diff, double* shift_diff, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  return bp_backward<double, true>(N, C, H, W, kh, kw, x, top, top_diff, save_pool, scale, shift, save_mean, save_std,
+                                   bottom_diff, scale_diff, shift_diff, workspace, workspace_bytes, as_stream(stream));
 }
 
 }  // extern "C"
