@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from cross_grid_model import assert_fp32_mode, term_budget
 from mms_answer_selection_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -129,12 +130,7 @@ def test_cross_geometry_fp32_mode(shape, oracle, hiplib):
     dT = r.standard_normal((N, 1, W1, W2)).astype(np.float32)
     top_ref, _, _ = oracle.simcross_forward(1, q, a)
     dq_ref, da_ref, _, _ = oracle.simcross_backward(1, q, a, top_ref, dT)
-    # magnitude budget: sum_k |tt| in float64
-    T = top_ref.astype(np.float64)[:, 0]
-    coef = np.abs(dT.astype(np.float64)[:, 0] * T ** 3 / (T - 1 + 1e-9))          # (N, W1, W2)
-    diff = np.abs(q.astype(np.float64)[:, :, None, :] - a.astype(np.float64)[:, None, :, :])
-    mag_q = (coef[..., None] * diff).sum(axis=2)
-    mag_a = (coef[..., None] * diff).sum(axis=1)
+    mag_q, mag_a = term_budget(q, a, top_ref, dT)                                  # sum_k |tt|, sum_j |tt| in float64
     qd, ad, dTd = (torch.from_numpy(x).cuda() for x in (q, a, dT))
     capi.set_euclid_backward_mode("fp32")
     top = torch.empty(N, 1, W1, W2, device="cuda")
@@ -143,10 +139,8 @@ def test_cross_geometry_fp32_mode(shape, oracle, hiplib):
     dq, da = torch.empty_like(qd), torch.empty_like(ad)
     capi.simcross_backward(1, qd, ad, top, dTd, dq, da)
     g, h = dq.cpu().numpy(), da.cpu().numpy()
-    eps = np.finfo(np.float32).eps
-    assert (np.abs(g - dq_ref) <= 4 * eps * mag_q + 1e-30).all()
-    assert (np.abs(h - da_ref) <= 4 * eps * mag_a + 1e-30).all()
-    np.testing.assert_allclose(g, dq_ref, rtol=0, atol=1e-5 * max(1.0, np.abs(dq_ref).max()))
+    assert_fp32_mode(g, dq_ref, mag_q)                       # 4 eps sum |tt|, and 1e-5 max(1, max |dq_ref|)
+    assert_fp32_mode(h, da_ref, mag_a, north_star=False)     # 4 eps sum |tt|
     capi.set_euclid_backward_mode("reference")
     capi.simcross_backward(1, qd, ad, top, dTd, dq, da)
     assert (dq.cpu().numpy().view(np.uint32) == dq_ref.view(np.uint32)).all()
