@@ -3,7 +3,7 @@
 // Shared by simcross_rows_cosine.hip (cosine_pair32_kernel, cosine_rows_kernel) and by the fused cosine triplet
 // step in triplet_steps.hip, whose scores, norms and gradients must carry the bits of those kernels: one definition
 // of every expression, built with -ffp-contract=off, so the same operands give the same bits wherever it is
-// inlined.
+// inlined.  The word-grid backward kernels (cross_grid.h) take their factors and their per-(j, k) terms from here too.
 #ifndef MMS_COSINE_MATH_H_
 #define MMS_COSINE_MATH_H_
 
@@ -41,8 +41,14 @@ __device__ __forceinline__ CosineFactors cosine_factors(float T, float n0, float
   f.ca = T / (n1 * n1);
   return f;
 }
+// The bare term, for callers that add it to an accumulator started at +0.f (the word-grid kernels of cross_grid.h):
+// there `0.f +` changes no bit -- it turns a term of -0 into +0, and acc + (-0) = acc + (+0) for every acc such a
+// sum can hold (an accumulation from +0 never reaches -0).  cosine_grad_fac is the element itself: -0 becomes +0.
+__device__ __forceinline__ float cosine_term_fac(float g, float inv01, float c, float other, float self) {
+  return g * (other * inv01 - self * c);
+}
 __device__ __forceinline__ float cosine_grad_fac(float g, float inv01, float c, float other, float self) {
-  return 0.f + g * (other * inv01 - self * c);
+  return 0.f + cosine_term_fac(g, inv01, c, other, self);
 }
 __device__ __forceinline__ float4 cosine_grad4_fac(float g, float inv01, float c, const float4& other, const float4& self) {
   float4 o;
@@ -53,8 +59,12 @@ __device__ __forceinline__ float4 cosine_grad4_fac(float g, float inv01, float c
 
 // ---- backward, the reference's expression written out (cosine_rows_kernel, :239-245):
 //   dq += g*(a/n0/n1 - q*T/(n0*n0)) ; da += g*(q/n0/n1 - a*T/(n1*n1));   nss = n0*n0 for dq, n1*n1 for da.
+// cosine_term_div: the bare term, as cosine_term_fac.
+__device__ __forceinline__ float cosine_term_div(float g, float n0, float n1, float T, float nss, float other, float self) {
+  return g * (other / n0 / n1 - self * T / nss);
+}
 __device__ __forceinline__ float cosine_grad_div(float g, float n0, float n1, float T, float nss, float other, float self) {
-  return 0.f + g * (other / n0 / n1 - self * T / nss);
+  return 0.f + cosine_term_div(g, n0, n1, T, nss, other, self);
 }
 __device__ __forceinline__ float4 cosine_grad4_div(float g, float n0, float n1, float T, float nss, const float4& other,
                                                    const float4& self) {

@@ -1,6 +1,6 @@
 // csrc/cross_acc.h -- the register tile of one lane of the word-grid SimCross forward (dist_mode 0 / 1): the one
-// definition of the d-ascending sums and of T, shared by the fp32 kernels (simcross_cross.hip) and the fp16-storage
-// ones (simcross_cross_f16.hip), which differ in how q and a reach LDS and in nothing else.
+// definition of the d-ascending sums and of T, used by the two forward kernels of cross_grid.h for either storage
+// (float, half): the operands are fp32 by the time they are in LDS.
 #ifndef MMS_CROSS_ACC_H_
 #define MMS_CROSS_ACC_H_
 

@@ -1,6 +1,6 @@
 // csrc/cross_gather.h -- the Embed gather fused into the word-grid SimCross forward (dist_mode 0 / 1): the one
-// definition of the id clamp and of the gather's operands, shared by the fp32 kernels (simcross_cross.hip) and the
-// fp16-storage ones (simcross_cross_f16.hip), which differ in the table's element type and in nothing else.
+// definition of the id clamp and of the gather's operands, used by the forward and norm kernels of cross_grid.h for
+// either element type of the table (float, half).
 #ifndef MMS_CROSS_GATHER_H_
 #define MMS_CROSS_GATHER_H_
 

@@ -1,463 +1,16 @@
-// csrc/simcross_cross.hip -- SimCross dist_mode 0 (cosine) and 1 (Euclidean) on general W1 x W2 word grids
-// (TREC-QA 40x40) for gfx950, and the three fp32 entry points.  HBM-bound: no MFMA here.
+// csrc/simcross_cross.hip -- SimCross dist_mode 0 (cosine) and 1 (Euclidean) with fp32 storage: the float
+// instantiations of the word-grid kernels and launch plan of cross_grid.h (reference semantics there), the Euclidean
+// lane kernel, which exists for fp32 storage alone, and the three fp32 entry points.
 //
-// Reference semantics (all file:line in src/caffe/layers/sim_cross_layer.cpp):
-//   Euclid fwd  :96-111   T = 1/(1+sqrt(sum_d (q-a)^2)), d ascending, fp32.
-//   Euclid bwd  :208-225  tt = dT*T*T*T*(q-a)/(T-1+1e-9) (double divide);
-//                         dq[j,d] = sum_k tt (k ascending from 0),
-//                         da[k,d] = sum_j -tt (j ascending from 0).
-//   Cosine fwd  :112-139  n0,n1 = sqrt(dot) cached; T = dot/n0/n1.
-//   Cosine bwd  :226-250.
-//
-// Forward: one wave per (pair, j-tile, k-tile), q/a d-chunks staged in LDS, an RJ x RK register tile per lane, d
-// ascending per output.  W1 == W2 == 1 (sentence-vector pairs) has kernels of its own in simcross_rows.hip
-// (Euclid) and simcross_rows_cosine.hip; the entry points at the end of this file try those first and fall through to
-// the grid kernels.
+// W1 == W2 == 1 (sentence-vector pairs) has kernels of its own in simcross_rows.hip (Euclid) and
+// simcross_rows_cosine.hip; the entry points at the end of this file try those first and fall through to the grid
+// kernels.
 //
 // Compiled with -ffp-contract=off: the reference CPU build has no FMA
 // contraction, so mul and add must round separately to match it bitwise.
-#include "cosine_math.h"
-#include "cross_acc.h"
-#include "cross_gather.h"
-#include "euclid_math.h"
-#include "mms_internal.h"
+#include "cross_grid.h"
 
 namespace mms {
-
-// L2 norms of `rows` rows of length D: one wave per row (cosine, general W).
-// index != nullptr: row `row` is table row index[row] of x (K rows) -- the Embed gather fused in.
-__global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__ x,
-                                                       float* __restrict__ nrm,
-                                                       long long rows, int D,
-                                                       const float* __restrict__ index, int K,
-                                                       const float* __restrict__ ebias = nullptr) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* r = x + (index ? (long long)gather_id(index[row], K) : row) * D;
-  float s = 0.f;
-  for (int i = lane; i < D; i += 64) { const float v = ebias ? ebias[i] + r[i] : r[i]; s += v * v; }
-  s = wave_sum(s);
-  if (lane == 0) nrm[row] = sqrtf(s);
-}
-
-// Forward for general W1 x W2, MODE 0 (cosine; norms precomputed) or 1.
-// One wave per (pair, j-tile, k-tile); tile = (8*RJ) x (8*RK) outputs,
-// lane (lj = lane>>3, lk = lane&7) owns outputs j = j0+lj+8*rj, k = k0+lk+8*rk: CrossAcc (cross_acc.h).
-// The fused Embed gather (a CrossGather with iq != nullptr; gather_id clamps the ids): cross_gather.h.
-
-// Generic staging: q/a are staged DC floats of d at a time in LDS with stride DC+1 (bank =
-// (row + d) mod 32: conflict-free across rows, broadcast within a row).
-template <int RJ, int RK, int MODE>
-__global__ __launch_bounds__(256) void cross_fwd_kernel(
-    const float* __restrict__ q, const float* __restrict__ a,
-    const float* __restrict__ norm0, const float* __restrict__ norm1,
-    float* __restrict__ top, int N, int W1, int W2, int D, int tilesJ, int tilesK, CrossGather gt) {
-  constexpr int TJ = 8 * RJ, TK = 8 * RK, DC = 32, LS = DC + 1;
-  __shared__ float qs[4][TJ * LS];
-  __shared__ float as[4][TK * LS];
-  __shared__ int rowoff[4][TJ + TK];               // gather: element offset of each tile row in the table
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long work = (long long)blockIdx.x * 4 + wave;
-  const long long total = (long long)N * tilesJ * tilesK;
-  const bool valid = work < total;
-  const long long w = valid ? work : 0;
-  const int n = (int)(w / (tilesJ * tilesK));
-  const int rem = (int)(w % (tilesJ * tilesK));
-  const int j0 = (rem / tilesK) * TJ, k0 = (rem % tilesK) * TK;
-  const int lj = lane >> 3, lk = lane & 7;
-  const float* qn = q + (size_t)n * W1 * D;
-  const float* an = a + (size_t)n * W2 * D;
-
-  CrossAcc<RJ, RK, MODE> acc;
-  acc.clear();
-
-  const int lrow = lane >> 5, lcol = lane & 31;
-  // Staging: every load of a chunk is issued (clamped, hence unconditional, addresses) before the
-  // first LDS write; out-of-range elements are zeroed when written.  Written as `ok ? load : 0` the
-  // compiler emitted load / wait / write per row: 40 serialized round trips per chunk (18 of 38 us
-  // at 1517 x 40 x 40 x 50).  The NEXT chunk's loads are issued right after the LDS writes of the
-  // current one, so they are in flight behind its arithmetic.
-  float rq[TJ / 2], ra[TK / 2];
-  const bool gather = gt.iq != nullptr;
-  if (gather) {                                  // word ids of this tile's rows -> table offsets, once
-    for (int r = lane; r < TJ + TK; r += 64) {
-      const bool isq = r < TJ;
-      const int rr = isq ? min(j0 + r, W1 - 1) : min(k0 + r - TJ, W2 - 1);
-      const float id = isq ? gt.iq[(size_t)n * W1 + rr] : gt.ia[(size_t)n * W2 + rr];
-      rowoff[wave][r] = gather_id(id, gt.K) * D;
-    }
-    wave_lds_sync();
-  }
-  auto fetch = [&](int d0) {
-    const int col = min(d0 + lcol, D - 1);
-    if (gather) {
-#pragma unroll
-      for (int r = 0; r < TJ; r += 2) rq[r / 2] = q[(size_t)rowoff[wave][r + lrow] + col];
-#pragma unroll
-      for (int r = 0; r < TK; r += 2) ra[r / 2] = a[(size_t)rowoff[wave][TJ + r + lrow] + col];
-      if (gt.bias) {
-        const float bv = gt.bias[col];
-#pragma unroll
-        for (int r = 0; r < TJ; r += 2) rq[r / 2] = bv + rq[r / 2];
-#pragma unroll
-        for (int r = 0; r < TK; r += 2) ra[r / 2] = bv + ra[r / 2];
-      }
-      return;
-    }
-#pragma unroll
-    for (int r = 0; r < TJ; r += 2) rq[r / 2] = qn[(size_t)min(j0 + r + lrow, W1 - 1) * D + col];
-#pragma unroll
-    for (int r = 0; r < TK; r += 2) ra[r / 2] = an[(size_t)min(k0 + r + lrow, W2 - 1) * D + col];
-  };
-  fetch(0);
-  for (int d0 = 0; d0 < D; d0 += DC) {
-    const int dn = min(DC, D - d0);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < TJ; r += 2)
-      qs[wave][(r + lrow) * LS + lcol] = (valid && j0 + r + lrow < W1 && lcol < dn) ? rq[r / 2] : 0.f;
-#pragma unroll
-    for (int r = 0; r < TK; r += 2)
-      as[wave][(r + lrow) * LS + lcol] = (valid && k0 + r + lrow < W2 && lcol < dn) ? ra[r / 2] : 0.f;
-    __syncthreads();
-    if (d0 + DC < D) fetch(d0 + DC);
-    acc.accumulate(&qs[wave][lj * LS], &as[wave][lk * LS], LS, dn);
-  }
-  if (!valid) return;
-  acc.finish(top, norm0, norm1, n, j0, k0, lj, lk, W1, W2);
-}
-
-// "Pair image" staging for small D (the driver's default 50-d vectors): a wave owns one whole pair,
-// W1 = 8*RJ and W2 = 8*RK exactly, and the (W1 x D) and (W2 x D) blocks of q and a -- contiguous in
-// memory -- are COPIED to LDS as they are, 16 bytes per lane per load, row stride D (no padding, no
-// chunking over d, no index arithmetic).  Rows 8 apart must fall into different banks for the
-// broadcast reads of accumulate(): gcd(D, 64) <= 8 (launch_cross_fwd checks).  Against the generic
-// staging at 1517 x 40 x 40 x 50 this replaces 80 4-byte load instructions and 80 predicated LDS
-// writes per wave by 16 + 16.  Waves are independent: 2 per workgroup, 32 KB of LDS each.
-// D is a template parameter: with a run-time row stride the ten row addresses of accumulate() are
-// recomputed per d step (VALU-bound loop: +15 % time); compiled in, they are immediate offsets.
-template <int RJ, int RK, int MODE, int D>
-__global__ __launch_bounds__(128) void cross_fwd_image_kernel(
-    const float* __restrict__ q, const float* __restrict__ a,
-    const float* __restrict__ norm0, const float* __restrict__ norm1,
-    float* __restrict__ top, int N, CrossGather gt) {
-  constexpr int W1 = 8 * RJ, W2 = 8 * RK;
-  extern __shared__ float4 img4[];                 // [2 waves][(W1 + W2) * D / 4]
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int work = blockIdx.x * 2 + wave;
-  const bool valid = work < N;
-  const int n = valid ? work : N - 1;
-  const int nq4 = W1 * D / 4, na4 = W2 * D / 4;
-  float4* qs4 = img4 + (size_t)wave * (nq4 + na4);
-  float4* as4 = qs4 + nq4;
-  const float4* q4 = reinterpret_cast<const float4*>(q + (size_t)n * W1 * D);
-  const float4* a4 = reinterpret_cast<const float4*>(a + (size_t)n * W2 * D);
-  if (gt.iq != nullptr) {
-    // Embed fused in: image row r is table row id[r]; rows are D floats = 8-byte aligned for even D, so
-    // the copy runs in float2.  Per batch: the ids of 8 + 8 elements, then their 16 loads, then the writes.
-    constexpr int R2 = D / 2;                      // float2 per row
-    float2* qs2 = reinterpret_cast<float2*>(qs4);
-    float2* as2 = reinterpret_cast<float2*>(as4);
-    const float2* t2 = reinterpret_cast<const float2*>(q);
-    const float* iq = gt.iq + (size_t)n * W1;
-    const float* ia = gt.ia + (size_t)n * W2;
-    constexpr int NQ2 = W1 * R2, NA2 = W2 * R2, NMAX = NQ2 > NA2 ? NQ2 : NA2;
-    for (int e0 = 0; e0 < NMAX; e0 += 512) {
-      float idq[8], ida[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = e0 + 64 * u + lane;
-        idq[u] = iq[min(e, NQ2 - 1) / R2];
-        ida[u] = ia[min(e, NA2 - 1) / R2];
-      }
-      float2 rq[8], ra[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = e0 + 64 * u + lane;
-        rq[u] = t2[(size_t)gather_id(idq[u], gt.K) * R2 + min(e, NQ2 - 1) % R2];
-        ra[u] = t2[(size_t)gather_id(ida[u], gt.K) * R2 + min(e, NA2 - 1) % R2];
-      }
-      if (gt.bias) {
-        const float2* b2 = reinterpret_cast<const float2*>(gt.bias);   // D even: the row pitch makes this 8-byte aligned with the table
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int e = e0 + 64 * u + lane;
-          const float2 bq = b2[min(e, NQ2 - 1) % R2], ba = b2[min(e, NA2 - 1) % R2];
-          rq[u].x = bq.x + rq[u].x; rq[u].y = bq.y + rq[u].y;
-          ra[u].x = ba.x + ra[u].x; ra[u].y = ba.y + ra[u].y;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = e0 + 64 * u + lane;
-        if (e < NQ2) qs2[e] = rq[u];
-        if (e < NA2) as2[e] = ra[u];
-      }
-    }
-  } else
-  // copy in batches of 4 + 4 loads (all issued before the first LDS write of the batch)
-  for (int i0 = 0; i0 < max(nq4, na4); i0 += 256) {
-    float4 rq[4], ra[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + 64 * u + lane;
-      rq[u] = q4[min(i, nq4 - 1)];
-      ra[u] = a4[min(i, na4 - 1)];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + 64 * u + lane;
-      if (i < nq4) qs4[i] = rq[u];
-      if (i < na4) as4[i] = ra[u];
-    }
-  }
-  wave_lds_sync();
-  const int lj = lane >> 3, lk = lane & 7;
-  CrossAcc<RJ, RK, MODE> acc;
-  acc.clear();
-  acc.accumulate(reinterpret_cast<const float*>(qs4) + lj * D, reinterpret_cast<const float*>(as4) + lk * D, D, D);
-  if (!valid) return;
-  acc.finish(top, norm0, norm1, n, 0, 0, lj, lk, W1, W2);
-}
-
-// Backward for general W1 x W2, MODE 0/1: one workgroup per pair n.  Thread
-// owns one (j,d) of dq and walks k ascending, then one (k,d) of da and walks
-// j ascending -- the reference's accumulation order (:209-223), so Euclidean
-// is bit-exact.  q/a/top rows of one n stay L1/L2-resident across the walk.
-template <int MODE>
-__global__ __launch_bounds__(256) void cross_bwd_kernel(
-    const float* __restrict__ q, const float* __restrict__ a,
-    const float* __restrict__ top, const float* __restrict__ top_diff,
-    const float* __restrict__ norm0, const float* __restrict__ norm1,
-    float* __restrict__ dq, float* __restrict__ da, int W1, int W2, int D) {
-  const int n = blockIdx.x;
-  const float* qn = q + (size_t)n * W1 * D;
-  const float* an = a + (size_t)n * W2 * D;
-  const float* Tn = top + (size_t)n * W1 * W2;
-  const float* gn = top_diff + (size_t)n * W1 * W2;
-  float* dqn = dq + (size_t)n * W1 * D;
-  float* dan = da + (size_t)n * W2 * D;
-  const float* n0n = MODE == 0 ? norm0 + (size_t)n * W1 : nullptr;
-  const float* n1n = MODE == 0 ? norm1 + (size_t)n * W2 : nullptr;
-
-  for (int e = threadIdx.x; e < W1 * D; e += 256) {
-    const int j = e / D, d = e - j * D;
-    const float qv = qn[e];
-    float acc = 0.f;
-    if (MODE == 1) {
-      for (int k = 0; k < W2; ++k) {
-        const EuclidCoef kc = euclid_coef(Tn[j * W2 + k], gn[j * W2 + k]);
-        acc += euclid_tt_exact(kc.c, kc.den, qv - an[(size_t)k * D + d]);
-      }
-    } else {
-      const float nrm0 = n0n[j];
-      for (int k = 0; k < W2; ++k) {
-        const float nrm1 = n1n[k];
-        acc += gn[j * W2 + k] * (an[(size_t)k * D + d] / nrm0 / nrm1 -
-                                 qv * Tn[j * W2 + k] / (nrm0 * nrm0));
-      }
-    }
-    dqn[e] = acc;
-  }
-  for (int e = threadIdx.x; e < W2 * D; e += 256) {
-    const int k = e / D, d = e - k * D;
-    const float av = an[e];
-    float acc = 0.f;
-    if (MODE == 1) {
-      for (int j = 0; j < W1; ++j) {
-        const EuclidCoef kc = euclid_coef(Tn[j * W2 + k], gn[j * W2 + k]);
-        acc += -euclid_tt_exact(kc.c, kc.den, qn[(size_t)j * D + d] - av);
-      }
-    } else {
-      const float nrm1 = n1n[k];
-      for (int j = 0; j < W1; ++j) {
-        const float nrm0 = n0n[j];
-        acc += gn[j * W2 + k] * (qn[(size_t)j * D + d] / nrm0 / nrm1 -
-                                 av * Tn[j * W2 + k] / (nrm1 * nrm1));
-      }
-    }
-    dan[e] = acc;
-  }
-}
-
-// Tiled backward for general W1 x W2 (the fast path when the per-pair tables fit
-// LDS).  One workgroup per (pair, 32-wide d chunk):
-//   * per-(j,k) coefficient tables are built ONCE per workgroup in LDS
-//     (Euclid: c, den, 1/den; cosine: g, 1/(n0 n1), T/n0^2, T/n1^2);
-//   * the q / a chunk is staged in LDS (stride 33: conflict-free);
-//   * a thread owns one (j,d) of dq and walks k ascending, then one (k,d) of da
-//     walking j ascending -- the reference's accumulation order (:209-223).
-// Euclid stays bit-exact (euclid_tt's self-checking reciprocal path).  Cosine
-// multiplies by precomputed reciprocals instead of dividing per term: it is
-// held to 1e-5 like everything that is BLAS-ordered in the reference.
-constexpr int kBwdDC = 32;
-
-template <int MODE, bool EXACT>
-__global__ __launch_bounds__(256) void cross_bwd_tiled_kernel(
-    const float* __restrict__ q, const float* __restrict__ a,
-    const float* __restrict__ top, const float* __restrict__ top_diff,
-    const float* __restrict__ norm0, const float* __restrict__ norm1,
-    float* __restrict__ dq, float* __restrict__ da, int W1, int W2, int D, int nchunks, int split) {
-  extern __shared__ double lds_d[];
-  constexpr int LS = kBwdDC + 1;
-  // split: blockIdx.x = (n * nchunks + chunk) * 2 + pass -- the dq pass and the da pass of one
-  // (pair, chunk) run as separate workgroups (twice the parallelism; small batches).
-  // Otherwise one workgroup does both and the tables are built once (large batches).
-  const int bid = split ? (blockIdx.x >> 1) : blockIdx.x;
-  const bool do_dq = !split || (blockIdx.x & 1) == 0, do_da = !split || (blockIdx.x & 1) == 1;
-  const int n = bid / nchunks, chunk = bid % nchunks;
-  const int d0 = chunk * kBwdDC, dn = min(kBwdDC, D - d0);
-  const int JK = W1 * W2;
-  // carve: doubles first (8-byte aligned), then floats
-  double* t_den = lds_d;                          // MODE 1: [JK]
-  double* t_rcp = lds_d + (MODE == 1 ? JK : 0);   // MODE 1: [JK]
-  float* fbase = reinterpret_cast<float*>(lds_d + (MODE == 1 ? 2 * JK : 0));
-  float* t_c = fbase;                             // MODE 1: c       MODE 0: g
-  float* t_i01 = fbase + JK;                      // MODE 0: 1/(n0 n1)
-  float* t_b1 = fbase + 2 * JK;                   // MODE 0: T/n0^2
-  float* t_b2 = fbase + 3 * JK;                   // MODE 0: T/n1^2
-  float* qs = fbase + (MODE == 1 ? JK : 4 * JK);
-  float* as = qs + W1 * LS;
-  // fp32 backward arithmetic (include/mms.h): the double tables are not needed; fl32(1/den)
-  // lives in their place
-  float* t_r = reinterpret_cast<float*>(lds_d);
-
-  const float* qn = q + (size_t)n * W1 * D;
-  const float* an = a + (size_t)n * W2 * D;
-  const float* Tn = top + (size_t)n * JK;
-  const float* gn = top_diff + (size_t)n * JK;
-
-  for (int e0 = threadIdx.x; MODE == 1 && e0 < JK; e0 += 256 * 8) {
-    float tv[8], gv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { const int e = min(e0 + 256 * u, JK - 1); tv[u] = Tn[e]; gv[u] = gn[e]; }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int e = e0 + 256 * u;
-      if (e >= JK) break;
-      const EuclidCoef k = euclid_coef(tv[u], gv[u]);
-      t_c[e] = k.c;
-      if (EXACT) { t_den[e] = k.den; t_rcp[e] = k.rcp; } else { t_r[e] = (float)k.rcp; }
-    }
-  }
-  for (int e = threadIdx.x; MODE != 1 && e < JK; e += 256) {
-    if (MODE == 1) {
-    } else {
-      const int j = e / W2, kk = e - j * W2;
-      const float n0 = norm0[(size_t)n * W1 + j], n1 = norm1[(size_t)n * W2 + kk];
-      t_c[e] = gn[e];
-      t_i01[e] = 1.0f / n0 / n1;
-      t_b1[e] = Tn[e] / (n0 * n0);
-      t_b2[e] = Tn[e] / (n1 * n1);
-    }
-  }
-  // eight unconditional (clamped) loads per thread in flight before the first LDS write; a rolled
-  // `ok ? load : 0` loop paid one memory round trip per iteration
-  auto stage = [&](const float* src, float* dst, int W) {
-    for (int base = 0; base < W * kBwdDC; base += 256 * 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = base + threadIdx.x + 256 * u;
-        v[u] = src[(size_t)min(e >> 5, W - 1) * D + min(d0 + (e & 31), D - 1)];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = base + threadIdx.x + 256 * u;
-        if (e < W * kBwdDC) dst[(e >> 5) * LS + (e & 31)] = (e & 31) < dn ? v[u] : 0.f;
-      }
-    }
-  };
-  stage(qn, qs, W1);
-  stage(an, as, W2);
-  __syncthreads();
-
-  float* dqn = dq + (size_t)n * W1 * D;
-  float* dan = da + (size_t)n * W2 * D;
-  if (MODE == 1 && !EXACT) {
-    // fp32 arithmetic: a thread owns FOUR consecutive d of one row, so the per-(j,k) coefficients
-    // c and fl32(1/den) are read from LDS once per four terms (6 LDS reads per 4 terms instead of
-    // 12: this loop is LDS-bandwidth-bound); every sum still runs over k (or j) ascending.
-    for (int e = threadIdx.x; do_dq && e < W1 * (kBwdDC / 4); e += 256) {
-      const int j = e >> 3, dd0 = (e & 7) * 4;
-      if (dd0 >= dn) continue;
-      float qv[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) qv[u] = qs[j * LS + dd0 + u];
-      for (int k = 0; k < W2; ++k) {
-        const float c = t_c[j * W2 + k], r = t_r[j * W2 + k];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] += (c * (qv[u] - as[k * LS + dd0 + u])) * r;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (dd0 + u < dn) dqn[(size_t)j * D + d0 + dd0 + u] = acc[u];
-    }
-    for (int e = threadIdx.x; do_da && e < W2 * (kBwdDC / 4); e += 256) {
-      const int k = e >> 3, dd0 = (e & 7) * 4;
-      if (dd0 >= dn) continue;
-      float av[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) av[u] = as[k * LS + dd0 + u];
-      for (int j = 0; j < W1; ++j) {
-        const float c = t_c[j * W2 + k], r = t_r[j * W2 + k];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] += -((c * (qs[j * LS + dd0 + u] - av[u])) * r);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (dd0 + u < dn) dan[(size_t)k * D + d0 + dd0 + u] = acc[u];
-    }
-    return;
-  }
-  for (int e = threadIdx.x; do_dq && e < W1 * kBwdDC; e += 256) {
-    const int j = e >> 5, dd = e & 31;
-    if (dd >= dn) continue;
-    const float qv = qs[j * LS + dd];
-    float acc = 0.f;
-    for (int k = 0; k < W2; ++k) {
-      const int t = j * W2 + k;
-      const float av = as[k * LS + dd];
-      if (MODE == 1 && EXACT) {
-        EuclidCoef kc;
-        kc.c = t_c[t]; kc.den = t_den[t]; kc.rcp = t_rcp[t];
-        acc += euclid_tt(kc, qv - av);
-      } else if (MODE == 1) {
-        acc += (t_c[t] * (qv - av)) * t_r[t];
-      } else {
-        acc += t_c[t] * (av * t_i01[t] - qv * t_b1[t]);
-      }
-    }
-    dqn[(size_t)j * D + d0 + dd] = acc;
-  }
-  for (int e = threadIdx.x; do_da && e < W2 * kBwdDC; e += 256) {
-    const int k = e >> 5, dd = e & 31;
-    if (dd >= dn) continue;
-    const float av = as[k * LS + dd];
-    float acc = 0.f;
-    for (int j = 0; j < W1; ++j) {
-      const int t = j * W2 + k;
-      const float qv = qs[j * LS + dd];
-      if (MODE == 1 && EXACT) {
-        EuclidCoef kc;
-        kc.c = t_c[t]; kc.den = t_den[t]; kc.rcp = t_rcp[t];
-        acc += -euclid_tt(kc, qv - av);
-      } else if (MODE == 1) {
-        acc += -((t_c[t] * (qv - av)) * t_r[t]);
-      } else {
-        acc += t_c[t] * (qv * t_i01[t] - av * t_b2[t]);
-      }
-    }
-    dan[(size_t)k * D + d0 + dd] = acc;
-  }
-}
-
-static size_t cross_bwd_tiled_lds(int mode, int W1, int W2) {
-  const size_t JK = (size_t)W1 * W2;
-  const size_t tables = mode == 1 ? JK * (8 + 8 + 4) : JK * 16;
-  return tables + (size_t)(W1 + W2) * (kBwdDC + 1) * sizeof(float) + 16;
-}
 
 // ---- Euclidean cross-geometry backward for MANY pairs of narrow word grids (cfg 4's 1517 x 40 x 40 x 50) ------
 // cross_bwd_tiled_kernel computes every term tt[j,k,d] twice (once in the k-ordered sum of dq[j,d], once in
@@ -612,84 +165,19 @@ static bool cross_bwd_lane_ok(bool exact, int N, int W1, int W2, int D) {
   // the tiled kernel wins (1517 x 40 x 40 x 50: 236 vs 183 us; 4096 x 20 x 20 x 50: 50 vs 92 us)
   return width && D <= 64 && N >= 512 && cross_bwd_lane_lds(exact, W1, W2) <= (exact ? 16 : 64) * 1024;
 }
-
-// ================================ dispatch ==================================
-
-template <int MODE>
-static void launch_cross_fwd(const float* q, const float* a, const float* n0,
-                             const float* n1, float* top, int N, int W1, int W2,
-                             int D, hipStream_t s, CrossGather gt = CrossGather{nullptr, nullptr, 0, nullptr}) {
-  // Register tile per lane: as large as possible (fewer LDS reads per flop) while the
-  // launch still has enough waves to occupy the chip (small N: smaller tiles, more waves).
-  auto r_cap = [](int w, int cap) { int r = (w + 7) / 8; return r > cap ? cap : r; };
-  int rj = 1, rk = 1, tilesJ = 1, tilesK = 1;
-  for (int cap = 5; cap >= 1; --cap) {
-    rj = r_cap(W1, cap); rk = r_cap(W2, cap);
-    tilesJ = (W1 + 8 * rj - 1) / (8 * rj); tilesK = (W2 + 8 * rk - 1) / (8 * rk);
-    if ((long long)N * tilesJ * tilesK >= 1024) break;
-  }
-  const long long work = (long long)N * tilesJ * tilesK;
-  // small D: the whole pair as one LDS image per wave (cross_fwd_image_kernel)
-  {
-    auto gcd64 = [](int d) { int g = 64; while (d % g) g >>= 1; return g; };
-    const size_t img = (size_t)(W1 + W2) * D * sizeof(float);
-    constexpr int DI = 50;   // the driver's default embedding width (do_trec_qa_clean.py -d 50)
-    const bool fits = W1 % 8 == 0 && W2 % 8 == 0 && W1 / 8 <= 5 && W2 / 8 <= 5 && N >= 1024 &&
-                      D == DI && aligned16(q) && aligned16(a) && gcd64(D) <= 8 && 2 * img <= 64 * 1024;
-    static_assert(DI % 2 == 0, "gather copies float2");
-    if (fits) {
-      const unsigned g2 = (unsigned)((N + 1) / 2);
-#define MMS_IMG_CASE(J, K)                                                                      \
-  if (W1 == 8 * J && W2 == 8 * K) {                                                             \
-    hipLaunchKernelGGL((cross_fwd_image_kernel<J, K, MODE, DI>), dim3(g2), dim3(128), 2 * img,  \
-                       s, q, a, n0, n1, top, N, gt);                                            \
-    return;                                                                                     \
-  }
-#define MMS_IMG_ROW(J) MMS_IMG_CASE(J, 1) MMS_IMG_CASE(J, 2) MMS_IMG_CASE(J, 3) MMS_IMG_CASE(J, 4) MMS_IMG_CASE(J, 5)
-      MMS_IMG_ROW(1) MMS_IMG_ROW(2) MMS_IMG_ROW(3) MMS_IMG_ROW(4) MMS_IMG_ROW(5)
-#undef MMS_IMG_ROW
-#undef MMS_IMG_CASE
-    }
-  }
-  const unsigned grid = (unsigned)((work + 3) / 4);
-#define MMS_CROSS_CASE(J, K)                                                        \
-  if (rj == J && rk == K) {                                                         \
-    hipLaunchKernelGGL((cross_fwd_kernel<J, K, MODE>), dim3(grid), dim3(256), 0, s, \
-                       q, a, n0, n1, top, N, W1, W2, D, tilesJ, tilesK, gt);        \
-    return;                                                                         \
-  }
-#define MMS_CROSS_ROW(J) MMS_CROSS_CASE(J, 1) MMS_CROSS_CASE(J, 2) MMS_CROSS_CASE(J, 3) \
-                         MMS_CROSS_CASE(J, 4) MMS_CROSS_CASE(J, 5)
-  MMS_CROSS_ROW(1) MMS_CROSS_ROW(2) MMS_CROSS_ROW(3) MMS_CROSS_ROW(4) MMS_CROSS_ROW(5)
-#undef MMS_CROSS_ROW
-#undef MMS_CROSS_CASE
-}
-
-// =============================== entry points ===============================
-// DESIGN.md 4.4b is the table this section is read against.  W1 == W2 == 1 tries simcross_rows.hip (Euclid) or
-// simcross_rows_cosine.hip first.
-
-// The word-grid forward; gt.iq != nullptr: q and a are the embedding table and the Embed gather is fused in.
-static void cross_forward(int mode, int N, int W1, int W2, int D, const float* q, const float* a, float* top,
-                          float* norm0, float* norm1, hipStream_t s, CrossGather gt) {
-  if (mode == 1) {
-    launch_cross_fwd<1>(q, a, nullptr, nullptr, top, N, W1, W2, D, s, gt);
-    return;
-  }
-  const long long r0 = (long long)N * W1, r1 = (long long)N * W2;
-  hipLaunchKernelGGL(row_norm_kernel, dim3((unsigned)((r0 + 3) / 4)), dim3(256), 0, s, q, norm0, r0, D, gt.iq, gt.K, gt.bias);
-  hipLaunchKernelGGL(row_norm_kernel, dim3((unsigned)((r1 + 3) / 4)), dim3(256), 0, s, a, norm1, r1, D, gt.ia, gt.K, gt.bias);
-  launch_cross_fwd<0>(q, a, norm0, norm1, top, N, W1, W2, D, s, gt);
-}
-
-// The word-grid backward: lane kernel (Euclid, narrow grids, many pairs), else tiled, else plain.
-static void cross_backward(int mode, int N, int W1, int W2, int D, const float* q, const float* a, const float* top,
-                           const float* top_diff, const float* norm0, const float* norm1, float* dq, float* da,
-                           bool exact, hipStream_t s) {
-  const int nchunks = (D + kBwdDC - 1) / kBwdDC;
-  if (mode == 1) norm0 = norm1 = nullptr;                          // Euclid caches no norms
-  if (mode == 1 && cross_bwd_lane_ok(exact, N, W1, W2, D)) {
-    const size_t lds = cross_bwd_lane_lds(exact, W1, W2);
+// cross_bwd_tiled_kernel (cross_grid.h), which the figures above compare this kernel with and which takes over where
+// cross_bwd_lane_ok declines, walks d in chunks of kBwdDC.  Those figures (44 % of the second chunk idle at D = 50, the
+// lane kernel up to D = 64 = two chunks) were taken at this width; a retune of the chunk has to revisit them.
+namespace lane_figures {
+constexpr int kBwdDC = 32;
+static_assert(kBwdDC == ::mms::kBwdDC, "the lane kernel's thresholds were measured against 32-wide chunks of the tiled kernel");
+}  // namespace lane_figures
+// the first of cross_backward's three routes (cross_grid.h), for fp32 storage
+template <>
+inline bool launch_cross_bwd_lane<float>(int N, int W1, int W2, int D, const float* q, const float* a, const float* top,
+                                         const float* top_diff, float* dq, float* da, bool exact, hipStream_t s) {
+  if (!cross_bwd_lane_ok(exact, N, W1, W2, D)) return false;
+  const size_t lds = cross_bwd_lane_lds(exact, W1, W2);
 #define MMS_LANE(W2_)                                                                                     \
   case W2_:                                                                                               \
     if (exact)                                                                                            \
@@ -699,22 +187,14 @@ static void cross_backward(int mode, int N, int W1, int W2, int D, const float* 
       hipLaunchKernelGGL((cross_bwd_lane_kernel<W2_, false, 2>), dim3((unsigned)N), dim3(128), lds, s, q, \
                          a, top, top_diff, dq, da, W1, D);                                                \
     break;
-    switch (W2) { MMS_LANE(8) MMS_LANE(16) MMS_LANE(20) MMS_LANE(24) MMS_LANE(32) MMS_LANE(40) MMS_LANE(48) }
+  switch (W2) { MMS_LANE(8) MMS_LANE(16) MMS_LANE(20) MMS_LANE(24) MMS_LANE(32) MMS_LANE(40) MMS_LANE(48) }
 #undef MMS_LANE
-  } else if (cross_bwd_tiled_lds(mode, W1, W2) <= 64 * 1024 && 2LL * N * nchunks <= 0x7fffffffLL) {
-    const size_t lds = cross_bwd_tiled_lds(mode, W1, W2);
-    const int split = ((long long)N * nchunks < 1024) ? 1 : 0;     // fill the chip when the batch is small
-    const unsigned grid = (unsigned)((split ? 2LL : 1LL) * N * nchunks);
-    // cosine has one arithmetic: its instance is <0, true>
-    const auto k = mode == 0 ? cross_bwd_tiled_kernel<0, true>
-                   : exact   ? cross_bwd_tiled_kernel<1, true> : cross_bwd_tiled_kernel<1, false>;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, q, a, top, top_diff, norm0, norm1, dq, da, W1, W2, D,
-                       nchunks, split);
-  } else {
-    hipLaunchKernelGGL((mode == 1 ? cross_bwd_kernel<1> : cross_bwd_kernel<0>), dim3(N), dim3(256), 0, s, q, a, top,
-                       top_diff, norm0, norm1, dq, da, W1, W2, D);
-  }
+  return true;
 }
+
+// =============================== entry points ===============================
+// DESIGN.md 4.4b is the table this section is read against.  W1 == W2 == 1 tries simcross_rows.hip (Euclid) or
+// simcross_rows_cosine.hip first.
 
 static bool rows_geometry(int W1, int W2) { return W1 == 1 && W2 == 1; }
 
@@ -726,7 +206,7 @@ int simcross_elementwise_forward(int mode, int N, int W1, int W2, int D,
   if (rows && mode == 0)
     launch_cosine_rows<true, false>(N, D, q, a, nullptr, top, norm0, norm1, nullptr, nullptr, s);
   else if (!(rows && launch_euclid_rows<true, false>(N, D, q, a, nullptr, nullptr, top, nullptr, nullptr, false, s)))
-    cross_forward(mode, N, W1, W2, D, q, a, top, norm0, norm1, s, CrossGather{nullptr, nullptr, 0, nullptr});
+    cross_forward<float, false>(mode, N, W1, W2, D, q, a, top, norm0, norm1, s, kNoGather);
   return launch_status();
 }
 
@@ -738,7 +218,8 @@ int embed_simcross_forward(int mode, int N, int W1, int W2, int D, int K, const 
                            const float* index_a, const float* weight, const float* embed_bias, float* top,
                            float* norm0, float* norm1, hipStream_t s) {
   if (N == 0) return MMS_OK;
-  cross_forward(mode, N, W1, W2, D, weight, weight, top, norm0, norm1, s, CrossGather{index_q, index_a, K, embed_bias});
+  cross_forward<float, true>(mode, N, W1, W2, D, weight, weight, top, norm0, norm1, s,
+                             CrossGather{index_q, index_a, K, embed_bias});
   return launch_status();
 }
 
@@ -747,7 +228,7 @@ static int backward_with_mode(int mode, int N, int W1, int W2, int D, const floa
                               const float* top, const float* top_diff, const float* norm0, const float* norm1,
                               float* dq, float* da, bool exact, hipStream_t s) {
   if (!rows_geometry(W1, W2))
-    cross_backward(mode, N, W1, W2, D, q, a, top, top_diff, norm0, norm1, dq, da, exact, s);
+    cross_backward<float>(mode, N, W1, W2, D, q, a, top, top_diff, norm0, norm1, dq, da, exact, s);
   else if (mode == 1)
     launch_euclid_rows<false, true>(N, D, q, a, top, top_diff, nullptr, dq, da, exact, s);
   else

@@ -15,11 +15,11 @@ every seventh of a hold a single nonzero, whose position moves with the row.
 Backward bars, counted in roundings of at most u = 2^-24 each of the value rounded; t1 = g other / (n0 n1) and
 t2 = g self T / n^2 are the two terms of ONE (j, k) contribution, in exact arithmetic on the fp32 inputs (q, a, g and the
 forward's fp32 T, n0, n1):
-  factor form (cosine_factors / cosine_grad_fac: cosine_pair32_kernel, cross_bwd_tiled_kernel<0, .>):
+  factor form (cosine_factors / cosine_grad_fac: cosine_pair32_kernel, cross_bwd_tiled_kernel<float, 0, .>):
       1/n0 and /n1: 2, x other: 1             -> 3 u |t1|
       n0 n0: 1, T / that: 1, x self: 1        -> 3 u |t2|
       the subtraction: 1, x g: 1              -> 2 u |t1 - t2|           total 5 u (|t1| + |t2|), "0 +" is exact
-  reference form (cosine_grad_div: cosine_rows_kernel, cross_bwd_kernel<0>, and the CPU oracle):
+  reference form (cosine_grad_div: cosine_rows_kernel, cross_bwd_plain_kernel<float, 0>, and the CPU oracle):
       other / n0 / n1: 2;  self T: 1, n0 n0: 1, the division: 1;  the subtraction and x g: 2      total 5 u (|t1| + |t2|)
 so both forms are held to BAR_GRAD = 5 u / (1 - 5 u) of |t1| + |t2| (the denominator carries the second-order terms).  With
 one nonzero g per row (dq) or per column (da) of a word grid an element is ONE such contribution -- the others are g = 0

@@ -1,14 +1,20 @@
-"""The fp32 word-grid SimCross (dist_mode 0 and 1; csrc/simcross_cross.hip, csrc/cross_acc.h): the host routing restated in Python, the
-shapes that reach every kernel instantiation and straddle every routing threshold, the inputs and the references.
+"""The word-grid SimCross (dist_mode 0 and 1; csrc/cross_grid.h -- one kernel set and one launch plan for float and half storage --
+csrc/simcross_cross.hip with the fp32-only lane kernel, csrc/cross_acc.h): the host routing restated in Python, the shapes that reach every
+fp32 kernel instantiation and straddle every routing threshold, the inputs and the references.
 
 Routing, one function per host decision, each a line-for-line restatement:
-  fwd_tile       launch_cross_fwd: the register tile (rj, rk) = ceil(W / 8) capped at 5, 4, .. 1 until N tilesJ tilesK >= 1024
-  fwd_route      launch_cross_fwd: ("image", W1 / 8, W2 / 8) for whole 8-row tiles of at most 5, N >= 1024, D == 50, q and a 16-byte
-                 aligned, rows 8 apart in different banks and two pairs' images in 64 KB; else ("fwd", rj, rk).  MODE 0 and 1 alike.
+  fwd_tile       cross_fwd_tile: the register tile (rj, rk) = ceil(W / 8) capped at 5, 4, .. 1 until N tilesJ tilesK >= 1024
+  fwd_image_ok   cross_fwd_image_ok: whole 8-row tiles of at most 5, N >= 1024, D == 50, q and a aligned to `need` bytes (16; gathered from a
+                 table GridStorage::kGatherAlign: 16 for floats, 4 for halves), two pairs' fp32 images in 64 KB; rows 8 apart fall in different banks
+                 at that D (a static_assert there)
+  fwd_route      launch_cross_fwd: ("image", W1 / 8, W2 / 8) if fwd_image_ok, else ("fwd", rj, rk).  MODE 0 and 1 alike.
   bwd_lane_lds   cross_bwd_lane_lds        bwd_tiled_lds  cross_bwd_tiled_lds        bwd_lane_ok  cross_bwd_lane_ok
-  bwd_route      cross_backward, Euclid: ("lane", W2, exact), ("tiled", exact, "split" | "unsplit") or ("plain",)
-kBwdDC is read from the source; the other constants are literals there, and source_lines() names the lines that hold them so that
-tests/test_cross_grid_model.py can assert they still read as restated here: a retune breaks the model instead of passing it by.
+  bwd_tiled      cross_backward: the tiled kernel ("split" | "unsplit") while its tables fit 64 KB, else None (the plain kernel)
+  bwd_route      cross_backward<float>, Euclid: ("lane", W2, exact), ("tiled", exact, "split" | "unsplit") or ("plain",)
+tests/f16_cross_model.py and tests/embed_f16_cross_model.py import fwd_tile, fwd_image_ok, bwd_tiled_lds and bwd_tiled from here: the half calls
+go through the same host functions.  The named constants are read from the source; the lane kernel's are literals there, and source_lines()
+names the lines that hold every decision so that tests/test_cross_grid_model.py can assert they still read as restated here: a retune breaks
+the model instead of passing it by.
 
 CPU only; tests/test_cross_grid_model.py proves this module, tests/test_gpu_cross_grid.py uses it.
 """
@@ -19,51 +25,71 @@ import numpy as np
 from layer_plans import CSRC, constants
 from util import TOL, qa
 
-SOURCE = "simcross_cross.hip"
-BWD_DC = constants(SOURCE, ["kBwdDC"])["kBwdDC"]
+GRID = "cross_grid.h"                           # the kernels and the launch plan of both storages
+LANE = "simcross_cross.hip"                     # the fp32-only lane kernel and its route
+_K = constants(GRID, ["kBwdDC", "kMaxTile", "kFill", "kImageD", "kLdsBytes"])
+BWD_DC = _K["kBwdDC"]
 LANE_WIDTHS = (8, 16, 20, 24, 32, 40, 48)       # cross_bwd_lane_ok, MMS_LANE
 LANE_MIN_N, LANE_MAX_D = 512, 64                # cross_bwd_lane_ok
 LANE_LDS_KB = {True: 16, False: 64}             # cross_bwd_lane_ok: reference rounding, fp32 arithmetic
-LDS_BYTES = 64 * 1024                           # cross_backward (tiled), launch_cross_fwd (two images)
-FILL = 1024                                     # launch_cross_fwd: N tiles >= 1024; cross_backward: split while N nchunks < 1024
-IMAGE_D, IMAGE_MIN_N, MAX_TILE = 50, 1024, 5    # launch_cross_fwd
+LDS_BYTES = _K["kLdsBytes"]                     # cross_backward (tiled), cross_fwd_image_ok (two images)
+FILL = _K["kFill"]                              # cross_fwd_tile: N tiles >= 1024; cross_fwd_image_ok: N >= 1024; cross_backward: split while N nchunks < 1024
+IMAGE_D, IMAGE_MIN_N, MAX_TILE = _K["kImageD"], FILL, _K["kMaxTile"]
+RESTATED = dict(kBwdDC=32, kMaxTile=5, kFill=1024, kImageD=50, kLdsBytes=64 * 1024)      # what the shape tables below were chosen for
+GATHER_ALIGN = {"float": 16, "_Float16": 4}     # GridStorage<S>::kGatherAlign
 
 
 def source_lines():
-    """{what: (regular expression, the text its group must hold, runs of blanks apart)}: the lines of the source with the literals
-    restated above."""
+    """{what: (file, regular expression, the text its group must hold, runs of blanks apart)}: the lines of the sources with the decisions
+    and literals restated above."""
     return {
-        "lane widths": (r"const bool width = ([^;]+);", " || ".join("W2 == %d" % w for w in LANE_WIDTHS)),
-        "lane widths instantiated": (r"switch \(W2\) \{ ([^}]+) \}", " ".join("MMS_LANE(%d)" % w for w in LANE_WIDTHS)),
-        "lane conditions": (r"return width && ([^;]+);",
+        "lane widths": (LANE, r"const bool width = ([^;]+);", " || ".join("W2 == %d" % w for w in LANE_WIDTHS)),
+        "lane widths instantiated": (LANE, r"switch \(W2\) \{ ([^}]+) \}", " ".join("MMS_LANE(%d)" % w for w in LANE_WIDTHS)),
+        "lane conditions": (LANE, r"return width && ([^;]+);",
                             "D <= %d && N >= %d && cross_bwd_lane_lds(exact, W1, W2) <= (exact ? %d : %d) * 1024"
                             % (LANE_MAX_D, LANE_MIN_N, LANE_LDS_KB[True], LANE_LDS_KB[False])),
-        "lane table bytes": (r"return (\(size_t\)W1 \* W2 \* \(exact [^;]+);",
+        "lane table bytes": (LANE, r"return (\(size_t\)W1 \* W2 \* \(exact [^;]+);",
                              "(size_t)W1 * W2 * (exact ? 8 + 8 + 4 : 8) + (exact ? 0 : (size_t)W2 * 64 * sizeof(float)) + 16"),
-        "tiled table bytes": (r"const size_t tables = ([^;]+);", "mode == 1 ? JK * (8 + 8 + 4) : JK * 16"),
-        "tiled staging bytes": (r"return tables \+ ([^;]+);", "(size_t)(W1 + W2) * (kBwdDC + 1) * sizeof(float) + 16"),
-        "tiled condition": (r"\} else if \((cross_bwd_tiled_lds[^{]+)\) \{", "cross_bwd_tiled_lds(mode, W1, W2) <= 64 * 1024 && 2LL * N * nchunks <= 0x7fffffffLL"),
-        "split": (r"const int split = ([^;]+);", "((long long)N * nchunks < %d) ? 1 : 0" % FILL),
-        "chunks": (r"const int nchunks = ([^;]+);", "(D + kBwdDC - 1) / kBwdDC"),
-        "tile cap": (r"for \(int cap = (\d+); cap >= 1; --cap\)", "%d" % MAX_TILE),
-        "tile fill": (r"if \(\(long long\)N \* tilesJ \* tilesK >= (\d+)\) break;", "%d" % FILL),
-        "image width": (r"constexpr int DI = (\d+);", "%d" % IMAGE_D),
-        "image conditions": (r"const bool fits = ([^;]+);",
-                             "W1 % 8 == 0 && W2 % 8 == 0 && W1 / 8 <= {t} && W2 / 8 <= {t} && N >= {n} && "
-                             "D == DI && aligned16(q) && aligned16(a) && gcd64(D) <= 8 && 2 * img <= 64 * 1024"
-                             .format(t=MAX_TILE, n=IMAGE_MIN_N)),
+        "lane first": (GRID, r"if \((mode == 1 && launch_cross_bwd_lane<S>\([^;]+)\) return;",
+                       "mode == 1 && launch_cross_bwd_lane<S>(N, W1, W2, D, q, a, top, top_diff, dq, da, exact, s)"),
+        "lane route": (LANE, r"if \((!cross_bwd_lane_ok\([^;]+)\) return false;", "!cross_bwd_lane_ok(exact, N, W1, W2, D)"),
+        "lane figures' chunk": (LANE, r"namespace lane_figures \{\s*(constexpr int kBwdDC = \d+;\s*static_assert\([^,]+),",
+                                "constexpr int kBwdDC = %d; static_assert(kBwdDC == ::mms::kBwdDC" % BWD_DC),
+        "tiled table bytes": (GRID, r"const size_t tables = ([^;]+);", "mode == 1 ? JK * (8 + 8 + 4) : JK * 16"),
+        "tiled staging bytes": (GRID, r"return tables \+ ([^;]+);", "(size_t)(W1 + W2) * (kBwdDC + 1) * sizeof(float) + 16"),
+        "tiled bytes": (GRID, r"const size_t lds = ([^;]+);", "cross_bwd_tiled_lds(mode, W1, W2)"),
+        "tiled condition": (GRID, r"\n  if \((lds <= [^{]+)\) \{", "lds <= kLdsBytes && 2LL * N * nchunks <= 0x7fffffffLL"),
+        "split": (GRID, r"const int split = ([^;]+);", "((long long)N * nchunks < kFill) ? 1 : 0"),
+        "chunks": (GRID, r"const int nchunks = ([^;]+);", "(D + kBwdDC - 1) / kBwdDC"),
+        "tile cap": (GRID, r"for \(int cap = (\w+); cap >= 1; --cap\)", "kMaxTile"),
+        "tile fill": (GRID, r"if \(\(long long\)N \* t\.tilesJ \* t\.tilesK >= (\w+)\) break;", "kFill"),
+        "image conditions": (GRID, r"return (W1 % 8 == 0 [^;]+);",
+                             "W1 % 8 == 0 && W2 % 8 == 0 && W1 / 8 <= kMaxTile && W2 / 8 <= kMaxTile && N >= kFill && D == kImageD && "
+                             "(reinterpret_cast<uintptr_t>(q) & need) == 0 && (reinterpret_cast<uintptr_t>(a) & need) == 0 && 2 * img <= kLdsBytes"),
+        "image bytes": (GRID, r"inline bool cross_fwd_image_ok\([^{]+\{[^}]*?const size_t img = ([^;]+);", "(size_t)(W1 + W2) * D * sizeof(float)"),
+        "image alignment": (GRID, r"const uintptr_t need = ([^;]+);", "(GATHER ? GridStorage<S>::kGatherAlign : 16) - 1"),
+        "image banks": (GRID, r"static_assert\((kImageD[^,]+),", "kImageD % 2 == 0 && kImageD % 16 != 0"),
+        "gather alignment, floats": (GRID, r"struct GridStorage<float> \{[^}]*?kGatherAlign = (\d+),", "%d" % GATHER_ALIGN["float"]),
+        "gather alignment, halves": (GRID, r"struct GridStorage<_Float16> \{[^}]*?kGatherAlign = (\d+),", "%d" % GATHER_ALIGN["_Float16"]),
+        "tile table row": (GRID, r"#define MMS_TILES5\(K, S, J, \.\.\.\) \\\n\s*\{([^}]+)\}", ", ".join("K<S, J, %d, __VA_ARGS__>" % k for k in range(1, MAX_TILE + 1))),
+        "tile table": (GRID, r"#define MMS_TILES5X5\(K, S, \.\.\.\)[ \\\n]*\{([^}]+)\}",
+                       ", ".join("MMS_TILES5(K, S, %d, __VA_ARGS__)" % j for j in range(1, MAX_TILE + 1))),
+        "image kernels": (GRID, r"image\[kMaxTile\]\[kMaxTile\] =\s*(MMS_TILES5X5\([^;]+);", "MMS_TILES5X5(cross_fwd_image_kernel, S, MODE, kImageD, GATHER)"),
+        "generic kernels": (GRID, r"generic\[kMaxTile\]\[kMaxTile\] =\s*(MMS_TILES5X5\([^;]+);", "MMS_TILES5X5(cross_fwd_kernel, S, MODE, GATHER)"),
+        "image kernel chosen": (GRID, r"hipLaunchKernelGGL\((image\[[^,]+),", "image[W1 / 8 - 1][W2 / 8 - 1]"),
+        "generic kernel chosen": (GRID, r"hipLaunchKernelGGL\((generic\[[^,]+),", "generic[t.rj - 1][t.rk - 1]"),
     }
 
 
-def source_text():
-    return open(os.path.join(CSRC, SOURCE)).read()
+def source_text(source=GRID):
+    return open(os.path.join(CSRC, source)).read()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # routing
 # ----------------------------------------------------------------------------------------------------------------------
 def fwd_tile(N, W1, W2):
-    """launch_cross_fwd: (rj, rk, tilesJ, tilesK)."""
+    """cross_fwd_tile: (rj, rk, tilesJ, tilesK)."""
     for cap in range(MAX_TILE, 0, -1):
         rj, rk = min((W1 + 7) // 8, cap), min((W2 + 7) // 8, cap)
         tj, tk = (W1 + 8 * rj - 1) // (8 * rj), (W2 + 8 * rk - 1) // (8 * rk)
@@ -79,12 +105,16 @@ def gcd64(d):
     return g
 
 
-def fwd_route(N, W1, W2, D, aligned=True):
-    """launch_cross_fwd: ("image", J, K) or ("fwd", rj, rk); aligned: q and a both on a 16-byte boundary."""
+def fwd_image_ok(N, W1, W2, D, q=0, a=0, need=16):
+    """cross_fwd_image_ok; q, a are addresses, need the alignment asked of them: 16, or gathered GATHER_ALIGN of the storage."""
     img = (W1 + W2) * D * 4
-    fits = (W1 % 8 == 0 and W2 % 8 == 0 and W1 // 8 <= MAX_TILE and W2 // 8 <= MAX_TILE and N >= IMAGE_MIN_N and D == IMAGE_D and aligned
-            and gcd64(D) <= 8 and 2 * img <= LDS_BYTES)
-    if fits:
+    return (W1 % 8 == 0 and W2 % 8 == 0 and W1 // 8 <= MAX_TILE and W2 // 8 <= MAX_TILE and N >= IMAGE_MIN_N and D == IMAGE_D
+            and q % need == 0 and a % need == 0 and 2 * img <= LDS_BYTES)
+
+
+def fwd_route(N, W1, W2, D, aligned=True):
+    """launch_cross_fwd<float>: ("image", J, K) or ("fwd", rj, rk); aligned: q and a both on a 16-byte boundary."""
+    if fwd_image_ok(N, W1, W2, D, q=0 if aligned else 4):
         return ("image", W1 // 8, W2 // 8)
     return ("fwd",) + fwd_tile(N, W1, W2)[:2]
 
@@ -102,14 +132,20 @@ def bwd_lane_ok(exact, N, W1, W2, D):
     return W2 in LANE_WIDTHS and D <= LANE_MAX_D and N >= LANE_MIN_N and bwd_lane_lds(exact, W1, W2) <= LANE_LDS_KB[bool(exact)] * 1024
 
 
-def bwd_route(N, W1, W2, D, exact):
-    """cross_backward, mode 1."""
+def bwd_tiled(mode, N, W1, W2, D):
+    """cross_backward behind the lane kernel: "split" or "unsplit" for the tiled kernel, None for the plain one."""
     nchunks = (D + BWD_DC - 1) // BWD_DC
+    if bwd_tiled_lds(mode, W1, W2) <= LDS_BYTES and 2 * N * nchunks <= 0x7fffffff:
+        return "split" if N * nchunks < FILL else "unsplit"
+    return None
+
+
+def bwd_route(N, W1, W2, D, exact):
+    """cross_backward<float>, mode 1."""
     if bwd_lane_ok(exact, N, W1, W2, D):
         return ("lane", W2, bool(exact))
-    if bwd_tiled_lds(1, W1, W2) <= LDS_BYTES and 2 * N * nchunks <= 0x7fffffff:
-        return ("tiled", bool(exact), "split" if N * nchunks < FILL else "unsplit")
-    return ("plain",)
+    tiled = bwd_tiled(1, N, W1, W2, D)
+    return ("tiled", bool(exact), tiled) if tiled else ("plain",)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -1,15 +1,16 @@
-"""mms_embed_simcross_forward_f16 (csrc/simcross_cross_f16.hip with the Embed gather of csrc/cross_gather.h): the host routing restated in
+"""mms_embed_simcross_forward_f16 (csrc/simcross_cross_f16.hip: the GATHER instantiations of csrc/cross_grid.h, with the Embed gather of csrc/cross_gather.h): the host routing restated in
 Python, the table of cases the GPU test runs, their data and their references.  index_q (N, W1), index_a (N, W2) word ids as floats, table
 (K, D) halves, embed_bias (D) fp32 or None; top (N, 1, W1, W2), norm0 (N, W1), norm1 (N, W2) fp32.
 
 Routing, one function per host decision:
   refusal        mms_abi.hip: embed_simcross_refusal -- a dist_mode other than 0 / 1 UNSUPPORTED (before the sizes, as the _f32 twin); bad sizes,
                  K <= 0, K D > 2^31 - 1 INVALID_ARG.  W1 == W2 == 1 is served.
-  fwd_tile       launch_cross_fwd_f16: the function mms_simcross_forward_f16 goes through -- f16_cross_model.fwd_tile, not restated twice
-  fwd_image_ok   cross_fwd_image_ok_f16 with gather: whole 8-row tiles of at most 5, N >= 1024, D == 50, two images in 64 KB and the table
-                 4-byte aligned -- the image kernel gathers in half2, and a row of 50 halves = 100 bytes keeps 4-byte alignment and no more
+  fwd_tile       cross_fwd_tile: the function mms_simcross_forward_f16 goes through -- cross_grid_model.fwd_tile, not restated twice
+  fwd_image_ok   cross_fwd_image_ok<_Float16, GATHER = true> (cross_grid_model.fwd_image_ok): whole 8-row tiles of at most 5, N >= 1024, D == 50,
+                 two images in 64 KB and the table 4-byte aligned (GridStorage<_Float16>::kGatherAlign) -- the image kernel gathers in half2, and a
+                 row of 50 halves = 100 bytes keeps 4-byte alignment and no more
   fwd_route      the image kernel <W1 / 8, W2 / 8> if fwd_image_ok, else the generic kernel <rj, rk>
-  launches       cross_forward_f16: dist_mode 1 the forward alone; dist_mode 0 row_norm_f16_kernel twice, then the forward
+  launches       cross_forward: dist_mode 1 the forward alone; dist_mode 0 row_norm_kernel<_Float16> twice, then the forward
 
 What the call is held to (tests/test_gpu_embed_simcross_f16.py):
   Euclid: top is the CPU oracle's on the fp32 rows bias + widen(table)[clamped ids], bit for bit.
@@ -24,8 +25,9 @@ CPU only; tests/test_embed_f16_cross_model.py proves this module.
 import numpy as np
 
 import cosine_model as cm
+import cross_grid_model as gm
 import f16_cross_model as xm
-from f16_cross_model import fwd_tile            # noqa: F401 (the same host function: launch_cross_fwd_f16)
+from cross_grid_model import fwd_tile            # noqa: F401 (the same host function: cross_fwd_tile)
 
 OK, INVALID_ARG, UNSUPPORTED = xm.OK, xm.INVALID_ARG, xm.UNSUPPORTED
 IMAGE_D = xm.IMAGE_D
@@ -50,10 +52,8 @@ def refusal(mode, N, W1, W2, D, K):
 
 
 def fwd_image_ok(N, W1, W2, D, table=0):
-    """cross_fwd_image_ok_f16(gather = true); table is the table's address."""
-    img = (W1 + W2) * D * 4
-    return (W1 % 8 == 0 and W2 % 8 == 0 and W1 // 8 <= 5 and W2 // 8 <= 5 and N >= 1024 and D == IMAGE_D and table % 4 == 0
-            and 2 * img <= LDS_BYTES)
+    """cross_fwd_image_ok<_Float16, GATHER = true>: q == a == the table; table is the table's address."""
+    return gm.fwd_image_ok(N, W1, W2, D, table, table, need=gm.GATHER_ALIGN["_Float16"])
 
 
 def fwd_route(N, W1, W2, D, table=0):

@@ -1,17 +1,20 @@
-"""The fp16-storage word-grid family (csrc/simcross_cross_f16.hip behind mms_simcross_forward_f16, mms_simcross_backward_f16 and
-mms_simcross_forward_backward_f16): the host routing restated in Python, the shapes that reach every kernel instantiation, the
-references and the bars.  q (N, W1, D), a (N, W2, D), dq, da halves; top, top_diff (N, 1, W1, W2), norm0 (N, W1), norm1 (N, W2) fp32.
+"""The fp16-storage word-grid family (the _Float16 instantiations of csrc/cross_grid.h, entered through csrc/simcross_cross_f16.hip behind
+mms_simcross_forward_f16, mms_simcross_backward_f16 and mms_simcross_forward_backward_f16): the host routing, the shapes that reach every
+kernel instantiation, the references and the bars.  q (N, W1, D), a (N, W2, D), dq, da halves; top, top_diff (N, 1, W1, W2), norm0 (N, W1),
+norm1 (N, W2) fp32.
 
-Routing, one function per host decision:
+Routing, one function per host decision; the launch plan is the fp32 call's (one template for both storages), so its restatement is
+tests/cross_grid_model.py's, held to the source's literals by tests/test_cross_grid_model.py, and imported here:
   refusal        mms_abi.hip: grid_f16_refusal -- bad sizes INVALID_ARG, dist_mode 2 and W1 == W2 == 1 UNSUPPORTED
-  fwd_tile       launch_cross_fwd_f16: the register tile (rj, rk) = ceil(W / 8) capped at 5, 4, .. 1 until N tilesJ tilesK >= 1024
-  fwd_image_ok   cross_fwd_image_ok_f16: whole 8-row tiles of at most 5, N >= 1024, D == 50, q and a 16-byte aligned, 2 images in 64 KB
+  fwd_tile       cross_grid_model.fwd_tile (cross_fwd_tile)
+  fwd_image_ok   cross_grid_model.fwd_image_ok (cross_fwd_image_ok) with q and a 16-byte aligned
   fwd_route      the image kernel <W1 / 8, W2 / 8> if fwd_image_ok, else the generic kernel <rj, rk>; either for MODE 0 and 1
-  bwd_tiled_lds  cross_bwd_tiled_lds_f16: bytes of the coefficient tables and the staged chunk
-  bwd_route      cross_backward_f16: tiled <MODE, EXACT> while that fits 64 KB, split when N nchunks < 1024; else plain <MODE>
+  bwd_tiled_lds  cross_grid_model.bwd_tiled_lds (cross_bwd_tiled_lds): bytes of the coefficient tables and the staged chunk
+  bwd_route      cross_backward<_Float16> -- no lane kernel for halves: tiled <MODE, EXACT> while cross_grid_model.bwd_tiled says so, split
+                 when N nchunks < 1024; else plain <MODE>
 Every instantiation is reachable: FWD_REACHABLE is 25 generic and 25 image tiles for each mode, BWD_REACHABLE the tiled kernel's three
 arithmetics (cosine, Euclid reference rounding, Euclid fp32) split and unsplit and the two plain kernels.  UNREACHABLE is empty
-(cross_bwd_tiled_f16_kernel<0, false> is never instantiated: cosine has one arithmetic).
+(cross_bwd_tiled_kernel<_Float16, 0, false> is never instantiated: cosine has one arithmetic).
 
 What the kernels are held to:
   Euclid forward: top is the fp32 oracle's on the widened inputs bit for bit, and the fp32 call's.
@@ -40,14 +43,14 @@ CPU only; tests/test_f16_cross_model.py proves this module, tests/test_gpu_f16_c
 import numpy as np
 
 import cosine_model as cm
+import cross_grid_model as gm
+from cross_grid_model import bwd_tiled_lds, fwd_image_ok, fwd_tile            # noqa: F401 (the same host functions: cross_grid.h)
 from f16_rows_model import PINNED_MIN, check_bracket, half_bracket, in_bracket, pinned_share, finite_error  # noqa: F401 (re-exported)
 from util import TOL
 
 OK, INVALID_ARG, UNSUPPORTED = 0, 1, 2          # include/mms.h
 FP32_TERM_BAR = 4.0 * cm.U24                    # 2 ulp of a term = 2 x 2^-23 of its value
-IMAGE_D = 50
-LDS_BYTES = 64 * 1024
-BWD_DC = 32
+IMAGE_D, LDS_BYTES, BWD_DC = gm.IMAGE_D, gm.LDS_BYTES, gm.BWD_DC
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -65,38 +68,17 @@ def refusal(mode, N, W1, W2, D):
     return OK
 
 
-def fwd_tile(N, W1, W2):
-    """launch_cross_fwd_f16: (rj, rk, tilesJ, tilesK)."""
-    for cap in (5, 4, 3, 2, 1):
-        rj, rk = min((W1 + 7) // 8, cap), min((W2 + 7) // 8, cap)
-        tj, tk = (W1 + 8 * rj - 1) // (8 * rj), (W2 + 8 * rk - 1) // (8 * rk)
-        if N * tj * tk >= 1024:
-            break
-    return rj, rk, tj, tk
-
-
-def fwd_image_ok(N, W1, W2, D, q=0, a=0):
-    """cross_fwd_image_ok_f16; q, a are addresses."""
-    img = (W1 + W2) * D * 4
-    return (W1 % 8 == 0 and W2 % 8 == 0 and W1 // 8 <= 5 and W2 // 8 <= 5 and N >= 1024 and D == IMAGE_D and q % 16 == 0 and a % 16 == 0
-            and 2 * img <= LDS_BYTES)
-
-
 def fwd_route(N, W1, W2, D, q=0, a=0):
     if fwd_image_ok(N, W1, W2, D, q, a):
         return ("image", W1 // 8, W2 // 8)
     return ("generic",) + fwd_tile(N, W1, W2)[:2]
 
 
-def bwd_tiled_lds(mode, W1, W2):
-    return W1 * W2 * (20 if mode == 1 else 16) + (W1 + W2) * (BWD_DC + 1) * 4 + 16
-
-
 def bwd_route(mode, exact, N, W1, W2, D):
-    """cross_backward_f16: ("tiled", mode, exact, split) or ("plain", mode); cosine's tiled instance is <0, true>."""
-    nchunks = (D + BWD_DC - 1) // BWD_DC
-    if bwd_tiled_lds(mode, W1, W2) <= LDS_BYTES and 2 * N * nchunks <= 0x7fffffff:
-        return ("tiled", mode, True if mode == 0 else bool(exact), 1 if N * nchunks < 1024 else 0)
+    """cross_backward<_Float16>: ("tiled", mode, exact, split) or ("plain", mode); cosine's tiled instance is <0, true>."""
+    tiled = gm.bwd_tiled(mode, N, W1, W2, D)
+    if tiled:
+        return ("tiled", mode, True if mode == 0 else bool(exact), 1 if tiled == "split" else 0)
     return ("plain", mode)
 
 

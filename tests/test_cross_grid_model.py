@@ -9,18 +9,23 @@ import cross_grid_model as gm
 
 
 def test_constants_match_the_source():
-    txt = gm.source_text()
-    assert re.search(r"constexpr int kBwdDC = %d;" % gm.BWD_DC, txt) and gm.BWD_DC == 32
-    blanks = lambda s: " ".join(s.split())
-    for what, (pattern, want) in gm.source_lines().items():
-        found = re.findall(pattern, txt)
-        assert len(found) == 1, "%s: %d lines of %s match %r" % (what, len(found), gm.SOURCE, pattern)
-        assert blanks(found[0]) == blanks(want), "%s: %s now reads %r, the model restates %r" % (what, gm.SOURCE, blanks(found[0]), want)
-    # the instantiation lists of the two forward kernels: every <J, K> in 1..5
-    for name in ("IMG", "CROSS"):
-        cases = re.search(r"#define MMS_%s_ROW\(J\) ((?:MMS_%s_CASE\(J, \d\)[ \\\n]*)+)" % (name, name), txt).group(1)
-        assert re.findall(r"CASE\(J, (\d)\)", cases) == ["1", "2", "3", "4", "5"], name
-        assert re.search(r"MMS_%s_ROW\(1\) MMS_%s_ROW\(2\) MMS_%s_ROW\(3\) MMS_%s_ROW\(4\) MMS_%s_ROW\(5\)\n" % ((name,) * 5), txt), name
+    txt = {f: gm.source_text(f) for f in (gm.GRID, gm.LANE)}
+    assert re.search(r"constexpr int kBwdDC = %d;" % gm.BWD_DC, txt[gm.GRID]) and gm.BWD_DC == 32
+    # the named constants, each defined once, hold what the shape tables were chosen for
+    assert dict(kBwdDC=gm.BWD_DC, kMaxTile=gm.MAX_TILE, kFill=gm.FILL, kImageD=gm.IMAGE_D, kLdsBytes=gm.LDS_BYTES) == gm.RESTATED
+    for name in gm.RESTATED:
+        assert len(re.findall(r"constexpr \w+ %s =" % name, txt[gm.GRID])) == 1, name
+    # the lane kernel's source restates the chunk width its figures were taken at, and holds it to the definition
+    assert re.findall(r"constexpr \w+ (k\w+) =", txt[gm.LANE]) == ["kBwdDC"]
+    assert gm.IMAGE_MIN_N == 1024 and gm.gcd64(gm.IMAGE_D) <= 8, "rows 8 apart of the pair image fall in different banks"
+    blanks = lambda s: " ".join(s.replace("\\\n", " ").split())          # runs of blanks and a macro's line continuations apart
+    # the instantiation lists of the two forward kernels ("tile table row", "tile table": every <J, K> in 1..5, one helper used by both
+    # tables) are among the lines
+    for what, (source, pattern, want) in gm.source_lines().items():
+        found = re.findall(pattern, txt[source])
+        assert len(found) == 1, "%s: %d lines of %s match %r" % (what, len(found), source, pattern)
+        assert blanks(found[0]) == blanks(want), "%s: %s now reads %r, the model restates %r" % (what, source, blanks(found[0]), want)
+    assert txt[gm.GRID].count("#define MMS_TILES5X5(") == 1 and "MMS_TILES5" not in txt[gm.LANE]
     assert gm.bwd_lane_lds(True, 20, 40) == 16016 and gm.bwd_lane_lds(False, 138, 48) == 65296
     assert gm.bwd_tiled_lds(1, 40, 40) == 1600 * 20 + 80 * 33 * 4 + 16 and gm.bwd_tiled_lds(0, 40, 40) == 1600 * 16 + 80 * 33 * 4 + 16
 

@@ -37,7 +37,7 @@ def test_the_image_predicate_and_its_alignment():
     for bad in ((1023, 40, 40, 50), (1024, 40, 40, 48), (1024, 40, 41, 50), (1024, 48, 40, 50), (1024, 40, 40, 52)):
         assert not em.fwd_image_ok(*bad), bad
     assert em.fwd_image_ok(1024, 8, 8, 50) and em.fwd_route(1024, 8, 16, 50, table=2) == ("generic", 1, 2)
-    # the tile of the route that takes over is launch_cross_fwd_f16's, whatever the alignment
+    # the tile of the route that takes over is launch_cross_fwd<_Float16>'s, whatever the alignment
     assert em.fwd_route(4, 40, 40, 50) == ("generic", 1, 1) and em.fwd_route(1024, 40, 40, 48) == ("generic", 5, 5)
 
 

@@ -18,8 +18,8 @@ instantiations, the scalar rows kernel on a misaligned view and the vec4 rows ke
 Route table: (N, W1, W2, D) -> forward | backward | fused, read off simcross_elementwise_forward, simcross_elementwise_backward,
 simcross_elementwise_forward_backward and launch_cross_fwd.  pair32<d4, F, B> = cosine_pair32_kernel<d4, FWD, BWD, 8> (16 pairs per
 workgroup, 32 lanes per pair, NIT = ceil(d4 / 32) loads per lane); rows<V, F, B> = cosine_rows_kernel<VEC4, FWD, BWD> (4 pairs per
-workgroup); fwd<J, K> = row_norm_kernel x 2 + cross_fwd_kernel<J, K, 0>; image<J, K> = row_norm_kernel x 2 +
-cross_fwd_image_kernel<J, K, 0, 50>; tiled(split) = cross_bwd_tiled_kernel<0, true>, split = 1 while N ceil(D / 32) < 1024.  On
+workgroup); fwd<J, K> = row_norm_kernel x 2 + cross_fwd_kernel<float, J, K, 0>; image<J, K> = row_norm_kernel x 2 +
+cross_fwd_image_kernel<float, J, K, 0, 50>; tiled(split) = cross_bwd_tiled_kernel<float, 0, true>, split = 1 while N ceil(D / 32) < 1024.  On
 word grids the fused call is the forward followed by the backward.  profiles/cosine_routes.txt records the kernels a trace of
 this file saw per test id.
 
@@ -56,7 +56,7 @@ this file saw per test id.
   ( 512,  8,  8,  50)  fwd<1, 1>: N < 1024 declines the image | tiled(unsplit): 1024, the first unsplit size
   (1024,  5,  7,  20)  fwd<1, 1>: W % 8 != 0 declines the image | tiled(unsplit): D < 32, one chunk with dn = 20
   ( 600, 40, 40,  50)  fwd<4, 4>: 2 x 2 tiles of 32 x 32 with remainders | tiled(unsplit): 1200
-  (   1, 70, 60,   9)  fwd<1, 1>: 9 x 8 tiles | cross_bwd_kernel<0>: the factor tables (84 KB) exceed LDS; the reference's expression
+  (   1, 70, 60,   9)  fwd<1, 1>: 9 x 8 tiles | cross_bwd_plain_kernel<float, 0>: the factor tables (84 KB) exceed LDS; the reference's expression
                        in the reference's order: bit for bit
  dense data only
   ( 520, 24, 24,  34)  fwd<2, 2> | tiled(unsplit): 1040

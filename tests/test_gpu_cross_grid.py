@@ -2,13 +2,13 @@
 sides of every routing threshold.  tests/cross_grid_model.py has the routing, the shapes and the inputs; tests/test_cross_grid_model.py
 proves on the CPU which launch each shape takes.
 
- forward   cross_fwd_kernel<rj, rk, MODE> for every rj, rk in 1..5 (GENERIC_TILES: ragged widths, chunks of 3, 8, 32 + 1, 32 + 2),
-           cross_fwd_image_kernel<j, k, MODE, 50> for every j, k in 1..5 (IMAGE_TILES, odd and even N); the same shapes with q and a one
-           float off a 16-byte boundary (the image declines: cross_fwd_kernel<j, k> on whole tiles); N, D and W1 next to the image's
+ forward   cross_fwd_kernel<float, rj, rk, MODE> for every rj, rk in 1..5 (GENERIC_TILES: ragged widths, chunks of 3, 8, 32 + 1, 32 + 2),
+           cross_fwd_image_kernel<float, j, k, MODE, 50> for every j, k in 1..5 (IMAGE_TILES, odd and even N); the same shapes with q and a one
+           float off a 16-byte boundary (the image declines: cross_fwd_kernel<float, j, k> on whole tiles); N, D and W1 next to the image's
            conditions (FWD_EDGES); all of them through the Embed-fused call's gathering loads, with and without the Embed bias.
            Euclid: the oracle's words.  Cosine: top, norm0, norm1 at the dense bar of tests/test_gpu_cosine_accuracy.py.
  backward  BWD in both euclid_backward_modes: cross_bwd_lane_kernel<W2, true> and <W2, false, 2> at all seven widths, D below the
-           wave, one row of q; cross_bwd_tiled_kernel<1, true> and <1, false> split and unsplit; cross_bwd_kernel<1>.  Reference
+           wave, one row of q; cross_bwd_tiled_kernel<float, 1, true> and <1, false> split and unsplit; cross_bwd_plain_kernel<float, 1>.  Reference
            rounding: the oracle's words from simcross_backward and simcross_forward_backward.  fp32 arithmetic: the bound of
            tests/test_gpu_bwd_modes.py (cross_grid_model.assert_fp32_mode).  One shape per route again with every operand one float off
            a 16-byte boundary.

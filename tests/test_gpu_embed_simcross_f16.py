@@ -4,14 +4,14 @@ has the routing, the cases, their data and references; tests/test_embed_f16_cros
 inside a sentinel-filled buffer and starts as NaN.
 
 Route table, ((N, W1, W2, D), K, halves past a 16-byte boundary) -> the forward launch (embed_f16_cross_model.EXPECTED_ROUTE):
-  (   3,  5,  7, 33) K 97      cross_fwd_f16_kernel<1, 1>: ragged tile, chunks of 32 + 1            the same, K 1: every id is row 0
-  (   2,  1,  1,  1) K 97      cross_fwd_f16_kernel<1, 1>: W1 == W2 == 1 stays on the word-grid kernels
-  (   2,  1,  9, 64) K 97      cross_fwd_f16_kernel<1, 1>: two k tiles, two full chunks
-  (   4, 40, 40, 50) K 97      cross_fwd_f16_kernel<1, 1>: small N, 25 tiles per pair
-  (1024, 40, 40, 48) K 97      cross_fwd_f16_kernel<5, 5>
-  (1024,  8, 16, 50) K 97      cross_fwd_image_f16_kernel<1, 2>;  + 1 half: cross_fwd_f16_kernel<1, 2>;  + 2 halves: the image kernel again
-  (1024, 40, 40, 50) K 97      cross_fwd_image_f16_kernel<5, 5>;  + 1 half: cross_fwd_f16_kernel<5, 5>
-  cosine: row_norm_f16_kernel twice in front of either
+  (   3,  5,  7, 33) K 97      cross_fwd_kernel<_Float16, 1, 1>: ragged tile, chunks of 32 + 1            the same, K 1: every id is row 0
+  (   2,  1,  1,  1) K 97      cross_fwd_kernel<_Float16, 1, 1>: W1 == W2 == 1 stays on the word-grid kernels
+  (   2,  1,  9, 64) K 97      cross_fwd_kernel<_Float16, 1, 1>: two k tiles, two full chunks
+  (   4, 40, 40, 50) K 97      cross_fwd_kernel<_Float16, 1, 1>: small N, 25 tiles per pair
+  (1024, 40, 40, 48) K 97      cross_fwd_kernel<_Float16, 5, 5>
+  (1024,  8, 16, 50) K 97      cross_fwd_image_kernel<_Float16, 1, 2>;  + 1 half: cross_fwd_kernel<_Float16, 1, 2>;  + 2 halves: the image kernel again
+  (1024, 40, 40, 50) K 97      cross_fwd_image_kernel<_Float16, 5, 5>;  + 1 half: cross_fwd_kernel<_Float16, 5, 5>
+  cosine: row_norm_kernel<_Float16> twice in front of either
 """
 import ctypes
 

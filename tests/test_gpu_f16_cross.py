@@ -4,20 +4,20 @@ default backward mode and the cosine gradients held to the half bracket, exact-s
 refusals.  tests/f16_cross_model.py has the routing, the shapes, the references and the bars; tests/test_f16_cross_model.py proves them
 on the CPU.  Every output sits inside a sentinel-filled buffer and starts as NaN.
 
-Route table, (N, W1, W2, D) -> launch, read off launch_cross_fwd_f16 / cross_backward_f16 (MODE 0 cosine, 1 Euclid, both run):
+Route table, (N, W1, W2, D) -> launch, read off launch_cross_fwd<_Float16> / cross_backward<_Float16> (MODE 0 cosine, 1 Euclid, both run):
  forward
-  (   3,  5,  7, 50)  cross_fwd_f16_kernel<1, 1>: one ragged tile, 100-byte rows
-  (   2,  9, 17, 33)  cross_fwd_f16_kernel<1, 1>: 2 x 3 ragged tiles, odd D, a chunk of one d, rows only 2-byte aligned
-  (1024, 40, 40,  8)  cross_fwd_f16_kernel<5, 5>          (1024, 40, 24, 34)  cross_fwd_f16_kernel<5, 3>: accq and accs of CrossAcc
-  (1024, 24, 40, 50)  cross_fwd_image_f16_kernel<3, 5>    (1025,  8,  8, 50)  cross_fwd_image_f16_kernel<1, 1>, last workgroup one wave
-  (1024, 24, 40, 50), q one half past a 16-byte boundary: cross_fwd_f16_kernel<3, 5>, the image kernel's bits
-  f16_cross_model.GENERIC_TILES: cross_fwd_f16_kernel<rj, rk> for every rj, rk in 1..5 (N = 1024, ragged widths, D in 3, 8, 33, 34)
-  f16_cross_model.IMAGE_TILES:   cross_fwd_image_f16_kernel<J, K> for every J, K in 1..5 (N = 1024, D = 50)
-  cosine: row_norm_f16_kernel twice in front of either
- backward: cross_bwd_tiled_f16_kernel<0, true> (cosine), <1, true> (Euclid, reference rounding), <1, false> (Euclid, fp32 arithmetic)
+  (   3,  5,  7, 50)  cross_fwd_kernel<_Float16, 1, 1>: one ragged tile, 100-byte rows
+  (   2,  9, 17, 33)  cross_fwd_kernel<_Float16, 1, 1>: 2 x 3 ragged tiles, odd D, a chunk of one d, rows only 2-byte aligned
+  (1024, 40, 40,  8)  cross_fwd_kernel<_Float16, 5, 5>          (1024, 40, 24, 34)  cross_fwd_kernel<_Float16, 5, 3>: accq and accs of CrossAcc
+  (1024, 24, 40, 50)  cross_fwd_image_kernel<_Float16, 3, 5>    (1025,  8,  8, 50)  cross_fwd_image_kernel<_Float16, 1, 1>, last workgroup one wave
+  (1024, 24, 40, 50), q one half past a 16-byte boundary: cross_fwd_kernel<_Float16, 3, 5>, the image kernel's bits
+  f16_cross_model.GENERIC_TILES: cross_fwd_kernel<_Float16, rj, rk> for every rj, rk in 1..5 (N = 1024, ragged widths, D in 3, 8, 33, 34)
+  f16_cross_model.IMAGE_TILES:   cross_fwd_image_kernel<_Float16, J, K> for every J, K in 1..5 (N = 1024, D = 50)
+  cosine: row_norm_kernel<_Float16> twice in front of either
+ backward: cross_bwd_tiled_kernel<_Float16, 0, true> (cosine), <1, true> (Euclid, reference rounding), <1, false> (Euclid, fp32 arithmetic)
   (   3,  5,  7, 50)  tiled, split        (  2,  9, 17, 33)  tiled, split, a chunk of one d      (70, 40, 40, 50)  tiled, split
   ( 512, 16, 24, 50)  tiled, not split    (  2, 12, 20, 70)  tiled, split, three chunks
-  (   2, 60, 60, 16)  cross_bwd_plain_f16_kernel<MODE>: the tables exceed 64 KB
+  (   2, 60, 60, 16)  cross_bwd_plain_kernel<_Float16, MODE>: the tables exceed 64 KB
 """
 import ctypes
 

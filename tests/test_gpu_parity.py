@@ -114,7 +114,7 @@ def test_euclid_forward_backward_bitexact(shape, bwd_mode, oracle, hiplib):
 def test_euclid_shape_fuzz_bitexact(oracle, hiplib):
     """Many small random geometries (wave kernel with 1 or 2 pairs per wave and NIT 1..4, generic
     rows kernel, ragged word grids): everything Euclidean stays bit-exact.  With N <= 5 and
-    W <= 47 every word grid here takes cross_fwd_kernel<1, 1> (the register tile shrinks until
+    W <= 47 every word grid here takes cross_fwd_kernel<float, 1, 1> (the register tile shrinks until
     N tiles >= 1024) and the split tiled backward (47 x 47 tables fit 64 KB); the other register
     tiles, the image kernel, the lane kernels, the unsplit tiled and the plain backward are swept
     by tests/test_gpu_cross_grid.py."""
