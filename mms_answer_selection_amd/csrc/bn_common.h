@@ -1,5 +1,6 @@
-// csrc/bn_common.h -- what csrc/bn.hip (BN) and csrc/bn_pool.hip (BN -> AvePool -> TanH) share: the sizes of the two
-// routes, the workgroup sum with its fixed order, and the ascending fold of a channel's chunk sums.
+// csrc/bn_common.h -- what csrc/bn.hip (BN) and csrc/bn_pool.hip (BN -> AvePool / MaxPool -> TanH) share: the sizes of
+// the two routes, the workgroup sum with its fixed order, and the ascending fold of a channel's chunk sums; and what
+// csrc/bn_pool.hip shares with csrc/conv_stage.hip: a window's TEST-phase finish, AVE and MAX, and MAX's scan step.
 #ifndef MMS_BN_COMMON_H_
 #define MMS_BN_COMMON_H_
 
@@ -36,6 +37,44 @@ __device__ __forceinline__ T bn_pool_test_finish(T s, T ke, T nmean, T std, T sc
   const T sp = (m + nmean) / std;
   *save_pool = sp;
   return bn_tanh(sp * sc + sh);
+}
+
+// BN for one element, from nmean = -mean, std, scale and shift of its channel, in its two steps: bn_out(x) is
+// bp_bn_out(bp_normalised(x, ...), ...).  The only place that forms them: the MAX forward's finish and the MAX
+// backward's search for the mask compare their words.
+template <typename T>
+__device__ __forceinline__ T bp_normalised(T x, T nmean, T std) {
+  return (x + nmean) / std;
+}
+template <typename T>
+__device__ __forceinline__ T bp_bn_out(T xn, T sc, T sh) {
+  return xn * sc + sh;
+}
+
+// MAX: one step of the scan for a window's extremum, in (h, w) order.  The first element starts it; a later one
+// replaces *e where it is strictly larger (dir > 0: the channel's scale is positive) or smaller (dir < 0: negative); a
+// NaN never does, and with dir == 0 (scale == 0: every BN output is shift, the mask is the first element) nothing does.
+// csrc/bn_pool.hip's sweeps and csrc/conv_stage.hip's MAX epilogue all scan with it.
+template <typename T>
+__device__ __forceinline__ void bp_keep(bool first, T v, int dir, T* e) {
+  const bool less = v < *e, more = v > *e;           // both formed, then selected: no branch per element
+  *e = first || (dir < 0 ? less : dir > 0 && more) ? v : *e;
+}
+
+// dir of bp_keep for a channel's scale
+template <typename T>
+__device__ __forceinline__ int bp_dir(T sc) {
+  return sc < T(0) ? -1 : sc > T(0) ? 1 : 0;
+}
+
+// The TEST-phase finish of one pooling window of BN -> MaxPool -> TanH, from the window's extremum e (bp_keep's):
+// *save_pool and the return value, top.  csrc/bn_pool.hip's sweep and csrc/conv_stage.hip's MAX epilogue both finish
+// with it.
+template <typename T>
+__device__ __forceinline__ T bn_maxpool_test_finish(T e, T nmean, T std, T sc, T sh, T* save_pool) {
+  const T sp = bp_normalised(e, nmean, std);
+  *save_pool = sp;
+  return bn_tanh(bp_bn_out(sp, sc, sh));
 }
 
 __device__ __forceinline__ float bn_wave_sum(float v) { return wave_sum(v); }

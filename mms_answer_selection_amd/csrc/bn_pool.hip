@@ -190,33 +190,6 @@ __device__ __forceinline__ void bp_walk(const T* xw, const BpGeom& g, F&&... f) 
   }
 }
 
-// BN for one element, from nmean = -mean, std, scale and shift of its channel, in its two steps: bn_out(x) is
-// bp_bn_out(bp_normalised(x, ...), ...).  The only place that forms them: the forward's finish and the MAX backward's
-// search for the mask compare their words.
-template <typename T>
-__device__ __forceinline__ T bp_normalised(T x, T nmean, T std) {
-  return (x + nmean) / std;
-}
-template <typename T>
-__device__ __forceinline__ T bp_bn_out(T xn, T sc, T sh) {
-  return xn * sc + sh;
-}
-
-// MAX: one step of the scan for a window's extremum, in (h, w) order.  The first element starts it; a later one
-// replaces *e where it is strictly larger (dir > 0: the channel's scale is positive) or smaller (dir < 0: negative); a
-// NaN never does, and with dir == 0 (scale == 0: every BN output is shift, the mask is the first element) nothing does.
-template <typename T>
-__device__ __forceinline__ void bp_keep(bool first, T v, int dir, T* e) {
-  const bool less = v < *e, more = v > *e;           // both formed, then selected: no branch per element
-  *e = first || (dir < 0 ? less : dir > 0 && more) ? v : *e;
-}
-
-// dir of bp_keep for a channel's scale
-template <typename T>
-__device__ __forceinline__ int bp_dir(T sc) {
-  return sc < T(0) ? -1 : sc > T(0) ? 1 : 0;
-}
-
 // TRAIN: mean, var, std of channel c from its two sums, as bn_forward_kernel does; the writer updates the blobs.
 template <typename T>
 __device__ __forceinline__ void bp_statistics(const T (&tot)[2], int c, bool writer, T bn_memory, T inv_S, T inv_N,
@@ -297,8 +270,8 @@ __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_forwa
     });
     if (test) {
       T sp;
-      if constexpr (MAX) sp = bp_normalised(s, nmean, std);
-      const T t = MAX ? bn_tanh(bp_bn_out(sp, sc, sh)) : bn_pool_test_finish(s, ke, nmean, std, sc, sh, &sp);
+      const T t = MAX ? bn_maxpool_test_finish(s, nmean, std, sc, sh, &sp)
+                      : bn_pool_test_finish(s, ke, nmean, std, sc, sh, &sp);
       save_pool[at.p] = sp;
       top[at.p] = t;
     } else {

@@ -1,14 +1,21 @@
-// csrc/conv_stage.hip -- the TEST-phase stage Convolution -> BN -> AvePool -> TanH as one call, and its extern "C" entry
-// points (include/mms_conv_stage.h: mms_conv_stage_*).  With y = conv(x, w) (+ bias), per output channel k and pooling
+// csrc/conv_stage.hip -- the TEST-phase stages Convolution -> BN -> AvePool -> TanH (include/mms_conv_stage.h:
+// mms_conv_stage_*) and Convolution -> BN -> MaxPool -> TanH (include/mms_conv_maxpool_stage.h:
+// mms_conv_maxpool_stage_*), each as one call, and their extern "C" entry points.  The two families are one set of
+// templates with a `MAX` parameter: the checks, the plan, the accumulator tile, the workspace and the launchers are
+// stated once; what differs is what a thread keeps of its window, the finish (csrc/bn_common.h has both), the second
+// call of the sequence and the measured routing rule.  With y = conv(x, w) (+ bias), per output channel k and pooling
 // window (ph x pw, the windows tile y's (OH, OW)):
 //
-//   m = the window's y added in (h, w) order, starting from 0, / (ph pw)
+//   AVE  m = the window's y added in (h, w) order, starting from 0, / (ph pw)
+//   MAX  m = the window's y scanned in (h, w) order from its first element: the larger kept for scale[k] > 0, the
+//        smaller for scale[k] < 0, the first for scale[k] == 0; a NaN never wins (bp_keep)
 //   save_pool = (m + (-mean[k])) / sqrt(var[k] + 1e-9)          top = tanh(save_pool * scale[k] + shift[k])
 //
-// Two routes (conv_stage_route, the one place that decides):
+// Two routes (stage_route<MAX>, the one place that decides for a family):
 //
-//   sequence  mms_conv_forward_* into the workspace, then mms_bn_pool_tanh_forward_* in TEST phase from it: the two
-//             public calls, nothing of their own here.  All of double; float where the fused route does not reach.
+//   sequence  mms_conv_forward_* into the workspace, then mms_bn_pool_tanh_forward_* (MAX:
+//             mms_bn_maxpool_tanh_forward_*) in TEST phase from it: the two public calls, nothing of their own here.
+//             All of double; float where the fused route does not reach.
 //             Workspace: [y: N K OH OW][save_mean: K][save_std: K][save_pool: N K OH/ph OW/pw], the last used when the
 //             caller passes no save_pool.
 //   fused     float, where the convolution's forward is on its fast route (csrc/conv_tile.h) with a band whose height
@@ -17,14 +24,17 @@
 //             csrc/conv.hip runs; the epilogue puts accumulator + bias in LDS as tile[k][pixel], over the band and the
 //             weights the last chunk has finished with (K <= 64 channels x 256 pixels is the 64 KB those had at most),
 //             and after a barrier thread e takes (image, channel, window) e, e + 256, ...: it adds its window from the
-//             tile in (h, w) order as one chain from 0 and finishes with bn_pool_test_finish, csrc/bn_pool.hip's own.
+//             tile in (h, w) order as one chain from 0 and finishes with bn_pool_test_finish, csrc/bn_pool.hip's own
+//             (MAX: scans it with bp_keep and finishes with bn_maxpool_test_finish, csrc/bn_pool.hip's own too).
 //             Only pooled-size arrays are stored; y is never in device memory.
 //
-// A shape the fused route reaches but does not pay at goes to the sequence: conv_stage_route has the rule.
+// A shape the fused route reaches but does not pay at goes to the sequence: stage_route<MAX> has each family's rule.
 // An element of y is the same chain of MFMA steps on both routes wherever both cut the input channels into the same
 // chunks (CC of conv_prod_plan: the band's height enters it), and then the two routes give the same words.
 #include "bn_common.h"
 #include "conv_tile.h"
+#include "mms_bn_maxpool.h"
+#include "mms_conv_maxpool_stage.h"
 #include "mms_conv_stage.h"
 #include "mms_internal.h"
 
@@ -32,6 +42,11 @@ namespace mms {
 namespace {
 
 static_assert(kConvMaxChannels * kConvTilePixels <= kConvLdsFloats, "the accumulator tile of any fast plan fits the LDS");
+// One set of route values for both families: the code below names MMS_CONV_STAGE_ROUTE_* only.
+static_assert(MMS_CONV_MAXPOOL_STAGE_ROUTE_NONE == MMS_CONV_STAGE_ROUTE_NONE &&
+                  MMS_CONV_MAXPOOL_STAGE_ROUTE_SEQUENCE == MMS_CONV_STAGE_ROUTE_SEQUENCE &&
+                  MMS_CONV_MAXPOOL_STAGE_ROUTE_FUSED == MMS_CONV_STAGE_ROUTE_FUSED,
+              "the MAX stage's routes carry the AVE stage's values");
 
 struct StageDims {
   ConvDims d;
@@ -77,8 +92,20 @@ StageArgs stage_plan(const StageDims& g) {
   return a;
 }
 
-// The measured rules (tools/bench_conv_stage.py, profiles/conv_stage_bench.txt: fused against sequence at network_v4's
-// two stages over a range of N; `groups` is the launch's workgroups).
+// The launch's workgroups.
+long long stage_groups(const StageArgs& a) { return (long long)((a.p.N + a.p.G - 1) / a.p.G) * a.p.bands; }
+
+// whether the window made the band lower than the convolution's own
+bool stage_band_shrunk(const StageDims& g, const StageArgs& a) {
+  return a.p.R < conv_prod_plan(g.d, MMS_CONV_PASS_FORWARD, 1).R;
+}
+
+// The one routing decision of a family, for a shape and window stage_check accepts.
+template <bool MAX>
+int stage_route(const StageDims& g);
+
+// AVE.  The measured rules (tools/bench_conv_stage.py, profiles/conv_stage_bench.txt: fused against sequence at
+// network_v4's two stages over a range of N; `groups` is the launch's workgroups).
 //   Whole images per workgroup (conv1, ten each): slower at 5 workgroups (189.7 against 180.7 us), faster at 10, 20, 40,
 //   80 and 152 (1.03 to 1.09 x).  Few workgroups are latency-bound and the epilogue is on each one's critical path.
 //   Fused from the smallest count measured to win.
@@ -89,29 +116,67 @@ constexpr long long kStageMinImageGroups = 10;
 //   computed against 10 per 6.  Fused up to a count between the last win and the tie.
 constexpr long long kStageMaxShrunkBandGroups = 2048;
 
-int conv_stage_route(const StageDims& g) {
+template <>
+int stage_route<false>(const StageDims& g) {
   const StageArgs a = stage_plan(g);
   if (!a.p.ok) return MMS_CONV_STAGE_ROUTE_SEQUENCE;
-  const long long groups = (long long)((a.p.N + a.p.G - 1) / a.p.G) * a.p.bands;
+  const long long groups = stage_groups(a);
   if (a.p.G > 1) return groups >= kStageMinImageGroups ? MMS_CONV_STAGE_ROUTE_FUSED : MMS_CONV_STAGE_ROUTE_SEQUENCE;
-  if (a.p.R < conv_prod_plan(g.d, MMS_CONV_PASS_FORWARD, 1).R && groups > kStageMaxShrunkBandGroups)
-    return MMS_CONV_STAGE_ROUTE_SEQUENCE;
+  if (stage_band_shrunk(g, a) && groups > kStageMaxShrunkBandGroups) return MMS_CONV_STAGE_ROUTE_SEQUENCE;
   return MMS_CONV_STAGE_ROUTE_FUSED;
 }
 
-// PH, PW > 0: the window's size at compile time (== s.ph, s.pw); 0: any window.
-template <int PH, int PW>
+// MAX.  Measured (tools/bench_conv_maxpool_stage.py, profiles/conv_maxpool_stage_bench.txt): network_v3's and
+// network_v5's five stages, N from 6 to 3000, fused against sequence; "faster" is a median ratio above 1 with the two
+// ranges of seven passes apart, "level" is ranges that touch.  The rule: three kinds of plan, told apart by what a
+// workgroup holds.  Each stage of a kind gives a span of workgroup counts: from the first measured count at which fused
+// is faster and from which on it is never slower, to the last count measured.  The kind is FUSED on the counts that
+// lie in the span of every one of its stages, and the SEQUENCE on everything else, unmeasured counts included.  A level
+// point inside a span stays with it: a rule keyed on the count cannot carve it out from the faster points around it.
+//   Several whole images (v3's second stage, ten each; v5's third, seven each).  v3's: slower at 5, 10, 20 and 40
+//   workgroups (0.98 to 1.00 x), faster at 60, 80, 152 and 300 (1.01 to 1.03 x): 60 .. 300.  v5's: faster at all of
+//   8 to 429 (1.04 to 1.12 x).  So v5's third stage is left on the sequence below 60 workgroups and above 300.
+//   A band of rows of one image (v3's first stage, 4 rows where the convolution takes 6; v5's first, 6 rows).  v3's:
+//   faster at 54, 450, 675, 900, 9900, 13653 and 18000 (1.06 to 1.50 x), level at 225, 1800, 3600 and 7200 (medians
+//   1.42, 1.01, 1.03, 1.02 x): 54 .. 18000.  v5's: faster at all of 49 to 14000 (1.08 to 1.39 x) but 56, level for one
+//   slow pass of each route (1.34 x).  A band the window made lower pays here (AVE's does not beyond 2048 workgroups).
+//   One whole image (v5's second stage, 16 x 16).  Slower at 6 workgroups, level at 25, faster at 50 (1.01 x) and at
+//   all of 100 to 2000 (1.03 to 1.06 x): 50 .. 2000.
+struct MaxStageSpan {
+  long long least, most;       // workgroups
+};
+constexpr MaxStageSpan kMaxStageImages = {60, 300}, kMaxStageRowBands = {54, 14000}, kMaxStageOneImage = {50, 2000};
+
+template <>
+int stage_route<true>(const StageDims& g) {
+  const StageArgs a = stage_plan(g);
+  if (!a.p.ok) return MMS_CONV_STAGE_ROUTE_SEQUENCE;
+  const long long groups = stage_groups(a);
+  const MaxStageSpan& k = a.p.G > 1 ? kMaxStageImages : a.p.bands > 1 ? kMaxStageRowBands : kMaxStageOneImage;
+  return groups >= k.least && groups <= k.most ? MMS_CONV_STAGE_ROUTE_FUSED : MMS_CONV_STAGE_ROUTE_SEQUENCE;
+}
+
+// PH, PW > 0: the window's size at compile time (== s.ph, s.pw); 0: any window.  MAX: the window's extremum where AVE
+// has its sum.
+template <bool MAX, int PH, int PW>
 struct StagePoolEpilogue {
   const StageArgs& s;
   float* tile;
   int kc;                // the channel whose values follow: that of the thread's first (image, channel, window)
   float nmean, std, sc, sh;
+  int dir;               // MAX: bp_dir(sc)
   __device__ __forceinline__ void channel(int k) {
     kc = k;
     nmean = -s.mean[k];
     std = bn_sqrt(s.var[k] + 1e-9f);
     sc = s.scale[k];
     sh = s.shift[k];
+    if constexpr (MAX) dir = bp_dir(sc);
+  }
+  // one element of the window, in (h, w) order
+  __device__ __forceinline__ void keep(bool first, float v, float* m) const {
+    if constexpr (MAX) bp_keep(first, v, dir, m);
+    else *m += v;
   }
   // Before the product: the loads are long back when the epilogue, on the workgroup's critical path, needs them.
   __device__ __forceinline__ void pixel(const ConvProdArgs& a, const ConvTile& t, int nt, int, int, int) {
@@ -146,7 +211,8 @@ struct StagePoolEpilogue {
       const int k = u % a.Cout, img = u / a.Cout;
       const int wr = q / s.POW, wc = q - wr * s.POW;
       const float* src = tile + k * PS + img * t.per + wr * ph * a.OWt + wc * pw;
-      float sum = 0.f;
+      if (MAX && k != kc) channel(k);                   // the scan needs the channel's direction
+      float sum = 0.f;                                  // AVE: the window's sum; MAX: its extremum
       if constexpr (PH > 0) {
         float v[PH][PW];
 #pragma unroll
@@ -156,36 +222,43 @@ struct StagePoolEpilogue {
 #pragma unroll
         for (int i = 0; i < PH; ++i)
 #pragma unroll
-          for (int j = 0; j < PW; ++j) sum += v[i][j];
+          for (int j = 0; j < PW; ++j) keep(i == 0 && j == 0, v[i][j], &sum);
       } else {
         for (int i = 0; i < ph; ++i)
-          for (int j = 0; j < pw; ++j) sum += src[i * a.OWt + j];
+          for (int j = 0; j < pw; ++j) keep(i == 0 && j == 0, src[i * a.OWt + j], &sum);
       }
       const size_t o = ((size_t)(t.n0 + img) * a.Cout + k) * PP + q0 + q;
-      if (k != kc) channel(k);
+      if (!MAX && k != kc) channel(k);
       float sp;
-      const float tv = bn_pool_test_finish(sum, ke, nmean, std, sc, sh, &sp);
+      const float tv = MAX ? bn_maxpool_test_finish(sum, nmean, std, sc, sh, &sp)
+                           : bn_pool_test_finish(sum, ke, nmean, std, sc, sh, &sp);
       if (s.save_pool) s.save_pool[o] = sp;
       s.top[o] = tv;
     }
   }
 };
 
-template <int MT, int PH, int PW>
+template <int MT, bool MAX, int PH, int PW>
 __global__ __launch_bounds__(kConvThreads) void conv_stage_kernel(StageArgs s) {
   extern __shared__ float conv_lds[];
-  StagePoolEpilogue<PH, PW> epi{s, conv_lds};
+  StagePoolEpilogue<MAX, PH, PW> epi{s, conv_lds};
   conv_tile_product<MT>(s.p, conv_lds, epi);
 }
 
 template <int K>
 using stage_int = std::integral_constant<int, K>;
 
-// f(PH, PW) as types: network_v4's two windows at compile time, any other at run time.
-template <class F>
+// f(PH, PW) as types.  AVE: network_v4's two windows at compile time, any other at run time.  MAX: 4 x 4 and 2 x 2 at
+// compile time, any other -- the nets' 5 x 5 and 6 x 6 included -- at run time.  Against a build with the run-time scan
+// only, process by process in turn, the fused launch with the 4 x 4 is 6 to 8 % faster at v3's first stage and with the
+// 2 x 2 6 to 7 % (N = 50) and 4 to 5 % (N = 1517) at v5's first and 0.8 to 1.4 % at v5's second, ranges apart in both
+// rounds (profiles/conv_maxpool_stage_bench.txt, second section).  A 5 x 5 and a 6 x 6 instantiation gained under 1 %
+// where the main call fuses, inside the spread, and are not kept.
+template <bool MAX, class F>
 void stage_dispatch(int ph, int pw, F&& f) {
   if (ph == 4 && pw == 4) f(stage_int<4>{}, stage_int<4>{});
-  else if (ph == 5 && pw == 5) f(stage_int<5>{}, stage_int<5>{});
+  else if (!MAX && ph == 5 && pw == 5) f(stage_int<5>{}, stage_int<5>{});
+  else if (MAX && ph == 2 && pw == 2) f(stage_int<2>{}, stage_int<2>{});
   else f(stage_int<0>{}, stage_int<0>{});
 }
 
@@ -195,11 +268,11 @@ size_t stage_sequence_bytes(const StageDims& g) {
   return (map + 2 * (size_t)g.d.K + pooled) * sizeof(T);
 }
 
-template <typename T>
+template <typename T, bool MAX>
 size_t stage_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, bool sequence) {  // sequence: whatever the route
   StageDims g;
   if (stage_check(shape, ph, pw, &g) != MMS_OK || g.d.N == 0) return 0;
-  if (std::is_same<T, float>::value && !sequence && conv_stage_route(g) == MMS_CONV_STAGE_ROUTE_FUSED) return 0;
+  if (std::is_same<T, float>::value && !sequence && stage_route<MAX>(g) == MMS_CONV_STAGE_ROUTE_FUSED) return 0;
   return stage_sequence_bytes<T>(g);
 }
 
@@ -210,22 +283,25 @@ inline int conv_public(const mms_conv_shape* s, const double* x, const double* w
   return mms_conv_forward_f64(s, x, w, b, y, nullptr, 0, st);
 }
 // TEST phase reads running_mean / running_var and writes neither; it needs no workspace.
+template <bool MAX>
 inline int bn_pool_public(const StageDims& g, const float* y, const float* scale, const float* shift, const float* mean,
                           const float* var, float* top, float* sp, float* sm, float* ss, void* st) {
-  return mms_bn_pool_tanh_forward_f32(1, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, 0.f, y, scale, shift,
-                                      const_cast<float*>(mean), const_cast<float*>(var), top, sp, sm, ss, nullptr, 0, st);
+  const auto call = MAX ? mms_bn_maxpool_tanh_forward_f32 : mms_bn_pool_tanh_forward_f32;
+  return call(1, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, 0.f, y, scale, shift, const_cast<float*>(mean),
+              const_cast<float*>(var), top, sp, sm, ss, nullptr, 0, st);
 }
+template <bool MAX>
 inline int bn_pool_public(const StageDims& g, const double* y, const double* scale, const double* shift,
                           const double* mean, const double* var, double* top, double* sp, double* sm, double* ss,
                           void* st) {
-  return mms_bn_pool_tanh_forward_f64(1, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, 0., y, scale, shift,
-                                      const_cast<double*>(mean), const_cast<double*>(var), top, sp, sm, ss, nullptr, 0,
-                                      st);
+  const auto call = MAX ? mms_bn_maxpool_tanh_forward_f64 : mms_bn_pool_tanh_forward_f64;
+  return call(1, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, 0., y, scale, shift, const_cast<double*>(mean),
+              const_cast<double*>(var), top, sp, sm, ss, nullptr, 0, st);
 }
 
-// force: MMS_CONV_STAGE_ROUTE_NONE (conv_stage_route decides), _SEQUENCE or _FUSED (float; MMS_ERR_UNSUPPORTED where the
+// force: MMS_CONV_STAGE_ROUTE_NONE (stage_route<MAX> decides), _SEQUENCE or _FUSED (float; MMS_ERR_UNSUPPORTED where the
 // fused plan does not reach).
-template <typename T>
+template <typename T, bool MAX>
 int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const T* w, const T* bias, const T* mean,
                   const T* var, const T* scale, const T* shift, T* top, T* save_pool, void* workspace,
                   size_t workspace_bytes, int force, void* stream) {
@@ -242,15 +318,15 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
   if constexpr (std::is_same<T, float>::value) {
     if (force == MMS_CONV_STAGE_ROUTE_FUSED && !stage_plan(g).p.ok) return MMS_ERR_UNSUPPORTED;
     if (force == MMS_CONV_STAGE_ROUTE_FUSED ||
-        (force == MMS_CONV_STAGE_ROUTE_NONE && conv_stage_route(g) == MMS_CONV_STAGE_ROUTE_FUSED)) {
+        (force == MMS_CONV_STAGE_ROUTE_NONE && stage_route<MAX>(g) == MMS_CONV_STAGE_ROUTE_FUSED)) {
       StageArgs a = stage_plan(g);
       a.p.in = x; a.p.w = w; a.p.bias = bias; a.p.out = nullptr;
       a.mean = mean; a.var = var; a.scale = scale; a.shift = shift; a.top = top; a.save_pool = save_pool;
       const dim3 grid((unsigned)((a.p.N + a.p.G - 1) / a.p.G), (unsigned)a.p.bands);
       conv_with_mt(a.p.MT, [&](auto M) {
-        stage_dispatch(ph, pw, [&](auto PH, auto PW) {
-          hipLaunchKernelGGL((conv_stage_kernel<decltype(M)::value, decltype(PH)::value, decltype(PW)::value>), grid,
-                             dim3(kConvThreads), a.lds_bytes, as_stream(stream), a);
+        stage_dispatch<MAX>(ph, pw, [&](auto PH, auto PW) {
+          hipLaunchKernelGGL((conv_stage_kernel<decltype(M)::value, MAX, decltype(PH)::value, decltype(PW)::value>),
+                             grid, dim3(kConvThreads), a.lds_bytes, as_stream(stream), a);
         });
       });
       return launch_status();
@@ -265,7 +341,7 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
   const int rc1 = conv_public(shape, x, w, bias, y, stream);
   if (rc1 != MMS_OK) return rc1;
-  return bn_pool_public(g, y, scale, shift, mean, var, top, sp, save_mean, save_std, stream);
+  return bn_pool_public<MAX>(g, y, scale, shift, mean, var, top, sp, save_mean, save_std, stream);
 }
 
 }  // namespace
@@ -278,48 +354,98 @@ extern "C" {
 int mms_conv_stage_route(const mms_conv_shape* shape, int ph, int pw) {
   StageDims g;
   if (stage_check(shape, ph, pw, &g) != MMS_OK) return MMS_CONV_STAGE_ROUTE_NONE;
-  return conv_stage_route(g);
+  return stage_route<false>(g);
 }
 
 size_t mms_conv_stage_workspace_bytes(const mms_conv_shape* shape, int ph, int pw) {
-  return stage_workspace_bytes<float>(shape, ph, pw, false);
+  return stage_workspace_bytes<float, false>(shape, ph, pw, false);
 }
 size_t mms_conv_stage_workspace_bytes_f64(const mms_conv_shape* shape, int ph, int pw) {
-  return stage_workspace_bytes<double>(shape, ph, pw, false);
+  return stage_workspace_bytes<double, false>(shape, ph, pw, false);
 }
 size_t mms_conv_stage_sequence_workspace_bytes(const mms_conv_shape* shape, int ph, int pw) {
-  return stage_workspace_bytes<float>(shape, ph, pw, true);
+  return stage_workspace_bytes<float, false>(shape, ph, pw, true);
 }
 
 int mms_conv_stage_forward_f32(const mms_conv_shape* shape, int ph, int pw, const float* x, const float* weight,
                                const float* bias, const float* mean, const float* var, const float* scale,
                                const float* shift, float* top, float* save_pool, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  return stage_forward<float>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
-                              workspace_bytes, MMS_CONV_STAGE_ROUTE_NONE, stream);
+  return stage_forward<float, false>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
+                                     workspace_bytes, MMS_CONV_STAGE_ROUTE_NONE, stream);
 }
 
 int mms_conv_stage_forward_f64(const mms_conv_shape* shape, int ph, int pw, const double* x, const double* weight,
                                const double* bias, const double* mean, const double* var, const double* scale,
                                const double* shift, double* top, double* save_pool, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  return stage_forward<double>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
-                               workspace_bytes, MMS_CONV_STAGE_ROUTE_SEQUENCE, stream);
+  return stage_forward<double, false>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool,
+                                      workspace, workspace_bytes, MMS_CONV_STAGE_ROUTE_SEQUENCE, stream);
 }
 
 int mms_conv_stage_forward_sequence_f32(const mms_conv_shape* shape, int ph, int pw, const float* x,
                                         const float* weight, const float* bias, const float* mean, const float* var,
                                         const float* scale, const float* shift, float* top, float* save_pool,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-  return stage_forward<float>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
-                              workspace_bytes, MMS_CONV_STAGE_ROUTE_SEQUENCE, stream);
+  return stage_forward<float, false>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
+                                     workspace_bytes, MMS_CONV_STAGE_ROUTE_SEQUENCE, stream);
 }
 
 int mms_conv_stage_forward_fused_f32(const mms_conv_shape* shape, int ph, int pw, const float* x, const float* weight,
                                      const float* bias, const float* mean, const float* var, const float* scale,
                                      const float* shift, float* top, float* save_pool, void* stream) {
-  return stage_forward<float>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, nullptr, 0,
-                              MMS_CONV_STAGE_ROUTE_FUSED, stream);
+  return stage_forward<float, false>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, nullptr,
+                                     0, MMS_CONV_STAGE_ROUTE_FUSED, stream);
+}
+
+// include/mms_conv_maxpool_stage.h: the MAX form, the same arguments.
+int mms_conv_maxpool_stage_route(const mms_conv_shape* shape, int ph, int pw) {
+  StageDims g;
+  if (stage_check(shape, ph, pw, &g) != MMS_OK) return MMS_CONV_STAGE_ROUTE_NONE;
+  return stage_route<true>(g);
+}
+
+size_t mms_conv_maxpool_stage_workspace_bytes(const mms_conv_shape* shape, int ph, int pw) {
+  return stage_workspace_bytes<float, true>(shape, ph, pw, false);
+}
+size_t mms_conv_maxpool_stage_workspace_bytes_f64(const mms_conv_shape* shape, int ph, int pw) {
+  return stage_workspace_bytes<double, true>(shape, ph, pw, false);
+}
+size_t mms_conv_maxpool_stage_sequence_workspace_bytes(const mms_conv_shape* shape, int ph, int pw) {
+  return stage_workspace_bytes<float, true>(shape, ph, pw, true);
+}
+
+int mms_conv_maxpool_stage_forward_f32(const mms_conv_shape* shape, int ph, int pw, const float* x, const float* weight,
+                                       const float* bias, const float* mean, const float* var, const float* scale,
+                                       const float* shift, float* top, float* save_pool, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  return stage_forward<float, true>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
+                                    workspace_bytes, MMS_CONV_STAGE_ROUTE_NONE, stream);
+}
+
+int mms_conv_maxpool_stage_forward_f64(const mms_conv_shape* shape, int ph, int pw, const double* x,
+                                       const double* weight, const double* bias, const double* mean, const double* var,
+                                       const double* scale, const double* shift, double* top, double* save_pool,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  return stage_forward<double, true>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
+                                     workspace_bytes, MMS_CONV_STAGE_ROUTE_SEQUENCE, stream);
+}
+
+int mms_conv_maxpool_stage_forward_sequence_f32(const mms_conv_shape* shape, int ph, int pw, const float* x,
+                                                const float* weight, const float* bias, const float* mean,
+                                                const float* var, const float* scale, const float* shift, float* top,
+                                                float* save_pool, void* workspace, size_t workspace_bytes,
+                                                void* stream) {
+  return stage_forward<float, true>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, workspace,
+                                    workspace_bytes, MMS_CONV_STAGE_ROUTE_SEQUENCE, stream);
+}
+
+int mms_conv_maxpool_stage_forward_fused_f32(const mms_conv_shape* shape, int ph, int pw, const float* x,
+                                             const float* weight, const float* bias, const float* mean,
+                                             const float* var, const float* scale, const float* shift, float* top,
+                                             float* save_pool, void* stream) {
+  return stage_forward<float, true>(shape, ph, pw, x, weight, bias, mean, var, scale, shift, top, save_pool, nullptr, 0,
+                                    MMS_CONV_STAGE_ROUTE_FUSED, stream);
 }
 
 }  // extern "C"
