@@ -4,10 +4,11 @@ tensors.
 The calls live in the library `capi.lib()` loads; their signatures are applied here, to that handle, and nothing is
 added to `capi`.  Arguments follow capi's bn_pool_tanh_* wrappers -- the backward also takes `shift`, which the mask is
 made from.  Errors are capi's: a library error code goes through `capi.check`.  The stream is torch's current one.
+The binding itself is _pooled.py's, shared with capi's AvePool calls.
 """
 import ctypes as C
 
-from . import capi
+from . import _pooled, capi
 
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 _QUERY = (_sz, [_i] * 6)
@@ -29,38 +30,16 @@ def lib():
     return capi._bound_lib(_SIGNATURES)
 
 
-def _workspace_bytes(e, *dims):
-    return getattr(lib(), "mms_bn_maxpool_tanh_workspace_bytes" + e.query)(*dims)
+_FAMILY = _pooled.Family("mms_bn_maxpool_tanh_", "BN + pooling", lib, shift=True)
 
 
 def bn_maxpool_tanh_workspace_bytes(N, C, H, W, kh, kw):
     """mms_bn_pool_tanh_workspace_bytes' figure: 0 where one workgroup per channel serves."""
-    return _workspace_bytes(capi._F32, N, C, H, W, kh, kw)
+    return _pooled.bn_pool_workspace_bytes(_FAMILY, capi._F32, N, C, H, W, kh, kw)
 
 
 def bn_maxpool_tanh_workspace_bytes_f64(N, C, H, W, kh, kw):
-    return _workspace_bytes(capi._F64, N, C, H, W, kh, kw)
-
-
-def _forward(e, x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std, phase,
-             bn_memory, ws):
-    dims, dt, p = capi._bn_pool_shape(x, kernel), e.dtype, capi._ptr
-    wsp, wsb = capi._scratch(ws, _workspace_bytes(e, *dims), x.device)      # binds: the signatures are on the handle
-    capi._call("mms_bn_maxpool_tanh_forward_" + e.suffix, int(phase), *dims, float(bn_memory), p(x, "x", dtype=dt),
-               p(scale, "scale", dtype=dt), p(shift, "shift", dtype=dt), p(running_mean, "running_mean", dtype=dt),
-               p(running_var, "running_var", dtype=dt), p(top, "top", dtype=dt), p(save_pool, "save_pool", dtype=dt),
-               p(save_mean, "save_mean", dtype=dt), p(save_std, "save_std", dtype=dt), wsp, wsb)
-
-
-def _backward(e, x, kernel, top, top_diff, save_pool, scale, shift, save_mean, save_std, bottom_diff, scale_diff,
-              shift_diff, ws):
-    dims, dt, p = capi._bn_pool_shape(x, kernel), e.dtype, capi._ptr
-    wsp, wsb = capi._scratch(ws, _workspace_bytes(e, *dims), x.device)
-    capi._call("mms_bn_maxpool_tanh_backward_" + e.suffix, *dims, p(x, "x", dtype=dt), p(top, "top", dtype=dt),
-               p(top_diff, "top_diff", dtype=dt), p(save_pool, "save_pool", dtype=dt), p(scale, "scale", dtype=dt),
-               p(shift, "shift", dtype=dt), p(save_mean, "save_mean", dtype=dt), p(save_std, "save_std", dtype=dt),
-               p(bottom_diff, "bottom_diff", True, dt), p(scale_diff, "scale_diff", True, dt),
-               p(shift_diff, "shift_diff", True, dt), wsp, wsb)
+    return _pooled.bn_pool_workspace_bytes(_FAMILY, capi._F64, N, C, H, W, kh, kw)
 
 
 def bn_maxpool_tanh_forward(x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
@@ -69,25 +48,25 @@ def bn_maxpool_tanh_forward(x, kernel, scale, shift, running_mean, running_var, 
     mms_bn_maxpool_tanh_forward_f32).  x (N, C, H, W); kernel k or (kh, kw); top, save_pool (N, C, H/kh, W/kw); the
     other six C floats.  phase as in capi.bn_forward.  save_pool, save_mean, save_std and top are what
     bn_maxpool_tanh_backward needs."""
-    _forward(capi._F32, x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std, phase,
-             bn_memory, ws)
+    _pooled.bn_pool_forward(_FAMILY, capi._F32, x, kernel, scale, shift, running_mean, running_var, top, save_pool,
+                            save_mean, save_std, phase, bn_memory, ws)
 
 
 def bn_maxpool_tanh_forward_f64(x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean,
                                 save_std, phase=0, bn_memory=0.9, ws=None):
-    _forward(capi._F64, x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std, phase,
-             bn_memory, ws)
+    _pooled.bn_pool_forward(_FAMILY, capi._F64, x, kernel, scale, shift, running_mean, running_var, top, save_pool,
+                            save_mean, save_std, phase, bn_memory, ws)
 
 
 def bn_maxpool_tanh_backward(x, kernel, top, top_diff, save_pool, scale, shift, save_mean, save_std, bottom_diff=None,
                              scale_diff=None, shift_diff=None, ws=None):
     """Each of bottom_diff (N, C, H, W), scale_diff, shift_diff (C) may be None (skipped); those given are overwritten.
     scale and shift are the forward's."""
-    _backward(capi._F32, x, kernel, top, top_diff, save_pool, scale, shift, save_mean, save_std, bottom_diff,
-              scale_diff, shift_diff, ws)
+    _pooled.bn_pool_backward(_FAMILY, capi._F32, x, kernel, top, top_diff, save_pool, scale, shift, save_mean, save_std,
+                             bottom_diff, scale_diff, shift_diff, ws)
 
 
 def bn_maxpool_tanh_backward_f64(x, kernel, top, top_diff, save_pool, scale, shift, save_mean, save_std,
                                  bottom_diff=None, scale_diff=None, shift_diff=None, ws=None):
-    _backward(capi._F64, x, kernel, top, top_diff, save_pool, scale, shift, save_mean, save_std, bottom_diff,
-              scale_diff, shift_diff, ws)
+    _pooled.bn_pool_backward(_FAMILY, capi._F64, x, kernel, top, top_diff, save_pool, scale, shift, save_mean, save_std,
+                             bottom_diff, scale_diff, shift_diff, ws)

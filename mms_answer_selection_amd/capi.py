@@ -574,45 +574,16 @@ def bn_backward_f64(x, top_diff, scale, save_mean, save_std, bottom_diff=None, s
 
 def _bn_pool_shape(x, kernel):
     """(N, C, H, W, kh, kw) of a 4-D blob and a pooling kernel (k or (kh, kw))."""
-    if x.dim() != 4:
-        raise MMSArgumentError("BN + pooling: x must be (N, C, H, W), got %s" % (tuple(x.shape),))
-    kh, kw = (kernel, kernel) if isinstance(kernel, int) else kernel
-    return tuple(int(d) for d in x.shape) + (int(kh), int(kw))
-
-
-def _bn_pool_tanh_workspace_bytes(e, *dims):
-    return getattr(lib(), "mms_bn_pool_tanh_workspace_bytes" + e.query)(*dims)
+    return _pooled.bn_pool_shape(_BN_POOL, x, kernel)
 
 
 def bn_pool_tanh_workspace_bytes(N, C, H, W, kh, kw):
     """0 where one workgroup per channel serves (include/mms.h: mms_bn_pool_tanh_workspace_bytes)."""
-    return _bn_pool_tanh_workspace_bytes(_F32, N, C, H, W, kh, kw)
+    return _pooled.bn_pool_workspace_bytes(_BN_POOL, _F32, N, C, H, W, kh, kw)
 
 
 def bn_pool_tanh_workspace_bytes_f64(N, C, H, W, kh, kw):
-    return _bn_pool_tanh_workspace_bytes(_F64, N, C, H, W, kh, kw)
-
-
-def _bn_pool_tanh_forward(e, x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
-                          phase, bn_memory, ws):
-    dims, dt = _bn_pool_shape(x, kernel), e.dtype
-    wsp, wsb = _scratch(ws, _bn_pool_tanh_workspace_bytes(e, *dims), x.device)
-    _call("mms_bn_pool_tanh_forward_" + e.suffix, int(phase), *dims, float(bn_memory), _ptr(x, "x", dtype=dt),
-          _ptr(scale, "scale", dtype=dt), _ptr(shift, "shift", dtype=dt),
-          _ptr(running_mean, "running_mean", dtype=dt), _ptr(running_var, "running_var", dtype=dt),
-          _ptr(top, "top", dtype=dt), _ptr(save_pool, "save_pool", dtype=dt), _ptr(save_mean, "save_mean", dtype=dt),
-          _ptr(save_std, "save_std", dtype=dt), wsp, wsb)
-
-
-def _bn_pool_tanh_backward(e, x, kernel, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                           scale_diff, shift_diff, ws):
-    dims, dt = _bn_pool_shape(x, kernel), e.dtype
-    wsp, wsb = _scratch(ws, _bn_pool_tanh_workspace_bytes(e, *dims), x.device)
-    _call("mms_bn_pool_tanh_backward_" + e.suffix, *dims, _ptr(x, "x", dtype=dt), _ptr(top, "top", dtype=dt),
-          _ptr(top_diff, "top_diff", dtype=dt), _ptr(save_pool, "save_pool", dtype=dt), _ptr(scale, "scale", dtype=dt),
-          _ptr(save_mean, "save_mean", dtype=dt), _ptr(save_std, "save_std", dtype=dt),
-          _ptr(bottom_diff, "bottom_diff", True, dt), _ptr(scale_diff, "scale_diff", True, dt),
-          _ptr(shift_diff, "shift_diff", True, dt), wsp, wsb)
+    return _pooled.bn_pool_workspace_bytes(_BN_POOL, _F64, N, C, H, W, kh, kw)
 
 
 def bn_pool_tanh_forward(x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
@@ -620,28 +591,28 @@ def bn_pool_tanh_forward(x, kernel, scale, shift, running_mean, running_var, top
     """BN -> AvePool(kernel = stride, windows tile the map) -> TanH (include/mms.h: mms_bn_pool_tanh_forward_f32).
     x (N, C, H, W); kernel k or (kh, kw); top, save_pool (N, C, H/kh, W/kw); the other six C floats.  phase as in
     bn_forward.  save_pool, save_mean, save_std and top are what bn_pool_tanh_backward needs."""
-    _bn_pool_tanh_forward(_F32, x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean,
-                          save_std, phase, bn_memory, ws)
+    _pooled.bn_pool_forward(_BN_POOL, _F32, x, kernel, scale, shift, running_mean, running_var, top, save_pool,
+                            save_mean, save_std, phase, bn_memory, ws)
 
 
 def bn_pool_tanh_forward_f64(x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
                              phase=0, bn_memory=0.9, ws=None):
-    _bn_pool_tanh_forward(_F64, x, kernel, scale, shift, running_mean, running_var, top, save_pool, save_mean,
-                          save_std, phase, bn_memory, ws)
+    _pooled.bn_pool_forward(_BN_POOL, _F64, x, kernel, scale, shift, running_mean, running_var, top, save_pool,
+                            save_mean, save_std, phase, bn_memory, ws)
 
 
 def bn_pool_tanh_backward(x, kernel, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff=None,
                           scale_diff=None, shift_diff=None, ws=None):
     """Each of bottom_diff (N, C, H, W), scale_diff, shift_diff (C) may be None (skipped); those given are
     overwritten."""
-    _bn_pool_tanh_backward(_F32, x, kernel, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                           scale_diff, shift_diff, ws)
+    _pooled.bn_pool_backward(_BN_POOL, _F32, x, kernel, top, top_diff, save_pool, scale, None, save_mean, save_std,
+                             bottom_diff, scale_diff, shift_diff, ws)
 
 
 def bn_pool_tanh_backward_f64(x, kernel, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff=None,
                               scale_diff=None, shift_diff=None, ws=None):
-    _bn_pool_tanh_backward(_F64, x, kernel, top, top_diff, save_pool, scale, save_mean, save_std, bottom_diff,
-                           scale_diff, shift_diff, ws)
+    _pooled.bn_pool_backward(_BN_POOL, _F64, x, kernel, top, top_diff, save_pool, scale, None, save_mean, save_std,
+                             bottom_diff, scale_diff, shift_diff, ws)
 
 
 # ---- fused triplet steps ---------------------------------------------------------------------------------------
@@ -1187,3 +1158,11 @@ for _stem, _names, _rule, _has_getter, _doc in _MODES:
     globals()[_setter.__name__] = _setter
     if _has_getter:
         globals()[_getter.__name__] = _getter
+
+
+# ---- the pooled stages' shared binding -------------------------------------------------------------------------
+# _pooled.py is written against this module and conv.py, which both have to be whole before it loads: hence here.
+from . import _pooled  # noqa: E402
+
+# bn_pool_tanh_*, above; `lib` is looked up per call, like everywhere in this module
+_BN_POOL = _pooled.Family("mms_bn_pool_tanh_", "BN + pooling", lambda: lib())

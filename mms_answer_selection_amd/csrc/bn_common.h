@@ -1,6 +1,7 @@
 // csrc/bn_common.h -- what csrc/bn.hip (BN) and csrc/bn_pool.hip (BN -> AvePool / MaxPool -> TanH) share: the sizes of
-// the two routes, the workgroup sum with its fixed order, and the ascending fold of a channel's chunk sums; and what
-// csrc/bn_pool.hip shares with csrc/conv_stage.hip: a window's TEST-phase finish, AVE and MAX, and MAX's scan step.
+// the two routes, the workgroup sum with its fixed order, the ascending fold of a channel's chunk sums and the TRAIN
+// statistics made from them; and what csrc/bn_pool.hip shares with csrc/conv_stage.hip: a window's TEST-phase finish,
+// AVE and MAX, and MAX's scan step.
 #ifndef MMS_BN_COMMON_H_
 #define MMS_BN_COMMON_H_
 
@@ -113,6 +114,27 @@ __device__ __forceinline__ void bn_fold(const T* __restrict__ ws, int c, int chu
   for (int j = 1; j < chunks; ++j) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) tot[q] += p[j * kBnSlots + q];
+  }
+}
+
+// TRAIN: mean, var and std of channel c from its two sums over N images of S elements (inv_N, inv_S: the reciprocals);
+// the writer updates the running blobs and stores mean and std for the backward.  *nmean = -mean.  Both TRAIN forwards
+// of csrc/bn_pool.hip call it, and a new caller should.  bn_forward_kernel (csrc/bn.hip) still spells the same formulas
+// out, with one sqrt after its TRAIN and TEST branches join: calling this there changes the kernel's instructions.
+template <typename T>
+__device__ __forceinline__ void bn_statistics(const T (&tot)[2], int c, bool writer, T bn_memory, T inv_S, T inv_N,
+                                              T* running_mean, T* running_var, T* save_mean, T* save_std, T* nmean,
+                                              T* std) {
+  const T mean = inv_N * (inv_S * tot[0]);
+  const T var = inv_N * (inv_S * tot[1]) - mean * mean;        // not clamped: the reference does not either
+  *nmean = -mean;
+  *std = bn_sqrt(var + T(1e-9));
+  if (writer) {
+    const T keep = bn_memory, take = T(1) - bn_memory;
+    running_mean[c] = take * mean + keep * running_mean[c];
+    running_var[c] = take * var + keep * running_var[c];
+    save_mean[c] = mean;
+    save_std[c] = *std;
   }
 }
 

@@ -190,24 +190,6 @@ __device__ __forceinline__ void bp_walk(const T* xw, const BpGeom& g, F&&... f) 
   }
 }
 
-// TRAIN: mean, var, std of channel c from its two sums, as bn_forward_kernel does; the writer updates the blobs.
-template <typename T>
-__device__ __forceinline__ void bp_statistics(const T (&tot)[2], int c, bool writer, T bn_memory, T inv_S, T inv_N,
-                                              T* running_mean, T* running_var, T* save_mean, T* save_std, T* nmean,
-                                              T* std) {
-  const T mean = inv_N * (inv_S * tot[0]);
-  const T var = inv_N * (inv_S * tot[1]) - mean * mean;        // not clamped: the reference does not either
-  *nmean = -mean;
-  *std = bn_sqrt(var + T(1e-9));
-  if (writer) {
-    const T keep = bn_memory, take = T(1) - bn_memory;
-    running_mean[c] = take * mean + keep * running_mean[c];
-    running_var[c] = take * var + keep * running_var[c];
-    save_mean[c] = mean;
-    save_std[c] = *std;
-  }
-}
-
 // Window w of channel c in top / top_diff / save_pool (bp_window's p, without the division by PW).
 __device__ __forceinline__ size_t bp_pooled_index(const BpGeom& g, unsigned c, unsigned w) {
   const unsigned n = w / g.P, r = w - n * g.P;
@@ -282,7 +264,7 @@ __global__ __launch_bounds__(SMALL ? kBnSmallThreads : kBnThreads) void bp_forwa
   bn_block_sum<THREADS, 2>(acc, red);
   if constexpr (SMALL) {
     // the barrier inside bn_block_sum also orders this workgroup's save_pool writes before bp_finish's reads
-    bp_statistics(acc, (int)c, writer, bn_memory, inv_S, inv_N, running_mean, running_var, save_mean, save_std, &nmean,
+    bn_statistics(acc, (int)c, writer, bn_memory, inv_S, inv_N, running_mean, running_var, save_mean, save_std, &nmean,
                   &std);
     bp_finish<T, THREADS>(g, c, w0, w1, nmean, std, sc, sh, save_pool, top);
   } else if (threadIdx.x == 0) {
@@ -303,7 +285,7 @@ __global__ __launch_bounds__(kBnThreads) void bp_forward_finish_kernel(
   bp_chunk(g.windows, wpc, blockIdx.y, &w0, &w1);
   T tot[2], nmean, std;
   bn_fold<2>(ws, (int)c, (int)gridDim.y, tot);
-  bp_statistics(tot, (int)c, blockIdx.y == 0 && threadIdx.x == 0, bn_memory, inv_S, inv_N, running_mean, running_var,
+  bn_statistics(tot, (int)c, blockIdx.y == 0 && threadIdx.x == 0, bn_memory, inv_S, inv_N, running_mean, running_var,
                 save_mean, save_std, &nmean, &std);
   bp_finish<T, kBnThreads>(g, c, w0, w1, nmean, std, scale[c], shift[c], save_pool, top);
 }

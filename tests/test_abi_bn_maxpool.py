@@ -12,7 +12,7 @@ import sys
 
 import pytest
 
-import test_abi_bn_pool as A
+import pooled_stage_suite as A
 from conftest import ROOT
 
 OK, INVALID, WORKSPACE = A.OK, A.INVALID, A.WORKSPACE
@@ -31,8 +31,8 @@ def _backward(t):
 SIGNATURES = {
     "mms_bn_maxpool_tanh_workspace_bytes": ("size_t", A.DIMS),
     "mms_bn_maxpool_tanh_workspace_bytes_f64": ("size_t", A.DIMS),
-    "mms_bn_maxpool_tanh_forward_f32": ("int", A._forward("float")),
-    "mms_bn_maxpool_tanh_forward_f64": ("int", A._forward("double")),
+    "mms_bn_maxpool_tanh_forward_f32": ("int", A.bn_pool_forward_params("float")),
+    "mms_bn_maxpool_tanh_forward_f64": ("int", A.bn_pool_forward_params("double")),
     "mms_bn_maxpool_tanh_backward_f32": ("int", _backward("float")),
     "mms_bn_maxpool_tanh_backward_f64": ("int", _backward("double")),
 }

@@ -9,17 +9,8 @@ import re
 import pytest
 
 from conftest import ROOT
-
-WS = ["void* workspace", "size_t workspace_bytes", "void* stream"]
-DIMS = ["int N", "int C", "int H", "int W", "int kh", "int kw"]
-
-
-def _forward(t):
-    c = "const %s* " % t
-    m = "%s* " % t
-    return (["int phase"] + DIMS + [t + " bn_memory", c + "x", c + "scale", c + "shift", m + "running_mean",
-                                    m + "running_var", m + "top", m + "save_pool", m + "save_mean", m + "save_std"] + WS)
-
+from pooled_stage_suite import (BAD_SHAPES, DIMS, EMPTY, INVALID, LARGE, OK, SMALL, WORKSPACE, WS, P,
+                                bn_pool_forward_params)
 
 def _backward(t):
     c = "const %s* " % t
@@ -31,8 +22,8 @@ def _backward(t):
 SIGNATURES = {
     "mms_bn_pool_tanh_workspace_bytes": ("size_t", DIMS),
     "mms_bn_pool_tanh_workspace_bytes_f64": ("size_t", DIMS),
-    "mms_bn_pool_tanh_forward_f32": ("int", _forward("float")),
-    "mms_bn_pool_tanh_forward_f64": ("int", _forward("double")),
+    "mms_bn_pool_tanh_forward_f32": ("int", bn_pool_forward_params("float")),
+    "mms_bn_pool_tanh_forward_f64": ("int", bn_pool_forward_params("double")),
     "mms_bn_pool_tanh_backward_f32": ("int", _backward("float")),
     "mms_bn_pool_tanh_backward_f64": ("int", _backward("double")),
 }
@@ -40,11 +31,6 @@ NAMES = sorted(SIGNATURES)
 WRAPPERS = {n: n[len("mms_"):].replace("_f32", "") for n in NAMES}
 FORWARDS = ["mms_bn_pool_tanh_forward_f32", "mms_bn_pool_tanh_forward_f64"]
 BACKWARDS = ["mms_bn_pool_tanh_backward_f32", "mms_bn_pool_tanh_backward_f64"]
-OK, INVALID, WORKSPACE = 0, 1, 3
-P = 4096                                  # stands for arrays that are never touched: every call here returns first
-LARGE = (1517, 32, 36, 36, 4, 4)          # needs a workspace
-SMALL = (50, 64, 5, 5, 5, 5)              # does not
-EMPTY = (0, 64, 5, 5, 5, 5)
 N_FWD, N_BWD = 9, 10                      # arrays of a forward / a backward call
 
 
@@ -99,18 +85,7 @@ def _bwd(fn, shape, arrays=None, ws=P, ws_bytes=1 << 40):
     return fn(*shape, *arrays, ws, ws_bytes, None)
 
 
-BAD_SHAPES = [(-1, 2, 5, 5, 5, 5), (8, 0, 5, 5, 5, 5), (8, -2, 5, 5, 5, 5), (8, 2, 0, 5, 1, 5), (8, 2, 5, 0, 5, 1),
-              (8, 2, -4, 4, 2, 2), (8, 2, 4, -4, 2, 2),
-              (8, 2, 4, 4, 0, 2), (8, 2, 4, 4, 2, 0), (8, 2, 4, 4, -2, 2), (8, 2, 4, 4, 2, -2),
-              (8, 2, 36, 36, 5, 4),                 # H % kh != 0
-              (8, 2, 36, 36, 4, 5),                 # W % kw != 0
-              (8, 2, 5, 5, 3, 5), (8, 2, 5, 5, 5, 3),
-              (8, 2, 4, 4, 8, 2),                   # kh > H
-              (8, 2, 4, 4, 2, 8),                   # kw > W
-              (4096, 1024, 32, 16, 4, 4),           # N*C*H*W = 2^31 > INT_MAX: the reference indexes with int
-              (2 ** 16, 2 ** 16, 1, 1, 1, 1),       # ... already in N*C
-              (2 ** 15, 2 ** 15, 2, 1, 1, 1),       # ... in N*C*H
-              (2 ** 30, 2 ** 30, 2 ** 30, 2 ** 30, 1, 1)]      # ... and past 64 bits
+
 
 
 @pytest.mark.parametrize("name", FORWARDS)

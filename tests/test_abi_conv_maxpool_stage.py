@@ -15,7 +15,7 @@ import pytest
 import conv_reference as CR
 import conv_maxpool_stage_reference as R
 from conftest import ROOT
-from test_abi_conv_stage import (INVALID, OK, SAVE_POOL, SCALE, SHIFT, TOP, UNSUPPORTED, VAR, WEIGHT, WORKSPACE, MEAN, P, X,
+from pooled_stage_suite import (INVALID, OK, SAVE_POOL, SCALE, SHIFT, TOP, UNSUPPORTED, VAR, WEIGHT, WORKSPACE, MEAN, P, X,
                                  _cshape, _distinct, _refused, _shape)
 
 PREFIX = "mms_conv_maxpool_stage_"

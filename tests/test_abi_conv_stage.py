@@ -14,15 +14,14 @@ import pytest
 import conv_reference as CR
 import conv_stage_reference as R
 from conftest import ROOT
+from pooled_stage_suite import (INVALID, MEAN, OK, SAVE_POOL, SCALE, SHIFT, TOP, UNSUPPORTED, VAR, WEIGHT, WORKSPACE,
+                                P, X, _cshape, _distinct, _refused, _shape)
 
-OK, INVALID, UNSUPPORTED, WORKSPACE = 0, 1, 2, 3
-P = 4096                                  # stands for arrays that are never touched: every call here returns first
 FORWARDS = ["mms_conv_stage_forward_f32", "mms_conv_stage_forward_f64", "mms_conv_stage_forward_sequence_f32"]
 FUSED = "mms_conv_stage_forward_fused_f32"            # the same arguments without the workspace pair
 QUERIES = ["mms_conv_stage_workspace_bytes", "mms_conv_stage_workspace_bytes_f64",
            "mms_conv_stage_sequence_workspace_bytes"]
 V4 = [((4, 40, 40, 32), 4), ((32, 9, 9, 64), 5)]      # (C, H, W, K) of network_v4's two stages, 5 x 5, and the window
-X, WEIGHT, BIAS, MEAN, VAR, SCALE, SHIFT, TOP, SAVE_POOL = range(9)
 
 
 @pytest.fixture(scope="module")
@@ -43,15 +42,6 @@ def _declared():
     txt = open(os.path.join(ROOT, "include", "mms_conv_stage.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(mms_\w+)\s*\(", txt)))
-
-
-def _distinct(n=9):
-    return [P + 64 * i for i in range(n)]
-
-
-def _cshape(conv, st, N=None):
-    s = st.conv
-    return conv.conv_shape(s.N if N is None else N, s.C, s.H, s.W, s.K, (s.kh, s.kw), s.stride, s.pad, s.group)
 
 
 def test_every_declared_name_is_exported_and_bound(stage, hiplib):
@@ -84,31 +74,6 @@ def test_the_frozen_surface_is_untouched(stage, hiplib):
     assert not [n for n in capi.EXPORTED_SYMBOLS + conv.EXPORTED_SYMBOLS if "stage" in n]
     assert not [n for n in dir(conv) if "stage" in n]
     assert hiplib.mms_version() == 212 and capi.MMS_VERSION == 212
-
-
-def _shape(conv, **kw):
-    d = dict(N=2, C_=4, H=12, W=12, K=6, kernel=3, stride=1, pad=0, group=1, dilation=1)       # a 10 x 10 map
-    d.update(kw)
-    return conv.conv_shape(**d)
-
-
-def _refused(conv):
-    """(shape, (ph, pw), code): what mms_conv_forward refuses with its code, then the windows."""
-    big = 2 ** 16
-    shapes = [(_shape(conv, N=-1), INVALID), (_shape(conv, C_=0), INVALID), (_shape(conv, H=0), INVALID),
-              (_shape(conv, W=-1), INVALID), (_shape(conv, K=0), INVALID), (_shape(conv, kernel=(0, 3)), INVALID),
-              (_shape(conv, stride=(0, 1)), INVALID), (_shape(conv, group=0), INVALID),
-              (_shape(conv, dilation=(0, 1)), INVALID), (_shape(conv, pad=(-1, 0)), INVALID),
-              (_shape(conv, group=3), INVALID), (_shape(conv, kernel=13), INVALID),
-              (_shape(conv, N=big, C_=big, H=1, W=1, kernel=1), INVALID),
-              (_shape(conv, N=1, C_=1, H=4, W=4, K=2 ** 30, kernel=3, pad=1), INVALID),
-              (_shape(conv, dilation=2), UNSUPPORTED), (_shape(conv, N=0, dilation=(1, 2)), UNSUPPORTED)]
-    out = [(s, (2, 5), code) for s, code in shapes]
-    good = _shape(conv)
-    for pool in ((0, 2), (2, 0), (-1, 2), (2, -5), (3, 2), (2, 3), (20, 2), (2, 11), (4, 4)):
-        out.append((good, pool, INVALID))
-        out.append((_shape(conv, N=0), pool, INVALID))
-    return out
 
 
 def test_shape_and_window_refusals_in_every_call(stage, conv, hiplib):

@@ -2,96 +2,34 @@
 float64 run of tests/bn_maxpool_reference.py -- the three reference layers in sequence -- on the same inputs.  Parity is
 the project's 1e-5 (float32) and 1e-12 (float64) in assert_close's metric, on inputs whose windows all have a top-two
 gap (tests/test_bn_maxpool_reference.py); where the gradient goes among equal BN outputs, the statistics' order,
-alignment, what the workspace held and what is written are tested by equality of words or on exact probes."""
-import functools
-
+alignment, what the workspace held and what is written are tested by equality of words or on exact probes.  The bodies
+that do not depend on the pooling method are tests/pooled_stage_suite.py's, bound here to these calls."""
 import numpy as np
 import pytest
 import torch
 
 import bn_maxpool_reference as R
-from test_gpu_bn import BAR, DTYPES, IDS, Guarded, assert_words_equal, host, placed
-from test_gpu_bn_pool import BACKWARD_OUTPUTS, check_parity, same_words
-from test_gpu_bn_pool import run as run_ave
+import bn_pool_reference as P
+from pooled_stage_suite import BAR, BnPool, same_words
+from test_gpu_bn import DTYPES, IDS, assert_words_equal, host
 from util import SEED, assert_close
 
 pytestmark = pytest.mark.gpu
 
-
-def api(dtype):
-    from mms_answer_selection_amd import bn_maxpool as M
-    if dtype == np.float32:
-        return M.bn_maxpool_tanh_forward, M.bn_maxpool_tanh_backward, M.bn_maxpool_tanh_workspace_bytes
-    return M.bn_maxpool_tanh_forward_f64, M.bn_maxpool_tanh_backward_f64, M.bn_maxpool_tanh_workspace_bytes_f64
-
-
-@functools.lru_cache(maxsize=None)
-def inputs(shape, dtype):
-    return R.conditioned_inputs(shape, dtype, SEED)
-
-
-@functools.lru_cache(maxsize=None)
-def model(shape, dtype):
-    """The float64 sequence model on the inputs as the device gets them, computed once and shared (never modified)."""
-    out = R.model_outputs(inputs(shape, dtype), shape[4:], np.float64)
-    for v in out.values():
-        v.setflags(write=False)
-    return out
-
-
-def run(inp, kernel, dtype, shift=0, ws=None, outputs=(True, True, True), phases=("train", "test")):
-    """test_gpu_bn_pool.run for the MAX calls: TRAIN forward, backward, TEST forward (from the same running blobs),
-    backward; every output starts as NaN (the two parameter diffs as 123) between guard zones; every operand is `shift`
-    elements off a 16-byte boundary."""
-    fwd, bwd, _ = api(dtype)
-    shape, pooled, C = inp["x"].shape, inp["top_diff"].shape, inp["x"].shape[1]
-    x, top_diff = placed(inp["x"], dtype, shift), placed(inp["top_diff"], dtype, shift)
-    scale, shift_blob = placed(inp["scale"], dtype, shift), placed(inp["shift"], dtype, shift)
-    nan = float("nan")
-    out = {}
-    for name in phases:
-        g = dict(top=Guarded(pooled, dtype, nan, shift), save_pool=Guarded(pooled, dtype, nan, shift),
-                 save_mean=Guarded((C,), dtype, nan, shift), save_std=Guarded((C,), dtype, nan, shift),
-                 running_mean=Guarded((C,), dtype, inp["running_mean"], shift),
-                 running_var=Guarded((C,), dtype, inp["running_var"], shift))
-        fwd(x, kernel, scale, shift_blob, g["running_mean"].t, g["running_var"].t, g["top"].t, g["save_pool"].t,
-            g["save_mean"].t, g["save_std"].t, phase=R.TRAIN if name == "train" else R.TEST, bn_memory=R.BN_MEMORY, ws=ws)
-        b = dict(bottom_diff=Guarded(shape, dtype, nan, shift), scale_diff=Guarded((C,), dtype, 123.0, shift),
-                 shift_diff=Guarded((C,), dtype, 123.0, shift))
-        given = {k: b[k].t if want else None for k, want in zip(BACKWARD_OUTPUTS, outputs)}
-        bwd(x, kernel, g["top"].t, top_diff, g["save_pool"].t, scale, shift_blob, g["save_mean"].t, g["save_std"].t,
-            ws=ws, **given)
-        for k, v in g.items():
-            out[name + "_" + k] = v.host(name + " " + k)
-        for k, v in b.items():
-            h = v.host(name + " " + k)
-            if given[k] is not None:
-                out[name + "_" + k] = h
-            else:
-                assert (h == 123.0).all() if k != "bottom_diff" else np.isnan(h).all(), k + " was not asked for"
-    if "test" in phases:
-        assert_words_equal(out["test_running_mean"], inp["running_mean"], "TEST phase: running mean")
-        assert_words_equal(out["test_running_var"], inp["running_var"], "TEST phase: running variance")
-        assert_words_equal(out["test_save_mean"], inp["running_mean"], "TEST phase: saved mean")
-    return out
+S = BnPool("bn_maxpool", "bn_maxpool_tanh", R, shift_in_backward=True)
+AVE = BnPool("capi", "bn_pool_tanh", P, shift_in_backward=False)
+api, inputs, run = S.api, S.inputs, S.run
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("shape", R.PARITY_SHAPES, ids=str)
 def test_parity_and_determinism(shape, dtype, hiplib):
-    inp = inputs(shape, dtype)
-    first = run(inp, shape[4:], dtype)
-    check_parity(first, model(shape, dtype), dtype)
-    same_words(run(inp, shape[4:], dtype), first, "second run")
+    S.check_parity_and_determinism(shape, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_both_sides_of_the_routing_threshold(dtype, hiplib):
-    _, _, query = api(dtype)
-    below, above = R.THRESHOLD_SHAPES[dtype]
-    assert query(*below) == 0 and query(*above) > 0
-    for shape in (below, above):
-        check_parity(run(inputs(shape, dtype), shape[4:], dtype), model(shape, dtype), dtype)
+    S.check_both_sides_of_the_routing_threshold(dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -101,18 +39,15 @@ def test_statistics_are_the_ave_calls(shape, dtype, hiplib):
     """save_mean, save_std, running_mean and running_var of the TRAIN forward are mms_bn_pool_tanh_forward's words on
     the same x, on both routes: one workgroup per channel, a few chunks, 64 ragged chunks, and 63 chunks of a window
     the kernels learn at run time."""
-    from mms_answer_selection_amd import capi
-    _, _, query = api(dtype)
-    ave_query = capi.bn_pool_tanh_workspace_bytes if dtype == np.float32 else capi.bn_pool_tanh_workspace_bytes_f64
+    query, ave_query = api(dtype)[2], AVE.api(dtype)[2]
     assert query(*shape) == ave_query(*shape)
     item = np.dtype(dtype).itemsize
     if shape[0] == 405 and dtype == np.float32:
         assert query(*shape) == shape[1] * 64 * 4 * item
     if shape[0] == 3652 and dtype == np.float32:
         assert query(*shape) >= shape[1] * 63 * 4 * item
-    import bn_pool_reference as P
     inp = P.conditioned_inputs(shape, dtype, SEED)
-    got, want = run(inp, shape[4:], dtype, phases=("train",)), run_ave(inp, shape[4:], dtype)
+    got, want = run(inp, shape[4:], dtype, phases=("train",)), AVE.run(inp, shape[4:], dtype)
     for k in ("save_mean", "save_std", "running_mean", "running_var"):
         assert_words_equal(got["train_" + k], want["train_" + k], k)
 
@@ -199,30 +134,13 @@ def test_rounding_collapse_follows_the_bn_output(shift, dtype, hiplib):
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_zero_variance_is_exact(dtype, hiplib):
-    inp = inputs((1, 1, 1, 1, 1, 1), dtype)
-    out = run(inp, (1, 1), dtype)
-    assert (out["train_save_pool"] == 0).all() and (out["train_bottom_diff"] == 0).all()
-    assert (out["train_scale_diff"] == 0).all()
-    assert_words_equal(out["train_save_std"], np.sqrt(np.array([1e-9], dtype)), "std == sqrt(var_eps)")
-    assert_words_equal(out["train_save_mean"], inp["x"].reshape(1), "mean == x")
-    t = out["train_top"].reshape(1)
-    assert_words_equal(out["train_shift_diff"], inp["top_diff"].reshape(1) * (dtype(1) - t * t), "shift_diff == gp")
+    S.check_zero_variance_is_exact(dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("shape", [(2, 3, 4, 6, 2, 3), (65, 5, 9, 37, 3, 37)], ids=str)
 def test_optional_backward_outputs(shape, dtype, hiplib):
-    from mms_answer_selection_amd import capi
-    inp = inputs(shape, dtype)
-    full = run(inp, shape[4:], dtype)
-    for mask in range(1, 7):
-        outputs = tuple(bool(mask >> b & 1) for b in range(3))
-        part = run(inp, shape[4:], dtype, outputs=outputs)
-        assert len(part) == len(full) - 2 * outputs.count(False)
-        for k, v in part.items():
-            assert_words_equal(v, full[k], "%s with outputs %s" % (k, outputs))
-    with pytest.raises(capi.MMSError):
-        run(inp, shape[4:], dtype, outputs=(False, False, False))
+    S.check_optional_backward_outputs(shape, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)

@@ -3,161 +3,58 @@ the float64 run of tests/bn_pool_reference.py -- the three reference layers in s
 the project's 1e-5 (float32) and 1e-12 (float64) in assert_close's metric, on inputs tests/test_bn_pool_reference.py
 shows to be conditioned for it; everything a tolerance would hide -- the order of the sums, strides, alignment, what the
 workspace held, what is and is not written -- is tested by equality of words."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import bn_pool_reference as R
-from test_gpu_bn import BAR, DTYPES, IDS, Guarded, assert_words_equal, host, placed
-from util import SEED, assert_close
+from pooled_stage_suite import BnPool, same_words
+from test_gpu_bn import DTYPES, IDS, assert_words_equal, host
+from util import SEED
 
 pytestmark = pytest.mark.gpu
 
-BACKWARD_OUTPUTS = ("bottom_diff", "scale_diff", "shift_diff")
+S = BnPool("capi", "bn_pool_tanh", R, shift_in_backward=False)
+api, inputs, model, run = S.api, S.inputs, S.model, S.run
 SMALL_ROUTE = [(3, 2, 36, 36, 4, 4), (7, 4, 5, 5, 5, 5)]                      # compile-time windows, one launch
 LARGE_ROUTE = [(20, 3, 36, 36, 4, 4), (65, 5, 9, 37, 3, 37)]                  # two launches; a run-time window
-
-
-def api(dtype):
-    from mms_answer_selection_amd import capi
-    if dtype == np.float32:
-        return capi.bn_pool_tanh_forward, capi.bn_pool_tanh_backward, capi.bn_pool_tanh_workspace_bytes
-    return capi.bn_pool_tanh_forward_f64, capi.bn_pool_tanh_backward_f64, capi.bn_pool_tanh_workspace_bytes_f64
-
-
-@functools.lru_cache(maxsize=None)
-def inputs(shape, dtype):
-    return R.conditioned_inputs(shape, dtype, SEED)
-
-
-@functools.lru_cache(maxsize=None)
-def model(shape, dtype):
-    """The float64 model on the inputs as the device gets them, computed once and shared (never modified)."""
-    out = R.model_outputs(inputs(shape, dtype), shape[4:], np.float64)
-    for v in out.values():
-        v.setflags(write=False)
-    return out
-
-
-def run(inp, kernel, dtype, shift=0, ws=None, outputs=(True, True, True)):
-    """TRAIN forward, backward, TEST forward (from the same running blobs), backward; every output starts as NaN (the
-    two parameter diffs as 123) between guard zones.  x, top_diff, top, save_pool and bottom_diff are `shift` elements
-    off a 16-byte boundary.  -> {"train_top": ..., "test_shift_diff": ...} on the host, the keys of
-    bn_pool_reference.model_outputs; a backward output not asked for (outputs = bottom_diff, scale_diff, shift_diff) is
-    absent, and its prefill is checked to be intact."""
-    fwd, bwd, _ = api(dtype)
-    shape = inp["x"].shape
-    pooled = inp["top_diff"].shape
-    C = shape[1]
-    x, top_diff = placed(inp["x"], dtype, shift), placed(inp["top_diff"], dtype, shift)
-    scale, shift_blob = placed(inp["scale"], dtype), placed(inp["shift"], dtype)
-    nan = float("nan")
-    out = {}
-    for name, phase in (("train", R.TRAIN), ("test", R.TEST)):
-        g = dict(top=Guarded(pooled, dtype, nan, shift), save_pool=Guarded(pooled, dtype, nan, shift),
-                 save_mean=Guarded((C,), dtype, nan), save_std=Guarded((C,), dtype, nan),
-                 running_mean=Guarded((C,), dtype, inp["running_mean"]),
-                 running_var=Guarded((C,), dtype, inp["running_var"]))
-        fwd(x, kernel, scale, shift_blob, g["running_mean"].t, g["running_var"].t, g["top"].t, g["save_pool"].t,
-            g["save_mean"].t, g["save_std"].t, phase=phase, bn_memory=R.BN_MEMORY, ws=ws)
-        b = dict(bottom_diff=Guarded(shape, dtype, nan, shift), scale_diff=Guarded((C,), dtype, 123.0),
-                 shift_diff=Guarded((C,), dtype, 123.0))
-        given = {k: b[k].t if want else None for k, want in zip(BACKWARD_OUTPUTS, outputs)}
-        bwd(x, kernel, g["top"].t, top_diff, g["save_pool"].t, scale, g["save_mean"].t, g["save_std"].t, ws=ws, **given)
-        for k, v in g.items():
-            out[name + "_" + k] = v.host(name + " " + k)
-        for k, v in b.items():
-            h = v.host(name + " " + k)
-            if given[k] is not None:
-                out[name + "_" + k] = h
-            else:
-                assert (h == 123.0).all() if k != "bottom_diff" else np.isnan(h).all(), k + " was not asked for"
-    assert_words_equal(out["test_running_mean"], inp["running_mean"], "TEST phase: running mean")
-    assert_words_equal(out["test_running_var"], inp["running_var"], "TEST phase: running variance")
-    assert_words_equal(out["test_save_mean"], inp["running_mean"], "TEST phase: saved mean")
-    return out
-
-
-def check_parity(got, want, dtype):
-    assert sorted(got) == sorted(want)
-    for k in sorted(want):
-        assert got[k].dtype == dtype and not np.isnan(got[k]).any(), k
-        scale = max(1.0, float(np.max(np.abs(want[k]))))
-        print("%-22s %.3e" % (k, float(np.max(np.abs(got[k].astype(np.float64) - want[k]))) / scale))
-    for k in sorted(want):
-        assert_close(got[k], want[k], BAR[dtype], k)
-
-
-def same_words(got, want, what):
-    assert sorted(got) == sorted(want)
-    for k in want:
-        assert_words_equal(got[k], want[k], "%s, %s" % (k, what))
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("shape", R.PARITY_SHAPES, ids=str)
 def test_parity_and_determinism(shape, dtype, hiplib):
-    """Every output of TRAIN forward, TEST forward and the backward after each against the float64 model; NaN / 123
-    prefills gone, guards intact, TEST leaves the running blobs' words alone (inside run); a second run on fresh outputs
-    gives the same words."""
-    inp = inputs(shape, dtype)
-    first = run(inp, shape[4:], dtype)
-    check_parity(first, model(shape, dtype), dtype)
-    same_words(run(inp, shape[4:], dtype), first, "second run")
+    S.check_parity_and_determinism(shape, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_zero_variance_is_exact(dtype, hiplib):
-    inp = inputs((1, 1, 1, 1, 1, 1), dtype)
-    out = run(inp, (1, 1), dtype)
-    assert (out["train_save_pool"] == 0).all() and (out["train_bottom_diff"] == 0).all()
-    assert (out["train_scale_diff"] == 0).all()
-    assert_words_equal(out["train_save_std"], np.sqrt(np.array([1e-9], dtype)), "std == sqrt(var_eps)")
-    assert_words_equal(out["train_save_mean"], inp["x"].reshape(1), "mean == x")
-    t = out["train_top"].reshape(1)
-    assert_words_equal(out["train_shift_diff"], inp["top_diff"].reshape(1) * (dtype(1) - t * t), "shift_diff == gp")
+    S.check_zero_variance_is_exact(dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 def test_both_sides_of_the_routing_threshold(dtype, hiplib):
-    """The largest channel of the one-launch route and the next batch size up, found from the workspace query, both
-    against the model; their 2 x 4 windows are 16-byte rows of a size the kernels learn at run time."""
-    _, _, query = api(dtype)
+    """BnPool.check_both_sides_of_the_routing_threshold; the shapes' 2 x 4 windows are 16-byte rows of a size the
+    kernels learn at run time."""
     below, above = R.THRESHOLD_SHAPES[dtype]
     per_group = 16 // np.dtype(dtype).itemsize
     assert below[1:] == above[1:] and above[0] == below[0] + 1
     assert below[0] * below[2] * below[3] == 4096 * per_group
-    assert query(*below) == 0 and query(*above) > 0
-    for shape in (below, above):
-        check_parity(run(inputs(shape, dtype), shape[4:], dtype), model(shape, dtype), dtype)
+    S.check_both_sides_of_the_routing_threshold(dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("shape", [(2, 3, 4, 6, 2, 3), (65, 5, 9, 37, 3, 37)], ids=str)
 def test_optional_backward_outputs(shape, dtype, hiplib):
-    """A NULL bottom_diff, scale_diff or shift_diff skips that output and nothing else (run checks the prefill of the
-    ones left out), on both routes; with none of the three the call is refused."""
-    from mms_answer_selection_amd import capi
-    inp = inputs(shape, dtype)
-    full = run(inp, shape[4:], dtype)
-    for mask in range(1, 7):
-        outputs = tuple(bool(mask >> b & 1) for b in range(3))
-        part = run(inp, shape[4:], dtype, outputs=outputs)
-        assert len(part) == len(full) - 2 * outputs.count(False)
-        for k, v in part.items():
-            assert_words_equal(v, full[k], "%s with outputs %s" % (k, outputs))
-    with pytest.raises(capi.MMSError):
-        run(inp, shape[4:], dtype, outputs=(False, False, False))
+    """BnPool.check_optional_backward_outputs, on both routes."""
+    S.check_optional_backward_outputs(shape, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("shape", [(3, 2, 36, 36, 4, 4), (20, 3, 36, 36, 4, 4), (129, 3, 8, 16, 2, 4)], ids=str)
 def test_unaligned_bases_give_the_same_words(shape, dtype, hiplib):
-    """x, top_diff, top, save_pool and bottom_diff 1, 2 and 3 elements off a 16-byte boundary (window rows read and
-    written one element at a time instead of 16 bytes at a time, except where 2 doubles are 16 bytes again) give the
-    words of the aligned run: compile-time and run-time windows, both routes."""
+    """Every operand 1, 2 and 3 elements off a 16-byte boundary (window rows read and written one element at a time
+    instead of 16 bytes at a time, except where 2 doubles are 16 bytes again) gives the words of the aligned run:
+    compile-time and run-time windows, both routes."""
     inp = inputs(shape, dtype)
     aligned = run(inp, shape[4:], dtype)
     for shift in (1, 2, 3):

@@ -3,214 +3,55 @@ csrc/conv_stage.hip) against tests/conv_stage_reference.py.  The fused launch (m
 every shape it reaches, whichever route the main call's measured rules pick there) is held to the sequence route -- the
 two public calls -- by EQUALITY on integer probes, whatever order a kernel sums the products in, and at network_v4's
 two stages on conditioned inputs too; the main call to the route mms_conv_stage_route names; every shape to the
-float64 model at the project's 1e-5 (float32) and 1e-12 (float64) in assert_close's metric; the fixed order and the workspace's irrelevance by equality of words between two runs."""
-import functools
-
+float64 model at the project's 1e-5 (float32) and 1e-12 (float64) in assert_close's metric; the fixed order and the workspace's irrelevance by equality of words between two runs.
+The bodies that do not depend on the pooling method are tests/pooled_stage_suite.py's, bound here to this stage."""
 import numpy as np
 import pytest
-import torch
 
 import conv_stage_reference as R
-from test_gpu_conv import GUARD, SENTINEL, TORCH, Guarded, assert_words_equal, host, placed
-from util import SEED, TOL, assert_close
+from pooled_stage_suite import ConvStage
+from test_gpu_conv import assert_words_equal
 
 pytestmark = pytest.mark.gpu
 
-BAR = {np.float32: TOL, np.float64: 1e-12}
-NAMES = ("x", "weight", "bias", "mean", "var", "scale", "shift")
+S = ConvStage("conv_stage", R, assert_words_equal)
 FUSED_IDS = [R.stage_id(st) for st in R.FUSED_STAGES]
 ALL_IDS = [R.stage_id(st) for st in R.GPU_STAGES]
-
-
-def mod():
-    from mms_answer_selection_amd import conv_stage
-    return conv_stage
-
-
-def cshape(st, N=None):
-    from mms_answer_selection_amd import conv
-    s = st.conv
-    return conv.conv_shape(s.N if N is None else N, s.C, s.H, s.W, s.K, (s.kh, s.kw), s.stride, s.pad, s.group)
-
-
-def route_of(st):
-    return mod().conv_stage_route(cshape(st), st.pool)
-
-
-class GuardedWorkspace:
-    """What capi._scratch asks a Workspace for: exactly the queried bytes, every word a NaN, between two zones of
-    sentinels."""
-
-    def __init__(self, nbytes):
-        assert nbytes % 4 == 0
-        self.nbytes, self.asked = nbytes, None
-        self.buf = torch.full((2 * GUARD + nbytes // 4,), SENTINEL, dtype=torch.float32, device="cuda")
-        self.buf[GUARD:GUARD + nbytes // 4].fill_(float("nan"))
-
-    def get(self, nbytes, device):
-        self.asked = nbytes
-        assert nbytes == self.nbytes
-        return (self.buf[GUARD:].data_ptr(), nbytes) if nbytes else (None, 0)
-
-    def check(self):
-        b = host(self.buf)
-        assert self.asked == self.nbytes
-        assert (b[:GUARD] == SENTINEL).all() and (b[GUARD + self.nbytes // 4:] == SENTINEL).all(), "workspace guard"
-
-
-def query(st, dtype, route):
-    m = mod()
-    q = m.conv_stage_workspace_bytes if dtype == np.float32 else m.conv_stage_workspace_bytes_f64
-    return q(cshape(st), st.pool, route=route)
-
-
-def run(st, inp, dtype=np.float32, route="auto", shift=0, guarded_ws=False, save_pool=True):
-    """One forward.  top and save_pool start as NaN between guard zones; x, weight, top and save_pool are `shift`
-    elements off a 16-byte boundary.  -> {"top"[, "save_pool"]} on the host; the inputs are checked to be unchanged."""
-    m = mod()
-    fwd = m.conv_stage_forward if dtype == np.float32 else m.conv_stage_forward_f64
-    s = st.conv
-    dev = {k: (None if inp[k] is None else placed(inp[k], dtype, shift)) for k in NAMES}
-    nan = float("nan")
-    top = Guarded(R.pooled_shape(st), dtype, nan, shift)
-    sp = Guarded(R.pooled_shape(st), dtype, nan, shift) if save_pool else None
-    ws = GuardedWorkspace(query(st, dtype, route)) if guarded_ws and route != "fused" else None     # fused takes none
-    got = fwd(dev["x"], dev["weight"], dev["bias"], st.pool, dev["mean"], dev["var"], dev["scale"], dev["shift"], top.t,
-              sp.t if sp else None, stride=s.stride, pad=s.pad, group=s.group, ws=ws, route=route)
-    assert got is top.t
-    torch.cuda.synchronize()
-    if ws:
-        ws.check()
-    out = dict(top=top.host("top"))
-    if sp:
-        out["save_pool"] = sp.host("save_pool")
-    for k in NAMES:
-        if inp[k] is not None:
-            assert_words_equal(host(dev[k]), np.array(inp[k], dtype=dtype), k + " is an input")
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def inputs(st, dtype):
-    return R.conditioned_inputs(st, dtype, SEED)
-
-
-@functools.lru_cache(maxsize=None)
-def model(st, dtype):
-    """The float64 model on the inputs as the device gets them, computed once and shared (never modified)."""
-    out = R.model_outputs(st, inputs(st, dtype), np.float64)
-    for v in out.values():
-        v.setflags(write=False)
-    return out
-
-
-def named_route(st):
-    """The forced route whose words the main call must give: the one mms_conv_stage_route names."""
-    return {mod().ROUTE_FUSED: "fused", mod().ROUTE_SEQUENCE: "sequence"}[route_of(st)]
 
 
 @pytest.mark.parametrize("st", R.FUSED_STAGES, ids=FUSED_IDS)
 def test_integer_probe_fused_equals_sequence(st, hiplib):
     """The map is exact whatever order its products are summed in, so both routes pool the same numbers: top and
     save_pool equal word for word, and save_pool equals the float32 restatement of the finish."""
-    assert R.probe_bound(st) < 2 ** 24
-    inp = R.integer_probe(st, SEED)
-    fused, seq, auto = run(st, inp, route="fused"), run(st, inp, route="sequence"), run(st, inp)
-    want_top, want_sp = R.probe_outputs(st, inp)
-    for k in ("top", "save_pool"):
-        assert not np.isnan(fused[k]).any(), k
-        assert_words_equal(fused[k], seq[k], "integer probe, fused against sequence, " + k)
-        assert_words_equal(auto[k], seq[k], "integer probe, the main call against sequence, " + k)
-    assert_words_equal(fused["save_pool"], want_sp, "integer probe, save_pool against the float32 restatement")
-    assert_close(fused["top"], want_top, TOL, "integer probe, top")
+    S.check_integer_probe_fused_equals_sequence(st)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 @pytest.mark.parametrize("st", R.GPU_STAGES, ids=ALL_IDS)
 def test_parity_and_determinism(st, dtype, hiplib):
-    """Per shape and route: the conditioned inputs against the float64 model at the bar; a second run with every
-    operand one element off a 16-byte boundary and a NaN-filled workspace of exactly the queried size gives the same
-    words and leaves the workspace's guard zones alone.  The main call gives the words of the route it names.
-    network_v4's stages: fused and sequence, the same words."""
-    from mms_answer_selection_amd import capi
-    m = mod()
-    inp, want = inputs(st, dtype), model(st, dtype)
-    reached = st in R.FUSED_STAGES
-    if not reached:
-        assert route_of(st) == m.ROUTE_SEQUENCE
-        with pytest.raises(capi.MMSError):
-            run(st, inputs(st, np.float32), route="fused")        # refused host-side: the launch does not reach
-    routes = ["fused", "sequence", "auto"] if dtype == np.float32 and reached else ["auto"]
-    first = {}
-    for route in routes:
-        first[route] = run(st, inp, dtype, route)
-        for k in ("top", "save_pool"):
-            got = first[route][k]
-            assert got.dtype == dtype and not np.isnan(got).any(), k
-            scale = max(1.0, float(np.max(np.abs(want[k]))))
-            print("%-8s %-9s %.3e" % (route, k, float(np.max(np.abs(got.astype(np.float64) - want[k]))) / scale))
-    for route in routes:
-        for k in ("top", "save_pool"):
-            assert_close(first[route][k], want[k], BAR[dtype], "%s, %s route" % (k, route))
-        second = run(st, inp, dtype, route, shift=1, guarded_ws=True)
-        for k in ("top", "save_pool"):
-            assert_words_equal(second[k], first[route][k], "%s, %s route, second run" % (k, route))
-    if len(routes) == 3:
-        for k in ("top", "save_pool"):
-            assert_words_equal(first["auto"][k], first[named_route(st)][k], "the main call against the route it names, " + k)
-            if st in R.V4_STAGES:
-                assert_words_equal(first["fused"][k], first["sequence"][k], "fused against sequence, " + k)
+    """ConvStage.check_parity_and_determinism; network_v4's stages: fused and sequence, the same words."""
+    S.check_parity_and_determinism(st, dtype, R.V4_STAGES)
 
 
 def test_the_main_call_reaches_both_routes_on_the_fused_list(hiplib):
-    m = mod()
-    assert [route_of(st) for st in R.V4_STAGES] == [m.ROUTE_FUSED, m.ROUTE_SEQUENCE, m.ROUTE_FUSED]
+    m = S.mod()
+    assert [S.route_of(st) for st in R.V4_STAGES] == [m.ROUTE_FUSED, m.ROUTE_SEQUENCE, m.ROUTE_FUSED]
 
 
 @pytest.mark.parametrize("st", [R.FUSED_STAGES[0], R.FUSED_STAGES[4], R.SEQUENCE_STAGES[0]],
                          ids=[ALL_IDS[0], ALL_IDS[4], R.stage_id(R.SEQUENCE_STAGES[0])])
 def test_save_pool_is_optional(st, hiplib):
-    inp = inputs(st, np.float32)
-    for route in ("auto", "sequence") + (("fused",) if st in R.FUSED_STAGES else ()):
-        full = run(st, inp, route=route)
-        part = run(st, inp, route=route, save_pool=False, guarded_ws=True)
-        assert sorted(part) == ["top"]
-        assert_words_equal(part["top"], full["top"], "top without a save_pool, %s route" % route)
-    st64 = run(st, inp, np.float64, save_pool=False, guarded_ws=True)
-    assert_close(st64["top"], model(st, np.float32)["top"], 1e-12, "top without a save_pool, f64")
+    S.check_save_pool_is_optional(st)
 
 
 @pytest.mark.parametrize("st", R.SEQUENCE_STAGES, ids=[R.stage_id(st) for st in R.SEQUENCE_STAGES])
 def test_sequence_route_is_the_two_public_calls(st, hiplib):
     """The main call on a shape it routes to the sequence, against mms_conv_forward_f32 and
     mms_bn_pool_tanh_forward_f32 (TEST) issued here."""
-    from mms_answer_selection_amd import capi, conv
-    assert route_of(st) == mod().ROUTE_SEQUENCE
-    s, inp = st.conv, inputs(st, np.float32)
-    got = run(st, inp)
-    dev = {k: (None if inp[k] is None else placed(inp[k], np.float32)) for k in NAMES}
-    y = conv.conv_forward(dev["x"], dev["weight"], dev["bias"], stride=s.stride, pad=s.pad, group=s.group)
-    top, sp = (torch.full(R.pooled_shape(st), float("nan"), device="cuda") for _ in range(2))
-    sm, ss = torch.empty(s.K, device="cuda"), torch.empty(s.K, device="cuda")
-    capi.bn_pool_tanh_forward(y, st.pool, dev["scale"], dev["shift"], dev["mean"], dev["var"], top, sp, sm, ss, phase=1)
-    assert_words_equal(got["top"], host(top), "top")
-    assert_words_equal(got["save_pool"], host(sp), "save_pool")
+    from mms_answer_selection_amd import capi
+    S.check_sequence_route_is_the_two_public_calls(st, capi.bn_pool_tanh_forward)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 def test_empty_batch_writes_nothing(dtype, hiplib):
-    m = mod()
-    fwd = m.conv_stage_forward if dtype == np.float32 else m.conv_stage_forward_f64
-    t = TORCH[dtype]
-    x = torch.empty(0, 4, 12, 12, dtype=t, device="cuda")
-    w, bias = Guarded((6, 4, 3, 3), dtype, 1.0), Guarded((6,), dtype, 2.0)
-    k = [Guarded((6,), dtype, 1.5) for _ in range(4)]
-    for route in ("auto", "sequence"):
-        top = fwd(x, w.t, bias.t, (2, 5), *(g.t for g in k), route=route)
-        assert tuple(top.shape) == (0, 6, 5, 2)
-        sp = torch.empty(0, 6, 5, 2, dtype=t, device="cuda")
-        fwd(x, w.t, bias.t, (2, 5), *(g.t for g in k), top, sp, route=route)
-    torch.cuda.synchronize()
-    assert (w.host("weight") == 1.0).all() and (bias.host("bias") == 2.0).all()
-    for g in k:
-        assert (g.host("a BN array") == 1.5).all()
+    S.check_empty_batch_writes_nothing(dtype)

@@ -17,6 +17,7 @@ import bn_reference as BNR
 import layer_plans as L
 import test_gpu_bn as bn
 import test_gpu_bn_pool as bp
+from pooled_stage_suite import check_parity, same_words
 from test_gpu_bn import Guarded, assert_words_equal, host, placed
 from test_gpu_fm import BIAS, case as fm_case
 from util import SEED
@@ -204,11 +205,11 @@ def test_bn_pool_parity_past_64_minimum_chunks(case, hiplib):
     need, _, _ = bp_route_checked(case)
     inp = bp.inputs(shape, dtype)
     first = bp.run(inp, shape[4:], dtype)
-    bp.check_parity(first, bp.model(shape, dtype), dtype)
+    check_parity(first, bp.model(shape, dtype), dtype)
     ws = ExactWorkspace(need, dtype)
     second = bp.run(inp, shape[4:], dtype, ws=ws.ws)
     ws.guards_intact()
-    bp.same_words(second, first, "NaN-filled workspace")
+    same_words(second, first, "NaN-filled workspace")
 
 
 @pytest.mark.parametrize("case", L.BP_CASES, ids=L.case_id)
