@@ -46,6 +46,7 @@
 
 #include <type_traits>
 
+#include "bx3_waits.h"
 #include "mms_common.h"
 #include "panel_gemm.h"
 
@@ -81,7 +82,7 @@ struct Bx3Geom {
   static constexpr int BLK = 3 * NTW;                 // 1-KB image blocks per k-step (one column group)
   static constexpr int A_OFF = BLK * 1024;
   static constexpr int SLOT = A_OFF + 8192;           // + 128 rows x 16 k of raw fp32 A
-  static constexpr int NS = 6;
+  static constexpr int NS = kBx3NS;                   // the operand ring: bx3_waits.h
   static constexpr int LDC = 32 * NTW + 8;            // staging stride (4 rows apart = 32 banks apart)
   static constexpr int SIDE_OFF = NS * SLOT + 256;    // behind the ring and the 256-byte sink of the Y prefetch
   static constexpr size_t kLdsBytes =                 // (the ring is reused by the epilogue's staging)
@@ -196,27 +197,26 @@ __device__ __forceinline__ void bx3_dma4s(const void* sbase, unsigned voff, unsi
 template <int N>
 __device__ __forceinline__ void bx3_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// the loader's loop: PER DMAs per k-step, issued by issue(step)
-template <int PER, int NS, class Issue, class Side, class SideOps>
-__device__ __forceinline__ void bx3_loader_loop(int ksteps, Issue&& issue, Side&& side, SideOps&& side_ops) {
-  for (int s = 0; s < NS - 1 && s < ksteps; ++s) issue(s);
+// The loader's loop: PER DMAs per k-step, issued by issue(step); side(j) is the side step of a wave with side_cnt indices.
+// What each wait may leave in flight, and why, is bx3_waits.h (proved on the host by tests/native/bx3_waits_host.cpp).
+template <int PER, int NS, class Issue, class Side>
+__device__ __forceinline__ void bx3_loader_loop(int ksteps, int side_cnt, Issue&& issue, Side&& side) {
+  static_assert(NS == kBx3NS, "bx3_waits.h is derived for this ring depth");
+  static_assert(bx3_wait_imm(PER, kBx3WaitBuckets - 1) <= kBx3VmcntMax, "vmcnt has six bits");
+  for (int s = 0; s < bx3_prologue_steps(ksteps); ++s) issue(s);
   for (int j = 0; j <= ksteps; ++j) {
-    // barrier j: steps j and j+1 have landed; issued so far: up to step j + NS - 2
-    const int last = ksteps - 1;
-    const int hi = j + NS - 2 < last ? j + NS - 2 : last, need = j + 1 < last ? j + 1 : last;
-    const int out = hi - need;                       // steps allowed to be in flight: 0 .. NS - 3
-    if (out >= 3) {
-      const int so = side_ops();                      // side operations among the youngest 3 PER + so
-      if (so >= 9) bx3_wait_vm<3 * PER + 9>();
-      else if (so >= 6) bx3_wait_vm<3 * PER + 6>();
-      else bx3_wait_vm<3 * PER>();
+    switch (bx3_wait_bucket(bx3_sched(j, ksteps).out, bx3_side_ops_younger_than_in_flight(j, side_cnt))) {
+      case 5: bx3_wait_vm<bx3_wait_imm(PER, 5)>(); break;
+      case 4: bx3_wait_vm<bx3_wait_imm(PER, 4)>(); break;
+      case 3: bx3_wait_vm<bx3_wait_imm(PER, 3)>(); break;
+      case 2: bx3_wait_vm<bx3_wait_imm(PER, 2)>(); break;
+      case 1: bx3_wait_vm<bx3_wait_imm(PER, 1)>(); break;
+      default: bx3_wait_vm<bx3_wait_imm(PER, 0)>();
     }
-    else if (out == 2) bx3_wait_vm<2 * PER>();
-    else if (out == 1) bx3_wait_vm<PER>();
-    else bx3_wait_vm<0>();
-    __builtin_amdgcn_s_barrier();
-    side(j);                                          // (its requests are older than this step's DMAs: see Bx3Side)
-    if (j + NS - 1 < ksteps) issue(j + NS - 1);       // into the slot of step j - 1, which the barrier just released
+    __builtin_amdgcn_s_barrier();                     // barrier j: steps j and j + 1 have landed
+    side(j);
+    const int s = bx3_issue_behind_barrier(j, ksteps);
+    if (s >= 0) issue(s);
   }
 }
 
@@ -225,18 +225,17 @@ __device__ __forceinline__ void bx3_loader_loop(int ksteps, Issue&& issue, Side&
 // columns, ONE float4 (and its row's scale) per loader lane and step, requested by LDS-DMA into a four-deep ring
 // behind the operand ring and read back, scaled and stored three steps later.  (Through LDS, not registers: a load
 // issued by hand lands whenever it lands, in a register the compiler may by then have copied or given away -- seen as a
-// write fault.)  Three steps on, 3 PER younger DMAs have been issued behind a request, so the loop's counted wait
-// covers it; the loop in turn is told how many side operations sit among the youngest (ops()), or its waits would reach
-// into the DMAs it means to leave in flight (measured: +4 us on the main loop).  The stores are the compiler's.
+// write fault.)  Which step issues what, and the wait that covers a request before its store: bx3_waits.h.  The stores
+// are the compiler's.
 struct Bx3Side {
   static constexpr int SLOT = 4096 + 1024;          // 256 lanes x (16 + 4) bytes per step
-  static constexpr int BYTES = 4 * SLOT;
+  static constexpr int BYTES = kBx3SideRing * SLOT;
+  static_assert((kBx3SideRing & (kBx3SideRing - 1)) == 0, "slot of index i: i & (ring - 1)");
   const float* in; float* out; const float* scale; long long ld;
   int out_half;
   int row0, total, c0, nc;         // rows from row0, total = rows * nc float4, float4 columns [c0, c0 + nc)
   int lane, w;                     // loader wave w
   int cnt;                         // float4 per lane: indices 0 .. cnt-1 (index i is requested at step i)
-  int n1, n2, n3;                  // side operations issued one, two and three steps ago
   unsigned lds;                    // LDS byte address of the side ring
   const unsigned char* ldsp;
 
@@ -251,20 +250,19 @@ struct Bx3Side {
     total = rows * nc;
     w = w_; lane = lane_;
     cnt = in ? (total + 255) >> 8 : 0;
-    n1 = n2 = n3 = 0;
     lds = lds_byte; ldsp = lds_ptr;
   }
   __device__ __forceinline__ void request(int i) {
     int f = i * 256 + w * 64 + lane;
     f = f < total ? f : total - 1;
     const int r = f / nc, cc = f - r * nc;
-    const unsigned slot = lds + (unsigned)((i & 3) * SLOT);
+    const unsigned slot = lds + (unsigned)((i & (kBx3SideRing - 1)) * SLOT);
     bx3_dma16s(in, (unsigned)(((long long)(row0 + r) * ld + 4 * (c0 + cc)) * 4), slot + (unsigned)(w * 1024));
     bx3_dma4s(scale, (unsigned)((row0 + r) * 4), slot + 4096u + (unsigned)(w * 256));
   }
   __device__ __forceinline__ void store(int i) {      // only behind a wait that covers request i
     const int f = i * 256 + w * 64 + lane;
-    const unsigned char* slot = ldsp + (i & 3) * SLOT;
+    const unsigned char* slot = ldsp + (i & (kBx3SideRing - 1)) * SLOT;
     const pg_v4f x = *reinterpret_cast<const pg_v4f*>(slot + w * 1024 + lane * 16);
     const float sc = *reinterpret_cast<const float*>(slot + 4096 + w * 256 + lane * 4);
     if (f < total) {
@@ -279,22 +277,19 @@ struct Bx3Side {
       }
     }
   }
-  __device__ __forceinline__ int ops() const { return n1 + n2 + n3; }     // among the youngest at the next wait
   __device__ __forceinline__ void step(int j) {
-    int n = 0;
     asm volatile("" ::: "memory");
-    if (j >= 3 && j - 3 < cnt) { store(j - 3); n += 1; }
-    if (j < cnt) { request(j); n += 2; }
-    n3 = n2; n2 = n1; n1 = n;
+    if (bx3_side_stores(j, cnt)) store(j - kBx3SideLag);
+    if (bx3_side_requests(j, cnt)) request(j);
   }
   __device__ __forceinline__ void finish(int steps_done) {   // what the loop was too short for
     if (!cnt) return;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int loaded = steps_done < cnt ? steps_done : cnt;           // indices < loaded were requested
-    for (int i = steps_done - 3 > 0 ? steps_done - 3 : 0; i < loaded; ++i) store(i);
-    for (int i = loaded; i < cnt; ++i) {
+    bx3_wait_vm<0>();
+    const int requested = bx3_finish_requested(steps_done, cnt);
+    for (int i = bx3_finish_first(steps_done); i < requested; ++i) store(i);
+    for (int i = requested; i < cnt; ++i) {
       request(i);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      bx3_wait_vm<0>();
       store(i);
     }
   }
@@ -305,7 +300,6 @@ struct Bx3Side {
 template <int NTW, bool AH = false>
 __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
   using G = Bx3Geom<NTW>;
-  static_assert(G::NS == 6, "bx3_loader_loop's waits assume three steps in flight");
   static_assert(Bx3Side::BYTES == 20480, "Bx3Geom::kLdsBytes reserves 20480 bytes for the side ring");
   extern __shared__ __attribute__((aligned(16))) unsigned char bx3_lds[];
   const int lane = threadIdx.x & 63;
@@ -345,12 +339,12 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
       const char* const src0 = reinterpret_cast<const char*>(p.img) + ((size_t)grp * NTW * 3 + w) * 1024;
       const size_t step_bytes = (size_t)ngroups * NTW * 3 * 1024;
       const unsigned voff = (unsigned)lane * 16u;
-      bx3_loader_loop<NTW, G::NS>(ksteps, [&](int s) {
+      bx3_loader_loop<NTW, G::NS>(ksteps, sd.cnt, [&](int s) {
         const unsigned slot = lds0 + (unsigned)((s % G::NS) * G::SLOT + w * 1024);
         const char* src = src0 + (size_t)s * step_bytes;
 #pragma unroll
         for (int t = 0; t < NTW; ++t) bx3_dma16s(src + t * 3072, voff, slot + (unsigned)(t * 3072));
-      }, [&](int j) { sd.step(j); }, [&]() { return sd.ops(); });
+      }, [&](int j) { sd.step(j); });
     } else if (AH) {
       // the panel's raw A as halves: 4 blocks = row tiles; lane fetches row 32 wr + l % 32, the 8 halves k = 16 s + 8 (l / 32)
       const _Float16* const abase_h = reinterpret_cast<const _Float16*>(p.A) + (long long)row0 * p.lda;
@@ -369,7 +363,7 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
       const char* const ybase = reinterpret_cast<const char*>(p.Y ? (const void*)p.Y : (const void*)p.A);
       const long long ystride = p.Y ? p.ldy * 2 : 0;
       const long long ymax = p.Y ? ((long long)(p.M - 1) * p.ldy + p.N) * 2 - 4 : 0;
-      bx3_loader_loop<5, G::NS>(ksteps, [&](int s) {
+      bx3_loader_loop<5, G::NS>(ksteps, sd.cnt, [&](int s) {
         {
           int idx = (s - 3) * 64 + lane;
           idx = idx > 0 ? idx : 0;
@@ -384,7 +378,7 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
 #pragma unroll
         for (int wr = 0; wr < 4; ++wr)
           bx3_dma16s(sb, s < ksteps - 1 ? aoffh[wr] : aoffh_t[wr], slot + (unsigned)(wr * 1024));
-      }, [&](int j) { sd.step(j); }, [&]() { return sd.ops(); });
+      }, [&](int j) { sd.step(j); });
     } else {
       // the panel's raw A: 8 blocks = (row tile wr, k quad q): lane fetches row 32 wr + l % 32, k = 16 s + 8 (l / 32) + 4 q.
       // Per-lane byte offsets from the panel's first row, fixed for the whole loop (rows past M: the last row); the
@@ -409,7 +403,7 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
       const char* const ybase = reinterpret_cast<const char*>(p.Y ? p.Y : p.A);
       const long long ystride = p.Y ? p.ldy * 4 : 0;
       const long long ymax = p.Y ? ((long long)(p.M - 1) * p.ldy + p.N) * 4 - 4 : 0;
-      bx3_loader_loop<9, G::NS>(ksteps, [&](int s) {
+      bx3_loader_loop<9, G::NS>(ksteps, sd.cnt, [&](int s) {
         {
           int idx = (s - 3) * 64 + lane;            // (from step 3 on: in front of the first steps they delay barrier 0)
           idx = idx > 0 ? idx : 0;
@@ -435,7 +429,7 @@ __global__ __launch_bounds__(512, 1) void bx3_kernel(const Bx3Args p) {
             bx3_dma16s(sb, aoff_t1[wr], slot + (unsigned)(wr * 2048 + 1024));
           }
         }
-      }, [&](int j) { sd.step(j); }, [&]() { return sd.ops(); });
+      }, [&](int j) { sd.step(j); });
     }
     sd.finish(ksteps + 1);
   } else {

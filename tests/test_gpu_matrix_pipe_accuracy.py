@@ -31,10 +31,26 @@ pytestmark = pytest.mark.gpu
 #   (2048, 24, 8):    NTW 1 both ways, K % 16 = 8 and a single 8-deep step, the side job's 8-column minimum
 #   (2125, 96, 128):  NTW 4 / NTW 3
 #   (2085, 200, 72):  NTW 3 / two groups NTW 4, K % 16 = 8
-SHAPES = [(2049, 300, 300), (2125, 52, 304), (2049, 64, 160), (2048, 24, 8), (2125, 96, 128), (2085, 200, 72)]
-# the fp16-storage family needs K1 % 8 == 0 and K2 % 8 == 0: bx3_kernel<NTW, true> 5 (two groups), 5 / 2, 1, 4 / 3, 3 / 4
-HALF_SHAPES = [(2049, 304, 304), (2125, 64, 160), (2048, 24, 8), (2125, 96, 128), (2085, 200, 72)]
-
+#   (2088, 16, 64):   NTW 2 / NTW 1; the side job's regimes below
+# The loader waves' side job (da, in the dq launch: csrc/bx3_waits.h) per shape, as (ksteps = ceil(K2 / 16), cnt = ceil(rows *
+# nc / 256) per loader lane, column groups of the dq launch: nc = K2 / 4 float4 columns, or its halves with two groups);
+# "full" = the 128-row panels, "last" = the ragged last panel:
+#   (2049, 300, 300): (19, 19, 2) full: cnt == ksteps, every store but the last three inside the loop, steady-state waits;
+#                     (19, 1, 2) last: one request, its store at barrier 3, then side steps that issue nothing
+#   (2125, 52, 304):  (19, 38, 1) full, (19, 23, 1) last: cnt > ksteps + 1, finish requests and stores one index at a time
+#   (2049, 64, 160):  (10, 20, 1) full: the same with a short steady state; (10, 1, 1) last
+#   (2048, 24, 8):    (1, 1, 1): one k-step, nothing but tail waits, the only store is finish's
+#   (2125, 96, 128):  (8, 16, 1) full, (8, 10, 1) last: steady state for barriers 0 .. 3 only
+#   (2085, 200, 72):  (5, 5, 2) full: ksteps == NS - 1, one barrier that leaves three steps in flight; (5, 2, 2) last
+#   (2088, 16, 64):   (4, 8, 1) full: ksteps == NS - 2, every wait a tail wait (side operations not counted) with stores
+#                     and requests in each side step, then finish's one-at-a-time part; (4, 3, 1) last: cnt == 3, the
+#                     last request in side step 2, the first store in side step 3, the rest in finish
+# The forward has no side job (cnt == 0) at ksteps = ceil(K1 / 16) = 19, 4, 4, 2, 6, 13, 1.
+SHAPES = [(2049, 300, 300), (2125, 52, 304), (2049, 64, 160), (2048, 24, 8), (2125, 96, 128), (2085, 200, 72), (2088, 16, 64)]
+# the fp16-storage family needs K1 % 8 == 0 and K2 % 8 == 0: bx3_kernel<NTW, true> 5 (two groups), 5 / 2, 1, 4 / 3, 3 / 4,
+# 2 / 1; side job (19, 19, 2) + (19, 1, 2), (10, 20, 1) + (10, 13, 1), (1, 1, 1), (8, 16, 1) + (8, 10, 1), (5, 5, 2) + (5, 2, 2),
+# (4, 8, 1) + (4, 3, 1)
+HALF_SHAPES = [(2049, 304, 304), (2125, 64, 160), (2048, 24, 8), (2125, 96, 128), (2085, 200, 72), (2088, 16, 64)]
 
 def dev(x):
     return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda()
