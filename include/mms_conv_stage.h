@@ -17,7 +17,7 @@
  *   x (N, C, H, W)   weight (K, C/group, kh, kw)   bias (K) or NULL   mean, var, scale, shift (K)
  *   top, save_pool (N, K, OH/ph, OW/pw); save_pool (= sp) is optional: NULL skips it.
  *
- * TRAIN phase needs the batch statistics of y and is not offered: run the two calls.
+ * TRAIN phase needs the batch statistics of y and is not offered here: include/mms_conv_stage_train.h has it.
  *
  * Two routes (mms_conv_stage_route, the one place that decides; the launchers call it too):
  *   SEQUENCE  the two calls above, y in the caller's workspace.

@@ -1,7 +1,7 @@
 // csrc/bn_common.h -- what csrc/bn.hip (BN) and csrc/bn_pool.hip (BN -> AvePool / MaxPool -> TanH) share: the sizes of
 // the two routes, the workgroup sum with its fixed order, the ascending fold of a channel's chunk sums and the TRAIN
 // statistics made from them; and what csrc/bn_pool.hip shares with csrc/conv_stage.hip: a window's TEST-phase finish,
-// AVE and MAX, and MAX's scan step.
+// AVE and MAX, and MAX's scan step; and with csrc/conv_stage_train.hip: the TRAIN-phase finish and the statistics.
 #ifndef MMS_BN_COMMON_H_
 #define MMS_BN_COMMON_H_
 
@@ -74,6 +74,16 @@ __device__ __forceinline__ int bp_dir(T sc) {
 template <typename T>
 __device__ __forceinline__ T bn_maxpool_test_finish(T e, T nmean, T std, T sc, T sh, T* save_pool) {
   const T sp = bp_normalised(e, nmean, std);
+  *save_pool = sp;
+  return bn_tanh(bp_bn_out(sp, sc, sh));
+}
+
+// The TRAIN-phase finish of one pooling window, AVE and MAX alike, once the channel's statistics are known: from m, the
+// window's mean (AVE: its sum / (kh kw)) or extremum (MAX: bp_keep's) as the sweep left it, *save_pool and the return
+// value, top.  csrc/bn_pool.hip's bp_finish and csrc/conv_stage_train.hip's second launch both finish with it.
+template <typename T>
+__device__ __forceinline__ T bn_pool_train_finish(T m, T nmean, T std, T sc, T sh, T* save_pool) {
+  const T sp = bp_normalised(m, nmean, std);
   *save_pool = sp;
   return bn_tanh(bp_bn_out(sp, sc, sh));
 }

@@ -203,9 +203,10 @@ __device__ __forceinline__ void bp_finish(const BpGeom& g, unsigned c, unsigned 
                                           T sh, T* save_pool, T* __restrict__ top) {
   for (unsigned w = w0 + threadIdx.x; w < w1; w += THREADS) {
     const size_t p = bp_pooled_index(g, c, w);
-    const T sp = bp_normalised(save_pool[p], nmean, std);
+    T sp;
+    const T t = bn_pool_train_finish(save_pool[p], nmean, std, sc, sh, &sp);
     save_pool[p] = sp;
-    top[p] = bn_tanh(bp_bn_out(sp, sc, sh));
+    top[p] = t;
   }
 }
 

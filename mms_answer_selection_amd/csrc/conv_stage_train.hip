@@ -1,0 +1,559 @@
+// csrc/conv_stage_train.hip -- the TRAIN-phase stage Convolution -> BN -> AvePool / MaxPool -> TanH, forward and
+// backward each as one call (include/mms_conv_stage_train.h: mms_conv_stage_train_*), and their extern "C" entry
+// points.  The formulas are those of csrc/conv.hip and csrc/bn_pool.hip; what is new here is the forward's FUSED route.
+//
+//   sequence  forward: mms_conv_forward_* into the caller's y, then mms_bn_pool_tanh_forward_* /
+//             mms_bn_maxpool_tanh_forward_* with phase 0 on it -- three launches at the training batch (the
+//             convolution, BN's sweep of the whole map, the pooled-size finish).  backward: the BN -> pool -> TanH
+//             backward leaves dy in the workspace, mms_conv_backward_* runs on it.  Nothing of their own here.
+//   fused     forward, float: two launches.
+//             Launch 1 (train_product_kernel) is csrc/conv_tile.h's product with a band whose height is a multiple of
+//             ph (conv_prod_plan with rq = ph, as csrc/conv_stage.hip) AND the chunk of input channels of the
+//             convolution's own plan (rq = 1), so an element of y is the convolution's own chain of MFMA steps.  The
+//             epilogue stores accumulator + bias to y and to LDS as tile[k][pixel], over the band and the weights the
+//             last chunk has finished with.  After a barrier the 256 / (16 MT) adjacent lanes that serve channel k
+//             walk the workgroup's windows of k: lane j takes windows j, j + T, ... in (image, window row, window
+//             column) order, adds (MAX: scans, bp_keep) each from the tile in (h, w) order, stores the window's mean
+//             (MAX: extremum) to save_pool, and adds the same values in the same order into one sum of y and one of
+//             y*y.  Only real pixels are windows: a band's tail and a ragged last image group add nothing.  The T
+//             lanes' sums are combined by xor-shuffles 1, 2 (, 4, 8) apart -- registers and lanes, no LDS beside the
+//             full tile -- and lane 0 writes them to the workspace slot of (channel, workgroup).
+//             Launch 2 (train_finish_kernel) is pooled-size: grid (K, chunks); every workgroup adds its channel's
+//             partials (thread t those of workgroups t, t + 256, ..., then bn_block_sum), forms the statistics with
+//             bn_statistics -- chunk 0's first thread updates the running blobs and writes save_mean / save_std --
+//             and finishes its chunk of the channel's pooled elements in place with bn_pool_train_finish,
+//             csrc/bn_pool.hip's own.
+// train_route is the one place that decides; its thresholds are lines of profiles/conv_stage_train_bench.txt.
+#include "bn_common.h"
+#include "conv_tile.h"
+#include "mms_conv_stage_train.h"
+#include "mms_internal.h"
+
+namespace mms {
+namespace {
+
+static_assert(kConvMaxChannels * kConvTilePixels <= kConvLdsFloats, "the accumulator tile of any fast plan fits the LDS");
+
+struct TrainDims {
+  ConvDims d;
+  int ph, pw, POH, POW;
+  bool max;
+};
+
+// the refusal of the shape, the pool and the window, else MMS_OK and *g
+int train_check(const mms_conv_shape* shape, int ph, int pw, int pool, TrainDims* g) {
+  const int rc = conv_check(shape, &g->d);
+  if (rc != MMS_OK) return rc;
+  if (pool != MMS_STAGE_POOL_AVE && pool != MMS_STAGE_POOL_MAX) return MMS_ERR_INVALID_ARG;
+  if (ph < 1 || pw < 1 || g->d.OH % ph || g->d.OW % pw) return MMS_ERR_INVALID_ARG;
+  g->ph = ph;
+  g->pw = pw;
+  g->POH = g->d.OH / ph;
+  g->POW = g->d.OW / pw;
+  g->max = pool == MMS_STAGE_POOL_MAX;
+  return MMS_OK;
+}
+
+struct TrainArgs {
+  ConvProdArgs p;        // the product; p.out is y
+  const float* scale;    // MAX: the direction of a channel's scan
+  float* save_pool;      // (N, K, POH, POW): launch 1 leaves the windows' means / extrema here
+  float* part;           // [K][groups][2]: sum y, sum y*y of a workgroup's real pixels
+  int ph, pw, POH, POW;
+  int PS;                // row length of the accumulator tile [Cout][PS]
+  int groups;            // workgroups of launch 1
+  size_t lds_bytes;
+};
+
+// p.ok false: the fused launches do not reach.
+TrainArgs train_plan(const TrainDims& g) {
+  TrainArgs a = {};
+  ConvProdArgs p = conv_prod_plan(g.d, MMS_CONV_PASS_FORWARD, g.ph);
+  if (!p.ok) return a;
+  // The chunk of the convolution's own plan: the two plans walk the same states until one image is left per workgroup
+  // (so G is the same), then the own plan may halve its band below ph rows.  A band no higher than the own one holds
+  // the own chunk as it is; a higher one is halved, in units of ph rows, until it does.
+  const int CC = conv_prod_plan(g.d, MMS_CONV_PASS_FORWARD, 1).CC;
+  const int khkw = p.kh * p.kw, Mpad = 16 * p.MT;
+  const long long kp = conv_round4(CC * khkw);
+  const auto fits = [&] {
+    return (long long)p.G * CC * ((p.R + p.kh - 1) * p.BW) + (long long)Mpad * kp + kp <= kConvLdsFloats;
+  };
+  while (!fits() && p.G == 1 && p.R > g.ph) {
+    p.R = (p.R / g.ph + 1) / 2 * g.ph;
+    p.bands = (p.OHt + p.R - 1) / p.R;
+  }
+  if (!fits()) return a;
+  p.CC = CC;
+  p.plane = (p.R + p.kh - 1) * p.BW;
+  p.Kpad = (int)kp;
+  p.lds_bytes = ((size_t)p.G * p.CC * p.plane + (size_t)Mpad * p.Kpad + p.Kpad) * sizeof(float);
+  a.p = p;
+  a.ph = g.ph; a.pw = g.pw; a.POH = g.POH; a.POW = g.POW;
+  const int P = p.G * p.R * p.OWt;
+  // csrc/conv_stage.hip's row length: 4 or 12 mod 16 keeps the lane groups of an accumulator in separate banks
+  a.PS = P;
+  while (a.PS % 16 != 4 && a.PS % 16 != 12) ++a.PS;
+  if (p.Cout * a.PS > kConvLdsFloats) a.PS = P;
+  const size_t tile = (size_t)p.Cout * a.PS * sizeof(float);
+  a.lds_bytes = tile > p.lds_bytes ? tile : p.lds_bytes;
+  a.groups = (p.N + p.G - 1) / p.G * p.bands;
+  return a;
+}
+
+// The measured rule (tools/bench_conv_stage_train.py, profiles/conv_stage_train_bench.txt: forced FUSED against the two
+// public calls in one process, medians of seven alternating passes; "faster": the median ratio is above 1 and the two
+// ranges are apart).  A class of shapes -- pooling method x what a workgroup of launch 1 holds -- is FUSED on the span
+// of workgroup counts from the first to the last measured count at which every stage of the class is faster or level
+// with a faster count on either side; every other count, unmeasured ones included, is the SEQUENCE.  {0, -1}: no count.
+//   AVE, a band of rows (network_v4's conv0, 9 bands of 4 rows): faster at 450 workgroups (N = 50: 28.8 against 32.8 us,
+//     1.14 x), level at 1800 (0.98 x), slower at 3600, 7200 and 13653 (0.94 to 0.88 x).  FUSED at 450 only: nothing
+//     was measured between 450 and 1800.
+//   AVE, several whole images (conv1, ten each): slower at 5, 20 and 80 workgroups (0.97 x), faster at 152 (1.02 x),
+//     level at 300.  One winning count between a loss and a tie: not taken.
+//   MAX, a band of rows (network_v3's first stage, network_v5's first): v3's faster at 450 (1.13 x) and 13653 (1.06 x),
+//     level at 3600 (1.04 x); v5's faster at 350, 2800 and 10619 (1.20, 1.11, 1.08 x).  FUSED on 450 .. 10619, the
+//     counts inside both stages' spans.
+//   MAX, one whole image (v5's second stage): slower at 50, level at 400 and 1517.  Not taken.
+//   MAX, several whole images (v3's second stage, v5's third): slower or level at every count measured.  Not taken.
+//   AVE, one whole image: not measured.
+struct TrainSpan {
+  long long least, most;       // workgroups of launch 1
+};
+// [MAX][kind]: kind 0 several whole images per workgroup, 1 a band of rows of one image, 2 one whole image
+constexpr TrainSpan kTrainSpans[2][3] = {
+    {{0, -1}, {450, 450}, {0, -1}},
+    {{0, -1}, {450, 10619}, {0, -1}},
+};
+
+int train_route(const TrainDims& g) {
+  const TrainArgs a = train_plan(g);
+  if (!a.p.ok) return MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE;
+  const TrainSpan& k = kTrainSpans[g.max][a.p.G > 1 ? 0 : a.p.bands > 1 ? 1 : 2];
+  return a.groups >= k.least && a.groups <= k.most ? MMS_CONV_STAGE_TRAIN_ROUTE_FUSED
+                                                   : MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE;
+}
+
+// PH, PW > 0: the window's size at compile time (== s.ph, s.pw); 0: any window.
+template <bool MAX, int PH, int PW>
+struct TrainEpilogue {
+  const TrainArgs& s;
+  float* tile;
+  // Nothing is kept across the product loop: its register budget is csrc/conv.hip's less the store offsets.
+  __device__ __forceinline__ void pixel(const ConvProdArgs&, const ConvTile&, int, int, int, int) {}
+
+  template <int MT>
+  __device__ __forceinline__ void finish(const ConvProdArgs& a, const ConvTile& t, const conv_v4f (&acc)[MT][kConvNT],
+                                         const bool (&pvalid)[kConvNT]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, grp = lane >> 4;
+    const int PS = s.PS;
+    const size_t PI = (size_t)a.OHt * a.OWt;
+    // pixel p = (image p / per, row, column) of the band: rows are whole, so its place in the map is oy0 OWt + p % per
+    size_t yoff[kConvNT];
+#pragma unroll
+    for (int nt = 0; nt < kConvNT; ++nt) {
+      const int p = pvalid[nt] ? (wave + 4 * nt) * 16 + l16 : 0, img = p / t.per;
+      yoff[nt] = (size_t)(t.n0 + img) * a.Cout * PI + (size_t)t.oy0 * a.OWt + (p - img * t.per);
+    }
+    __syncthreads();                                    // every wave has finished with the band and the weights
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = 16 * mt + 4 * grp + r;
+        if (m >= a.Cout) continue;
+        const float b = a.bias ? a.bias[m] : 0.f;
+#pragma unroll
+        for (int nt = 0; nt < kConvNT; ++nt)
+          if (pvalid[nt]) {
+            const float v = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];     // ConvStoreEpilogue's word
+            tile[m * PS + (wave + 4 * nt) * 16 + l16] = v;
+            a.out[yoff[nt] + (size_t)m * PI] = v;
+          }
+      }
+    __syncthreads();
+    constexpr int TK = kConvThreads / (16 * MT);        // adjacent lanes per channel: 16, 8, 4
+    const int k = tid / TK, j = tid - k * TK;
+    const int ph = PH > 0 ? PH : s.ph, pw = PW > 0 ? PW : s.pw;
+    float s0 = 0.f, s1 = 0.f;
+    if (k < a.Cout) {
+      const int wper = t.rb / ph * s.POW;               // windows of the band: per image
+      const int PP = s.POH * s.POW, q0 = t.oy0 / ph * s.POW;
+      const float ke = (float)(ph * pw);
+      int dir = 0;
+      if constexpr (MAX) dir = bp_dir(s.scale[k]);
+      const auto element = [&](bool first, float v, float* m) {
+        if constexpr (MAX) bp_keep(first, v, dir, m);
+        else *m += v;
+        s0 += v;
+        s1 += v * v;
+      };
+      for (int e = j; e < t.gc * wper; e += TK) {
+        const int img = e / wper, q = e - img * wper, wr = q / s.POW, wc = q - wr * s.POW;
+        const float* src = tile + k * PS + img * t.per + wr * ph * a.OWt + wc * pw;
+        float m = 0.f;                                  // AVE: the window's sum; MAX: its extremum
+        if constexpr (PH > 0) {
+          float v[PH][PW];
+#pragma unroll
+          for (int i = 0; i < PH; ++i)
+#pragma unroll
+            for (int c = 0; c < PW; ++c) v[i][c] = src[i * a.OWt + c];
+#pragma unroll
+          for (int i = 0; i < PH; ++i)
+#pragma unroll
+            for (int c = 0; c < PW; ++c) element(i == 0 && c == 0, v[i][c], &m);
+        } else {
+          for (int i = 0; i < ph; ++i)
+            for (int c = 0; c < pw; ++c) element(i == 0 && c == 0, src[i * a.OWt + c], &m);
+        }
+        s.save_pool[((size_t)(t.n0 + img) * a.Cout + k) * PP + q0 + q] = MAX ? m : m / ke;
+      }
+    }
+    // every lane takes part: the TK lanes of a channel are an aligned run of one wave
+#pragma unroll
+    for (int d = 1; d < TK; d <<= 1) {
+      s0 += __shfl_xor(s0, d);
+      s1 += __shfl_xor(s1, d);
+    }
+    if (k < a.Cout && j == 0) {
+      const size_t wg = (size_t)blockIdx.x * gridDim.y + blockIdx.y;
+      float* o = s.part + ((size_t)k * s.groups + wg) * 2;
+      o[0] = s0;
+      o[1] = s1;
+    }
+  }
+};
+
+template <int MT, bool MAX, int PH, int PW>
+__global__ __launch_bounds__(kConvThreads) void train_product_kernel(TrainArgs s) {
+  extern __shared__ float conv_lds[];
+  TrainEpilogue<MAX, PH, PW> epi{s, conv_lds};
+  conv_tile_product<MT>(s.p, conv_lds, epi);
+}
+
+// Launch 2: grid (K, chunks), kBnThreads threads.  Windows [y wpc, (y + 1) wpc) of the channel's N * PP.
+__global__ __launch_bounds__(kBnThreads) void train_finish_kernel(
+    const float* __restrict__ part, int groups, const float* __restrict__ scale, const float* __restrict__ shift,
+    float* running_mean, float* running_var, float* __restrict__ top, float* save_pool, float* save_mean,
+    float* save_std, unsigned K, unsigned PP, unsigned windows, unsigned wpc, float bn_memory, float inv_S,
+    float inv_N) {
+  __shared__ float red[2 * kBnThreads / kWave];
+  const unsigned c = blockIdx.x;
+  const float* p = part + (size_t)c * groups * 2;
+  float tot[2] = {0.f, 0.f};
+  for (int g = threadIdx.x; g < groups; g += kBnThreads) {
+    tot[0] += p[2 * g];
+    tot[1] += p[2 * g + 1];
+  }
+  bn_block_sum<kBnThreads, 2>(tot, red);
+  float nmean, std;
+  bn_statistics(tot, (int)c, blockIdx.y == 0 && threadIdx.x == 0, bn_memory, inv_S, inv_N, running_mean, running_var,
+                save_mean, save_std, &nmean, &std);
+  const float sc = scale[c], sh = shift[c];
+  const unsigned w0 = blockIdx.y * wpc, w1 = windows - w0 < wpc ? windows : w0 + wpc;
+  for (unsigned w = w0 + threadIdx.x; w < w1; w += kBnThreads) {
+    const unsigned n = w / PP, r = w - n * PP;
+    const size_t o = ((size_t)n * K + c) * PP + r;
+    float sp;
+    const float t = bn_pool_train_finish(save_pool[o], nmean, std, sc, sh, &sp);
+    save_pool[o] = sp;
+    top[o] = t;
+  }
+}
+
+constexpr unsigned kTrainFinishWindows = 1024;     // pooled elements of a launch-2 workgroup, at least: four per thread
+constexpr unsigned kTrainFinishChunks = 64;        // ... unless that takes more workgroups per channel than this
+
+template <int K>
+using train_int = std::integral_constant<int, K>;
+
+// f(PH, PW) as types: csrc/conv_stage.hip's choice of windows known at compile time, any other at run time.
+template <bool MAX, class F>
+void train_dispatch(int ph, int pw, F&& f) {
+  if (ph == 4 && pw == 4) f(train_int<4>{}, train_int<4>{});
+  else if (!MAX && ph == 5 && pw == 5) f(train_int<5>{}, train_int<5>{});
+  else if (MAX && ph == 2 && pw == 2) f(train_int<2>{}, train_int<2>{});
+  else f(train_int<0>{}, train_int<0>{});
+}
+
+inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+template <typename T>
+size_t bn_bytes(const TrainDims& g) {
+  return std::is_same<T, float>::value
+             ? mms_bn_pool_tanh_workspace_bytes(g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw)
+             : mms_bn_pool_tanh_workspace_bytes_f64(g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw);
+}
+template <typename T>
+size_t conv_bytes(const mms_conv_shape* s) {
+  return std::is_same<T, float>::value ? mms_conv_workspace_bytes(s) : mms_conv_workspace_bytes_f64(s);
+}
+
+// The backward's workspace with every output: [dy][the BN call's][the convolution's], the first two rounded to 16 bytes.
+template <typename T>
+struct BackwardCarve {
+  size_t dy, bn, conv;
+  size_t all() const { return dy + bn + conv; }
+};
+template <typename T>
+BackwardCarve<T> backward_carve(const mms_conv_shape* shape, const TrainDims& g) {
+  const size_t map = (size_t)g.d.N * g.d.K * g.d.OH * g.d.OW;
+  return {round16(map * sizeof(T)), round16(bn_bytes<T>(g)), conv_bytes<T>(shape)};
+}
+
+size_t fused_bytes(const TrainArgs& a) { return (size_t)2 * a.p.Cout * a.groups * sizeof(float); }
+
+enum { kAuto = -1, kSequence = MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE, kFused = MMS_CONV_STAGE_TRAIN_ROUTE_FUSED };
+
+// What the forward needs on `force` (kAuto: train_route decides; kFused where it does not reach: 0).
+template <typename T>
+size_t forward_bytes(const TrainDims& g, int force) {
+  if (std::is_same<T, float>::value && force != kSequence) {
+    const TrainArgs a = train_plan(g);
+    if (force == kFused) return a.p.ok ? fused_bytes(a) : 0;
+    if (train_route(g) == MMS_CONV_STAGE_TRAIN_ROUTE_FUSED) return fused_bytes(a);
+  }
+  return bn_bytes<T>(g);
+}
+
+template <typename T>
+size_t train_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, int pool, int force) {
+  TrainDims g;
+  if (train_check(shape, ph, pw, pool, &g) != MMS_OK || g.d.N == 0) return 0;
+  if (force == kFused && !train_plan(g).p.ok) return 0;
+  const size_t f = forward_bytes<T>(g, force), b = backward_carve<T>(shape, g).all();
+  return f > b ? f : b;
+}
+
+inline int conv_fwd(const mms_conv_shape* s, const float* x, const float* w, const float* b, float* y, void* st) {
+  return mms_conv_forward_f32(s, x, w, b, y, nullptr, 0, st);
+}
+inline int conv_fwd(const mms_conv_shape* s, const double* x, const double* w, const double* b, double* y, void* st) {
+  return mms_conv_forward_f64(s, x, w, b, y, nullptr, 0, st);
+}
+inline int conv_bwd(const mms_conv_shape* s, const float* x, const float* w, const float* dy, float* dx, float* dw,
+                    float* db, void* ws, size_t wsb, void* st) {
+  return mms_conv_backward_f32(s, x, w, dy, dx, dw, db, ws, wsb, st);
+}
+inline int conv_bwd(const mms_conv_shape* s, const double* x, const double* w, const double* dy, double* dx, double* dw,
+                    double* db, void* ws, size_t wsb, void* st) {
+  return mms_conv_backward_f64(s, x, w, dy, dx, dw, db, ws, wsb, st);
+}
+inline int bn_fwd(const TrainDims& g, float mem, const float* y, const float* sc, const float* sh, float* rm, float* rv,
+                  float* top, float* sp, float* sm, float* ss, void* ws, size_t wsb, void* st) {
+  const auto call = g.max ? mms_bn_maxpool_tanh_forward_f32 : mms_bn_pool_tanh_forward_f32;
+  return call(0, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, mem, y, sc, sh, rm, rv, top, sp, sm, ss, ws, wsb, st);
+}
+inline int bn_fwd(const TrainDims& g, double mem, const double* y, const double* sc, const double* sh, double* rm,
+                  double* rv, double* top, double* sp, double* sm, double* ss, void* ws, size_t wsb, void* st) {
+  const auto call = g.max ? mms_bn_maxpool_tanh_forward_f64 : mms_bn_pool_tanh_forward_f64;
+  return call(0, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, mem, y, sc, sh, rm, rv, top, sp, sm, ss, ws, wsb, st);
+}
+inline int bn_bwd(const TrainDims& g, const float* y, const float* top, const float* td, const float* sp,
+                  const float* sc, const float* sh, const float* sm, const float* ss, float* dy, float* dsc, float* dsh,
+                  void* ws, size_t wsb, void* st) {
+  const int N = g.d.N, K = g.d.K, OH = g.d.OH, OW = g.d.OW;
+  return g.max ? mms_bn_maxpool_tanh_backward_f32(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sh, sm, ss, dy, dsc, dsh,
+                                                  ws, wsb, st)
+               : mms_bn_pool_tanh_backward_f32(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sm, ss, dy, dsc, dsh, ws,
+                                               wsb, st);
+}
+inline int bn_bwd(const TrainDims& g, const double* y, const double* top, const double* td, const double* sp,
+                  const double* sc, const double* sh, const double* sm, const double* ss, double* dy, double* dsc,
+                  double* dsh, void* ws, size_t wsb, void* st) {
+  const int N = g.d.N, K = g.d.K, OH = g.d.OH, OW = g.d.OW;
+  return g.max ? mms_bn_maxpool_tanh_backward_f64(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sh, sm, ss, dy, dsc, dsh,
+                                                  ws, wsb, st)
+               : mms_bn_pool_tanh_backward_f64(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sm, ss, dy, dsc, dsh, ws,
+                                               wsb, st);
+}
+
+// whether a non-NULL `out` is one of `others` (NULL entries are skipped)
+template <size_t M>
+bool among(const void* out, const void* const (&others)[M]) {
+  if (!out) return false;
+  for (const void* o : others) {
+    if (o && o == out) return true;
+  }
+  return false;
+}
+
+template <typename T>
+int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_memory, const T* x, const T* w,
+                  const T* bias, const T* scale, const T* shift, T* running_mean, T* running_var, T* y, T* top,
+                  T* save_pool, T* save_mean, T* save_std, void* workspace, size_t workspace_bytes, int force,
+                  void* stream) {
+  TrainDims g;
+  const int rc = train_check(shape, ph, pw, pool, &g);
+  if (rc != MMS_OK) return rc;
+  if (g.d.N == 0) return MMS_OK;
+  if (!x || !w || !scale || !shift || !running_mean || !running_var || !y || !top || !save_pool || !save_mean ||
+      !save_std)
+    return MMS_ERR_INVALID_ARG;
+  const void* const inputs[] = {x, w, bias, scale, shift};
+  const void* const outputs[] = {y, top, save_pool, save_mean, save_std, running_mean, running_var};
+  for (size_t i = 0; i < sizeof(outputs) / sizeof(outputs[0]); ++i) {
+    if (among(outputs[i], inputs)) return MMS_ERR_INVALID_ARG;
+    for (size_t j = 0; j < i; ++j) {
+      if (outputs[i] == outputs[j]) return MMS_ERR_INVALID_ARG;
+    }
+  }
+  if constexpr (std::is_same<T, float>::value) {
+    if (force == kFused && !train_plan(g).p.ok) return MMS_ERR_UNSUPPORTED;
+    if (force == kFused || (force == kAuto && train_route(g) == MMS_CONV_STAGE_TRAIN_ROUTE_FUSED)) {
+      TrainArgs a = train_plan(g);
+      if (!workspace || workspace_bytes < fused_bytes(a)) return MMS_ERR_WORKSPACE;
+      a.p.in = x; a.p.w = w; a.p.bias = bias; a.p.out = y;
+      a.scale = scale; a.save_pool = save_pool; a.part = static_cast<float*>(workspace);
+      const dim3 grid((unsigned)((a.p.N + a.p.G - 1) / a.p.G), (unsigned)a.p.bands);
+      conv_with_mt(a.p.MT, [&](auto M) {
+        with_bool(g.max, [&](auto MAX) {
+          train_dispatch<decltype(MAX)::value>(ph, pw, [&](auto PH, auto PW) {
+            hipLaunchKernelGGL(
+                (train_product_kernel<decltype(M)::value, decltype(MAX)::value, decltype(PH)::value, decltype(PW)::value>),
+                grid, dim3(kConvThreads), a.lds_bytes, as_stream(stream), a);
+          });
+        });
+      });
+      const int rc1 = launch_status();
+      if (rc1 != MMS_OK) return rc1;
+      const unsigned PP = (unsigned)(g.POH * g.POW), windows = (unsigned)g.d.N * PP;
+      unsigned wpc = (windows + kTrainFinishChunks - 1) / kTrainFinishChunks;
+      if (wpc < kTrainFinishWindows) wpc = kTrainFinishWindows;
+      const dim3 grid2((unsigned)g.d.K, (windows + wpc - 1) / wpc);
+      hipLaunchKernelGGL(train_finish_kernel, grid2, dim3(kBnThreads), 0, as_stream(stream), (const float*)a.part,
+                         a.groups, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
+                         (unsigned)g.d.K, PP, windows, wpc, bn_memory, (float)(1. / ((double)g.d.OH * g.d.OW)),
+                         (float)(1. / g.d.N));
+      return launch_status();
+    }
+  }
+  const size_t need = bn_bytes<T>(g);
+  if (need && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;
+  // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
+  const int rc1 = conv_fwd(shape, x, w, bias, y, stream);
+  if (rc1 != MMS_OK) return rc1;
+  return bn_fwd(g, bn_memory, y, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std, workspace,
+                workspace_bytes, stream);
+}
+
+template <typename T>
+int train_backward(const mms_conv_shape* shape, int ph, int pw, int pool, const T* x, const T* w, const T* y,
+                   const T* top, const T* top_diff, const T* save_pool, const T* scale, const T* shift,
+                   const T* save_mean, const T* save_std, T* dx, T* dw, T* db, T* dscale, T* dshift, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  TrainDims g;
+  const int rc = train_check(shape, ph, pw, pool, &g);
+  if (rc != MMS_OK) return rc;
+  if (g.d.N == 0) return MMS_OK;
+  if (!x || !w || !y || !top || !top_diff || !save_pool || !scale || (g.max && !shift) || !save_mean || !save_std ||
+      (!dx && !dw && !db && !dscale && !dshift))
+    return MMS_ERR_INVALID_ARG;
+  const void* const inputs[] = {x, w, y, top, top_diff, save_pool, scale, shift, save_mean, save_std};
+  const void* const outputs[] = {dx, dw, db, dscale, dshift};
+  for (size_t i = 0; i < sizeof(outputs) / sizeof(outputs[0]); ++i) {
+    if (among(outputs[i], inputs)) return MMS_ERR_INVALID_ARG;
+    for (size_t j = 0; j < i; ++j) {
+      if (outputs[i] && outputs[i] == outputs[j]) return MMS_ERR_INVALID_ARG;
+    }
+  }
+  const bool conv = dx || dw || db;
+  const BackwardCarve<T> carve = backward_carve<T>(shape, g);
+  const size_t need = conv ? carve.all() : bn_bytes<T>(g);
+  if (need && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;
+  char* base = static_cast<char*>(workspace);
+  T* dy = conv ? reinterpret_cast<T*>(base) : nullptr;
+  void* bn_ws = conv ? base + carve.dy : base;
+  // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
+  const int rc1 = bn_bwd(g, y, top, top_diff, save_pool, scale, shift, save_mean, save_std, dy, dscale, dshift, bn_ws,
+                         bn_bytes<T>(g), stream);
+  if (rc1 != MMS_OK || !conv) return rc1;
+  return conv_bwd(shape, x, w, dy, dx, dw, db, base + carve.dy + carve.bn, carve.conv, stream);
+}
+
+}  // namespace
+}  // namespace mms
+
+using namespace mms;
+
+extern "C" {
+
+int mms_conv_stage_train_route(const mms_conv_shape* shape, int ph, int pw, int pool) {
+  TrainDims g;
+  if (train_check(shape, ph, pw, pool, &g) != MMS_OK) return MMS_CONV_STAGE_TRAIN_ROUTE_NONE;
+  return train_route(g);
+}
+
+size_t mms_conv_stage_train_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, int pool) {
+  return train_workspace_bytes<float>(shape, ph, pw, pool, kAuto);
+}
+size_t mms_conv_stage_train_workspace_bytes_f64(const mms_conv_shape* shape, int ph, int pw, int pool) {
+  return train_workspace_bytes<double>(shape, ph, pw, pool, kSequence);
+}
+size_t mms_conv_stage_train_sequence_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, int pool) {
+  return train_workspace_bytes<float>(shape, ph, pw, pool, kSequence);
+}
+size_t mms_conv_stage_train_fused_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, int pool) {
+  return train_workspace_bytes<float>(shape, ph, pw, pool, kFused);
+}
+
+int mms_conv_stage_train_forward_f32(const mms_conv_shape* shape, int ph, int pw, int pool, float bn_memory,
+                                     const float* x, const float* weight, const float* bias, const float* scale,
+                                     const float* shift, float* running_mean, float* running_var, float* y, float* top,
+                                     float* save_pool, float* save_mean, float* save_std, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  return train_forward<float>(shape, ph, pw, pool, bn_memory, x, weight, bias, scale, shift, running_mean, running_var,
+                              y, top, save_pool, save_mean, save_std, workspace, workspace_bytes, kAuto, stream);
+}
+
+int mms_conv_stage_train_forward_f64(const mms_conv_shape* shape, int ph, int pw, int pool, double bn_memory,
+                                     const double* x, const double* weight, const double* bias, const double* scale,
+                                     const double* shift, double* running_mean, double* running_var, double* y,
+                                     double* top, double* save_pool, double* save_mean, double* save_std,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return train_forward<double>(shape, ph, pw, pool, bn_memory, x, weight, bias, scale, shift, running_mean, running_var,
+                               y, top, save_pool, save_mean, save_std, workspace, workspace_bytes, kSequence, stream);
+}
+
+int mms_conv_stage_train_forward_sequence_f32(const mms_conv_shape* shape, int ph, int pw, int pool, float bn_memory,
+                                              const float* x, const float* weight, const float* bias,
+                                              const float* scale, const float* shift, float* running_mean,
+                                              float* running_var, float* y, float* top, float* save_pool,
+                                              float* save_mean, float* save_std, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  return train_forward<float>(shape, ph, pw, pool, bn_memory, x, weight, bias, scale, shift, running_mean, running_var,
+                              y, top, save_pool, save_mean, save_std, workspace, workspace_bytes, kSequence, stream);
+}
+
+int mms_conv_stage_train_forward_fused_f32(const mms_conv_shape* shape, int ph, int pw, int pool, float bn_memory,
+                                           const float* x, const float* weight, const float* bias, const float* scale,
+                                           const float* shift, float* running_mean, float* running_var, float* y,
+                                           float* top, float* save_pool, float* save_mean, float* save_std,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  return train_forward<float>(shape, ph, pw, pool, bn_memory, x, weight, bias, scale, shift, running_mean, running_var,
+                              y, top, save_pool, save_mean, save_std, workspace, workspace_bytes, kFused, stream);
+}
+
+int mms_conv_stage_train_backward_f32(const mms_conv_shape* shape, int ph, int pw, int pool, const float* x,
+                                      const float* weight, const float* y, const float* top, const float* top_diff,
+                                      const float* save_pool, const float* scale, const float* shift,
+                                      const float* save_mean, const float* save_std, float* bottom_diff,
+                                      float* weight_diff, float* bias_diff, float* scale_diff, float* shift_diff,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  return train_backward<float>(shape, ph, pw, pool, x, weight, y, top, top_diff, save_pool, scale, shift, save_mean,
+                               save_std, bottom_diff, weight_diff, bias_diff, scale_diff, shift_diff, workspace,
+                               workspace_bytes, stream);
+}
+
+int mms_conv_stage_train_backward_f64(const mms_conv_shape* shape, int ph, int pw, int pool, const double* x,
+                                      const double* weight, const double* y, const double* top, const double* top_diff,
+                                      const double* save_pool, const double* scale, const double* shift,
+                                      const double* save_mean, const double* save_std, double* bottom_diff,
+                                      double* weight_diff, double* bias_diff, double* scale_diff, double* shift_diff,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  return train_backward<double>(shape, ph, pw, pool, x, weight, y, top, top_diff, save_pool, scale, shift, save_mean,
+                                save_std, bottom_diff, weight_diff, bias_diff, scale_diff, shift_diff, workspace,
+                                workspace_bytes, stream);
+}
+
+}  // extern "C"

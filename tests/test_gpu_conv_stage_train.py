@@ -1,0 +1,291 @@
+"""GPU suite of the TRAIN-phase stage Convolution -> BN -> AvePool / MaxPool -> TanH (include/mms_conv_stage_train.h):
+both passes on every route against the float64 model, y against the convolution's own words, exact probes on which the
+fused and the sequence route must agree to the word, determinism under garbage workspaces and shifted bases, padding
+pixels, optional backward outputs, and the sequence route against the public calls issued here."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import conv_stage_train_reference as R
+import test_gpu_conv as V
+from pooled_stage_suite import BAR, GuardedWorkspace, assert_words_equal, check_parity, cshape, same_words
+from util import SEED
+
+pytestmark = pytest.mark.gpu
+
+
+def IDS(stages):
+    return [R.stage_id(st) for st in stages]
+
+
+BACKWARD = ("bottom_diff", "weight_diff", "bias_diff", "scale_diff", "shift_diff")
+FORWARD_INPUTS = ("x", "weight", "bias", "scale", "shift")
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(st, dtype):
+    return R.conditioned_inputs(st, dtype, SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def model(st, method, dtype):
+    out = R.model_outputs(st, method, inputs(st, dtype), np.float64)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def probe(st):
+    return R.integer_probe(st, SEED)
+
+
+def mod():
+    from mms_answer_selection_amd import conv_stage_train
+    return conv_stage_train
+
+
+class GarbageWorkspace(GuardedWorkspace):
+    """GuardedWorkspace with another filling than NaN words."""
+
+    def __init__(self, nbytes, fill):
+        super().__init__(nbytes)
+        self.buf[V.GUARD:V.GUARD + nbytes // 4].fill_(fill)
+
+
+def run(st, method, inp, dtype=np.float32, route="auto", shift=0, ws_fill=None, outputs=(True,) * 5, memory=R.BN_MEMORY,
+        backward=True):
+    """Forward, then backward on top of the initial parameter diffs.  Every output starts as NaN (scale_diff and
+    shift_diff as 123, weight_diff and bias_diff as the inputs' diffs) between guard zones, `shift` elements off a
+    16-byte boundary; ws_fill: a workspace of exactly the queried size filled with that value, guarded.
+    -> every output on the host under R.OUTPUTS' names; a backward output not asked for is absent, its prefill intact."""
+    m, s, sfx = mod(), st.conv, "" if dtype == np.float32 else "_f64"
+    fwd, bwd = getattr(m, "conv_stage_train_forward" + sfx), getattr(m, "conv_stage_train_backward" + sfx)
+    query = getattr(m, "conv_stage_train_workspace_bytes" + sfx)
+    kw = dict(stride=s.stride, pad=s.pad, group=s.group)
+    dev = {k: (None if inp[k] is None else V.placed(inp[k], dtype, shift)) for k in FORWARD_INPUTS + ("top_diff",)}
+    K, pooled, nan = s.K, R.pooled_shape(st), float("nan")
+    OH, OW = R.CR.output_dims(s)
+    g = dict(y=V.Guarded((s.N, K, OH, OW), dtype, nan, shift), top=V.Guarded(pooled, dtype, nan, shift),
+             save_pool=V.Guarded(pooled, dtype, nan, shift), save_mean=V.Guarded((K,), dtype, nan, shift),
+             save_std=V.Guarded((K,), dtype, nan, shift),
+             running_mean=V.Guarded((K,), dtype, np.asarray(inp["running_mean"]), shift),
+             running_var=V.Guarded((K,), dtype, np.asarray(inp["running_var"]), shift))
+
+    def workspace(r):
+        return None if ws_fill is None else GarbageWorkspace(query(cshape(st), st.pool, method, route=r), ws_fill)
+
+    ws = workspace(route)
+    fwd(dev["x"], dev["weight"], dev["bias"], st.pool, method, dev["scale"], dev["shift"], g["running_mean"].t,
+        g["running_var"].t, g["y"].t, g["top"].t, g["save_pool"].t, g["save_mean"].t, g["save_std"].t, bn_memory=memory,
+        ws=ws, route=route, **kw)
+    torch.cuda.synchronize()
+    if ws:
+        ws.check()
+    out = {k: v.host(k) for k, v in g.items()}
+    if backward:
+        b = dict(bottom_diff=V.Guarded(inp["x"].shape, dtype, nan, shift),
+                 weight_diff=V.Guarded(inp["weight"].shape, dtype, np.asarray(inp["weight_diff0"]), shift),
+                 scale_diff=V.Guarded((K,), dtype, 123.0, shift), shift_diff=V.Guarded((K,), dtype, 123.0, shift))
+        if inp["bias_diff0"] is not None:
+            b["bias_diff"] = V.Guarded((K,), dtype, np.asarray(inp["bias_diff0"]), shift)
+        given = {k: (b[k].t if k in b and want else None) for k, want in zip(BACKWARD, outputs)}
+        ws = workspace("auto")
+        bwd(dev["x"], dev["weight"], st.pool, method, g["y"].t, g["top"].t, dev["top_diff"], g["save_pool"].t,
+            dev["scale"], dev["shift"], g["save_mean"].t, g["save_std"].t, ws=ws, **given, **kw)
+        torch.cuda.synchronize()
+        if ws:
+            ws.check()
+        for k, v in b.items():
+            h = v.host(k)
+            if given[k] is not None:
+                out[k] = h
+            elif k == "bottom_diff":
+                assert np.isnan(h).all(), k + " was not asked for"
+            elif k in ("scale_diff", "shift_diff"):
+                assert (h == 123.0).all(), k + " was not asked for"
+            else:
+                assert_words_equal(h, np.array(inp[k + "0"], dtype=dtype), k + " was not asked for")
+    for k in FORWARD_INPUTS + ("top_diff",):
+        if inp[k] is not None:
+            assert_words_equal(V.host(dev[k]), np.array(inp[k], dtype=dtype), k + " is an input")
+    return out
+
+
+def routes_of(st, dtype=np.float32):
+    if dtype != np.float32:
+        return ("auto",)
+    return ("auto", "sequence", "fused") if st in R.FUSED_STAGES else ("auto", "sequence")
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", R.PARITY_STAGES, ids=IDS(R.PARITY_STAGES))
+def test_parity(st, method, hiplib):
+    """The main call, the forced sequence and the forced fused launches in float, and the double call: every output
+    of both passes against the float64 model at the project's bars."""
+    from mms_answer_selection_amd import capi
+    if st in R.SEQUENCE_STAGES:
+        assert mod().conv_stage_train_route(cshape(st), st.pool, method) == mod().ROUTE_SEQUENCE
+        with pytest.raises(capi.MMSError):
+            run(st, method, inputs(st, np.float32), route="fused")
+    for dtype in (np.float32, np.float64):
+        for route in routes_of(st, dtype):
+            print(R.stage_id(st), method, dtype.__name__, route)
+            check_parity(run(st, method, inputs(st, dtype), dtype, route), model(st, method, dtype), dtype)
+
+
+@pytest.mark.parametrize("st", R.GPU_STAGES, ids=IDS(R.GPU_STAGES))
+def test_y_is_the_convolutions_own_words(st, hiplib):
+    from mms_answer_selection_amd import conv
+    s, inp = st.conv, inputs(st, np.float32) if st in R.PARITY_STAGES else R._draw(st, np.float32, SEED)
+    dev = {k: (None if inp[k] is None else V.placed(inp[k], np.float32)) for k in ("x", "weight", "bias")}
+    want = V.host(conv.conv_forward(dev["x"], dev["weight"], dev["bias"], stride=s.stride, pad=s.pad, group=s.group))
+    for method in R.METHODS:
+        for route in routes_of(st):
+            got = run(st, method, inp, route=route, backward=False)["y"]
+            assert_words_equal(got, want, "y, %s, %s route" % (method, route))
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", R.FUSED_STAGES, ids=IDS(R.FUSED_STAGES))
+def test_exact_probe_fused_equals_sequence(st, method, hiplib):
+    """Integer y, exact partial sums: the two routes give the same words in every output of both passes, and the
+    statistics are the float32 restatement from the int64 sums, bit for bit."""
+    inp = probe(st)
+    y, s0, s1 = R.probe_sums(st, inp)
+    fused = run(st, method, inp, route="fused", memory=R.PROBE_MEMORY)
+    seq = run(st, method, inp, route="sequence", memory=R.PROBE_MEMORY)
+    auto = run(st, method, inp, memory=R.PROBE_MEMORY)
+    for k, v in fused.items():
+        assert not np.isnan(v).any(), k
+    same_words(fused, seq, "exact probe, fused against sequence")
+    same_words(auto, seq, "exact probe, the main call against sequence")
+    assert_words_equal(fused["y"], y.astype(np.float32), "y against the int64 model")
+    for k, want in zip(("save_mean", "save_std", "running_mean", "running_var"), R.probe_statistics(st, inp, s0, s1)):
+        assert_words_equal(fused[k], want, k + " against the int64 sums")
+    if method == R.MAX:                       # ties: the scan's winner by the sign of scale, first element for scale == 0
+        w = R.BM.windows(y, *st.pool)
+        mean, std = fused["save_mean"], fused["save_std"]
+        for k, pick in ((R.ZERO_CHANNEL, w[:, R.ZERO_CHANNEL, ..., 0]),
+                        (R.NEGATIVE_CHANNEL, w[:, R.NEGATIVE_CHANNEL].min(axis=-1)),
+                        (R.POSITIVE_CHANNEL, w[:, R.POSITIVE_CHANNEL].max(axis=-1))):
+            want = (pick.astype(np.float32) + (-mean[k])) / std[k]
+            assert_words_equal(fused["save_pool"][:, k], want, "save_pool of channel %d" % k)
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", R.GPU_STAGES, ids=IDS(R.GPU_STAGES))
+def test_determinism_and_independence(st, method, hiplib):
+    """A second run, a workspace of exactly the queried size full of NaN words and one full of other garbage, every
+    array one element off a 16-byte boundary: the same words on every route."""
+    inp = inputs(st, np.float32) if st in R.PARITY_STAGES else R._draw(st, np.float32, SEED)
+    for dtype in (np.float32, np.float64):
+        for route in routes_of(st, dtype):
+            first = run(st, method, inp, dtype, route)
+            same_words(run(st, method, inp, dtype, route), first, "second run, " + route)
+            same_words(run(st, method, inp, dtype, route, shift=1, ws_fill=float("nan")), first, "NaN workspace, " + route)
+            same_words(run(st, method, inp, dtype, route, shift=1, ws_fill=-3.5e37), first, "garbage workspace, " + route)
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+def test_padding_contributes_nothing(method, hiplib):
+    """Shape B's 23 images against its first 20 (two full groups of ten) and its last 3 (one ragged group) run alone:
+    the exact probe's sums add up, so the statistics of the whole are those of the parts' sums."""
+    inp = probe(R.B)
+    _, s0, s1 = R.probe_sums(R.B, inp)
+    sums = []
+    for lo, hi in ((0, 20), (20, 23)):
+        part_st = R.ST(hi - lo, *R.B.conv[1:7], R.B.pool)
+        part = dict(inp, x=inp["x"][lo:hi], top_diff=inp["top_diff"][lo:hi])
+        out = run(part_st, method, part, route="fused", memory=R.PROBE_MEMORY, backward=False)
+        _, p0, p1 = R.probe_sums(R.B, inp, slice(lo, hi))
+        want = R.probe_statistics(part_st, part, p0, p1)
+        for k, w in zip(("save_mean", "save_std", "running_mean", "running_var"), want):
+            assert_words_equal(out[k], w, "%s of images %d..%d" % (k, lo, hi))
+        sums.append((p0, p1))
+    assert (sums[0][0] + sums[1][0] == s0).all() and (sums[0][1] + sums[1][1] == s1).all()
+    whole = run(R.B, method, inp, route="fused", memory=R.PROBE_MEMORY, backward=False)
+    for k, w in zip(("save_mean", "save_std", "running_mean", "running_var"), R.probe_statistics(R.B, inp, s0, s1)):
+        assert_words_equal(whole[k], w, k + " of all 23 images")
+    # shape A's band tail (F: bands of 12 and 8 rows) is in the exact probes by construction
+
+
+@pytest.mark.parametrize("dtype", V.DTYPES, ids=V.IDS)
+@pytest.mark.parametrize("method", R.METHODS)
+def test_optional_backward_outputs(method, dtype, hiplib):
+    """Each subset of NULL outputs leaves the others' words unchanged and its own prefill intact (run checks it);
+    weight_diff and bias_diff are accumulated into, the other three overwritten; with no output the call is refused."""
+    from mms_answer_selection_amd import capi
+    st = R.C
+    inp = inputs(st, dtype)
+    full = run(st, method, inp, dtype)
+    want = model(st, method, dtype)
+    bar = BAR[dtype]
+    # Accumulated on top of what was there: the prefill and weight_diff's batch term are both far above the bar, so the
+    # model is met only by adding.  (bias_diff's batch term is the sum of dy over a channel, which BN's backward makes
+    # zero: there the model is met only by KEEPING the prefill.)
+    assert np.abs(want["weight_diff"] - np.asarray(inp["weight_diff0"], np.float64)).max() > 100 * bar
+    for k0 in ("weight_diff0", "bias_diff0"):
+        assert np.abs(np.asarray(inp[k0])).max() > 100 * bar
+    check_parity(full, want, dtype)
+    for mask in range(1, 31):
+        outputs = tuple(bool(mask >> b & 1) for b in range(5))
+        part = run(st, method, inp, dtype, outputs=outputs)
+        assert len(part) == len(full) - outputs.count(False)
+        for k, v in part.items():
+            assert_words_equal(v, full[k], "%s with outputs %s" % (k, outputs))
+    with pytest.raises(capi.MMSError):
+        run(st, method, inp, dtype, outputs=(False,) * 5)
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", [R.A, R.D], ids=IDS([R.A, R.D]))
+def test_sequence_route_is_the_public_calls(st, method, hiplib):
+    """The forced sequence forward and the backward against mms_conv_forward_f32, the float BN -> pooling -> TanH forward
+    and backward of the method and mms_conv_backward_f32 issued here, word for word."""
+    from mms_answer_selection_amd import bn_maxpool, capi, conv
+    s, inp = st.conv, inputs(st, np.float32)
+    got = run(st, method, inp, route="sequence")
+    kw = dict(stride=s.stride, pad=s.pad, group=s.group)
+    dev = {k: (None if inp[k] is None else V.placed(inp[k], np.float32)) for k in inp}
+    y = conv.conv_forward(dev["x"], dev["weight"], dev["bias"], **kw)
+    K, pooled = s.K, R.pooled_shape(st)
+    top, sp = (torch.full(pooled, float("nan"), device="cuda") for _ in range(2))
+    sm, ss = torch.empty(K, device="cuda"), torch.empty(K, device="cuda")
+    rm, rv = dev["running_mean"].clone(), dev["running_var"].clone()
+    dy, dsc, dsh = torch.empty_like(y), torch.empty(K, device="cuda"), torch.empty(K, device="cuda")
+    if method == R.AVE:
+        capi.bn_pool_tanh_forward(y, st.pool, dev["scale"], dev["shift"], rm, rv, top, sp, sm, ss, phase=0,
+                                  bn_memory=R.BN_MEMORY)
+        capi.bn_pool_tanh_backward(y, st.pool, top, dev["top_diff"], sp, dev["scale"], sm, ss, bottom_diff=dy,
+                                   scale_diff=dsc, shift_diff=dsh)
+    else:
+        bn_maxpool.bn_maxpool_tanh_forward(y, st.pool, dev["scale"], dev["shift"], rm, rv, top, sp, sm, ss, phase=0,
+                                           bn_memory=R.BN_MEMORY)
+        bn_maxpool.bn_maxpool_tanh_backward(y, st.pool, top, dev["top_diff"], sp, dev["scale"], dev["shift"], sm, ss,
+                                            bottom_diff=dy, scale_diff=dsc, shift_diff=dsh)
+    dx, dw, db = torch.empty_like(dev["x"]), dev["weight_diff0"].clone(), dev["bias_diff0"].clone()
+    conv.conv_backward(dev["x"], dev["weight"], dy, dx, dw, db, **kw)
+    torch.cuda.synchronize()
+    want = dict(y=y, top=top, save_pool=sp, save_mean=sm, save_std=ss, running_mean=rm, running_var=rv, bottom_diff=dx,
+                weight_diff=dw, bias_diff=db, scale_diff=dsc, shift_diff=dsh)
+    same_words(got, {k: V.host(v) for k, v in want.items()}, "the sequence route against the public calls")
+
+
+@pytest.mark.parametrize("dtype", V.DTYPES, ids=V.IDS)
+def test_empty_batch_writes_nothing(dtype, hiplib):
+    m, t = mod(), V.TORCH[dtype]
+    sfx = "" if dtype == np.float32 else "_f64"
+    x = torch.empty(0, 4, 12, 12, dtype=t, device="cuda")
+    w, k = V.Guarded((6, 4, 3, 3), dtype, 1.0), [V.Guarded((6,), dtype, 1.5) for _ in range(4)]
+    for method in R.METHODS:
+        for route in ("auto", "sequence") + (("fused",) if dtype == np.float32 else ()):
+            saved = getattr(m, "conv_stage_train_forward" + sfx)(x, w.t, None, (2, 5), method, *(g.t for g in k),
+                                                                 route=route)
+            assert tuple(saved.y.shape) == (0, 6, 10, 10) and tuple(saved.top.shape) == (0, 6, 5, 2)
+    torch.cuda.synchronize()
+    assert (w.host("weight") == 1.0).all()
+    for g in k:
+        assert (g.host("a BN array") == 1.5).all()
