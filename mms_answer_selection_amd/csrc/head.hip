@@ -40,18 +40,13 @@
 //
 // z1, d, z2 and dz1 never go to memory on the fast route.  Nothing is read 16 bytes at a time, so alignment cannot
 // change an order; every workspace word that is read has been written by this call.
-#include <float.h>
-#include <limits.h>
-
+#include "head_tile.h"
 #include "mms_head.h"
 #include "mms_internal.h"
 
 namespace mms {
 namespace {
 
-typedef float head_v4f __attribute__((ext_vector_type(4)));
-
-constexpr int kHeadThreads = 256;
 constexpr int kHeadTileSamples = 64;       // samples of a tile: 16 per wave
 constexpr int kHeadSingleSamples = 256;    // up to here one workgroup walks every tile: one launch per pass
 constexpr int kHeadMaxSlabs = 256;         // one workgroup per CU
@@ -59,11 +54,11 @@ constexpr int kHeadMaxFeatures = 128;      // fast route: F0 + F1, eight column 
 constexpr int kHeadMaxHidden = 64;         // fast route: H, four tiles of 16
 constexpr int kHeadMaxClasses = 16;        // fast route: C; C H <= 4 elements of w2_diff per thread
 constexpr int kHeadHeaderBytes = 3088;     // count[256], loss[256] (8 bytes each), coef (16 bytes)
-constexpr int kHeadMaxLdsBytes = 131072;   // the fast kernels' dynamic LDS, at most (the CU has 160 KB)
-
-struct HeadDims {
-  int N, F0, F1, F, H, C, train, norm, has_ign, ign;
-};
+// The tile and the three limits are csrc/head_tile.h's, which the fast plan and the forward's steps are written
+// against; they stay named here, where the backward kernel and the tests' model of the route read them.
+static_assert(kHeadTileSamples == kHeadFastSamples && kHeadMaxFeatures == kHeadFastFeatures &&
+                  kHeadMaxHidden == kHeadFastHidden && kHeadMaxClasses == kHeadFastClasses,
+              "csrc/head_tile.h states the same tile and limits");
 
 template <typename T>
 struct HeadArgs {
@@ -79,23 +74,6 @@ struct HeadArgs {
   T* part;           // [slabs][P]
   int slabs, tps;    // head_slabs
 };
-
-// the shape's refusal, else MMS_OK and *d
-int head_check(const mms_head_shape* s, HeadDims* d) {
-  if (!s) return MMS_ERR_INVALID_ARG;
-  if (s->N < 0 || s->F0 <= 0 || s->F1 < 0 || s->H <= 0 || s->C <= 0) return MMS_ERR_INVALID_ARG;
-  if (!(s->dropout_ratio > 0.f && s->dropout_ratio < 1.f)) return MMS_ERR_INVALID_ARG;
-  if (s->phase != MMS_HEAD_TRAIN && s->phase != MMS_HEAD_TEST) return MMS_ERR_INVALID_ARG;
-  if (s->normalization < MMS_HEAD_NORM_FULL || s->normalization > MMS_HEAD_NORM_NONE) return MMS_ERR_INVALID_ARG;
-  const long long F = (long long)s->F0 + s->F1, N = s->N;
-  if (F > INT_MAX || N * s->F0 > INT_MAX || N * s->F1 > INT_MAX || N * s->H > INT_MAX || N * s->C > INT_MAX ||
-      F * s->H > INT_MAX || (long long)s->C * s->H > INT_MAX)
-    return MMS_ERR_INVALID_ARG;
-  if (F * s->H + s->H + (long long)s->C * s->H + s->C > INT_MAX) return MMS_ERR_INVALID_ARG;
-  *d = {s->N, s->F0, s->F1, (int)F, s->H, s->C, s->phase == MMS_HEAD_TRAIN, s->normalization, s->has_ignore_label != 0,
-        s->ignore_label};
-  return MMS_OK;
-}
 
 inline int head_params(const HeadDims& d) { return d.H * d.F + d.H + d.C * d.H + d.C; }
 
@@ -120,20 +98,7 @@ __device__ inline T head_feat(const HeadArgs<T>& a, int n, int f) {
 // the class of sample n, or -1: ignored (the ignore label, or outside [0, C))
 template <typename T>
 __device__ inline int head_label(const HeadArgs<T>& a, int n) {
-  const int lv = static_cast<int>(a.label[n]);
-  if ((a.d.has_ign && lv == a.d.ign) || lv < 0 || lv >= a.d.C) return -1;
-  return lv;
-}
-
-template <typename T>
-__device__ inline T head_normalizer(const HeadDims& d, int count) {
-  T v;
-  switch (d.norm) {
-    case MMS_HEAD_NORM_VALID: v = T(count); break;
-    case MMS_HEAD_NORM_NONE: v = T(1); break;
-    default: v = T(d.N); break;       // FULL: outer_num * inner_num; BATCH_SIZE: outer_num
-  }
-  return v > T(1) ? v : T(1);
+  return head_class(a.d, a.label[n]);
 }
 
 template <typename T>
@@ -153,11 +118,6 @@ __device__ inline void head_hidden(const HeadArgs<T>& a, int n, int j, T dd, T* 
     dh = (dd * m) * a.scale;
   }
   *dz1 = dh * (T(1) - hv * hv);
-}
-
-template <typename T>
-__device__ inline T head_loss_term(T p) {
-  return -log(p > T(FLT_MIN) ? p : T(FLT_MIN));
 }
 
 // ---- generic route --------------------------------------------------------------------------------------------------
@@ -335,36 +295,6 @@ __global__ __launch_bounds__(kHeadThreads) void head_param_finish_kernel(HeadArg
 }
 
 // ---- fast route -----------------------------------------------------------------------------------------------------
-struct HeadFastPlan {
-  int HT, FT;        // tiles of 16 hidden units / features
-  int Fp;            // forward: F rounded up to the K step of 4
-  int Fa, Ha;        // strides of [row][k] operands: 2 mod 4
-  int Fk, Hk;        // strides of [k][column] operands: 16 mod 32
-  size_t fwd_lds, bwd_lds;
-  bool ok;
-};
-
-inline int head_stride16(int tiles) { return 16 * tiles + ((tiles & 1) ? 0 : 16); }
-
-HeadFastPlan head_fast_plan(const HeadDims& d) {
-  HeadFastPlan p = {};
-  if (d.F > kHeadMaxFeatures || d.H > kHeadMaxHidden || d.C > kHeadMaxClasses) return p;
-  p.HT = (d.H + 15) / 16;
-  p.FT = (d.F + 15) / 16;
-  p.Fp = (d.F + 3) & ~3;
-  p.Fa = p.Fp + 2;
-  p.Ha = 16 * p.HT + 2;
-  p.Fk = head_stride16(p.FT);
-  p.Hk = head_stride16(p.HT);
-  const int T = kHeadTileSamples;
-  p.fwd_lds = sizeof(float) * ((size_t)16 * p.HT * p.Fa + T * p.Fa + T * p.Ha + d.C * (d.H + 1) + T * (d.C + 1) +
-                               16 * p.HT + d.C + 2 * T);
-  p.bwd_lds = sizeof(float) * ((size_t)16 * p.HT * p.Fk + T * p.Fk + T * p.Ha + T * p.Hk + d.C * (d.H + 1) +
-                               T * (d.C + 1) + 4);
-  p.ok = p.fwd_lds <= (size_t)kHeadMaxLdsBytes && p.bwd_lds <= (size_t)kHeadMaxLdsBytes;
-  return p;
-}
-
 __device__ inline float head_wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
@@ -380,28 +310,10 @@ __global__ __launch_bounds__(kHeadThreads) void head_fast_forward_kernel(HeadArg
   constexpr int TS = kHeadTileSamples;
   extern __shared__ float head_lds[];
   const HeadDims& d = a.d;
-  const int Hw = 16 * p.HT, W2 = d.H + 1, Z2 = d.C + 1;
-  float* w1s = head_lds;                    // [Hw][Fa]: w1, rows past H and columns F .. Fp zero
-  float* feats = w1s + Hw * p.Fa;           // [TS][Fa]
-  float* dbuf = feats + TS * p.Fa;          // [TS][Ha]: d
-  float* w2s = dbuf + TS * p.Ha;            // [C][H + 1]
-  float* z2s = w2s + d.C * W2;              // [TS][C + 1]
-  float* b1s = z2s + TS * Z2;               // [Hw]
-  float* b2s = b1s + Hw;                    // [C]
-  float* terms = b2s + d.C;                 // [TS]
-  int* valid = reinterpret_cast<int*>(terms + TS);
+  const HeadFwdLds L = head_fwd_carve(head_lds, d, p, TS);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, grp = lane >> 4;
 
-  for (int e = tid; e < Hw * p.Fp; e += kHeadThreads) {
-    const int j = e / p.Fp, f = e - j * p.Fp;
-    w1s[j * p.Fa + f] = (j < d.H && f < d.F) ? a.w1[(size_t)j * d.F + f] : 0.f;
-  }
-  for (int e = tid; e < d.C * d.H; e += kHeadThreads) {
-    const int c = e / d.H, j = e - c * d.H;
-    w2s[c * W2 + j] = a.w2[e];
-  }
-  for (int j = tid; j < Hw; j += kHeadThreads) b1s[j] = (a.b1 && j < d.H) ? a.b1[j] : 0.f;
-  for (int c = tid; c < d.C; c += kHeadThreads) b2s[c] = a.b2 ? a.b2[c] : 0.f;
+  head_stage_weights(L, d, p, a.w1, a.b1, a.w2, a.b2);
 
   float lossacc = 0.f;
   int cntacc = 0;
@@ -411,73 +323,32 @@ __global__ __launch_bounds__(kHeadThreads) void head_fast_forward_kernel(HeadArg
     __syncthreads();                        // the previous tile has been consumed (first tile: nothing to wait for)
     for (int e = tid; e < TS * p.Fp; e += kHeadThreads) {
       const int r = e / p.Fp, f = e - r * p.Fp, n = n0 + r;
-      feats[r * p.Fa + f] = (n < n1 && f < d.F) ? head_feat(a, n, f) : 0.f;
+      L.feats[r * p.Fa + f] = (n < n1 && f < d.F) ? head_feat(a, n, f) : 0.f;
     }
     __syncthreads();
-    // fc1: rows = this wave's 16 samples, columns = 16 hidden units, K = the features in steps of 4
-    for (int ht = 0; ht < p.HT; ++ht) {
-      head_v4f acc = {0.f, 0.f, 0.f, 0.f};
-      const float* ap = feats + (16 * wave + l16) * p.Fa + grp;
-      const float* bp = w1s + (16 * ht + l16) * p.Fa + grp;
-      for (int s = 0; s < p.Fp; s += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[s], bp[s], acc, 0, 0, 0);
-      const int j = 16 * ht + l16;          // lane: hidden unit j, samples 16 wave + 4 grp + r
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * wave + 4 * grp + r, n = n0 + row;
-        float dv = 0.f;
-        if (n < n1 && j < d.H) {
-          const float hv = tanhf(a.b1 ? acc[r] + b1s[j] : acc[r]);
-          a.h[(size_t)n * d.H + j] = hv;
-          dv = d.train ? (hv * float(a.mask[(size_t)n * d.H + j])) * a.scale : hv;
-        }
-        dbuf[row * p.Ha + j] = dv;
-      }
-    }
+    // fc1: rows = this wave's 16 samples, columns = 16 hidden units; tanh and Dropout on the accumulators
+    for (int ht = 0; ht < p.HT; ++ht)
+      head_fc1_block(L, d, p, wave, ht, a.b1 != nullptr, n0, n1, a.h, [&](float hv, int n, int j) {
+        return d.train ? (hv * float(a.mask[(size_t)n * d.H + j])) * a.scale : hv;
+      });
     __syncthreads();
     // fc2: lane (sample l16 of the wave, classes grp, grp + 4, ...)
-    {
-      const int row = 16 * wave + l16;
-      const float* dr = dbuf + row * p.Ha;
-      for (int c = grp; c < d.C; c += 4) {
-        const float* wc = w2s + c * W2;
-        float z = 0.f;
-        for (int j = 0; j < d.H; ++j) z += dr[j] * wc[j];
-        z2s[row * Z2 + c] = a.b2 ? z + b2s[c] : z;
-      }
-    }
+    for (int c = grp; c < d.C; c += 4) head_fc2_one(L, d, p, 16 * wave + l16, c, a.b2 != nullptr);
     __syncthreads();
     if (grp == 0) {                          // softmax and the loss term: one lane per sample
       const int row = 16 * wave + l16, n = n0 + row;
       float term = 0.f;
       int ok = 0;
-      if (n < n1) {
-        float* zr = z2s + row * Z2;
-        float mx = zr[0];
-        for (int c = 1; c < d.C; ++c) mx = zr[c] > mx ? zr[c] : mx;
-        float sum = 0.f;
-        for (int c = 0; c < d.C; ++c) {
-          const float e = expf(zr[c] - mx);
-          zr[c] = e;
-          sum += e;
-        }
-        const int lv = a.label ? head_label(a, n) : -1;
-        for (int c = 0; c < d.C; ++c) {
-          const float pv = zr[c] / sum;
-          a.prob[(size_t)n * d.C + c] = pv;
-          if (c == lv) {
-            term = head_loss_term(pv);
-            ok = 1;
-          }
-        }
-      }
-      terms[row] = term;
-      valid[row] = ok;
+      if (n < n1)
+        term = head_softmax_row(L, d, row, a.prob + (size_t)n * d.C, a.label ? head_label(a, n) : -1, &ok);
+      L.terms[row] = term;
+      L.valid[row] = ok;
     }
     if (a.loss) {                            // uniform
       __syncthreads();
       if (wave == 0) {
-        lossacc += head_wave_sum(terms[lane]);
-        cntacc += head_wave_sum(valid[lane]);
+        lossacc += head_wave_sum(L.terms[lane]);
+        cntacc += head_wave_sum(L.valid[lane]);
       }
     }
   }
