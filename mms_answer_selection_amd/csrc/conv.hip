@@ -191,10 +191,10 @@ struct ConvStoreEpilogue {
       for (int r = 0; r < 4; ++r) {
         const int m = 16 * mt + 4 * grp + r;
         if (m >= a.Cout) continue;
-        const float b = a.bias ? a.bias[m] : 0.f;
+        const float b = conv_tile_bias(a, m);
 #pragma unroll
         for (int nt = 0; nt < kConvNT; ++nt)
-          if (pvalid[nt]) a.out[outoff[nt] + (size_t)m * PI] = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];
+          if (pvalid[nt]) a.out[outoff[nt] + (size_t)m * PI] = conv_tile_word(a, acc[mt][nt][r], b);
       }
   }
 };

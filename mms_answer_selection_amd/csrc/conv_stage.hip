@@ -21,19 +21,15 @@
 //   fused     float, where the convolution's forward is on its fast route (csrc/conv_tile.h) with a band whose height
 //             is a multiple of ph: conv_prod_plan with rq = ph.  A workgroup's pixels -- whole rows of one image, or
 //             several whole small images -- are then whole windows.  The product is conv_tile_product, the one
-//             csrc/conv.hip runs; the epilogue puts accumulator + bias in LDS as tile[k][pixel], over the band and the
-//             weights the last chunk has finished with (K <= 64 channels x 256 pixels is the 64 KB those had at most),
-//             and after a barrier thread e takes (image, channel, window) e, e + 256, ...: it adds its window from the
-//             tile in (h, w) order as one chain from 0 and finishes with bn_pool_test_finish, csrc/bn_pool.hip's own
-//             (MAX: scans it with bp_keep and finishes with bn_maxpool_test_finish, csrc/bn_pool.hip's own too).
+//             csrc/conv.hip runs; the epilogue's steps are listed in csrc/conv_pool_tile.h, which has the tile.  Thread e
+//             takes (image, channel, window) e, e + 256, ... and finishes its window's sum with bn_pool_test_finish
+//             (MAX: its extremum with bn_maxpool_test_finish), both csrc/bn_pool.hip's own.
 //             Only pooled-size arrays are stored; y is never in device memory.
 //
 // A shape the fused route reaches but does not pay at goes to the sequence: stage_route<MAX> has each family's rule.
 // An element of y is the same chain of MFMA steps on both routes wherever both cut the input channels into the same
 // chunks (CC of conv_prod_plan: the band's height enters it), and then the two routes give the same words.
-#include "bn_common.h"
-#include "conv_tile.h"
-#include "mms_bn_maxpool.h"
+#include "conv_pool_tile.h"
 #include "mms_conv_maxpool_stage.h"
 #include "mms_conv_stage.h"
 #include "mms_internal.h"
@@ -41,28 +37,17 @@
 namespace mms {
 namespace {
 
-static_assert(kConvMaxChannels * kConvTilePixels <= kConvLdsFloats, "the accumulator tile of any fast plan fits the LDS");
 // One set of route values for both families: the code below names MMS_CONV_STAGE_ROUTE_* only.
 static_assert(MMS_CONV_MAXPOOL_STAGE_ROUTE_NONE == MMS_CONV_STAGE_ROUTE_NONE &&
                   MMS_CONV_MAXPOOL_STAGE_ROUTE_SEQUENCE == MMS_CONV_STAGE_ROUTE_SEQUENCE &&
                   MMS_CONV_MAXPOOL_STAGE_ROUTE_FUSED == MMS_CONV_STAGE_ROUTE_FUSED,
               "the MAX stage's routes carry the AVE stage's values");
 
-struct StageDims {
-  ConvDims d;
-  int ph, pw, POH, POW;
-};
-
 // the refusal of the shape and the window, else MMS_OK and *g
+template <bool MAX>
 int stage_check(const mms_conv_shape* shape, int ph, int pw, StageDims* g) {
-  const int rc = conv_check(shape, &g->d);
-  if (rc != MMS_OK) return rc;
-  if (ph < 1 || pw < 1 || g->d.OH % ph || g->d.OW % pw) return MMS_ERR_INVALID_ARG;
-  g->ph = ph;
-  g->pw = pw;
-  g->POH = g->d.OH / ph;
-  g->POW = g->d.OW / pw;
-  return MMS_OK;
+  g->max = MAX;
+  return stage_window_check(shape, ph, pw, g);
 }
 
 struct StageArgs {
@@ -82,18 +67,10 @@ StageArgs stage_plan(const StageDims& g) {
   if (!a.p.ok) return a;
   a.ph = g.ph; a.pw = g.pw; a.POH = g.POH; a.POW = g.POW;
   const int P = a.p.G * a.p.R * a.p.OWt;
-  // Lane groups of an accumulator are four channels apart: a row length of 4 or 12 mod 16 puts their 16 pixels in
-  // separate banks.  Taken where it still fits.
-  a.PS = P;
-  while (a.PS % 16 != 4 && a.PS % 16 != 12) ++a.PS;
-  if (a.p.Cout * a.PS > kConvLdsFloats) a.PS = P;
-  const size_t tile = (size_t)a.p.Cout * a.PS * sizeof(float);
-  a.lds_bytes = tile > a.p.lds_bytes ? tile : a.p.lds_bytes;
+  a.PS = stage_tile_row(a.p.Cout, P);
+  a.lds_bytes = stage_lds_bytes(a.p.Cout, P, a.p.lds_bytes);
   return a;
 }
-
-// The launch's workgroups.
-long long stage_groups(const StageArgs& a) { return (long long)((a.p.N + a.p.G - 1) / a.p.G) * a.p.bands; }
 
 // whether the window made the band lower than the convolution's own
 bool stage_band_shrunk(const StageDims& g, const StageArgs& a) {
@@ -120,8 +97,9 @@ template <>
 int stage_route<false>(const StageDims& g) {
   const StageArgs a = stage_plan(g);
   if (!a.p.ok) return MMS_CONV_STAGE_ROUTE_SEQUENCE;
-  const long long groups = stage_groups(a);
-  if (a.p.G > 1) return groups >= kStageMinImageGroups ? MMS_CONV_STAGE_ROUTE_FUSED : MMS_CONV_STAGE_ROUTE_SEQUENCE;
+  const long long groups = stage_groups(a.p);
+  if (stage_plan_kind(a.p) == kStageImages)
+    return groups >= kStageMinImageGroups ? MMS_CONV_STAGE_ROUTE_FUSED : MMS_CONV_STAGE_ROUTE_SEQUENCE;
   if (stage_band_shrunk(g, a) && groups > kStageMaxShrunkBandGroups) return MMS_CONV_STAGE_ROUTE_SEQUENCE;
   return MMS_CONV_STAGE_ROUTE_FUSED;
 }
@@ -142,18 +120,14 @@ int stage_route<false>(const StageDims& g) {
 //   slow pass of each route (1.34 x).  A band the window made lower pays here (AVE's does not beyond 2048 workgroups).
 //   One whole image (v5's second stage, 16 x 16).  Slower at 6 workgroups, level at 25, faster at 50 (1.01 x) and at
 //   all of 100 to 2000 (1.03 to 1.06 x): 50 .. 2000.
-struct MaxStageSpan {
-  long long least, most;       // workgroups
-};
-constexpr MaxStageSpan kMaxStageImages = {60, 300}, kMaxStageRowBands = {54, 14000}, kMaxStageOneImage = {50, 2000};
+constexpr StageSpan kMaxStageSpans[3] = {{60, 300}, {54, 14000}, {50, 2000}};      // by stage_plan_kind
 
 template <>
 int stage_route<true>(const StageDims& g) {
   const StageArgs a = stage_plan(g);
   if (!a.p.ok) return MMS_CONV_STAGE_ROUTE_SEQUENCE;
-  const long long groups = stage_groups(a);
-  const MaxStageSpan& k = a.p.G > 1 ? kMaxStageImages : a.p.bands > 1 ? kMaxStageRowBands : kMaxStageOneImage;
-  return groups >= k.least && groups <= k.most ? MMS_CONV_STAGE_ROUTE_FUSED : MMS_CONV_STAGE_ROUTE_SEQUENCE;
+  return kMaxStageSpans[stage_plan_kind(a.p)].holds(stage_groups(a.p)) ? MMS_CONV_STAGE_ROUTE_FUSED
+                                                                       : MMS_CONV_STAGE_ROUTE_SEQUENCE;
 }
 
 // PH, PW > 0: the window's size at compile time (== s.ph, s.pw); 0: any window.  MAX: the window's extremum where AVE
@@ -162,45 +136,17 @@ template <bool MAX, int PH, int PW>
 struct StagePoolEpilogue {
   const StageArgs& s;
   float* tile;
-  int kc;                // the channel whose values follow: that of the thread's first (image, channel, window)
-  float nmean, std, sc, sh;
-  int dir;               // MAX: bp_dir(sc)
-  __device__ __forceinline__ void channel(int k) {
-    kc = k;
-    nmean = -s.mean[k];
-    std = bn_sqrt(s.var[k] + 1e-9f);
-    sc = s.scale[k];
-    sh = s.shift[k];
-    if constexpr (MAX) dir = bp_dir(sc);
-  }
-  // one element of the window, in (h, w) order
-  __device__ __forceinline__ void keep(bool first, float v, float* m) const {
-    if constexpr (MAX) bp_keep(first, v, dir, m);
-    else *m += v;
-  }
+  StageChannel<MAX> ch;  // of the channel whose values follow: that of the thread's first (image, channel, window)
   // Before the product: the loads are long back when the epilogue, on the workgroup's critical path, needs them.
   __device__ __forceinline__ void pixel(const ConvProdArgs& a, const ConvTile& t, int nt, int, int, int) {
-    if (nt == 0) channel((int)threadIdx.x / (t.rb / s.ph * s.POW) % a.Cout);
+    if (nt == 0) ch.load(s, (int)threadIdx.x / (t.rb / s.ph * s.POW) % a.Cout);
   }
 
   template <int MT>
   __device__ __forceinline__ void finish(const ConvProdArgs& a, const ConvTile& t, const conv_v4f (&acc)[MT][kConvNT],
                                          const bool (&pvalid)[kConvNT]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, grp = lane >> 4;
-    const int PS = s.PS;
-    __syncthreads();                                    // every wave has finished with the band and the weights
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = 16 * mt + 4 * grp + r;
-        if (m >= a.Cout) continue;
-        const float b = a.bias ? a.bias[m] : 0.f;
-#pragma unroll
-        for (int nt = 0; nt < kConvNT; ++nt)
-          if (pvalid[nt]) tile[m * PS + (wave + 4 * nt) * 16 + l16] = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];
-      }
-    __syncthreads();
+    const int tid = threadIdx.x, PS = s.PS;
+    stage_tile_store(a, tile, PS, acc, pvalid);
     const int ph = PH > 0 ? PH : s.ph, pw = PW > 0 ? PW : s.pw;
     const int wrows = t.rb / ph, wper = wrows * s.POW;  // windows of the band: per image
     const int PP = s.POH * s.POW, q0 = t.oy0 / ph * s.POW;
@@ -211,8 +157,12 @@ struct StagePoolEpilogue {
       const int k = u % a.Cout, img = u / a.Cout;
       const int wr = q / s.POW, wc = q - wr * s.POW;
       const float* src = tile + k * PS + img * t.per + wr * ph * a.OWt + wc * pw;
-      if (MAX && k != kc) channel(k);                   // the scan needs the channel's direction
+      if (MAX && k != ch.kc) ch.load(s, k);                // the scan needs the channel's direction
       float sum = 0.f;                                  // AVE: the window's sum; MAX: its extremum
+      const auto keep = [&](bool first, float v) {      // one element of the window, in (h, w) order
+        if constexpr (MAX) bp_keep(first, v, ch.dir, &sum);
+        else sum += v;
+      };
       if constexpr (PH > 0) {
         float v[PH][PW];
 #pragma unroll
@@ -222,16 +172,16 @@ struct StagePoolEpilogue {
 #pragma unroll
         for (int i = 0; i < PH; ++i)
 #pragma unroll
-          for (int j = 0; j < PW; ++j) keep(i == 0 && j == 0, v[i][j], &sum);
+          for (int j = 0; j < PW; ++j) keep(i == 0 && j == 0, v[i][j]);
       } else {
         for (int i = 0; i < ph; ++i)
-          for (int j = 0; j < pw; ++j) keep(i == 0 && j == 0, src[i * a.OWt + j], &sum);
+          for (int j = 0; j < pw; ++j) keep(i == 0 && j == 0, src[i * a.OWt + j]);
       }
       const size_t o = ((size_t)(t.n0 + img) * a.Cout + k) * PP + q0 + q;
-      if (!MAX && k != kc) channel(k);
+      if (!MAX && k != ch.kc) ch.load(s, k);
       float sp;
-      const float tv = MAX ? bn_maxpool_test_finish(sum, nmean, std, sc, sh, &sp)
-                           : bn_pool_test_finish(sum, ke, nmean, std, sc, sh, &sp);
+      const float tv = MAX ? bn_maxpool_test_finish(sum, ch.nmean, ch.std, ch.sc, ch.sh, &sp)
+                           : bn_pool_test_finish(sum, ke, ch.nmean, ch.std, ch.sc, ch.sh, &sp);
       if (s.save_pool) s.save_pool[o] = sp;
       s.top[o] = tv;
     }
@@ -245,23 +195,6 @@ __global__ __launch_bounds__(kConvThreads) void conv_stage_kernel(StageArgs s) {
   conv_tile_product<MT>(s.p, conv_lds, epi);
 }
 
-template <int K>
-using stage_int = std::integral_constant<int, K>;
-
-// f(PH, PW) as types.  AVE: network_v4's two windows at compile time, any other at run time.  MAX: 4 x 4 and 2 x 2 at
-// compile time, any other -- the nets' 5 x 5 and 6 x 6 included -- at run time.  Against a build with the run-time scan
-// only, process by process in turn, the fused launch with the 4 x 4 is 6 to 8 % faster at v3's first stage and with the
-// 2 x 2 6 to 7 % (N = 50) and 4 to 5 % (N = 1517) at v5's first and 0.8 to 1.4 % at v5's second, ranges apart in both
-// rounds (profiles/conv_maxpool_stage_bench.txt, second section).  A 5 x 5 and a 6 x 6 instantiation gained under 1 %
-// where the main call fuses, inside the spread, and are not kept.
-template <bool MAX, class F>
-void stage_dispatch(int ph, int pw, F&& f) {
-  if (ph == 4 && pw == 4) f(stage_int<4>{}, stage_int<4>{});
-  else if (!MAX && ph == 5 && pw == 5) f(stage_int<5>{}, stage_int<5>{});
-  else if (MAX && ph == 2 && pw == 2) f(stage_int<2>{}, stage_int<2>{});
-  else f(stage_int<0>{}, stage_int<0>{});
-}
-
 template <typename T>
 size_t stage_sequence_bytes(const StageDims& g) {
   const size_t map = (size_t)g.d.N * g.d.K * g.d.OH * g.d.OW, pooled = (size_t)g.d.N * g.d.K * g.POH * g.POW;
@@ -271,32 +204,9 @@ size_t stage_sequence_bytes(const StageDims& g) {
 template <typename T, bool MAX>
 size_t stage_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, bool sequence) {  // sequence: whatever the route
   StageDims g;
-  if (stage_check(shape, ph, pw, &g) != MMS_OK || g.d.N == 0) return 0;
+  if (stage_check<MAX>(shape, ph, pw, &g) != MMS_OK || g.d.N == 0) return 0;
   if (std::is_same<T, float>::value && !sequence && stage_route<MAX>(g) == MMS_CONV_STAGE_ROUTE_FUSED) return 0;
   return stage_sequence_bytes<T>(g);
-}
-
-inline int conv_public(const mms_conv_shape* s, const float* x, const float* w, const float* b, float* y, void* st) {
-  return mms_conv_forward_f32(s, x, w, b, y, nullptr, 0, st);
-}
-inline int conv_public(const mms_conv_shape* s, const double* x, const double* w, const double* b, double* y, void* st) {
-  return mms_conv_forward_f64(s, x, w, b, y, nullptr, 0, st);
-}
-// TEST phase reads running_mean / running_var and writes neither; it needs no workspace.
-template <bool MAX>
-inline int bn_pool_public(const StageDims& g, const float* y, const float* scale, const float* shift, const float* mean,
-                          const float* var, float* top, float* sp, float* sm, float* ss, void* st) {
-  const auto call = MAX ? mms_bn_maxpool_tanh_forward_f32 : mms_bn_pool_tanh_forward_f32;
-  return call(1, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, 0.f, y, scale, shift, const_cast<float*>(mean),
-              const_cast<float*>(var), top, sp, sm, ss, nullptr, 0, st);
-}
-template <bool MAX>
-inline int bn_pool_public(const StageDims& g, const double* y, const double* scale, const double* shift,
-                          const double* mean, const double* var, double* top, double* sp, double* sm, double* ss,
-                          void* st) {
-  const auto call = MAX ? mms_bn_maxpool_tanh_forward_f64 : mms_bn_pool_tanh_forward_f64;
-  return call(1, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, 0., y, scale, shift, const_cast<double*>(mean),
-              const_cast<double*>(var), top, sp, sm, ss, nullptr, 0, st);
 }
 
 // force: MMS_CONV_STAGE_ROUTE_NONE (stage_route<MAX> decides), _SEQUENCE or _FUSED (float; MMS_ERR_UNSUPPORTED where the
@@ -306,15 +216,13 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
                   const T* var, const T* scale, const T* shift, T* top, T* save_pool, void* workspace,
                   size_t workspace_bytes, int force, void* stream) {
   StageDims g;
-  const int rc = stage_check(shape, ph, pw, &g);
+  const int rc = stage_check<MAX>(shape, ph, pw, &g);
   if (rc != MMS_OK) return rc;
   if (g.d.N == 0) return MMS_OK;
   if (!x || !w || !top || !mean || !var || !scale || !shift) return MMS_ERR_INVALID_ARG;
   const void* const inputs[] = {x, w, bias, mean, var, scale, shift};
-  for (const void* in : inputs) {
-    if (in && (top == in || save_pool == in)) return MMS_ERR_INVALID_ARG;
-  }
-  if (top == save_pool) return MMS_ERR_INVALID_ARG;
+  const void* const outputs[] = {top, save_pool};
+  if (stage_outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (force == MMS_CONV_STAGE_ROUTE_FUSED && !stage_plan(g).p.ok) return MMS_ERR_UNSUPPORTED;
     if (force == MMS_CONV_STAGE_ROUTE_FUSED ||
@@ -324,7 +232,7 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
       a.mean = mean; a.var = var; a.scale = scale; a.shift = shift; a.top = top; a.save_pool = save_pool;
       const dim3 grid((unsigned)((a.p.N + a.p.G - 1) / a.p.G), (unsigned)a.p.bands);
       conv_with_mt(a.p.MT, [&](auto M) {
-        stage_dispatch<MAX>(ph, pw, [&](auto PH, auto PW) {
+        stage_pool_dispatch<MAX>(ph, pw, [&](auto PH, auto PW) {
           hipLaunchKernelGGL((conv_stage_kernel<decltype(M)::value, MAX, decltype(PH)::value, decltype(PW)::value>),
                              grid, dim3(kConvThreads), a.lds_bytes, as_stream(stream), a);
         });
@@ -339,9 +247,10 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
   T* save_std = save_mean + g.d.K;
   T* sp = save_pool ? save_pool : save_std + g.d.K;
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
-  const int rc1 = conv_public(shape, x, w, bias, y, stream);
+  const int rc1 = stage_conv_forward(shape, x, w, bias, y, stream);
   if (rc1 != MMS_OK) return rc1;
-  return bn_pool_public<MAX>(g, y, scale, shift, mean, var, top, sp, save_mean, save_std, stream);
+  return stage_bn_pool_forward(g, 1, T(0), y, scale, shift, const_cast<T*>(mean), const_cast<T*>(var), top, sp, save_mean,
+                               save_std, nullptr, 0, stream);
 }
 
 }  // namespace
@@ -353,7 +262,7 @@ extern "C" {
 
 int mms_conv_stage_route(const mms_conv_shape* shape, int ph, int pw) {
   StageDims g;
-  if (stage_check(shape, ph, pw, &g) != MMS_OK) return MMS_CONV_STAGE_ROUTE_NONE;
+  if (stage_check<false>(shape, ph, pw, &g) != MMS_OK) return MMS_CONV_STAGE_ROUTE_NONE;
   return stage_route<false>(g);
 }
 
@@ -401,7 +310,7 @@ int mms_conv_stage_forward_fused_f32(const mms_conv_shape* shape, int ph, int pw
 // include/mms_conv_maxpool_stage.h: the MAX form, the same arguments.
 int mms_conv_maxpool_stage_route(const mms_conv_shape* shape, int ph, int pw) {
   StageDims g;
-  if (stage_check(shape, ph, pw, &g) != MMS_OK) return MMS_CONV_STAGE_ROUTE_NONE;
+  if (stage_check<true>(shape, ph, pw, &g) != MMS_OK) return MMS_CONV_STAGE_ROUTE_NONE;
   return stage_route<true>(g);
 }
 

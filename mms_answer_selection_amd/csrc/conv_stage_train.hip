@@ -10,12 +10,11 @@
 //             Launch 1 (train_product_kernel) is csrc/conv_tile.h's product with a band whose height is a multiple of
 //             ph (conv_prod_plan with rq = ph, as csrc/conv_stage.hip) AND the chunk of input channels of the
 //             convolution's own plan (rq = 1), so an element of y is the convolution's own chain of MFMA steps.  The
-//             epilogue stores accumulator + bias to y and to LDS as tile[k][pixel], over the band and the weights the
-//             last chunk has finished with.  After a barrier the 256 / (16 MT) adjacent lanes that serve channel k
-//             walk the workgroup's windows of k: lane j takes windows j, j + T, ... in (image, window row, window
-//             column) order, adds (MAX: scans, bp_keep) each from the tile in (h, w) order, stores the window's mean
-//             (MAX: extremum) to save_pool, and adds the same values in the same order into one sum of y and one of
-//             y*y.  Only real pixels are windows: a band's tail and a ragged last image group add nothing.  The T
+//             epilogue's steps are listed in csrc/conv_pool_tile.h, which has the tile; each word of the tile is
+//             stored to y as well.  The 256 / (16 MT) adjacent lanes that serve channel k walk the workgroup's windows of k: lane j
+//             takes windows j, j + T, ... in (image, window row, window column) order, stores the window's mean
+//             (MAX: extremum) to save_pool, and adds the window's values in the same order into one sum of y and one
+//             of y*y.  Only real pixels are windows: a band's tail and a ragged last image group add nothing.  The T
 //             lanes' sums are combined by xor-shuffles 1, 2 (, 4, 8) apart -- registers and lanes, no LDS beside the
 //             full tile -- and lane 0 writes them to the workspace slot of (channel, workgroup).
 //             Launch 2 (train_finish_kernel) is pooled-size: grid (K, chunks); every workgroup adds its channel's
@@ -24,32 +23,19 @@
 //             and finishes its chunk of the channel's pooled elements in place with bn_pool_train_finish,
 //             csrc/bn_pool.hip's own.
 // train_route is the one place that decides; its thresholds are lines of profiles/conv_stage_train_bench.txt.
-#include "bn_common.h"
-#include "conv_tile.h"
+#include "conv_pool_tile.h"
 #include "mms_conv_stage_train.h"
 #include "mms_internal.h"
 
 namespace mms {
 namespace {
 
-static_assert(kConvMaxChannels * kConvTilePixels <= kConvLdsFloats, "the accumulator tile of any fast plan fits the LDS");
-
-struct TrainDims {
-  ConvDims d;
-  int ph, pw, POH, POW;
-  bool max;
-};
-
-// the refusal of the shape, the pool and the window, else MMS_OK and *g
-int train_check(const mms_conv_shape* shape, int ph, int pw, int pool, TrainDims* g) {
-  const int rc = conv_check(shape, &g->d);
+// the refusal of the shape, the window and the pool, else MMS_OK and *g.  A shape's own refusal comes first; the
+// window's and the pool's are the same code.
+int train_check(const mms_conv_shape* shape, int ph, int pw, int pool, StageDims* g) {
+  const int rc = stage_window_check(shape, ph, pw, g);
   if (rc != MMS_OK) return rc;
   if (pool != MMS_STAGE_POOL_AVE && pool != MMS_STAGE_POOL_MAX) return MMS_ERR_INVALID_ARG;
-  if (ph < 1 || pw < 1 || g->d.OH % ph || g->d.OW % pw) return MMS_ERR_INVALID_ARG;
-  g->ph = ph;
-  g->pw = pw;
-  g->POH = g->d.OH / ph;
-  g->POW = g->d.OW / pw;
   g->max = pool == MMS_STAGE_POOL_MAX;
   return MMS_OK;
 }
@@ -66,7 +52,7 @@ struct TrainArgs {
 };
 
 // p.ok false: the fused launches do not reach.
-TrainArgs train_plan(const TrainDims& g) {
+TrainArgs train_plan(const StageDims& g) {
   TrainArgs a = {};
   ConvProdArgs p = conv_prod_plan(g.d, MMS_CONV_PASS_FORWARD, g.ph);
   if (!p.ok) return a;
@@ -91,13 +77,9 @@ TrainArgs train_plan(const TrainDims& g) {
   a.p = p;
   a.ph = g.ph; a.pw = g.pw; a.POH = g.POH; a.POW = g.POW;
   const int P = p.G * p.R * p.OWt;
-  // csrc/conv_stage.hip's row length: 4 or 12 mod 16 keeps the lane groups of an accumulator in separate banks
-  a.PS = P;
-  while (a.PS % 16 != 4 && a.PS % 16 != 12) ++a.PS;
-  if (p.Cout * a.PS > kConvLdsFloats) a.PS = P;
-  const size_t tile = (size_t)p.Cout * a.PS * sizeof(float);
-  a.lds_bytes = tile > p.lds_bytes ? tile : p.lds_bytes;
-  a.groups = (p.N + p.G - 1) / p.G * p.bands;
+  a.PS = stage_tile_row(p.Cout, P);
+  a.lds_bytes = stage_lds_bytes(p.Cout, P, p.lds_bytes);
+  a.groups = (int)stage_groups(p);
   return a;
 }
 
@@ -117,21 +99,17 @@ TrainArgs train_plan(const TrainDims& g) {
 //   MAX, one whole image (v5's second stage): slower at 50, level at 400 and 1517.  Not taken.
 //   MAX, several whole images (v3's second stage, v5's third): slower or level at every count measured.  Not taken.
 //   AVE, one whole image: not measured.
-struct TrainSpan {
-  long long least, most;       // workgroups of launch 1
-};
-// [MAX][kind]: kind 0 several whole images per workgroup, 1 a band of rows of one image, 2 one whole image
-constexpr TrainSpan kTrainSpans[2][3] = {
+// [MAX][stage_plan_kind]: workgroups of launch 1
+constexpr StageSpan kTrainSpans[2][3] = {
     {{0, -1}, {450, 450}, {0, -1}},
     {{0, -1}, {450, 10619}, {0, -1}},
 };
 
-int train_route(const TrainDims& g) {
+int train_route(const StageDims& g) {
   const TrainArgs a = train_plan(g);
   if (!a.p.ok) return MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE;
-  const TrainSpan& k = kTrainSpans[g.max][a.p.G > 1 ? 0 : a.p.bands > 1 ? 1 : 2];
-  return a.groups >= k.least && a.groups <= k.most ? MMS_CONV_STAGE_TRAIN_ROUTE_FUSED
-                                                   : MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE;
+  return kTrainSpans[g.max][stage_plan_kind(a.p)].holds(a.groups) ? MMS_CONV_STAGE_TRAIN_ROUTE_FUSED
+                                                                  : MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE;
 }
 
 // PH, PW > 0: the window's size at compile time (== s.ph, s.pw); 0: any window.
@@ -145,8 +123,7 @@ struct TrainEpilogue {
   template <int MT>
   __device__ __forceinline__ void finish(const ConvProdArgs& a, const ConvTile& t, const conv_v4f (&acc)[MT][kConvNT],
                                          const bool (&pvalid)[kConvNT]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, grp = lane >> 4;
-    const int PS = s.PS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, PS = s.PS;
     const size_t PI = (size_t)a.OHt * a.OWt;
     // pixel p = (image p / per, row, column) of the band: rows are whole, so its place in the map is oy0 OWt + p % per
     size_t yoff[kConvNT];
@@ -155,23 +132,7 @@ struct TrainEpilogue {
       const int p = pvalid[nt] ? (wave + 4 * nt) * 16 + l16 : 0, img = p / t.per;
       yoff[nt] = (size_t)(t.n0 + img) * a.Cout * PI + (size_t)t.oy0 * a.OWt + (p - img * t.per);
     }
-    __syncthreads();                                    // every wave has finished with the band and the weights
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = 16 * mt + 4 * grp + r;
-        if (m >= a.Cout) continue;
-        const float b = a.bias ? a.bias[m] : 0.f;
-#pragma unroll
-        for (int nt = 0; nt < kConvNT; ++nt)
-          if (pvalid[nt]) {
-            const float v = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];     // ConvStoreEpilogue's word
-            tile[m * PS + (wave + 4 * nt) * 16 + l16] = v;
-            a.out[yoff[nt] + (size_t)m * PI] = v;
-          }
-      }
-    __syncthreads();
+    stage_tile_store(a, tile, PS, acc, pvalid, [y = a.out, &yoff, PI](int nt, int m, float v) { y[yoff[nt] + (size_t)m * PI] = v; });
     constexpr int TK = kConvThreads / (16 * MT);        // adjacent lanes per channel: 16, 8, 4
     const int k = tid / TK, j = tid - k * TK;
     const int ph = PH > 0 ? PH : s.ph, pw = PW > 0 ? PW : s.pw;
@@ -264,22 +225,8 @@ __global__ __launch_bounds__(kBnThreads) void train_finish_kernel(
 constexpr unsigned kTrainFinishWindows = 1024;     // pooled elements of a launch-2 workgroup, at least: four per thread
 constexpr unsigned kTrainFinishChunks = 64;        // ... unless that takes more workgroups per channel than this
 
-template <int K>
-using train_int = std::integral_constant<int, K>;
-
-// f(PH, PW) as types: csrc/conv_stage.hip's choice of windows known at compile time, any other at run time.
-template <bool MAX, class F>
-void train_dispatch(int ph, int pw, F&& f) {
-  if (ph == 4 && pw == 4) f(train_int<4>{}, train_int<4>{});
-  else if (!MAX && ph == 5 && pw == 5) f(train_int<5>{}, train_int<5>{});
-  else if (MAX && ph == 2 && pw == 2) f(train_int<2>{}, train_int<2>{});
-  else f(train_int<0>{}, train_int<0>{});
-}
-
-inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 template <typename T>
-size_t bn_bytes(const TrainDims& g) {
+size_t bn_bytes(const StageDims& g) {
   return std::is_same<T, float>::value
              ? mms_bn_pool_tanh_workspace_bytes(g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw)
              : mms_bn_pool_tanh_workspace_bytes_f64(g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw);
@@ -296,7 +243,7 @@ struct BackwardCarve {
   size_t all() const { return dy + bn + conv; }
 };
 template <typename T>
-BackwardCarve<T> backward_carve(const mms_conv_shape* shape, const TrainDims& g) {
+BackwardCarve<T> backward_carve(const mms_conv_shape* shape, const StageDims& g) {
   const size_t map = (size_t)g.d.N * g.d.K * g.d.OH * g.d.OW;
   return {round16(map * sizeof(T)), round16(bn_bytes<T>(g)), conv_bytes<T>(shape)};
 }
@@ -307,7 +254,7 @@ enum { kAuto = -1, kSequence = MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE, kFused = MMS
 
 // What the forward needs on `force` (kAuto: train_route decides; kFused where it does not reach: 0).
 template <typename T>
-size_t forward_bytes(const TrainDims& g, int force) {
+size_t forward_bytes(const StageDims& g, int force) {
   if (std::is_same<T, float>::value && force != kSequence) {
     const TrainArgs a = train_plan(g);
     if (force == kFused) return a.p.ok ? fused_bytes(a) : 0;
@@ -318,19 +265,13 @@ size_t forward_bytes(const TrainDims& g, int force) {
 
 template <typename T>
 size_t train_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, int pool, int force) {
-  TrainDims g;
+  StageDims g;
   if (train_check(shape, ph, pw, pool, &g) != MMS_OK || g.d.N == 0) return 0;
   if (force == kFused && !train_plan(g).p.ok) return 0;
   const size_t f = forward_bytes<T>(g, force), b = backward_carve<T>(shape, g).all();
   return f > b ? f : b;
 }
 
-inline int conv_fwd(const mms_conv_shape* s, const float* x, const float* w, const float* b, float* y, void* st) {
-  return mms_conv_forward_f32(s, x, w, b, y, nullptr, 0, st);
-}
-inline int conv_fwd(const mms_conv_shape* s, const double* x, const double* w, const double* b, double* y, void* st) {
-  return mms_conv_forward_f64(s, x, w, b, y, nullptr, 0, st);
-}
 inline int conv_bwd(const mms_conv_shape* s, const float* x, const float* w, const float* dy, float* dx, float* dw,
                     float* db, void* ws, size_t wsb, void* st) {
   return mms_conv_backward_f32(s, x, w, dy, dx, dw, db, ws, wsb, st);
@@ -339,17 +280,7 @@ inline int conv_bwd(const mms_conv_shape* s, const double* x, const double* w, c
                     double* db, void* ws, size_t wsb, void* st) {
   return mms_conv_backward_f64(s, x, w, dy, dx, dw, db, ws, wsb, st);
 }
-inline int bn_fwd(const TrainDims& g, float mem, const float* y, const float* sc, const float* sh, float* rm, float* rv,
-                  float* top, float* sp, float* sm, float* ss, void* ws, size_t wsb, void* st) {
-  const auto call = g.max ? mms_bn_maxpool_tanh_forward_f32 : mms_bn_pool_tanh_forward_f32;
-  return call(0, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, mem, y, sc, sh, rm, rv, top, sp, sm, ss, ws, wsb, st);
-}
-inline int bn_fwd(const TrainDims& g, double mem, const double* y, const double* sc, const double* sh, double* rm,
-                  double* rv, double* top, double* sp, double* sm, double* ss, void* ws, size_t wsb, void* st) {
-  const auto call = g.max ? mms_bn_maxpool_tanh_forward_f64 : mms_bn_pool_tanh_forward_f64;
-  return call(0, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, mem, y, sc, sh, rm, rv, top, sp, sm, ss, ws, wsb, st);
-}
-inline int bn_bwd(const TrainDims& g, const float* y, const float* top, const float* td, const float* sp,
+inline int bn_bwd(const StageDims& g, const float* y, const float* top, const float* td, const float* sp,
                   const float* sc, const float* sh, const float* sm, const float* ss, float* dy, float* dsc, float* dsh,
                   void* ws, size_t wsb, void* st) {
   const int N = g.d.N, K = g.d.K, OH = g.d.OH, OW = g.d.OW;
@@ -358,7 +289,7 @@ inline int bn_bwd(const TrainDims& g, const float* y, const float* top, const fl
                : mms_bn_pool_tanh_backward_f32(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sm, ss, dy, dsc, dsh, ws,
                                                wsb, st);
 }
-inline int bn_bwd(const TrainDims& g, const double* y, const double* top, const double* td, const double* sp,
+inline int bn_bwd(const StageDims& g, const double* y, const double* top, const double* td, const double* sp,
                   const double* sc, const double* sh, const double* sm, const double* ss, double* dy, double* dsc,
                   double* dsh, void* ws, size_t wsb, void* st) {
   const int N = g.d.N, K = g.d.K, OH = g.d.OH, OW = g.d.OW;
@@ -368,22 +299,12 @@ inline int bn_bwd(const TrainDims& g, const double* y, const double* top, const 
                                                wsb, st);
 }
 
-// whether a non-NULL `out` is one of `others` (NULL entries are skipped)
-template <size_t M>
-bool among(const void* out, const void* const (&others)[M]) {
-  if (!out) return false;
-  for (const void* o : others) {
-    if (o && o == out) return true;
-  }
-  return false;
-}
-
 template <typename T>
 int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_memory, const T* x, const T* w,
                   const T* bias, const T* scale, const T* shift, T* running_mean, T* running_var, T* y, T* top,
                   T* save_pool, T* save_mean, T* save_std, void* workspace, size_t workspace_bytes, int force,
                   void* stream) {
-  TrainDims g;
+  StageDims g;
   const int rc = train_check(shape, ph, pw, pool, &g);
   if (rc != MMS_OK) return rc;
   if (g.d.N == 0) return MMS_OK;
@@ -392,12 +313,7 @@ int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_me
     return MMS_ERR_INVALID_ARG;
   const void* const inputs[] = {x, w, bias, scale, shift};
   const void* const outputs[] = {y, top, save_pool, save_mean, save_std, running_mean, running_var};
-  for (size_t i = 0; i < sizeof(outputs) / sizeof(outputs[0]); ++i) {
-    if (among(outputs[i], inputs)) return MMS_ERR_INVALID_ARG;
-    for (size_t j = 0; j < i; ++j) {
-      if (outputs[i] == outputs[j]) return MMS_ERR_INVALID_ARG;
-    }
-  }
+  if (stage_outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (force == kFused && !train_plan(g).p.ok) return MMS_ERR_UNSUPPORTED;
     if (force == kFused || (force == kAuto && train_route(g) == MMS_CONV_STAGE_TRAIN_ROUTE_FUSED)) {
@@ -408,7 +324,7 @@ int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_me
       const dim3 grid((unsigned)((a.p.N + a.p.G - 1) / a.p.G), (unsigned)a.p.bands);
       conv_with_mt(a.p.MT, [&](auto M) {
         with_bool(g.max, [&](auto MAX) {
-          train_dispatch<decltype(MAX)::value>(ph, pw, [&](auto PH, auto PW) {
+          stage_pool_dispatch<decltype(MAX)::value>(ph, pw, [&](auto PH, auto PW) {
             hipLaunchKernelGGL(
                 (train_product_kernel<decltype(M)::value, decltype(MAX)::value, decltype(PH)::value, decltype(PW)::value>),
                 grid, dim3(kConvThreads), a.lds_bytes, as_stream(stream), a);
@@ -431,10 +347,10 @@ int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_me
   const size_t need = bn_bytes<T>(g);
   if (need && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
-  const int rc1 = conv_fwd(shape, x, w, bias, y, stream);
+  const int rc1 = stage_conv_forward(shape, x, w, bias, y, stream);
   if (rc1 != MMS_OK) return rc1;
-  return bn_fwd(g, bn_memory, y, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std, workspace,
-                workspace_bytes, stream);
+  return stage_bn_pool_forward(g, 0, bn_memory, y, scale, shift, running_mean, running_var, top, save_pool, save_mean,
+                               save_std, workspace, workspace_bytes, stream);
 }
 
 template <typename T>
@@ -442,7 +358,7 @@ int train_backward(const mms_conv_shape* shape, int ph, int pw, int pool, const 
                    const T* top, const T* top_diff, const T* save_pool, const T* scale, const T* shift,
                    const T* save_mean, const T* save_std, T* dx, T* dw, T* db, T* dscale, T* dshift, void* workspace,
                    size_t workspace_bytes, void* stream) {
-  TrainDims g;
+  StageDims g;
   const int rc = train_check(shape, ph, pw, pool, &g);
   if (rc != MMS_OK) return rc;
   if (g.d.N == 0) return MMS_OK;
@@ -451,12 +367,7 @@ int train_backward(const mms_conv_shape* shape, int ph, int pw, int pool, const 
     return MMS_ERR_INVALID_ARG;
   const void* const inputs[] = {x, w, y, top, top_diff, save_pool, scale, shift, save_mean, save_std};
   const void* const outputs[] = {dx, dw, db, dscale, dshift};
-  for (size_t i = 0; i < sizeof(outputs) / sizeof(outputs[0]); ++i) {
-    if (among(outputs[i], inputs)) return MMS_ERR_INVALID_ARG;
-    for (size_t j = 0; j < i; ++j) {
-      if (outputs[i] && outputs[i] == outputs[j]) return MMS_ERR_INVALID_ARG;
-    }
-  }
+  if (stage_outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   const bool conv = dx || dw || db;
   const BackwardCarve<T> carve = backward_carve<T>(shape, g);
   const size_t need = conv ? carve.all() : bn_bytes<T>(g);
@@ -479,7 +390,7 @@ using namespace mms;
 extern "C" {
 
 int mms_conv_stage_train_route(const mms_conv_shape* shape, int ph, int pw, int pool) {
-  TrainDims g;
+  StageDims g;
   if (train_check(shape, ph, pw, pool, &g) != MMS_OK) return MMS_CONV_STAGE_TRAIN_ROUTE_NONE;
   return train_route(g);
 }

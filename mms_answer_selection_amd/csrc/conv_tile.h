@@ -1,7 +1,8 @@
-// csrc/conv_tile.h -- the fast route's PRODUCT tile, shared by csrc/conv.hip (forward and bottom_diff, whose epilogue
-// stores the map) and csrc/conv_stage.hip (whose epilogue pools it): the shape check, the geometry of a workgroup, the
-// plan of the product and ONE definition of the staging + MFMA loop, parameterised by what is done with the
-// accumulators.  csrc/conv.hip's header comment describes the product; the order of a sum is fixed here: channels
+// csrc/conv_tile.h -- the fast route's PRODUCT tile, shared by four sources: csrc/conv.hip (forward and bottom_diff,
+// whose epilogue stores the map) and csrc/conv_stage.hip, csrc/conv_stage_train.hip and csrc/score_tail.hip (whose
+// epilogues pool it: csrc/conv_pool_tile.h has what those three share).  Here: the shape check, the geometry of a
+// workgroup, the plan of the product and ONE definition of the staging + MFMA loop, parameterised by what is done with
+// the accumulators.  csrc/conv.hip's header comment describes the product; the order of a sum is fixed here: channels
 // ascending in chunks, (c, i, j) ascending inside a chunk in steps of four, the four of a step as the MFMA adds them.
 #ifndef MMS_CONV_TILE_H_
 #define MMS_CONV_TILE_H_
@@ -223,6 +224,13 @@ __device__ __forceinline__ void conv_tile_product(const ConvProdArgs& a, float* 
     }
   }
   epi.finish(a, t, acc, pvalid);
+}
+
+// The word of the map from an accumulator element of output channel m: b = conv_tile_bias(a, m), loaded once per
+// channel, is added where there is a bias.
+__device__ __forceinline__ float conv_tile_bias(const ConvProdArgs& a, int m) { return a.bias ? a.bias[m] : 0.f; }
+__device__ __forceinline__ float conv_tile_word(const ConvProdArgs& a, float acc, float b) {
+  return a.bias ? acc + b : acc;
 }
 
 template <class F>

@@ -15,18 +15,17 @@
 //   fused     float, where tail_plan says ok.  The product is conv_tile_product with conv_prod_plan's chunks (CC) and
 //             whole images per workgroup: kTailImages of them at most, the tail's own choice (below), not the stage's.  Before the
 //             product the workgroup stages w1, w2, the biases and its images' overlap rows into a region of LDS behind
-//             the convolution's.  The epilogue puts accumulator + bias in LDS as tile[k][pixel], as
-//             csrc/conv_stage.hip's does; thread e takes (image, channel) e, e + 256, ..., adds or scans the image's
-//             map in (h, w) order and finishes with bn_pool_test_finish / bn_maxpool_test_finish; the value goes to
-//             the image's feat row in LDS (and to flt where asked).  Then csrc/head_tile.h's steps on those rows: fc1
+//             the convolution's.  The epilogue's steps are those csrc/conv_pool_tile.h lists, the window being the
+//             image's whole map; thread e takes (image, channel) e, e + 256, ... and finishes with
+//             bn_pool_test_finish / bn_maxpool_test_finish; the value goes to the image's feat row in LDS (and to
+//             flt where asked).  Then csrc/head_tile.h's steps on those rows: fc1
 //             blocks of 16 samples x 16 hidden units dealt to the four waves, fc2 one thread per (sample, class),
 //             softmax one thread per sample.  With a loss each sample's term and whether it counts go to the workspace
 //             and tail_loss_finish_kernel, one thread, adds them in ascending n: a second launch.
 //
 // A value of flt, h or prob is the same chain of operations on both routes: the convolution's chunks are the
 // convolution's own (tail_plan refuses a plan that would cut them differently) and every later step is per sample.
-#include "bn_common.h"
-#include "conv_tile.h"
+#include "conv_pool_tile.h"
 #include "head_tile.h"
 #include "mms_conv_maxpool_stage.h"
 #include "mms_conv_stage.h"
@@ -46,10 +45,7 @@ constexpr int kTailMaxLdsBytes = 163840;   // the fused kernel's dynamic LDS, at
 // 256 CUs, which sit idle at these batch sizes.  Three is the fewest measured; one and two are not.
 constexpr int kTailImages = 3;
 
-struct TailDims {
-  ConvDims d;
-  int ph, pw, POH, POW;
-  bool max;
+struct TailDims : StageDims {
   mms_head_shape hs;         // the head call's shape
   HeadDims hd;
 };
@@ -58,13 +54,8 @@ struct TailDims {
 int tail_check(const mms_score_tail_shape* s, TailDims* g) {
   if (!s) return MMS_ERR_INVALID_ARG;
   if (s->pool != MMS_STAGE_POOL_AVE && s->pool != MMS_STAGE_POOL_MAX) return MMS_ERR_INVALID_ARG;
-  int rc = conv_check(&s->conv, &g->d);
+  const int rc = stage_window_check(&s->conv, s->ph, s->pw, g);
   if (rc != MMS_OK) return rc;
-  if (s->ph < 1 || s->pw < 1 || g->d.OH % s->ph || g->d.OW % s->pw) return MMS_ERR_INVALID_ARG;
-  g->ph = s->ph;
-  g->pw = s->pw;
-  g->POH = g->d.OH / s->ph;
-  g->POW = g->d.OW / s->pw;
   g->max = s->pool == MMS_STAGE_POOL_MAX;
   const long long F0 = (long long)g->d.K * g->POH * g->POW;       // at most K OH OW, which conv_check bounds
   g->hs = {g->d.N, (int)F0, s->F1, s->H, s->C, MMS_HEAD_TEST, 0.5f, s->normalization, s->has_ignore_label,
@@ -103,11 +94,8 @@ TailArgs tail_plan(const TailDims& g, int images) {
   const int Mpad = 16 * a.p.MT;
   a.p.lds_bytes = ((size_t)a.p.G * a.p.CC * a.p.plane + (size_t)Mpad * a.p.Kpad + a.p.Kpad) * sizeof(float);
   const int P = a.p.G * a.p.OHt * a.p.OWt;
-  a.PS = P;                  // csrc/conv_stage.hip: stage_plan's bank rule
-  while (a.PS % 16 != 4 && a.PS % 16 != 12) ++a.PS;
-  if (a.p.Cout * a.PS > kConvLdsFloats) a.PS = P;
-  const size_t tile = (size_t)a.p.Cout * a.PS * sizeof(float);
-  const size_t conv_bytes = tile > a.p.lds_bytes ? tile : a.p.lds_bytes;
+  a.PS = stage_tile_row(a.p.Cout, P);
+  const size_t conv_bytes = stage_lds_bytes(a.p.Cout, P, a.p.lds_bytes);
   a.head_off = (int)((conv_bytes + sizeof(float) - 1) / sizeof(float));
   a.rows = (a.p.G + 15) / 16 * 16;
   a.hd = g.hd;
@@ -116,8 +104,6 @@ TailArgs tail_plan(const TailDims& g, int images) {
   return a;
 }
 
-long long tail_groups(const TailArgs& a) { return (a.p.N + a.p.G - 1) / a.p.G; }
-
 // The one routing decision, for a shape tail_check accepts.  The measured rule (tools/bench_score_tail.py,
 // profiles/score_tail_bench.txt: fused against sequence, median of seven alternating passes, the two ranges apart at
 // every point).  Measured: workgroups of several whole small images -- network_v4's tail (AVE 5 x 5) at N = 50, 100, 400
@@ -125,16 +111,14 @@ long long tail_groups(const TailArgs& a) { return (a.p.N + a.p.G - 1) / a.p.G; }
 // (MAX 6 x 6) at N = 50 and 1517, 17 and 506 workgroups: 1.64 and 1.41 x.  FUSED on the workgroup counts between the
 // fewest and the most measured; fewer than 17 and more than 506 are not measured and go to the sequence, as does a
 // workgroup of one image of 129 to 256 pixels, which no net of the driver has.
-constexpr long long kTailMinGroups = 17;     // N = 50
-constexpr long long kTailMaxGroups = 506;    // N = 1517
+constexpr StageSpan kTailGroups = {17, 506};   // N = 50, N = 1517
 
 int tail_route(const TailDims& g) {
   const TailArgs a = tail_plan(g, kTailImages);
   if (!a.ok) return MMS_SCORE_TAIL_ROUTE_SEQUENCE;
   const bool small_images = a.p.OHt * a.p.OWt <= kConvTilePixels / 2;      // conv_tile_geometry: G > 1
-  const long long groups = tail_groups(a);
-  return small_images && groups >= kTailMinGroups && groups <= kTailMaxGroups ? MMS_SCORE_TAIL_ROUTE_FUSED
-                                                                             : MMS_SCORE_TAIL_ROUTE_SEQUENCE;
+  return small_images && kTailGroups.holds(stage_groups(a.p)) ? MMS_SCORE_TAIL_ROUTE_FUSED
+                                                              : MMS_SCORE_TAIL_ROUTE_SEQUENCE;
 }
 
 template <bool MAX>
@@ -142,20 +126,10 @@ struct TailEpilogue {
   const TailArgs& s;
   float* tile;
   HeadFwdLds L;
-  int kc;                    // the channel whose values follow: that of the thread's first (image, channel)
-  float nmean, std, sc, sh;
-  int dir;                   // MAX: bp_dir(sc)
-  __device__ __forceinline__ void channel(int k) {
-    kc = k;
-    nmean = -s.mean[k];
-    std = bn_sqrt(s.var[k] + 1e-9f);
-    sc = s.scale[k];
-    sh = s.shift[k];
-    if constexpr (MAX) dir = bp_dir(sc);
-  }
+  StageChannel<MAX> ch;      // of the channel whose values follow: that of the thread's first (image, channel)
   // Before the product: the loads are long back when the epilogue, on the workgroup's critical path, needs them.
   __device__ __forceinline__ void pixel(const ConvProdArgs& a, const ConvTile&, int nt, int, int, int) {
-    if (nt == 0) channel((int)threadIdx.x % a.Cout);
+    if (nt == 0) ch.load(s, (int)threadIdx.x % a.Cout);
   }
 
   template <int MT>
@@ -165,6 +139,7 @@ struct TailEpilogue {
     const int PS = s.PS;
     const HeadDims& hd = s.hd;
     const HeadFastPlan& hp = s.hp;
+    // stage_tile_store's body, written out: called from here it changed this kernel's register allocation
     __syncthreads();                                    // every wave has finished with the band and the weights
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -172,26 +147,26 @@ struct TailEpilogue {
       for (int r = 0; r < 4; ++r) {
         const int m = 16 * mt + 4 * grp + r;
         if (m >= a.Cout) continue;
-        const float b = a.bias ? a.bias[m] : 0.f;
+        const float b = conv_tile_bias(a, m);
 #pragma unroll
         for (int nt = 0; nt < kConvNT; ++nt)
-          if (pvalid[nt]) tile[m * PS + (wave + 4 * nt) * 16 + l16] = a.bias ? acc[mt][nt][r] + b : acc[mt][nt][r];
+          if (pvalid[nt]) tile[m * PS + (wave + 4 * nt) * 16 + l16] = conv_tile_word(a, acc[mt][nt][r], b);
       }
     __syncthreads();
-    // pool and finish: the window is the image's whole map, t.per = ph pw values in (h, w) order
+    // pool and finish: the window is the image's whole map, one row of t.per = ph pw values in (h, w) order
     const float ke = (float)t.per;
     for (int e = tid; e < t.gc * a.Cout; e += kConvThreads) {
       const int k = e % a.Cout, img = e / a.Cout;
+      if (k != ch.kc) ch.load(s, k);
       const float* src = tile + k * PS + img * t.per;
-      if (k != kc) channel(k);
       float sum = 0.f;                                  // AVE: the window's sum; MAX: its extremum
       for (int i = 0; i < t.per; ++i) {
-        if constexpr (MAX) bp_keep(i == 0, src[i], dir, &sum);
+        if constexpr (MAX) bp_keep(i == 0, src[i], ch.dir, &sum);
         else sum += src[i];
       }
       float sp;
-      const float tv = MAX ? bn_maxpool_test_finish(sum, nmean, std, sc, sh, &sp)
-                           : bn_pool_test_finish(sum, ke, nmean, std, sc, sh, &sp);
+      const float tv = MAX ? bn_maxpool_test_finish(sum, ch.nmean, ch.std, ch.sc, ch.sh, &sp)
+                           : bn_pool_test_finish(sum, ke, ch.nmean, ch.std, ch.sc, ch.sh, &sp);
       if (s.flt) s.flt[(size_t)(t.n0 + img) * a.Cout + k] = tv;
       L.feats[img * hp.Fa + k] = tv;
     }
@@ -248,8 +223,6 @@ __global__ void tail_loss_finish_kernel(const float* terms, const int* valid, He
   }
   *loss = sum / head_normalizer<float>(d, c);
 }
-
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 struct TailSequenceWorkspace {
   size_t stage, flt, h, head, total;       // bytes of each part; flt and h start at round16 offsets
@@ -317,7 +290,7 @@ template <int MT, bool MAX>
 int tail_launch(const TailArgs& a, void* stream) {
   static const hipError_t once = tail_allow_lds(&score_tail_kernel<MT, MAX>);
   if (once != hipSuccess) return MMS_ERR_LAUNCH;
-  hipLaunchKernelGGL((score_tail_kernel<MT, MAX>), dim3((unsigned)tail_groups(a)), dim3(kConvThreads), a.lds_bytes,
+  hipLaunchKernelGGL((score_tail_kernel<MT, MAX>), dim3((unsigned)stage_groups(a.p)), dim3(kConvThreads), a.lds_bytes,
                      as_stream(stream), a);
   return launch_status();
 }
@@ -337,13 +310,7 @@ int tail_forward(const mms_score_tail_shape* shape, const T* x, const T* w, cons
   if (!w1 || !w2 || !prob || (g.hd.F1 > 0 && !overlap) || (loss && !label)) return MMS_ERR_INVALID_ARG;
   const void* const outs[] = {flt, h, prob, loss};
   const void* const ins[] = {x, w, bias, mean, var, scale, shift, overlap, w1, b1, w2, b2, label};
-  for (int i = 0; i < 4; ++i) {
-    if (!outs[i]) continue;
-    for (const void* in : ins)
-      if (outs[i] == in) return MMS_ERR_INVALID_ARG;
-    for (int j = i + 1; j < 4; ++j)
-      if (outs[i] == outs[j]) return MMS_ERR_INVALID_ARG;
-  }
+  if (stage_outputs_alias(outs, ins)) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (force == MMS_SCORE_TAIL_ROUTE_FUSED && !tail_plan(g, kTailImages).ok) return MMS_ERR_UNSUPPORTED;
     if (force == MMS_SCORE_TAIL_ROUTE_FUSED ||
