@@ -329,7 +329,7 @@ __global__ __launch_bounds__(kHeadThreads) void head_fast_forward_kernel(HeadArg
     // fc1: rows = this wave's 16 samples, columns = 16 hidden units; tanh and Dropout on the accumulators
     for (int ht = 0; ht < p.HT; ++ht)
       head_fc1_block(L, d, p, wave, ht, a.b1 != nullptr, n0, n1, a.h, [&](float hv, int n, int j) {
-        return d.train ? (hv * float(a.mask[(size_t)n * d.H + j])) * a.scale : hv;
+        return d.train ? head_dropout(hv, a.mask[(size_t)n * d.H + j], a.scale) : hv;
       });
     __syncthreads();
     // fc2: lane (sample l16 of the wave, classes grp, grp + 4, ...)

@@ -1,6 +1,6 @@
 // csrc/head_tile.h -- the tile steps of the head's fast forward, shared by csrc/head.hip (whose kernel walks a slab's
-// tiles of samples read from memory) and csrc/score_tail.hip (whose epilogue runs them on the rows a convolution stage
-// left in LDS): the shape check, the fast plan, the LDS layout of a tile and ONE definition of each step -- staging the
+// tiles of samples read from memory), csrc/score_tail.hip (whose epilogue runs them on the rows a convolution stage
+// left in LDS) and csrc/train_tail.hip (whose second launch runs them in TRAIN phase): the shape check, the fast plan, the LDS layout of a tile and ONE definition of each step -- staging the
 // weights, fc1 on the matrix pipe with tanh, fc2, softmax with the loss term.  csrc/head.hip's header comment describes
 // the route; the order of every sum is fixed here and depends neither on the row a sample has in its tile nor on which
 // wave or lane takes it: fc1's features ascending four per MFMA step from 0, then the bias; fc2's hidden units ascending
@@ -148,6 +148,10 @@ __device__ inline void head_stage_weights(const HeadFwdLds& L, const HeadDims& d
   for (int j = tid; j < Hw; j += kHeadThreads) L.b1s[j] = (b1 && j < d.H) ? b1[j] : 0.f;
   for (int c = tid; c < d.C; c += kHeadThreads) L.b2s[c] = b2 ? b2[c] : 0.f;
 }
+
+// Dropout of one element of h in TRAIN phase, from its word of the caller's mask: (h * Dtype(mask)) * scale.  The `drop`
+// of head_fc1_block in csrc/head.hip (TRAIN) and in csrc/train_tail.hip.
+__device__ __forceinline__ float head_dropout(float hv, unsigned m, float scale) { return (hv * float(m)) * scale; }
 
 // fc1 and tanh of one block, by one wave: rows 16 rt .. 16 rt + 15 of the tile (sample n0 + row, below n1) by hidden
 // units 16 ht .. 16 ht + 15, K = the features in steps of 4.  h goes to memory where `h` is not NULL and
