@@ -7,7 +7,8 @@
 //   weight_diff  dw[k,c,i,j]    += sum_{n,oy,ox} dy[n,k,oy,ox] * x[n, g Cg + c, oy sh - ph + i, ox sw - pw + j]
 //   bias_diff    db[k]          += sum_{n,oy,ox} dy[n,k,oy,ox]
 //
-// Two routes (mms_conv_route, the one place that decides; conv_prod_plan / conv_wdiff_plan say what the fast one takes):
+// Two routes (mms_conv_route, the one place that decides; conv_prod_plan of csrc/conv_tile.h and conv_wdiff_plan of
+// csrc/conv_plans.h say what the fast one takes):
 //
 //   generic  direct kernels <T>, one thread per output element, sums in ascending (c, i, j) (forward), (k, i, j)
 //            (bottom_diff, gather form: no col2im scatter) and (n, oy, ox) (parameter diffs) order.  Every accepted
@@ -32,14 +33,13 @@
 //
 // Nothing is read 16 bytes at a time, so alignment cannot change an order; every workspace word that is read has been
 // written by this call.
+#include "conv_plans.h"
 #include "conv_tile.h"
 #include "mms_conv.h"
 #include "mms_internal.h"
 
 namespace mms {
 namespace {
-
-constexpr int kConvMaxSlabs = 64;          // partial sums of the parameter diffs per element, at most
 
 // ---- generic route ------------------------------------------------------------------------------------------------
 template <typename T>
@@ -165,13 +165,6 @@ __global__ __launch_bounds__(kConvThreads) void conv_reduce_kernel(const T* __re
   *out = *out + s;
 }
 
-int conv_generic_slabs(const ConvDims& d, int* rps) {
-  const int rows = d.N * d.OH;
-  const int want = rows < kConvMaxSlabs ? rows : kConvMaxSlabs;
-  *rps = (rows + want - 1) / want;
-  return (rows + *rps - 1) / *rps;
-}
-
 // ---- fast route ---------------------------------------------------------------------------------------------------
 // The product's tile, plan and loop are csrc/conv_tile.h's; this epilogue stores the map.
 struct ConvStoreEpilogue {
@@ -205,46 +198,6 @@ __global__ __launch_bounds__(kConvThreads) void conv_prod_kernel(ConvProdArgs a)
   ConvStoreEpilogue epi;
   epi.PI = (size_t)a.OHt * a.OWt;
   conv_tile_product<MT>(a, conv_lds, epi);
-}
-
-struct ConvWdiffArgs {
-  const float* x;        // (N, C, H, W)
-  const float* dy;       // (N, K, OH, OW)
-  float* part;           // [slab][nW + K]
-  int N, C, K, H, W, OH, OW, kh, kw;
-  int G, R, bands;       // conv_tile_geometry of the top pixels, shrunk to the LDS
-  int plane;             // (R + kh - 1) * W
-  int PP;                // row length of the staged top_diff tile: conv_round4(G * R * OW) + 1
-  int MT;
-  int units, ups, slabs; // (image group, band) units; units per slab; slabs
-  int want_w, want_b;
-  bool ok;
-  size_t lds_bytes;
-};
-
-ConvWdiffArgs conv_wdiff_plan(const ConvDims& d) {
-  ConvWdiffArgs a = {};
-  if (d.sh != 1 || d.sw != 1 || d.ph != 0 || d.pw != 0 || d.G != 1 || d.C > kConvMaxChannels || d.K > kConvMaxChannels)
-    return a;
-  a.N = d.N; a.C = d.C; a.K = d.K; a.H = d.H; a.W = d.W; a.OH = d.OH; a.OW = d.OW; a.kh = d.kh; a.kw = d.kw;
-  if (!conv_tile_geometry(d.OH, d.OW, 1, &a.G, &a.R, &a.bands)) return a;
-  a.MT = d.K <= 16 ? 1 : d.K <= 32 ? 2 : 4;
-  for (;;) {
-    a.plane = (a.R + d.kh - 1) * d.W;
-    a.PP = conv_round4(a.G * a.R * d.OW) + 1;
-    const long long need = (long long)a.G * d.C * a.plane + (long long)16 * a.MT * a.PP + a.PP;
-    if (need <= kConvLdsFloats) break;
-    if (a.G > 1) { --a.G; continue; }
-    if (a.R > 1) { --a.R; a.bands = (d.OH + a.R - 1) / a.R; continue; }
-    return a;
-  }
-  a.lds_bytes = ((size_t)a.G * d.C * a.plane + (size_t)16 * a.MT * a.PP + a.PP) * sizeof(float);
-  a.units = d.N ? ((d.N + a.G - 1) / a.G) * a.bands : 0;
-  const int want = a.units < kConvMaxSlabs ? a.units : kConvMaxSlabs;
-  a.ups = want ? (a.units + want - 1) / want : 1;
-  a.slabs = (a.units + a.ups - 1) / a.ups;
-  a.ok = true;
-  return a;
 }
 
 template <int MT>

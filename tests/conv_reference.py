@@ -33,6 +33,39 @@ GPU_SHAPES = V4_SHAPES + [
     S(2, 6, 8, 8, 4, 3, 3, stride=(2, 1), pad=(0, 1), group=2),     # everything at once, h and w apart
 ]
 
+# The shapes at which the fast route's launch plans (csrc/conv_tile.h: conv_prod_plan; csrc/conv_plans.h:
+# conv_wdiff_plan) leave by another branch than the shapes above, which all fit the LDS on the first pass.  What a
+# comment says of a plan, tests/test_conv_plans.py reads from the C++ itself (PLANS there); tests/test_gpu_conv_plans.py
+# runs the kernels.  Per entry: the shape, the routes of forward, bottom_diff and the parameter diffs (F fast,
+# G generic), and mms_conv_workspace_bytes: max(generic slabs, fast slabs) * (K C kh kw + K) * 4.
+PLAN_CASES = [
+    # forward: a 2 x 2 map, G halves 64 -> 1, then R 2 -> 1 (two bands), and leaves with 3 of 4 channels per chunk
+    # (chunks of 3 and 1), MT 2; parameter diff: G decrements 64 -> 23, eight column groups
+    (S(3, 4, 12, 12, 17, 11, 11), "FFF", 197880),
+    # bottom_diff: MT 4, G 3 -> 1, R 9 -> 1 (nine bands), 3 of 5 channels per chunk; forward: a 1 x 1 map, G 256 -> 32,
+    # nine chunks of 4 channels, the last of 1; parameter diff: 42 column groups, G 256 -> 6
+    (S(2, 33, 9, 9, 5, 9, 9), "FFF", 106960),
+    # a 1 x 1 map with one channel each way, the kernel as large as the image; C kh kw = 81
+    (S(3, 1, 9, 9, 1, 9, 9), "FFF", 984),
+    # OW = 256, the widest a tile takes: one row per workgroup; W = 258 is too wide for the bottom_diff's tile
+    (S(1, 1, 3, 258, 1, 3, 3, bias=False), "FGF", 40),
+    # parameter diff: R decrements 6 -> 5, bands of 5 rows and of 1 row, MT 4, four slabs
+    (S(2, 3, 6, 40, 33, 1, 1), "FFF", 6336),
+    # parameter diff: G 2 -> 1, then R 9 -> 8; forward: 64 channels in chunks of 51 and 13; bottom_diff: MT 4 on two
+    # whole images per workgroup
+    (S(2, 64, 9, 14, 33, 1, 1), "FFF", 154440),
+    # conv_wdiff_plan refuses (one row of 40 channels and its top_diff tile exceed the LDS): the parameter diffs take
+    # the generic kernel behind two fast products, and the workspace is the generic kernel's
+    (S(2, 40, 3, 130, 1, 3, 1), "FFG", 968),
+    # parameter diff: 70 (image, band) units on 35 slabs of 2 with 14 bands per image: slab boundaries inside images
+    (S(5, 1, 14, 130, 1, 1, 1), "FFF", 280),
+    # forward: two chunks (6 + 2 channels) x two bands of 5 rows; 16 column groups in the parameter diff
+    (S(2, 8, 20, 40, 1, 11, 11), "FFF", 77520),
+    # forward: G halves 7 -> 4 and stays above one: image groups of 4, 4 and 1; MT 4
+    (S(9, 4, 12, 12, 33, 7, 7), "FFF", 1404216),
+]
+PLAN_SHAPES = [c[0] for c in PLAN_CASES]
+
 
 def pair(v):
     return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
