@@ -22,9 +22,10 @@
 //             bn_statistics -- chunk 0's first thread updates the running blobs and writes save_mean / save_std --
 //             and finishes its chunk of the channel's pooled elements in place with bn_pool_train_finish,
 //             csrc/bn_pool.hip's own.
-// train_route is the one place that decides; its thresholds are lines of profiles/conv_stage_train_bench.txt.
-#include "conv_pool_tile.h"
-#include "mms_conv_stage_train.h"
+// train_route is the one place that decides; its thresholds are lines of profiles/conv_stage_train_bench.txt.  The host
+// side of the two launches -- TrainArgs, train_plan, train_route, fused_bytes, train_finish_grid -- is
+// csrc/conv_stage_train_plans.h, where tests/native/conv_stage_train_plans_host.cpp reads it.
+#include "conv_stage_train_plans.h"
 #include "mms_internal.h"
 
 namespace mms {
@@ -38,78 +39,6 @@ int train_check(const mms_conv_shape* shape, int ph, int pw, int pool, StageDims
   if (pool != MMS_STAGE_POOL_AVE && pool != MMS_STAGE_POOL_MAX) return MMS_ERR_INVALID_ARG;
   g->max = pool == MMS_STAGE_POOL_MAX;
   return MMS_OK;
-}
-
-struct TrainArgs {
-  ConvProdArgs p;        // the product; p.out is y
-  const float* scale;    // MAX: the direction of a channel's scan
-  float* save_pool;      // (N, K, POH, POW): launch 1 leaves the windows' means / extrema here
-  float* part;           // [K][groups][2]: sum y, sum y*y of a workgroup's real pixels
-  int ph, pw, POH, POW;
-  int PS;                // row length of the accumulator tile [Cout][PS]
-  int groups;            // workgroups of launch 1
-  size_t lds_bytes;
-};
-
-// p.ok false: the fused launches do not reach.
-TrainArgs train_plan(const StageDims& g) {
-  TrainArgs a = {};
-  ConvProdArgs p = conv_prod_plan(g.d, MMS_CONV_PASS_FORWARD, g.ph);
-  if (!p.ok) return a;
-  // The chunk of the convolution's own plan: the two plans walk the same states until one image is left per workgroup
-  // (so G is the same), then the own plan may halve its band below ph rows.  A band no higher than the own one holds
-  // the own chunk as it is; a higher one is halved, in units of ph rows, until it does.
-  const int CC = conv_prod_plan(g.d, MMS_CONV_PASS_FORWARD, 1).CC;
-  const int khkw = p.kh * p.kw, Mpad = 16 * p.MT;
-  const long long kp = conv_round4(CC * khkw);
-  const auto fits = [&] {
-    return (long long)p.G * CC * ((p.R + p.kh - 1) * p.BW) + (long long)Mpad * kp + kp <= kConvLdsFloats;
-  };
-  while (!fits() && p.G == 1 && p.R > g.ph) {
-    p.R = (p.R / g.ph + 1) / 2 * g.ph;
-    p.bands = (p.OHt + p.R - 1) / p.R;
-  }
-  if (!fits()) return a;
-  p.CC = CC;
-  p.plane = (p.R + p.kh - 1) * p.BW;
-  p.Kpad = (int)kp;
-  p.lds_bytes = ((size_t)p.G * p.CC * p.plane + (size_t)Mpad * p.Kpad + p.Kpad) * sizeof(float);
-  a.p = p;
-  a.ph = g.ph; a.pw = g.pw; a.POH = g.POH; a.POW = g.POW;
-  const int P = p.G * p.R * p.OWt;
-  a.PS = stage_tile_row(p.Cout, P);
-  a.lds_bytes = stage_lds_bytes(p.Cout, P, p.lds_bytes);
-  a.groups = (int)stage_groups(p);
-  return a;
-}
-
-// The measured rule (tools/bench_conv_stage_train.py, profiles/conv_stage_train_bench.txt: forced FUSED against the two
-// public calls in one process, medians of seven alternating passes; "faster": the median ratio is above 1 and the two
-// ranges are apart).  A class of shapes -- pooling method x what a workgroup of launch 1 holds -- is FUSED on the span
-// of workgroup counts from the first to the last measured count at which every stage of the class is faster or level
-// with a faster count on either side; every other count, unmeasured ones included, is the SEQUENCE.  {0, -1}: no count.
-//   AVE, a band of rows (network_v4's conv0, 9 bands of 4 rows): faster at 450 workgroups (N = 50: 28.8 against 32.8 us,
-//     1.14 x), level at 1800 (0.98 x), slower at 3600, 7200 and 13653 (0.94 to 0.88 x).  FUSED at 450 only: nothing
-//     was measured between 450 and 1800.
-//   AVE, several whole images (conv1, ten each): slower at 5, 20 and 80 workgroups (0.97 x), faster at 152 (1.02 x),
-//     level at 300.  One winning count between a loss and a tie: not taken.
-//   MAX, a band of rows (network_v3's first stage, network_v5's first): v3's faster at 450 (1.13 x) and 13653 (1.06 x),
-//     level at 3600 (1.04 x); v5's faster at 350, 2800 and 10619 (1.20, 1.11, 1.08 x).  FUSED on 450 .. 10619, the
-//     counts inside both stages' spans.
-//   MAX, one whole image (v5's second stage): slower at 50, level at 400 and 1517.  Not taken.
-//   MAX, several whole images (v3's second stage, v5's third): slower or level at every count measured.  Not taken.
-//   AVE, one whole image: not measured.
-// [MAX][stage_plan_kind]: workgroups of launch 1
-constexpr StageSpan kTrainSpans[2][3] = {
-    {{0, -1}, {450, 450}, {0, -1}},
-    {{0, -1}, {450, 10619}, {0, -1}},
-};
-
-int train_route(const StageDims& g) {
-  const TrainArgs a = train_plan(g);
-  if (!a.p.ok) return MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE;
-  return kTrainSpans[g.max][stage_plan_kind(a.p)].holds(a.groups) ? MMS_CONV_STAGE_TRAIN_ROUTE_FUSED
-                                                                  : MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE;
 }
 
 // PH, PW > 0: the window's size at compile time (== s.ph, s.pw); 0: any window.
@@ -222,9 +151,6 @@ __global__ __launch_bounds__(kBnThreads) void train_finish_kernel(
   }
 }
 
-constexpr unsigned kTrainFinishWindows = 1024;     // pooled elements of a launch-2 workgroup, at least: four per thread
-constexpr unsigned kTrainFinishChunks = 64;        // ... unless that takes more workgroups per channel than this
-
 template <typename T>
 size_t bn_bytes(const StageDims& g) {
   return std::is_same<T, float>::value
@@ -247,8 +173,6 @@ BackwardCarve<T> backward_carve(const mms_conv_shape* shape, const StageDims& g)
   const size_t map = (size_t)g.d.N * g.d.K * g.d.OH * g.d.OW;
   return {round16(map * sizeof(T)), round16(bn_bytes<T>(g)), conv_bytes<T>(shape)};
 }
-
-size_t fused_bytes(const TrainArgs& a) { return (size_t)2 * a.p.Cout * a.groups * sizeof(float); }
 
 enum { kAuto = -1, kSequence = MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE, kFused = MMS_CONV_STAGE_TRAIN_ROUTE_FUSED };
 
@@ -333,13 +257,12 @@ int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_me
       });
       const int rc1 = launch_status();
       if (rc1 != MMS_OK) return rc1;
-      const unsigned PP = (unsigned)(g.POH * g.POW), windows = (unsigned)g.d.N * PP;
-      unsigned wpc = (windows + kTrainFinishChunks - 1) / kTrainFinishChunks;
-      if (wpc < kTrainFinishWindows) wpc = kTrainFinishWindows;
-      const dim3 grid2((unsigned)g.d.K, (windows + wpc - 1) / wpc);
+      const unsigned PP = (unsigned)(g.POH * g.POW);
+      const TrainFinishGrid f = train_finish_grid(g.d.N, PP);
+      const dim3 grid2((unsigned)g.d.K, f.chunks);
       hipLaunchKernelGGL(train_finish_kernel, grid2, dim3(kBnThreads), 0, as_stream(stream), (const float*)a.part,
                          a.groups, scale, shift, running_mean, running_var, top, save_pool, save_mean, save_std,
-                         (unsigned)g.d.K, PP, windows, wpc, bn_memory, (float)(1. / ((double)g.d.OH * g.d.OW)),
+                         (unsigned)g.d.K, PP, f.windows, f.wpc, bn_memory, (float)(1. / ((double)g.d.OH * g.d.OW)),
                          (float)(1. / g.d.N));
       return launch_status();
     }

@@ -1,7 +1,8 @@
 """The TRAIN-phase stage Convolution -> BN -> AvePool / MaxPool -> TanH (include/mms_conv_stage_train.h) as numpy, both
 passes: the layers of tests/conv_reference.py and tests/bn_pool_reference.py / tests/bn_maxpool_reference.py (phase
 TRAIN) in sequence, generic over the dtype; the conditioned inputs of the GPU parity tests with their conditions
-checked here; and the exact probe, whose statistics are restated in float32 from int64 sums.
+checked here; the large shapes with the plans they claim, their forward-only conditioning and the fused route's order of
+sums in float32 numpy; and the exact probe, whose statistics are restated in float32 from int64 sums.
 
     x (N, C, H, W)   weight (K, C/group, kh, kw)   bias, scale, shift, running_mean, running_var (K)
     y (N, K, OH, OW)   top, save_pool, top_diff (N, K, OH/ph, OW/pw)
@@ -33,6 +34,38 @@ FUSED_STAGES = [A, B, C, E, F, G]
 SEQUENCE_STAGES = [D]
 GPU_STAGES = FUSED_STAGES + SEQUENCE_STAGES
 PARITY_STAGES = [A, B, C, D]
+
+# The shapes at which the fused forward's two launches take the sizes the main call routes to them (kTrainSpans), each
+# with the claim it is there for.  LARGE_PLANS has the claims as fields of what tests/native/
+# conv_stage_train_plans_host.cpp prints from the C++ (tests/test_conv_stage_train_plans.py holds them to it): launch 1's
+# plan, launch 2's grid and the route of the main call per method.
+P = ST(41, 3, 12, 12, 5, 3, 3, (2, 2))          # 2 images per workgroup, 21 workgroups, the last with one image; 1025
+                                                # pooled elements per channel: 2 chunks in launch 2, the second holds one
+Q = ST(513, 3, 12, 12, 5, 3, 3, (2, 2))         # 257 workgroups: thread 0 of launch 2 adds two partials, the last image
+                                                # group is ragged; 12825 pooled elements: 13 chunks, the last of 537
+R = ST(225, 3, 22, 22, 7, 3, 3, (4, 4))         # F at the batch where its bands of 12 and 8 rows are 450 workgroups: the
+                                                # main call FUSES, AVE and MAX; 5625 pooled elements: 6 chunks
+R_MINUS = ST(224, 3, 22, 22, 7, 3, 3, (4, 4))   # 448 workgroups: one step below both spans
+R_PLUS = ST(226, 3, 22, 22, 7, 3, 3, (4, 4))    # 452 workgroups: past AVE's span, inside MAX's
+W = ST(657, 2, 22, 22, 4, 3, 3, (2, 2))         # two bands of 10 rows, 1314 workgroups (blockIdx.x up to 656); 65700
+                                                # pooled elements: past the cap of 64 chunks, 1027 each, the last of 999
+LARGE_STAGES = [P, Q, R, R_MINUS, R_PLUS, W]
+SEQ, FUSED = "sequence", "fused"
+LARGE_PLANS = {
+    P: dict(plan=dict(kind=0, G=2, R=10, bands=1, groups=21, last_images=1, CC=3, MT=1),
+            finish=dict(windows=1025, wpc=1024, chunks=2, last=1), route={AVE: SEQ, MAX: SEQ}),
+    Q: dict(plan=dict(kind=0, G=2, R=10, bands=1, groups=257, last_images=1, CC=3, MT=1),
+            finish=dict(windows=12825, wpc=1024, chunks=13, last=537), route={AVE: SEQ, MAX: SEQ}),
+    R: dict(plan=dict(kind=1, G=1, R=12, bands=2, last_rows=8, groups=450, CC=3, MT=1),
+            finish=dict(windows=5625, wpc=1024, chunks=6, last=505), route={AVE: FUSED, MAX: FUSED}),
+    R_MINUS: dict(plan=dict(kind=1, G=1, R=12, bands=2, last_rows=8, groups=448, CC=3, MT=1),
+                  finish=dict(windows=5600, wpc=1024, chunks=6, last=480), route={AVE: SEQ, MAX: SEQ}),
+    R_PLUS: dict(plan=dict(kind=1, G=1, R=12, bands=2, last_rows=8, groups=452, CC=3, MT=1),
+                 finish=dict(windows=5650, wpc=1024, chunks=6, last=530), route={AVE: SEQ, MAX: FUSED}),
+    W: dict(plan=dict(kind=1, G=1, R=10, bands=2, last_rows=10, groups=1314, CC=2, MT=1),
+            finish=dict(windows=65700, wpc=1027, chunks=64, last=999), route={AVE: SEQ, MAX: FUSED}),
+}
+FOLD_THREADS, WAVE = 256, 64     # launch 2: kBnThreads threads fold the partials, csrc/bn_common.h; a wave's lanes
 
 GAP = BM.GAP                     # the least top-two gap of a window's BN outputs, relative to max(1, |y|)
 MIN_VAR, MIN_SCALE = 1e-2, 0.5
@@ -126,6 +159,100 @@ def conditioned_inputs(st, dtype, seed):
     raise AssertionError("no conditioned inputs for %s" % (st,))
 
 
+def forward_conditioned(st, inp):
+    var, scale, _ = conditions(st, inp)
+    return var >= MIN_VAR and scale >= MIN_SCALE
+
+
+def forward_conditioned_inputs(st, dtype, seed):
+    """conditioned_inputs' draws with the variance and the scale condition only.  The top-two gap protects the backward's
+    mask; it cannot hold over the 10^4 to 10^5 windows of LARGE_STAGES, whose parity is forward-only -- the forward's
+    extremum is continuous in y, whichever element attains it.  Read-only arrays."""
+    for attempt in range(200):
+        out = _draw(st, dtype, seed + RETRY_STEP * attempt)
+        if forward_conditioned(st, out):
+            for v in out.values():
+                if v is not None:
+                    v.setflags(write=False)
+            return out
+    raise AssertionError("no forward-conditioned inputs for %s" % (st,))
+
+
+def model_forward(st, method, inp):
+    """The seven forward outputs of the float64 model on inp (cast to float64), under FORWARD_OUTPUTS' names."""
+    c = {k: (None if v is None else np.asarray(v).astype(np.float64)) for k, v in inp.items()}
+    return dict(zip(FORWARD_OUTPUTS, forward(st, method, c["x"], c["weight"], c["bias"], c["scale"], c["shift"],
+                                             c["running_mean"], c["running_var"])))
+
+
+# ---- the fused route's statistics in float32 ---------------------------------------------------------------------
+def _tree_sum(v):
+    """(..., 2^k) -> (...): adjacent pairs, then pairs of pairs, ...: the shape of wave_sum's butterfly (csrc/mms_common.h)."""
+    while v.shape[-1] > 1:
+        v = v[..., 0::2] + v[..., 1::2]
+    return v[..., 0]
+
+
+def fused_partials(y, G, R, bands):
+    """Launch 1 as the fused route documents it: (K, groups, 2) float32, sum y and sum y*y of the real pixels of
+    workgroup wg = image group * bands + band -- G images, rows [band R, band R + R) of each, the last group and the last
+    band what is left -- each one numpy sum in float32."""
+    f = np.float32
+    assert y.dtype == f
+    N, K = y.shape[:2]
+    gx = (N + G - 1) // G
+    part = np.zeros((K, gx * bands, 2), f)
+    for bx in range(gx):
+        for by in range(bands):
+            blk = y[bx * G:(bx + 1) * G, :, by * R:(by + 1) * R]
+            assert blk.size
+            part[:, bx * bands + by, 0] = blk.sum(axis=(0, 2, 3), dtype=f)
+            part[:, bx * bands + by, 1] = (blk * blk).sum(axis=(0, 2, 3), dtype=f)
+    return part
+
+
+def fold_partials(part):
+    """Launch 2's prologue: thread t of FOLD_THREADS adds the partials of workgroups t, t + 256, ... ascending from 0,
+    then bn_block_sum -- a butterfly inside each wave, the waves ascending.  (K, groups, 2) -> (K, 2), float32."""
+    f = np.float32
+    K, groups = part.shape[:2]
+    rounds = (groups + FOLD_THREADS - 1) // FOLD_THREADS
+    padded = np.zeros((K, rounds * FOLD_THREADS, 2), f)
+    padded[:, :groups] = part
+    tot = np.zeros((K, FOLD_THREADS, 2), f)
+    for r in range(rounds):
+        tot = tot + padded[:, r * FOLD_THREADS:(r + 1) * FOLD_THREADS]
+    waves = _tree_sum(tot.reshape(K, FOLD_THREADS // WAVE, WAVE, 2).transpose(0, 1, 3, 2))      # (K, waves, 2)
+    out = waves[:, 0]
+    for w in range(1, FOLD_THREADS // WAVE):
+        out = out + waves[:, w]
+    assert out.dtype == f
+    return out
+
+
+def statistics_f32(st, inp, s0, s1, memory, N=None):
+    """bn_statistics (csrc/bn_common.h) in float32 from the two channel sums, every step one rounded operation.
+    -> save_mean, save_std, running_mean, running_var."""
+    f = np.float32
+    OH, OW = CR.output_dims(st.conv)
+    inv_S, inv_N = f(1.0 / (OH * OW)), f(1.0 / (st.conv.N if N is None else N))
+    mean = inv_N * (inv_S * s0.astype(f))
+    var = inv_N * (inv_S * s1.astype(f)) - mean * mean
+    std = np.sqrt(var + f(VAR_EPS))
+    keep, take = f(memory), f(1) - f(memory)
+    return mean, std, take * mean + keep * inp["running_mean"].astype(f), take * var + keep * inp["running_var"].astype(f)
+
+
+def fused_statistics_f32(st, inp, G, R, bands, memory=BN_MEMORY):
+    """save_mean, save_std, running_mean, running_var as float32 arithmetic alone gives them on the fused route's order of
+    sums: y is the float64 model's map rounded to float32, summed by fused_partials and fold_partials."""
+    c = {k: inp[k].astype(np.float64) for k in ("x", "weight")}
+    bias = None if inp["bias"] is None else inp["bias"].astype(np.float64)
+    y = CR.conv_forward(st.conv, c["x"], c["weight"], bias).astype(np.float32)
+    tot = fold_partials(fused_partials(y, G, R, bands))
+    return dict(zip(FORWARD_OUTPUTS[3:], statistics_f32(st, inp, tot[:, 0], tot[:, 1], memory)))
+
+
 # ---- the exact probe ---------------------------------------------------------------------------------------------
 PROBE_MEMORY = 0.5               # bn_memory of the probe: 1 - 0.5 is exact
 ZERO_CHANNEL, NEGATIVE_CHANNEL, POSITIVE_CHANNEL = 0, 1, 2
@@ -169,11 +296,4 @@ def probe_sums(st, inp, images=None):
 def probe_statistics(st, inp, s0, s1, N=None):
     """bn_statistics (csrc/bn_common.h) in float32 from the exact sums: every step one correctly rounded operation, so
     these are the library's words.  -> save_mean, save_std, running_mean, running_var."""
-    f = np.float32
-    OH, OW = CR.output_dims(st.conv)
-    inv_S, inv_N = f(1.0 / (OH * OW)), f(1.0 / (st.conv.N if N is None else N))
-    mean = inv_N * (inv_S * s0.astype(f))
-    var = inv_N * (inv_S * s1.astype(f)) - mean * mean
-    std = np.sqrt(var + f(VAR_EPS))
-    keep, take = f(PROBE_MEMORY), f(1) - f(PROBE_MEMORY)
-    return mean, std, take * mean + keep * inp["running_mean"], take * var + keep * inp["running_var"]
+    return statistics_f32(st, inp, s0, s1, PROBE_MEMORY, N)

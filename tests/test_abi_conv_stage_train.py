@@ -286,7 +286,7 @@ def test_route_and_queries_are_pure_functions_of_the_shape(stage, conv, hiplib):
 def test_the_gpu_lists_are_on_the_routes_they_claim(stage, conv, hiplib):
     no_x = [None] + distinct(12)[1:]
     for pool in POOLS:
-        for st in R.FUSED_STAGES:
+        for st in R.FUSED_STAGES + R.LARGE_STAGES:
             assert fwd(hiplib, FORWARDS[3], C.byref(_cshape(conv, st)), *st.pool, pool, no_x) == INVALID, st
         for st in R.SEQUENCE_STAGES:
             assert fwd(hiplib, FORWARDS[3], C.byref(_cshape(conv, st)), *st.pool, pool, distinct(12)) == UNSUPPORTED
@@ -307,6 +307,23 @@ def test_the_nets_stages_take_the_measured_routes(stage, conv):
         assert stage.conv_stage_train_route(conv.conv_shape(N, 32, 19, 19, 32, 4), 2, "max") == S
         assert stage.conv_stage_train_route(conv.conv_shape(N, 32, 8, 8, 32, 3), 6, "max") == S
         assert stage.conv_stage_train_route_f64(v4a(N), 4, "ave") == S
+
+
+def test_the_large_gpu_shapes_take_the_routes_they_claim(stage, conv):
+    """The shapes at which tests/test_gpu_conv_stage_train.py runs the main call inside and beside the spans: two bands
+    per image (R: 12 and 8 rows; W: 10 and 10), so 2 N workgroups."""
+    F, S = stage.ROUTE_FUSED, stage.ROUTE_SEQUENCE
+    r = lambda N: conv.conv_shape(N, 3, 22, 22, 7, 3)                                  # noqa: E731
+    w = lambda N: conv.conv_shape(N, 2, 22, 22, 4, 3)                                  # noqa: E731
+    assert [R.R_MINUS.conv.N, R.R.conv.N, R.R_PLUS.conv.N, R.W.conv.N] == [224, 225, 226, 657]
+    assert [stage.conv_stage_train_route(r(N), 4, "ave") for N in (224, 225, 226)] == [S, F, S]
+    assert [stage.conv_stage_train_route(r(N), 4, "max") for N in (224, 225, 226)] == [S, F, F]
+    assert [stage.conv_stage_train_route(w(N), 2, m) for N in (224, 225, 657) for m in ("ave", "max")] == [S, S, F, F, S, F]
+    for st in R.LARGE_STAGES:
+        for method in R.METHODS:
+            got = stage.conv_stage_train_route(_cshape(conv, st), st.pool, method)
+            assert got == (F if R.LARGE_PLANS[st]["route"][method] == R.FUSED else S), (st, method)
+            assert stage.conv_stage_train_route_f64(_cshape(conv, st), st.pool, method) == S
 
 
 def test_binding_refuses_before_the_library(stage):

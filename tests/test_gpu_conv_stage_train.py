@@ -1,7 +1,9 @@
 """GPU suite of the TRAIN-phase stage Convolution -> BN -> AvePool / MaxPool -> TanH (include/mms_conv_stage_train.h):
 both passes on every route against the float64 model, y against the convolution's own words, exact probes on which the
 fused and the sequence route must agree to the word, determinism under garbage workspaces and shifted bases, padding
-pixels, optional backward outputs, and the sequence route against the public calls issued here."""
+pixels, optional backward outputs, and the sequence route against the public calls issued here; then the same on the
+launch sizes the main call routes to the fused forward (R.LARGE_STAGES: several chunks per channel in launch 2, more
+than 256 partials per channel, the main call inside and beside the measured spans)."""
 import functools
 
 import numpy as np
@@ -272,6 +274,175 @@ def test_sequence_route_is_the_public_calls(st, method, hiplib):
     want = dict(y=y, top=top, save_pool=sp, save_mean=sm, save_std=ss, running_mean=rm, running_var=rv, bottom_diff=dx,
                 weight_diff=dw, bias_diff=db, scale_diff=dsc, shift_diff=dsh)
     same_words(got, {k: V.host(v) for k, v in want.items()}, "the sequence route against the public calls")
+
+
+# ---- the launch sizes the main call routes to the fused forward (R.LARGE_STAGES) ---------------------------------------
+# What each shape reaches is held to the C++ by tests/test_conv_stage_train_plans.py, on the CPU; the bar is the
+# project's, which float32 alone meets on the fused order of sums (same file).  Forward only beyond the exact probe: the
+# fused route has no backward of its own, and the large shapes' inputs carry no top-two gap.
+STATISTICS = ("save_mean", "save_std", "running_mean", "running_var")
+LARGE_ROUTES = ("auto", "sequence", "fused")
+
+
+@functools.lru_cache(maxsize=None)
+def large_inputs(st, dtype):
+    return R.forward_conditioned_inputs(st, dtype, SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def large_model(st, method, dtype):
+    out = R.model_forward(st, method, large_inputs(st, dtype))
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def large_forward(st, method, route):
+    """The float forward on the conditioned inputs, once per (shape, method, route); shared, never modified."""
+    out = run(st, method, large_inputs(st, np.float32), route=route, backward=False)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+def routed(st, method):
+    """The forced route whose words the main call must give: LARGE_PLANS' claim, which the CPU suite holds to the route
+    call."""
+    named = {mod().ROUTE_SEQUENCE: R.SEQ, mod().ROUTE_FUSED: R.FUSED}[mod().conv_stage_train_route(cshape(st), st.pool, method)]
+    assert named == R.LARGE_PLANS[st]["route"][method]
+    return named
+
+
+def check_forward_parity(got, want, dtype, what):
+    assert sorted(got) == sorted(want) == sorted(R.FORWARD_OUTPUTS)
+    ratios = {}
+    for k in R.FORWARD_OUTPUTS:
+        assert got[k].dtype == dtype and np.isfinite(got[k]).all(), k
+        scale = max(1.0, float(np.max(np.abs(want[k]))))
+        ratios[k] = float(np.max(np.abs(got[k].astype(np.float64) - want[k]))) / (BAR[dtype] * scale)
+    print("%-32s %s" % (what, "  ".join("%s %.3g" % (k, ratios[k]) for k in R.FORWARD_OUTPUTS)))
+    for k in R.FORWARD_OUTPUTS:
+        assert ratios[k] <= 1.0, "%s, %s: %.3g of the bar" % (k, what, ratios[k])
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", R.LARGE_STAGES, ids=IDS(R.LARGE_STAGES))
+def test_large_exact_probe_fused_equals_sequence(st, method, hiplib):
+    """Integer y, every partial sum exact in any order: the fused route (whatever its count of partials per thread and
+    of chunks per channel), the sequence and the main call give the same words in every output of both passes; y is the
+    int64 model's and the statistics are the float32 restatement from the int64 sums, bit for bit -- a statistic written
+    twice, a partial dropped, doubled or read from another slot shows here."""
+    inp = probe(st)
+    y, s0, s1 = R.probe_sums(st, inp)
+    fused = run(st, method, inp, route="fused", memory=R.PROBE_MEMORY)
+    seq = run(st, method, inp, route="sequence", memory=R.PROBE_MEMORY)
+    auto = run(st, method, inp, memory=R.PROBE_MEMORY)
+    for k, v in fused.items():
+        assert not np.isnan(v).any(), k
+    same_words(fused, seq, "exact probe, fused against sequence")
+    same_words(auto, seq, "exact probe, the main call against sequence")
+    assert_words_equal(fused["y"], y.astype(np.float32), "y against the int64 model")
+    for k, want in zip(STATISTICS, R.probe_statistics(st, inp, s0, s1)):
+        assert_words_equal(fused[k], want, k + " against the int64 sums")
+    if method == R.MAX:                       # ties: the scan's winner by the sign of scale, first element for scale == 0
+        w = R.BM.windows(y, *st.pool)
+        mean, std = fused["save_mean"], fused["save_std"]
+        for k, pick in ((R.ZERO_CHANNEL, w[:, R.ZERO_CHANNEL, ..., 0]),
+                        (R.NEGATIVE_CHANNEL, w[:, R.NEGATIVE_CHANNEL].min(axis=-1)),
+                        (R.POSITIVE_CHANNEL, w[:, R.POSITIVE_CHANNEL].max(axis=-1))):
+            want = (pick.astype(np.float32) + (-mean[k])) / std[k]
+            assert_words_equal(fused["save_pool"][:, k], want, "save_pool of channel %d" % k)
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", R.LARGE_STAGES, ids=IDS(R.LARGE_STAGES))
+def test_large_forward_parity(st, method, hiplib):
+    """The main call, the forced sequence and the forced fused launches in float, and the double call: the seven forward
+    outputs against the float64 model at the project's bars (printed: each output's share of its bar); y is the
+    convolution's own words on every float route."""
+    from mms_answer_selection_amd import conv
+    s, inp = st.conv, large_inputs(st, np.float32)
+    dev = {k: V.placed(inp[k], np.float32) for k in ("x", "weight", "bias")}
+    own = V.host(conv.conv_forward(dev["x"], dev["weight"], dev["bias"], stride=s.stride, pad=s.pad, group=s.group))
+    for route in LARGE_ROUTES:
+        got = large_forward(st, method, route)
+        check_forward_parity(got, large_model(st, method, np.float32), np.float32, "%s f32 %s" % (method, route))
+        assert_words_equal(got["y"], own, "y, %s, %s route" % (method, route))
+    got = run(st, method, large_inputs(st, np.float64), np.float64, backward=False)
+    check_forward_parity(got, large_model(st, method, np.float64), np.float64, "%s f64" % method)
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", R.LARGE_STAGES, ids=IDS(R.LARGE_STAGES))
+def test_large_determinism_and_workspace(st, method, hiplib):
+    """On every float route: a second run with every array one element off a 16-byte boundary, one with a workspace of
+    exactly the queried size full of NaN words and one full of other garbage give the first run's words and leave the
+    workspace's guard zones alone -- where the main call fuses (R.R; R.R_PLUS and R.W with MAX) the queried size is the
+    main call's own, max(the partial sums, the backward's carve).  The forced fused query holds the partial sums."""
+    inp = large_inputs(st, np.float32)
+    partials = 2 * st.conv.K * R.LARGE_PLANS[st]["plan"]["groups"] * 4
+    assert mod().conv_stage_train_workspace_bytes(cshape(st), st.pool, method, route="fused") >= partials
+    for route in LARGE_ROUTES:
+        first = large_forward(st, method, route)
+        same_words(run(st, method, inp, route=route, shift=1, backward=False), first, "shifted second run, " + route)
+        same_words(run(st, method, inp, route=route, ws_fill=float("nan"), backward=False), first, "NaN workspace, " + route)
+        same_words(run(st, method, inp, route=route, ws_fill=-3.5e37, backward=False), first, "garbage workspace, " + route)
+
+
+def routes_differ(st, method):
+    """The outputs in which the forced fused and the forced sequence forward differ in some word."""
+    fused, seq = large_forward(st, method, "fused"), large_forward(st, method, "sequence")
+    return [k for k in R.FORWARD_OUTPUTS if (fused[k].view(np.uint32) != seq[k].view(np.uint32)).any()]
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", R.LARGE_STAGES, ids=IDS(R.LARGE_STAGES))
+def test_the_main_call_fuses_inside_the_spans(st, method, hiplib):
+    """On conditioned inputs the main call gives the words of the forced route the span table names: fused at R.R (both
+    methods) and at R.R_PLUS and R.W with MAX; the sequence at R.R_MINUS, at R.R_PLUS and R.W with AVE and at R.P and
+    R.Q.  Where the two forced routes differ in a last bit (printed) this tells which one the main call ran;
+    test_the_two_routes_differ_somewhere asserts that they do."""
+    named = routed(st, method)
+    print("%s %s: the main call is the %s route; fused and sequence differ in %s" % (
+        R.stage_id(st), method, named, routes_differ(st, method) or "no word"))
+    same_words(large_forward(st, method, "auto"), large_forward(st, method, named), "the main call against " + named)
+
+
+def test_the_two_routes_differ_somewhere(hiplib):
+    """What makes test_the_main_call_fuses_inside_the_spans tell the routes apart: at one of its shapes at least, inside
+    a span and beside one, the two routes' statistics differ in some word (their orders of sums differ)."""
+    inside = [(st, m) for st in R.LARGE_STAGES for m in R.METHODS if R.LARGE_PLANS[st]["route"][m] == R.FUSED]
+    beside = [(st, m) for st in (R.R_MINUS, R.R_PLUS, R.W) for m in R.METHODS if R.LARGE_PLANS[st]["route"][m] == R.SEQ]
+    assert len(inside) == 4 and len(beside) == 4
+    for cases in (inside, beside):
+        assert any(set(routes_differ(st, m)) & set(STATISTICS + ("top", "save_pool")) for st, m in cases)
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+def test_finish_chunks_partition_the_batch(method, hiplib):
+    """R.P: 1025 pooled elements per channel, so launch 2's second workgroup of a channel finishes one element, the last
+    image's last.  Every element of top and save_pool is finite (none left as the NaN prefill or as the raw pooled
+    value's garbage), that element is at the model's value in every channel, and the first 40 images' y is the 40-image
+    run's (one chunk), word for word."""
+    st = R.P
+    assert R.LARGE_PLANS[st]["finish"] == dict(windows=1025, wpc=1024, chunks=2, last=1)
+    got, want = large_forward(st, method, "fused"), large_model(st, method, np.float32)
+    for k in ("top", "save_pool"):
+        assert np.isfinite(got[k]).all(), k
+        lone_got = got[k].transpose(1, 0, 2, 3).reshape(st.conv.K, -1)[:, 1024:]
+        lone_want = want[k].transpose(1, 0, 2, 3).reshape(st.conv.K, -1)[:, 1024:]
+        assert lone_got.shape == (st.conv.K, 1)
+        scale = max(1.0, float(np.max(np.abs(want[k]))))
+        err = float(np.max(np.abs(lone_got.astype(np.float64) - lone_want)))
+        print("%s, element 1024 of each channel: %.3g of the bar" % (k, err / (BAR[np.float32] * scale)))
+        assert err <= BAR[np.float32] * scale, k
+    inp = large_inputs(st, np.float32)
+    st40 = R.ST(40, *st.conv[1:7], st.pool)
+    part = {k: (v[:40] if k in ("x", "top_diff") else v) for k, v in inp.items()}
+    one_chunk = run(st40, method, part, route="fused", backward=False)
+    assert np.isfinite(one_chunk["top"]).all() and np.isfinite(one_chunk["save_pool"]).all()
+    assert_words_equal(one_chunk["y"], got["y"][:40], "y of images 0..39")
 
 
 @pytest.mark.parametrize("dtype", V.DTYPES, ids=V.IDS)
