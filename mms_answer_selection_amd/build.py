@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmms_hip.so")
 LAYER_LIB = os.path.join(HERE, "libmms_caffe.so")
 
-HIP_SOURCES = ["mms_abi.hip", "net_glue.hip", "simcross_rows.hip", "simcross_rows_cosine.hip", "simcross_rows_f16.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "rank_onewg.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "conv_stage.hip", "conv_stage_train.hip", "head.hip", "score_tail.hip", "train_tail.hip", "solver.hip", "dropout.hip", "pool.hip", "fc.hip"]
+HIP_SOURCES = ["mms_abi.hip", "net_glue.hip", "simcross_rows.hip", "simcross_rows_cosine.hip", "simcross_rows_f16.hip", "simcross_cross.hip", "simcross_cross_f16.hip", "gemm32.hip", "bilinear.hip", "bilinear_f16.hip", "simmatrix.hip", "pairrank.hip", "triplet_steps.hip", "ranking.hip", "rank_onewg.hip", "embed.hip", "f64_paths.hip", "fm.hip", "bn.hip", "bn_pool.hip", "conv.hip", "conv_stage.hip", "conv_stage_train.hip", "head.hip", "score_tail.hip", "train_tail.hip", "train_tail_backward.hip", "solver.hip", "dropout.hip", "pool.hip", "fc.hip"]
 # libmms_caffe.so: the Caffe-API mirror, host code compiled as HIP sources (caffe_api.hpp includes the HIP runtime header)
 LAYER_SOURCES = ["caffe_runtime.cpp", "prototxt_reader.cpp", "layers_scoring.cpp", "layers_embed.cpp", "layers_metrics.cpp",
                  "layers_hdf5data.cpp", "path_net.cpp", "layer_handles.cpp", "caffemodel_io.cpp", "hdf5_io.cpp"]

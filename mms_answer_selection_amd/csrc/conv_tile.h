@@ -137,13 +137,21 @@ struct ConvTile {
   int n0, gc, oy0, rb, per, P;
 };
 
+// The product's own read of its input: element (n, c, iy, ix) of a.in.  A caller that forms the operand on the fly
+// (csrc/train_tail_backward.hip: top_diff from y and per-channel coefficients) passes another.
+struct ConvLoadInput {
+  __device__ __forceinline__ float operator()(const ConvProdArgs& a, int n, int c, int iy, int ix) const {
+    return a.in[(((size_t)n * a.Cin + c) * a.IH + iy) * a.IW + ix];
+  }
+};
+
 // The product of one workgroup (kConvThreads threads, lds: a.lds_bytes at least).  Wave w owns pixel tiles w + 4 nt;
 // its lane (l16, grp) ends with acc[mt][nt][r] = pixel (w + 4 nt) * 16 + l16, output channel 16 mt + 4 grp + r, WITHOUT
 // the bias.  epi.pixel(a, t, nt, img, r, c) is told each of the lane's pixels before the loop (pixel 0's coordinates
 // where valid[nt] is false); epi.finish(a, t, acc, valid) gets the sums.  No barrier follows the last chunk: a finish
-// that writes LDS places one first.
-template <int MT, class Epi>
-__device__ __forceinline__ void conv_tile_product(const ConvProdArgs& a, float* lds, Epi& epi) {
+// that writes LDS places one first.  load(a, n, c, iy, ix) is element (n, c, iy, ix) of the (N, Cin, IH, IW) operand.
+template <int MT, class Epi, class Load = ConvLoadInput>
+__device__ __forceinline__ void conv_tile_product(const ConvProdArgs& a, float* lds, Epi& epi, Load load = Load()) {
   constexpr int NT = kConvNT, Mpad = 16 * MT;
   float* band = lds;                                    // [G][CC][BR][BW]
   float* wsm = band + a.G * a.CC * a.plane;             // [Kpad][Mpad]
@@ -200,8 +208,7 @@ __device__ __forceinline__ void conv_tile_product(const ConvProdArgs& a, float* 
       const int cl = tt % cc, img = tt / cc;
       const int iy = oy0 + br - a.vph, ix = bc - a.vpw;
       float v = 0.f;
-      if (iy >= 0 && iy < a.IH && ix >= 0 && ix < a.IW)
-        v = a.in[(((size_t)(n0 + img) * a.Cin + ci0 + cl) * a.IH + iy) * a.IW + ix];
+      if (iy >= 0 && iy < a.IH && ix >= 0 && ix < a.IW) v = load(a, n0 + img, ci0 + cl, iy, ix);
       band[(img * a.CC + cl) * a.plane + br * a.BW + bc] = v;
     }
     __syncthreads();
@@ -232,6 +239,32 @@ __device__ __forceinline__ float conv_tile_bias(const ConvProdArgs& a, int m) { 
 __device__ __forceinline__ float conv_tile_word(const ConvProdArgs& a, float acc, float b) {
   return a.bias ? acc + b : acc;
 }
+
+// The epilogue that stores the map: csrc/conv.hip's forward and bottom_diff, csrc/train_tail_backward.hip's bottom_diff.
+struct ConvStoreEpilogue {
+  size_t outoff[kConvNT];
+  size_t PI;
+  __device__ __forceinline__ void pixel(const ConvProdArgs& a, const ConvTile& t, int nt, int img, int r, int c) {
+    outoff[nt] = (size_t)(t.n0 + img) * a.Cout * PI + (size_t)(t.oy0 + r) * a.OWt + c;
+  }
+  // lane: pixel column l16, output channels 16 mt + 4 grp + r
+  template <int MT>
+  __device__ __forceinline__ void finish(const ConvProdArgs& a, const ConvTile&, const conv_v4f (&acc)[MT][kConvNT],
+                                         const bool (&pvalid)[kConvNT]) {
+    const int grp = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = 16 * mt + 4 * grp + r;
+        if (m >= a.Cout) continue;
+        const float b = conv_tile_bias(a, m);
+#pragma unroll
+        for (int nt = 0; nt < kConvNT; ++nt)
+          if (pvalid[nt]) a.out[outoff[nt] + (size_t)m * PI] = conv_tile_word(a, acc[mt][nt][r], b);
+      }
+  }
+};
 
 template <class F>
 inline void conv_with_mt(int MT, F&& f) {

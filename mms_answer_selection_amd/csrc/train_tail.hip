@@ -35,6 +35,7 @@
 #include "mms_conv_stage_train.h"
 #include "mms_internal.h"
 #include "mms_train_tail.h"
+#include "train_tail_check.h"
 
 namespace mms {
 namespace {
@@ -50,27 +51,6 @@ constexpr int kTrainTailMaxLdsBytes = 163840;   // a launch's LDS, at most: the 
 // second launch's workgroups each add N partials per channel; those counts go to the sequence (kTrainTailGroups).
 constexpr int kTrainTailImages = 1;
 constexpr int kTrainTailFold = 8;               // channels of one bn_block_sum in launch 2
-
-struct TrainTailDims : StageDims {
-  mms_head_shape hs;         // the head call's shape
-  HeadDims hd;
-  int pool;
-};
-
-// the refusal of the shape, else MMS_OK and *g
-int train_tail_check(const mms_score_tail_shape* s, int phase, float dropout_ratio, TrainTailDims* g) {
-  if (!s) return MMS_ERR_INVALID_ARG;
-  if (s->pool != MMS_STAGE_POOL_AVE && s->pool != MMS_STAGE_POOL_MAX) return MMS_ERR_INVALID_ARG;
-  const int rc = stage_window_check(&s->conv, s->ph, s->pw, g);
-  if (rc != MMS_OK) return rc;
-  if (g->d.OH != g->ph || g->d.OW != g->pw) return MMS_ERR_INVALID_ARG;
-  if (phase != MMS_HEAD_TRAIN) return MMS_ERR_INVALID_ARG;
-  g->max = s->pool == MMS_STAGE_POOL_MAX;
-  g->pool = s->pool;
-  g->hs = {g->d.N, g->d.K, s->F1, s->H, s->C, MMS_HEAD_TRAIN, dropout_ratio, s->normalization, s->has_ignore_label,
-           s->ignore_label};
-  return head_check(&g->hs, &g->hd);
-}
 
 struct TrainTailArgs {
   ConvProdArgs p;            // conv_prod_plan(d, forward, ph) with G cut to the tail's; p.out is y
@@ -502,16 +482,10 @@ int train_tail_backward(const mms_score_tail_shape* shape, int phase, float drop
   int rc = train_tail_check(shape, phase, dropout_ratio, &g);
   if (rc != MMS_OK) return rc;
   if (g.d.N == 0) return MMS_OK;
-  if (!x || !w || !y || !flt || !save_pool || !scale || (g.max && !shift) || !save_mean || !save_std || !w1 || !w2 ||
-      !mask || !h || !prob || !label || (g.hd.F1 > 0 && !overlap))
-    return MMS_ERR_INVALID_ARG;
-  if (g.hd.F1 == 0) doverlap = nullptr;      // an array of no elements
-  const bool stage = dx || dw || db || dscale || dshift, head = doverlap || w1d || b1d || w2d || b2d;
-  if (!stage && !head) return MMS_ERR_INVALID_ARG;
-  const void* const arrays[] = {x,    w,    y,     flt, save_pool, scale,  shift,  save_mean, save_std, overlap, w1,  w2,  mask,
-                                h,    prob, label, dx,  dw,        db,     dscale, dshift,    doverlap, w1d,     b1d, w2d, b2d};
-  const void* const ws_only[] = {workspace};
-  if (stage_outputs_alias(arrays, ws_only)) return MMS_ERR_INVALID_ARG;     // any two arrays, the workspace included
+  bool stage;
+  rc = train_tail_backward_args(g, x, w, y, flt, save_pool, scale, shift, save_mean, save_std, overlap, w1, w2, mask, h,
+                                prob, label, dx, dw, db, dscale, dshift, &doverlap, w1d, b1d, w2d, b2d, workspace, &stage);
+  if (rc != MMS_OK) return rc;
   const TrainTailCarve carve = train_tail_carve<T>(shape, g);
   if (!workspace || workspace_bytes < carve.total()) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(workspace);
