@@ -34,6 +34,10 @@ SEQUENCE_STAGES = A.SEQUENCE_STAGES
 GPU_STAGES = FUSED_STAGES + SEQUENCE_STAGES
 # the stages whose two routes cut the input channels into the same chunks (one chunk): fused and sequence, the same words
 SAME_CHUNK_STAGES = [NET_STAGES[0], NET_STAGES[2]]
+# ... and conv_stage_reference's INSTANTIATION_STAGES, one per instantiation of the pooling epilogue: both plans have the
+# same CC at each (several chunks at two of them), which tests/test_conv_stage_plans.py reads from the C++
+SAME_WORDS_STAGES = SAME_CHUNK_STAGES + A.INSTANTIATION_STAGES
+NAN_STAGES = SAME_CHUNK_STAGES + [A.INSTANTIATION["a"], A.INSTANTIATION["g"]]     # test_a_window_holding_one_nan's
 
 ZERO_CHANNEL, NEGATIVE_CHANNEL = 0, 1                   # scale exactly 0.0 / negative at every stage (K >= 3 everywhere)
 

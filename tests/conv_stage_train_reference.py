@@ -12,6 +12,7 @@ import numpy as np
 import bn_maxpool_reference as BM
 import bn_pool_reference as BP
 import conv_reference as CR
+import conv_stage_reference as SR
 from conv_stage_reference import ST, pooled_shape, stage_id                    # noqa: F401 (the callers' names)
 
 AVE, MAX = "ave", "max"
@@ -30,7 +31,25 @@ F = ST(2, 3, 22, 22, 7, 3, 3, (4, 4))           # 20 x 20: the window makes the 
 G = ST(2, 32, 24, 24, 32, 5, 5, (4, 4))         # 20 x 20 again, 32 channels: a band of 12 rows holds 13 input channels
                                                 # where the convolution's own 10 rows hold 14, so the fused plan
                                                 # halves its band to 8 rows to keep the convolution's chunk
-FUSED_STAGES = [A, B, C, E, F, G]
+# conv_stage_reference's shapes, one per instantiation of the pooling epilogue (train_product_kernel<MT, MAX, PH, PW>:
+# the same window forms, and TK = 256 / (16 MT) lanes folding a channel's sums), the two without a bias included.  What
+# each reaches is there; tests/test_conv_stage_plans.py holds it to the C++, train_plan's figures among them.
+I = SR.INSTANTIATION
+Ia, Ib, Ic, Id, Ie, If, Ig, Ih, Ik, Il, Im, Is = (I[k] for k in "abcdefghklms")
+INSTANTIATION_STAGES = SR.INSTANTIATION_STAGES
+# The exact probe's mean is exact where N * OH * OW is a power of two (Ia's 2048 and Is's 512 are): where the batch alone
+# keeps a shape above from it, the nearest batch that gives one; Il on a 16 x 16 map.  (Id, Ie, If, Ih, Ik and Im have maps of
+# 100, 300, 144, 36, 225 and 100 pixels: no batch does.)
+Ib8 = ST(8, 8, 10, 10, 64, 3, 3, (4, 4))        # 512: two full workgroups of four images
+Ic4 = ST(4, 3, 10, 10, 5, 3, 3, (4, 4))         # 256: the four images that fit
+Ig4 = ST(4, 4, 18, 18, 47, 3, 3, (2, 2))        # 1024
+Il4 = ST(4, 3, 18, 18, 17, 3, 3, (4, 4))        # 1024: 4 x 4 on one whole 16 x 16 image, K = 17
+EXACT_MEAN_STAGES = [Ib8, Ic4, Ig4, Il4]
+# TRAIN alone: none of the shapes above has MT = 2 under a 2 x 2 window, which the TEST-phase lists have of their own.
+# K = 20 on two whole 10 x 10 images per workgroup, the last workgroup with one: AVE (2, run-time), MAX (2, 2 x 2)
+It = ST(3, 3, 12, 12, 20, 3, 3, (2, 2))
+TRAIN_ONLY_STAGES = [It]
+FUSED_STAGES = [A, B, C, E, F, G] + INSTANTIATION_STAGES + EXACT_MEAN_STAGES + TRAIN_ONLY_STAGES
 SEQUENCE_STAGES = [D]
 GPU_STAGES = FUSED_STAGES + SEQUENCE_STAGES
 PARITY_STAGES = [A, B, C, D]
@@ -251,6 +270,27 @@ def fused_statistics_f32(st, inp, G, R, bands, memory=BN_MEMORY):
     y = CR.conv_forward(st.conv, c["x"], c["weight"], bias).astype(np.float32)
     tot = fold_partials(fused_partials(y, G, R, bands))
     return dict(zip(FORWARD_OUTPUTS[3:], statistics_f32(st, inp, tot[:, 0], tot[:, 1], memory)))
+
+
+# ---- the order probe (AVE) ----------------------------------------------------------------------------------------
+ORDER_STAGES = SR.ORDER_STAGES
+
+
+def order_probe(st, seed):
+    """conv_stage_reference.order_probe's x and weight (st an order_stage: no bias; every element of y one exact
+    product, window sums that round) with _draw's scale, shift and running blobs; top_diff is not used."""
+    p = SR.order_probe(st, seed)
+    d = _draw(st, np.float32, seed)
+    return dict(x=p["x"], weight=p["weight"], bias=None, weight_diff0=None, bias_diff0=None, top_diff=d["top_diff"],
+                **{k: d[k] for k in ("scale", "shift", "running_mean", "running_var")})
+
+
+def order_probe_forward(st, inp, y):
+    """The fused TRAIN forward of bn_pool_reference in float32 on the exact map y: the window added in (h, w) order from
+    0, the statistics by plainly sequential sums.  -> {top, save_pool, save_mean, save_std, running_mean, running_var}"""
+    assert y.dtype == np.float32
+    out = BP.fused_forward(y, st.pool, inp["scale"], inp["shift"], inp["running_mean"], inp["running_var"], BN_MEMORY, BP.TRAIN)
+    return dict(zip(FORWARD_OUTPUTS[1:], out))
 
 
 # ---- the exact probe ---------------------------------------------------------------------------------------------

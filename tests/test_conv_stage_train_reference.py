@@ -72,8 +72,10 @@ def test_probe_sums_are_exact_in_float(st):
     assert (y.astype(np.float32).astype(np.int64) == y).all()
     assert inp["scale"][R.ZERO_CHANNEL] == 0 and inp["scale"][R.NEGATIVE_CHANNEL] < 0 < inp["scale"][R.POSITIVE_CHANNEL]
     mean, std, _, _ = R.probe_statistics(st, inp, s0, s1)
-    if st is R.E:                                                              # N * OH * OW = 256: the mean is exact
-        assert (mean.astype(np.float64) == s0 / 256.0).all()
+    n = st.conv.N * int(np.prod(CR.output_dims(st.conv)))
+    assert st not in [R.E, R.Ia, R.Is] + R.EXACT_MEAN_STAGES or n & (n - 1) == 0
+    if n & (n - 1) == 0:                                                       # N * OH * OW a power of two (E's 256): the
+        assert (mean.astype(np.float64) == s0 / float(n)).all()                # mean is exact
     # windows with ties: an extremum attained more than once, in channels of every sign of scale
     w = R.BM.windows(y, *st.pool)
     for k in (R.ZERO_CHANNEL, R.NEGATIVE_CHANNEL, R.POSITIVE_CHANNEL):

@@ -34,9 +34,9 @@ def test_integer_probe_fused_equals_sequence(st, hiplib):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 @pytest.mark.parametrize("st", R.GPU_STAGES, ids=ALL_IDS)
 def test_parity_and_determinism(st, dtype, hiplib):
-    """ConvStage.check_parity_and_determinism; where both routes have one chunk of input channels: fused and
+    """ConvStage.check_parity_and_determinism; where both routes cut the input channels into the same chunks: fused and
     sequence, the same words."""
-    S.check_parity_and_determinism(st, dtype, R.SAME_CHUNK_STAGES)
+    S.check_parity_and_determinism(st, dtype, R.SAME_WORDS_STAGES)
 
 
 def test_the_main_call_reaches_both_routes_on_the_fused_list(hiplib):
@@ -65,7 +65,7 @@ def test_empty_batch_writes_nothing(dtype, hiplib):
     S.check_empty_batch_writes_nothing(dtype)
 
 
-@pytest.mark.parametrize("st", R.SAME_CHUNK_STAGES, ids=[R.stage_id(st) for st in R.SAME_CHUNK_STAGES])
+@pytest.mark.parametrize("st", R.NAN_STAGES, ids=[R.stage_id(st) for st in R.NAN_STAGES])
 def test_a_window_holding_one_nan(st, hiplib):
     """One NaN in x, in the middle of image 1: every element of y whose taps reach it is a NaN, in every channel.  The
     fused route gives the sequence route's words (a NaN for a NaN), and every window that holds none of those elements
@@ -74,17 +74,24 @@ def test_a_window_holding_one_nan(st, hiplib):
     s, (ph, pw) = st.conv, st.pool
     inp = dict(S.inputs(st, np.float32))
     x = np.array(inp["x"])
-    n, i, j = 1, s.H // 2 + 1, s.W // 2 + 1
+    n = 1
+
+    def masks(d):
+        """the NaN at (H / 2 + 1 + d, W / 2 + 1 + d) -> its place, the windows it reaches, those it starts"""
+        i, j = s.H // 2 + 1 + d, s.W // 2 + 1 + d
+        y = np.zeros((s.N, s.K) + R.CR.output_dims(s), bool)
+        y[n, :, max(0, i - s.kh + 1):i + 1, max(0, j - s.kw + 1):j + 1] = True        # the elements of y that are NaN
+        w = BM.windows(y, ph, pw)
+        return i, j, w.any(axis=-1), w[..., 0]
+
+    # the place nearest the middle at which some window starts with a NaN and some other holds one further on
+    i, j, touched, first = next(m for m in map(masks, (0, 1, -1, 2, -2)) if m[3].any() and (m[2] & ~m[3]).any())
     x[n, 0, i, j] = np.nan
     inp["x"] = x
     fused, seq = S.run(st, inp, route="fused"), S.run(st, inp, route="sequence")
     for k in ("top", "save_pool"):
         assert_bitexact(fused[k], seq[k], "a NaN in x, fused against sequence, " + k)
-    y = np.zeros((s.N, s.K) + R.CR.output_dims(s), bool)
-    y[n, :, max(0, i - s.kh + 1):i + 1, max(0, j - s.kw + 1):j + 1] = True            # the elements of y that are NaN
-    w = BM.windows(y, ph, pw)
-    touched, first = w.any(axis=-1), w[..., 0]
-    assert touched.any() and not touched.all() and (touched & ~first).any()
+    assert touched.any() and not touched.all() and (touched & ~first).any() and first.any()
     want = S.model(st, np.float32)
     for k in ("top", "save_pool"):
         got = np.where(touched, 0.0, fused[k])

@@ -326,6 +326,48 @@ def check_forward_parity(got, want, dtype, what):
         assert ratios[k] <= 1.0, "%s, %s: %.3g of the bar" % (k, what, ratios[k])
 
 
+# ---- one shape per instantiation of the pooling epilogue (R.INSTANTIATION_STAGES, R.EXACT_MEAN_STAGES, R.TRAIN_ONLY_STAGES) -------------------
+# They join the exact probe, y's own words and the determinism tests above through R.FUSED_STAGES; what each reaches is
+# held to the C++ by tests/test_conv_stage_plans.py, on the CPU.
+NEW_STAGES = R.INSTANTIATION_STAGES + R.EXACT_MEAN_STAGES + R.TRAIN_ONLY_STAGES
+
+
+@pytest.mark.parametrize("method", R.METHODS)
+@pytest.mark.parametrize("st", NEW_STAGES, ids=IDS(NEW_STAGES))
+def test_instantiation_forward_parity(st, method, hiplib):
+    """The forced fused, the forced sequence and the main call in float, and the double call: the seven forward outputs
+    against the float64 model at the project's bars (printed: each output's share of its bar)."""
+    for route in LARGE_ROUTES:
+        got = run(st, method, large_inputs(st, np.float32), route=route, backward=False)
+        check_forward_parity(got, large_model(st, method, np.float32), np.float32, "%s f32 %s" % (method, route))
+    got = run(st, method, large_inputs(st, np.float64), np.float64, backward=False)
+    check_forward_parity(got, large_model(st, method, np.float64), np.float64, "%s f64" % method)
+
+
+@pytest.mark.parametrize("st", R.ORDER_STAGES, ids=IDS(R.ORDER_STAGES))
+def test_order_probe_ave(st, hiplib):
+    """R.order_probe: every element of y is one exact product, so y is the exact map word for word on both routes.
+    save_pool before launch 2 is not observable; the finished save_pool, top and the statistics of the fused route are
+    held to the float32 restatement of bn_pool_reference's fused TRAIN forward on that map -- the window one chain in
+    (h, w) order -- at the float bar (printed: each output's share of it)."""
+    ost = R.SR.order_stage(st)
+    inp = R.order_probe(ost, R.SR.ORDER_SEED)
+    y = R.SR.order_probe_map(ost, inp)
+    assert min(R.SR.order_shares(y, ost.pool).values()) >= R.SR.ORDER_MIN_SHARE
+    want = R.order_probe_forward(ost, inp, y)
+    for route in ("fused", "sequence"):
+        got = run(ost, R.AVE, inp, route=route, backward=False)
+        assert_words_equal(got["y"], y, "order probe, y, %s route" % route)
+        ratios = {}
+        for k, w in want.items():
+            assert np.isfinite(got[k]).all(), k
+            scale = max(1.0, float(np.max(np.abs(w))))
+            ratios[k] = float(np.max(np.abs(got[k].astype(np.float64) - w.astype(np.float64)))) / (BAR[np.float32] * scale)
+        print("%-9s %s" % (route, "  ".join("%s %.3g" % kv for kv in ratios.items())))
+        for k, v in ratios.items():
+            assert v <= 1.0, "%s, %s route: %.3g of the bar" % (k, route, v)
+
+
 @pytest.mark.parametrize("method", R.METHODS)
 @pytest.mark.parametrize("st", R.LARGE_STAGES, ids=IDS(R.LARGE_STAGES))
 def test_large_exact_probe_fused_equals_sequence(st, method, hiplib):
