@@ -14,6 +14,7 @@ tests/test_abi_head.py and tests/test_gpu_head.py: the shape lists, the input ge
 int64 reference, and a reader of the fast route's named constants in csrc/head.hip.
 """
 import collections
+import functools
 
 import numpy as np
 
@@ -36,16 +37,36 @@ OUTPUTS_BWD = ("x0_diff", "x1_diff", "w1_diff", "b1_diff", "w2_diff", "b2_diff")
 V4 = S(50, 64, 2, 32, 2)                 # network_v4's training batch
 V4_TEST = S(1517, 64, 2, 32, 2)          # ... and the test split
 V4_2 = S(33, 32, 2, 64, 2)               # network_v4_2's head
+# More than kHeadMaxSlabs tiles (N > 16384): several slabs of several tiles each, the plan no smaller batch takes.  F, H
+# and C stay tiny but for one shape; (tiles, tiles per slab, slabs) beside each, tests/test_head_reference.py holds
+# slabs() to them.  The table these came from needed no other N.
+LARGE_PLANS = {
+    S(16385, 3, 2, 5, 3): (257, 2, 129),                     # the fewest samples with two tiles per slab; the last slab
+                                                             # has one tile of one sample
+    S(16449, MAX_F - 2, 2, MAX_H, MAX_C): (258, 2, 129),     # at every fast limit: all accumulators of a thread carried
+                                                             # over two tiles into slab partials; the last tile one sample
+    S(32833, 1, 0, 1, 2): (514, 3, 172),                     # the last slab clipped to one of its three tiles; no x1
+    S(65537, 2, 1, 3, 2): (1025, 5, 205),                    # 320 samples per slab: head_out_kernel's second trip
+    S(16385, 4, 1, MAX_H + 1, 2): (257, 2, 129),             # past a fast limit: generic by route, not by request
+}
+LARGE_SHAPES = list(LARGE_PLANS)
+INDEPENDENCE_SHAPE = LARGE_SHAPES[0]       # ... and its prefix of 16384 samples, cut with one tile per slab
+
+# The (tiles per slab, slabs) the list covers, FAST_PLANS below: one slab of 1, 2 or 4 tiles up to SINGLE samples; 5, 8
+# and 24 slabs of one tile from there to 16384 samples; (2, 129), (3, 172) and (5, 205) in LARGE_SHAPES.
+FAST_PLANS = {(1, 1), (2, 1), (4, 1), (1, 5), (1, 8), (1, 24), (2, 129), (3, 172), (5, 205)}
 FAST_SHAPES = [
-    V4, V4_TEST, V4_2,
+    V4, V4_TEST, V4_2,                                                       # V4_TEST: 24 slabs of one tile
     S(1, 1, 0, 1, 1), S(1, 1, 0, 1, 2),                                      # minimal
     S(17, 5, 3, 31, 3), S(65, 63, 2, 33, 5), S(16, 64, 0, 32, 2),            # the seam inside a K step, ragged tiles
     S(TILE - 1, 6, 1, 8, 2), S(TILE, 6, 1, 8, 2), S(TILE + 1, 6, 1, 8, 2),   # around one tile of samples
-    S(SINGLE - 1, 3, 2, 5, 3), S(SINGLE, 3, 2, 5, 3), S(SINGLE + 1, 3, 2, 5, 3),     # around the single-launch limit
-    S(3 * TILE + SINGLE + 7, 9, 2, 17, 4),                                   # eight slabs, the last with 7 samples
+    S(SINGLE - 1, 3, 2, 5, 3), S(SINGLE, 3, 2, 5, 3), S(SINGLE + 1, 3, 2, 5, 3),     # around the single-launch limit:
+                                                                             # one slab of four tiles, five slabs of one
+    S(3 * TILE + SINGLE + 7, 9, 2, 17, 4),                                   # eight slabs of one tile, the last with 7 samples
     S(20, MAX_F - 2, 2, MAX_H, MAX_C),                                       # at every limit
-]
-GENERIC_SHAPES = [S(9, MAX_F, 1, 4, 2), S(9, 4, 1, MAX_H + 1, 2), S(9, 4, 1, 4, MAX_C + 1)]     # just past each limit
+] + LARGE_SHAPES[:4]
+GENERIC_SHAPES = [S(9, MAX_F, 1, 4, 2), S(9, 4, 1, MAX_H + 1, 2), S(9, 4, 1, 4, MAX_C + 1)     # just past each limit
+                  ] + LARGE_SHAPES[4:]
 GPU_SHAPES = FAST_SHAPES + GENERIC_SHAPES
 
 # (cfg, ignored labels among the inputs?, out-of-range labels?)
@@ -135,8 +156,36 @@ def dropout(v, mask, cfg, t):
     return (v * mask.astype(t)) * scale_of(cfg, t) if cfg.phase == TRAIN else v
 
 
+SLAB_ORDER = "slabs"         # for `reverse`: the order csrc/head.hip adds a slab's samples and then the slabs in
+
+
+def slab_sum(v, t):
+    """The sum over samples (axis 0) one term at a time in `t`: ascending within a slab of slabs(N), each slab from 0,
+    then the slabs' partial sums ascending from slab 0's -- head_param_kernel and head_param_finish_kernel."""
+    n_slabs, tps = slabs(len(v))
+    per = tps * TILE
+    pad = np.zeros((n_slabs * per,) + v.shape[1:], dtype=t)           # + 0 after the last sample changes no sum
+    pad[:len(v)] = v
+    part = np.add.accumulate(pad.reshape((n_slabs, per) + v.shape[1:]), axis=1, dtype=t)[:, -1]
+    return np.add.accumulate(part, axis=0, dtype=t)[-1]
+
+
+def slab_products(a, b, t):
+    """a^T b, the sum over samples of the outer products: each slab's product on its own (the order within a slab is the
+    matrix product's), then the slabs' partial sums one at a time, ascending, in `t`."""
+    n_slabs, tps = slabs(len(a))
+    per = tps * TILE
+    pa, pb = np.zeros((n_slabs * per, a.shape[1]), dtype=t), np.zeros((n_slabs * per, b.shape[1]), dtype=t)
+    pa[:len(a)], pb[:len(b)] = a, b
+    part = np.matmul(pa.reshape(n_slabs, per, -1).transpose(0, 2, 1), pb.reshape(n_slabs, per, -1))
+    assert part.dtype == t
+    return np.add.accumulate(part, axis=0, dtype=t)[-1]
+
+
 def nsum(v, t, reverse):
-    """The sum over samples (axis 0), in `t`; reversed: the samples taken last to first."""
+    """The sum over samples (axis 0), in `t`; reversed: the samples taken last to first; SLAB_ORDER: slab_sum."""
+    if reverse == SLAB_ORDER:
+        return slab_sum(v.astype(t), t)
     return np.add.reduce(v[::-1] if reverse else v, axis=0, dtype=t)
 
 
@@ -178,12 +227,13 @@ def backward(s, cfg, inp, h, prob, dtype=np.float64, reverse=False):
     d = dropout(h, inp["mask"], cfg, t) if cfg.phase == TRAIN else h
     dh = dropout(dz2 @ w2, inp["mask"], cfg, t) if cfg.phase == TRAIN else dz2 @ w2
     dz1 = dh * (t(1) - h * h)
-    order = slice(None, None, -1) if reverse else slice(None)
+    order = slice(None, None, -1) if reverse is True else slice(None)
+    tn = slab_products if reverse == SLAB_ORDER else (lambda a, b, t_: a[order].T @ b[order])
     dx = dz1 @ w1
     out = dict(x0_diff=dx[:, :s.F0],
-               w1_diff=inp["w1_diff0"].astype(t) + dz1[order].T @ feat[order],
+               w1_diff=inp["w1_diff0"].astype(t) + tn(dz1, feat, t),
                b1_diff=inp["b1_diff0"].astype(t) + nsum(dz1, t, reverse),
-               w2_diff=inp["w2_diff0"].astype(t) + dz2[order].T @ d[order],
+               w2_diff=inp["w2_diff0"].astype(t) + tn(dz2, d, t),
                b2_diff=inp["b2_diff0"].astype(t) + nsum(dz2, t, reverse))
     if s.F1:
         out["x1_diff"] = dx[:, s.F0:]
@@ -211,6 +261,14 @@ def probe_cfg(s, k=0):
     return Cfg(TRAIN, PROBE_RATIO, (FULL, BATCH_SIZE)[k % 2] if pow2 else NONE, 1 if s.C > 1 else None)
 
 
+def imatmul(a, b):
+    """a @ b of integer arrays as int64, through float64's matrix product: exact in any order, the largest sum of
+    absolute products being below 2^53."""
+    fa, fb = a.astype(np.float64), b.astype(np.float64)
+    assert (np.abs(fa) @ np.abs(fb)).max(initial=0.0) < 2.0 ** 53
+    return (fa @ fb).astype(np.int64)
+
+
 def dyadic_probe(s, seed, k=0):
     """(cfg, inputs, saved h, saved prob, int64 reference, bound).  h in multiples of 1/4, prob rows from {0, 1/4, 3/4, 1},
     small-integer x, w1, w2 and initial diffs, loss_weight 2, some labels ignored and some out of range.  The reference
@@ -224,12 +282,11 @@ def dyadic_probe(s, seed, k=0):
     mask = r.integers(0, 2, (s.N, s.H))
     h4 = r.integers(-4, 5, (s.N, s.H))
     p4 = np.zeros((s.N, s.C), dtype=np.int64)
-    for n in range(s.N):
-        if s.C == 1 or r.random() < 0.3:
-            p4[n, r.integers(0, s.C)] = 4
-        else:
-            a, b = r.choice(s.C, 2, replace=False)
-            p4[n, a], p4[n, b] = 3, 1
+    one = (r.random(s.N) < 0.3) | (s.C == 1)                         # a row of one 1; else 3/4 and 1/4 in two classes
+    a = r.integers(0, s.C, s.N)
+    b = (a + r.integers(1, max(2, s.C), s.N)) % s.C
+    p4[np.arange(s.N), a] = np.where(one, 4, 3)
+    p4[np.arange(s.N)[~one], b[~one]] = 1
     lab = labels(s, r, True, True, cfg.ignore_label)
     diff0 = dict(w1_diff0=r.integers(-3, 4, (s.H, F)), b1_diff0=r.integers(-3, 4, s.H),
                  w2_diff0=r.integers(-3, 4, (s.C, s.H)), b2_diff0=r.integers(-3, 4, s.C))
@@ -242,13 +299,13 @@ def dyadic_probe(s, seed, k=0):
     onehot[np.arange(s.N), lv] = 4
     dz2 = np.where(ok[:, None], (p4 - onehot) * lw, 0)               # units of 1 / (4 norm)
     d4 = h4 * mask * 2                                               # units of 1 / 4
-    dz1 = (dz2 @ w2) * mask * 2 * (16 - h4 * h4)                     # units of 1 / (64 norm)
-    ref = dict(x_diff=dz1 @ w1, w1_diff=diff0["w1_diff0"] * unit + dz1.T @ x, b1_diff=diff0["b1_diff0"] * unit + dz1.sum(0),
-               w2_diff=diff0["w2_diff0"] * unit + 4 * (dz2.T @ d4), b2_diff=diff0["b2_diff0"] * unit + 16 * dz2.sum(0))
+    dz1 = imatmul(dz2, w2) * mask * 2 * (16 - h4 * h4)                     # units of 1 / (64 norm)
+    ref = dict(x_diff=imatmul(dz1, w1), w1_diff=diff0["w1_diff0"] * unit + imatmul(dz1.T, x), b1_diff=diff0["b1_diff0"] * unit + dz1.sum(0),
+               w2_diff=diff0["w2_diff0"] * unit + 4 * imatmul(dz2.T, d4), b2_diff=diff0["b2_diff0"] * unit + 16 * dz2.sum(0))
     a1, a2 = np.abs(dz1), np.abs(dz2)
-    bound = max(int((a1 @ np.abs(w1)).max()), int((3 * unit + a1.T @ np.abs(x)).max()), int((3 * unit + a1.sum(0)).max()),
-                int((3 * unit + 4 * (a2.T @ np.abs(d4))).max()), int((3 * unit + 16 * a2.sum(0)).max()),
-                int(16 * (a2 @ np.abs(w2)).max() * 2 * 16))
+    bound = max(int(imatmul(a1, np.abs(w1)).max()), int((3 * unit + imatmul(a1.T, np.abs(x))).max()), int((3 * unit + a1.sum(0)).max()),
+                int((3 * unit + 4 * imatmul(a2.T, np.abs(d4))).max()), int((3 * unit + 16 * a2.sum(0)).max()),
+                int(16 * imatmul(a2, np.abs(w2)).max() * 2 * 16))
     want = {k_: v.astype(np.float64) / unit for k_, v in ref.items()}
     want["x0_diff"] = np.ascontiguousarray(want["x_diff"][:, :s.F0])
     if s.F1:
@@ -259,3 +316,14 @@ def dyadic_probe(s, seed, k=0):
                label=lab, loss_weight=PROBE_LOSS_WEIGHT)
     inp.update({k_: v.astype(np.float64) for k_, v in diff0.items()})
     return cfg, inp, h4 / 4.0, p4 / 4.0, want, bound
+
+
+@functools.lru_cache(maxsize=None)
+def shared_probe(s, seed, k=0):
+    """dyadic_probe(s, seed, k), made once for all the tests that take it, its arrays read-only."""
+    probe = dyadic_probe(s, seed, k)
+    cfg, inp, h, prob, want, bound = probe
+    for v in list(inp.values()) + [h, prob] + list(want.values()):
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return probe

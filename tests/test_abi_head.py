@@ -252,6 +252,10 @@ def test_workspace_query(head):
         shape = head.head_shape(*s)
         assert head.head_workspace_bytes(shape) == R.workspace_bytes(s, 4), s
         assert head.head_workspace_bytes_f64(shape) == R.workspace_bytes(s, 8), s
+    big = R.S(65537, 2, 1, 3, 2)                              # 205 slabs of five tiles, 20 parameters
+    assert big in R.GPU_SHAPES and R.slabs(big.N) == (205, 5) and R.params(big) == 20
+    assert head.head_workspace_bytes(head.head_shape(*big)) == R.workspace_bytes(big, 4) == 3088 + 205 * 20 * 4
+    assert head.head_workspace_bytes_f64(head.head_shape(*big)) == R.workspace_bytes(big, 8) == 3088 + 205 * 20 * 8
 
 
 def test_binding_refuses_before_the_library(head):

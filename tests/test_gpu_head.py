@@ -3,7 +3,8 @@ route, the generic route in float, and in double.  The conditioned inputs (tests
 for it) are held to the float64 model at the project's 1e-5 (float32) and 1e-12 (float64) in assert_close's metric;
 indexing, the x0 | x1 seam, the mask, the accumulate / overwrite rule and NULL outputs are tested by EQUALITY on dyadic
 probes of the backward, whatever order a kernel sums in; the fixed order and the workspace's irrelevance by equality of
-words between two runs."""
+words between two runs.  R.LARGE_SHAPES (more than 256 tiles: several slabs of several tiles each) go through all of it
+and have three tests of their own at the end."""
 import functools
 
 import numpy as np
@@ -82,6 +83,29 @@ def nan_workspace(s, dtype):
     ws.get(q(head.head_shape(*s)), torch.device("cuda", torch.cuda.current_device()))
     ws.buf.fill_(255)
     return ws
+
+
+class ExactWorkspace:
+    """In place of a capi.Workspace: exactly the bytes the call asks for, `shift` bytes off a 16-byte boundary, every
+    byte of them `fill`, between two guard zones as long as one slab's partial sums."""
+
+    def __init__(self, s, dtype, fill, shift):
+        from mms_answer_selection_amd import head
+        q = head.head_workspace_bytes if dtype == np.float32 else head.head_workspace_bytes_f64
+        self.nbytes = q(head.head_shape(*s))
+        assert self.nbytes == R.workspace_bytes(s, np.dtype(dtype).itemsize)
+        self.lo = 16 * (-(-R.params(s) * np.dtype(dtype).itemsize // 16)) + shift
+        self.buf = torch.full((self.lo + self.nbytes + self.lo,), 0x5A, dtype=torch.uint8, device="cuda")
+        self.buf[self.lo:self.lo + self.nbytes] = fill
+        assert self.buf.data_ptr() % 16 == 0 and (self.buf.data_ptr() + self.lo) % 16 == shift
+
+    def get(self, nbytes, device):
+        assert nbytes == self.nbytes, (nbytes, self.nbytes)
+        return self.buf.data_ptr() + self.lo, self.nbytes
+
+    def check(self, what):
+        b = host(self.buf)
+        assert (b[:self.lo] == 0x5A).all() and (b[self.lo + self.nbytes:] == 0x5A).all(), what + ": written past the workspace"
 
 
 def kwargs(cfg, route, ws):
@@ -215,7 +239,7 @@ def test_dyadic_probes_of_the_backward(s, variant, hiplib):
     those given keep their words and the others are untouched."""
     _, dtype, route = variant
     for k in range(2):
-        cfg, inp, h, prob, want, bound = R.dyadic_probe(s, SEED, k)
+        cfg, inp, h, prob, want, bound = R.shared_probe(s, SEED, k)
         assert bound < 2 ** 24
         got = run_backward(s, cfg, inp, h, prob, dtype, route)
         assert sorted(got) == sorted(want)
@@ -263,7 +287,7 @@ def test_clamp(variant, hiplib):
         assert_close(got["prob"], np.tile(np.array([1.0, 0.0]), (s.N, 1)), BAR[dtype], "prob")
 
 
-@pytest.mark.parametrize("s", [R.V4, R.V4_TEST, R.V4_2], ids=R.sid)
+@pytest.mark.parametrize("s", [R.V4, R.V4_TEST, R.V4_2, R.INDEPENDENCE_SHAPE], ids=R.sid)
 def test_fast_and_generic_routes_agree(s, hiplib):
     from mms_answer_selection_amd import head
     for p in (head.PASS_FORWARD, head.PASS_BACKWARD):
@@ -337,3 +361,55 @@ def test_prob_goes_straight_to_the_ranking_calls(hiplib):
     assert capi.rank_map_mrr(mine, label, group) == capi.rank_map_mrr(model, label, group)
     assert capi.rank_auc(mine, label) == capi.rank_auc(model, label)
     assert capi.rank_map_mrr(mine, label, group)[2] > 0
+
+
+# ---- batches of more than kHeadMaxSlabs tiles: several slabs of several tiles each ------------------------------------
+LARGE_IDS = [R.sid(s) for s in R.LARGE_SHAPES]
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=VARIANT_IDS)
+@pytest.mark.parametrize("s", R.LARGE_SHAPES, ids=LARGE_IDS)
+def test_large_batches_leave_no_workspace_word_unwritten(s, variant, hiplib):
+    """Forward with a loss and backward with every diff, on a zeroed workspace and on one of NaNs that starts one element
+    off a 16-byte boundary, both of exactly mms_head_workspace_bytes: the same words in every output, and not a byte
+    written outside either workspace.  A slab whose partial sums or loss term were read without having been written
+    -- a clipped last slab, a slab taken for empty -- would show as NaN in one run and as a missing term in the other."""
+    _, dtype, route = variant
+    cfg, inp, _, _, h, prob = case(s, dtype, (s.N + s.H) % len(R.CASES))
+    runs = []
+    for fill, shift in ((0, 0), (255, np.dtype(dtype).itemsize)):
+        wf, wb = ExactWorkspace(s, dtype, fill, shift), ExactWorkspace(s, dtype, fill, shift)
+        out = run_forward(s, cfg, inp, dtype, route, ws=wf)
+        out.update(run_backward(s, cfg, inp, h, prob, dtype, route, ws=wb))
+        wf.check("forward")
+        wb.check("backward")
+        runs.append(out)
+    assert sorted(runs[0]) == sorted(R.OUTPUTS_FWD + R.OUTPUTS_BWD if s.F1 else
+                                     [k for k in R.OUTPUTS_FWD + R.OUTPUTS_BWD if k != "x1_diff"])
+    for key in sorted(runs[0]):
+        assert np.isfinite(runs[0][key]).all(), key
+        assert_words_equal(runs[1][key], runs[0][key], key + ": NaN workspace against zeroed workspace")
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=VARIANT_IDS)
+def test_large_batches_samples_are_independent(variant, hiplib):
+    """h, prob, x0_diff and x1_diff of the first 16384 samples are the same words whether the call has 16385 samples
+    (129 slabs of two tiles) or those 16384 alone (256 slabs of one tile): the cut moves no per-sample word.  The diffs
+    under NONE normalization, whose coef does not depend on the batch."""
+    _, dtype, route = variant
+    s = R.INDEPENDENCE_SHAPE
+    short = s._replace(N=s.N - 1)
+    assert R.slabs(s.N) == (129, 2) and R.slabs(short.N) == (256, 1)
+    cfg = R.Cfg(R.TRAIN, 0.5, R.NONE, 1)
+    inp = R.conditioned_inputs(s, dtype, SEED, cfg, True, True)
+    cut = {k: (v[:short.N] if k in ("x0", "x1", "mask", "label") else v) for k, v in inp.items()}
+    fwd = R.forward(s, cfg, inp)
+    h, prob = fwd["h"].astype(dtype), fwd["prob"].astype(dtype)
+    whole = run_forward(s, cfg, inp, dtype, route)
+    whole.update(run_backward(s, cfg, inp, h, prob, dtype, route))
+    part = run_forward(short, cfg, cut, dtype, route)
+    part.update(run_backward(short, cfg, cut, h[:short.N], prob[:short.N], dtype, route))
+    for key in ("h", "prob", "x0_diff", "x1_diff"):
+        assert whole[key].shape[0] == s.N and part[key].shape[0] == short.N
+        assert np.count_nonzero(part[key]) > part[key].size // 4, key
+        assert_words_equal(whole[key][:short.N], part[key], key + " of the first %d samples" % short.N)
