@@ -468,10 +468,8 @@ int bp_forward(int phase, int N, int C, int H, int W, int kh, int kw, T bn_memor
   if (!x || !scale || !shift || !running_mean || !running_var || !top || !save_pool || !save_mean || !save_std)
     return MMS_ERR_INVALID_ARG;
   const void* const inputs[] = {x, scale, shift, running_mean, running_var};
-  for (const void* in : inputs) {
-    if (top == in || save_pool == in) return MMS_ERR_INVALID_ARG;
-  }
-  if (top == save_pool) return MMS_ERR_INVALID_ARG;
+  const void* const outputs[] = {top, save_pool};
+  if (outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   const BpRoute r = bp_route<T>(N, H, W, kh, kw);
   const size_t need = bp_workspace_bytes<T>(N, C, H, W, kh, kw);
   if (need && phase == 0 && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;
@@ -510,10 +508,9 @@ int bp_backward(int N, int C, int H, int W, int kh, int kw, const T* x, const T*
   if (!x || !top || !top_diff || !save_pool || !scale || (MAX && !shift) || !save_mean || !save_std ||
       (!bottom_diff && !scale_diff && !shift_diff))
     return MMS_ERR_INVALID_ARG;
-  const void* const inputs[] = {x, top, top_diff, save_pool, scale, save_mean, save_std, MAX ? shift : x};   // AVE: x twice
-  for (const void* in : inputs) {
-    if (bottom_diff == in) return MMS_ERR_INVALID_ARG;
-  }
+  const void* const inputs[] = {x, top, top_diff, save_pool, scale, save_mean, save_std, MAX ? shift : nullptr};
+  const void* const outputs[] = {bottom_diff};
+  if (outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   const BpRoute r = bp_route<T>(N, H, W, kh, kw);
   const size_t need = bp_workspace_bytes<T>(N, C, H, W, kh, kw);
   if (need && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;

@@ -613,8 +613,7 @@ template <int NTW, bool AH = false>
 inline void bx3_launch_t(const Bx3Args& p, hipStream_t s) {
   using G = Bx3Geom<NTW>;
   static bool once = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&bx3_kernel<NTW, AH>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)G::kLdsBytes) == hipSuccess;
+    return allow_dynamic_lds(&bx3_kernel<NTW, AH>, (int)G::kLdsBytes) == hipSuccess;
   }();
   (void)once;
   const unsigned panels = (unsigned)((p.M + G::ROWS - 1) / G::ROWS);
@@ -865,8 +864,7 @@ inline bool bx3_tn_eligible(const Bx3TnArgs& p) {
 template <bool HALF>
 inline void bx3_tn_launch_t(const Bx3TnArgs& p, hipStream_t s) {
   static bool once = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&bx3_tn_kernel<HALF>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kBx3TnLds) == hipSuccess;
+    return allow_dynamic_lds(&bx3_tn_kernel<HALF>, (int)kBx3TnLds) == hipSuccess;
   }();
   (void)once;
   const int quads = bx3_tn_quads(p.M, p.N);

@@ -212,7 +212,10 @@ int conv_forward(const mms_conv_shape* shape, const T* x, const T* w, const T* b
   const int rc = conv_check(shape, &d);
   if (rc != MMS_OK) return rc;
   if (d.N == 0) return MMS_OK;
-  if (!x || !w || !top || (const T*)top == x) return MMS_ERR_INVALID_ARG;
+  if (!x || !w || !top) return MMS_ERR_INVALID_ARG;
+  const void* const outputs[] = {top};
+  const void* const inputs[] = {x};
+  if (outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (!generic && conv_route(d, MMS_CONV_PASS_FORWARD) == MMS_CONV_ROUTE_FAST) {
       conv_prod_launch(conv_prod_plan(d, MMS_CONV_PASS_FORWARD, 1), x, w, bias, top, s);
@@ -233,7 +236,9 @@ int conv_backward(const mms_conv_shape* shape, const T* x, const T* w, const T* 
   if (rc != MMS_OK) return rc;
   if (d.N == 0) return MMS_OK;
   if (!x || !w || !dy || (!dx && !dw && !db)) return MMS_ERR_INVALID_ARG;
-  if (dx && ((const T*)dx == x || (const T*)dx == dy)) return MMS_ERR_INVALID_ARG;
+  const void* const outputs[] = {dx};
+  const void* const inputs[] = {x, dy};
+  if (outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   if ((dw || db) && (!workspace || workspace_bytes < conv_workspace_bytes<T>(shape))) return MMS_ERR_WORKSPACE;
   constexpr bool kFloat = std::is_same<T, float>::value;
   if (dx) {

@@ -13,14 +13,16 @@
 //
 // The host side is here once as well: the window's refusal (stage_window_check), the tile's row length and the
 // launch's LDS bytes, the windows compiled in (stage_pool_dispatch), what a workgroup holds and a span of workgroup
-// counts for the measured routing rules (stage_plan_kind, StageSpan), the typed calls of the sequence route and the
-// refusal of an output that aliases another array.  The routing thresholds are each source's own.
+// counts for the measured routing rules (stage_plan_kind, StageSpan).  The routing thresholds are each source's own; the
+// sequence routes call the public entry points through csrc/typed_abi.h and refuse an output that is another array of
+// the call with csrc/host_args.h's outputs_alias.
 #ifndef MMS_CONV_POOL_TILE_H_
 #define MMS_CONV_POOL_TILE_H_
 
 #include "bn_common.h"
 #include "conv_tile.h"
-#include "mms_bn_maxpool.h"
+#include "host_args.h"
+#include "typed_abi.h"
 
 namespace mms {
 
@@ -88,53 +90,6 @@ void stage_pool_dispatch(int ph, int pw, F&& f) {
   else if (!MAX && ph == 5 && pw == 5) f(stage_int<5>{}, stage_int<5>{});
   else if (MAX && ph == 2 && pw == 2) f(stage_int<2>{}, stage_int<2>{});
   else f(stage_int<0>{}, stage_int<0>{});
-}
-
-inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// The sequence route's two public calls, by element type.  phase 1 (TEST) reads running_mean / running_var, writes
-// neither and needs no workspace.
-inline int stage_conv_forward(const mms_conv_shape* s, const float* x, const float* w, const float* b, float* y,
-                              void* st) {
-  return mms_conv_forward_f32(s, x, w, b, y, nullptr, 0, st);
-}
-inline int stage_conv_forward(const mms_conv_shape* s, const double* x, const double* w, const double* b, double* y,
-                              void* st) {
-  return mms_conv_forward_f64(s, x, w, b, y, nullptr, 0, st);
-}
-inline int stage_bn_pool_forward(const StageDims& g, int phase, float mem, const float* y, const float* sc,
-                                 const float* sh, float* rm, float* rv, float* top, float* sp, float* sm, float* ss,
-                                 void* ws, size_t wsb, void* st) {
-  const auto call = g.max ? mms_bn_maxpool_tanh_forward_f32 : mms_bn_pool_tanh_forward_f32;
-  return call(phase, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, mem, y, sc, sh, rm, rv, top, sp, sm, ss, ws, wsb, st);
-}
-inline int stage_bn_pool_forward(const StageDims& g, int phase, double mem, const double* y, const double* sc,
-                                 const double* sh, double* rm, double* rv, double* top, double* sp, double* sm,
-                                 double* ss, void* ws, size_t wsb, void* st) {
-  const auto call = g.max ? mms_bn_maxpool_tanh_forward_f64 : mms_bn_pool_tanh_forward_f64;
-  return call(phase, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, mem, y, sc, sh, rm, rv, top, sp, sm, ss, ws, wsb, st);
-}
-
-// whether a non-NULL `out` is one of `others` (NULL entries are skipped)
-template <size_t M>
-bool among(const void* out, const void* const (&others)[M]) {
-  if (!out) return false;
-  for (const void* o : others) {
-    if (o && o == out) return true;
-  }
-  return false;
-}
-
-// whether an output is an input or another output
-template <size_t M, size_t K>
-bool stage_outputs_alias(const void* const (&outputs)[M], const void* const (&inputs)[K]) {
-  for (size_t i = 0; i < M; ++i) {
-    if (among(outputs[i], inputs)) return true;
-    for (size_t j = 0; j < i; ++j) {
-      if (outputs[i] && outputs[i] == outputs[j]) return true;
-    }
-  }
-  return false;
 }
 
 // ---- device -------------------------------------------------------------------------------------------------------

@@ -136,7 +136,7 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
   if (!x || !w || !top || !mean || !var || !scale || !shift) return MMS_ERR_INVALID_ARG;
   const void* const inputs[] = {x, w, bias, mean, var, scale, shift};
   const void* const outputs[] = {top, save_pool};
-  if (stage_outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
+  if (outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (force == MMS_CONV_STAGE_ROUTE_FUSED && !stage_plan(g).p.ok) return MMS_ERR_UNSUPPORTED;
     if (force == MMS_CONV_STAGE_ROUTE_FUSED ||
@@ -161,10 +161,12 @@ int stage_forward(const mms_conv_shape* shape, int ph, int pw, const T* x, const
   T* save_std = save_mean + g.d.K;
   T* sp = save_pool ? save_pool : save_std + g.d.K;
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
-  const int rc1 = stage_conv_forward(shape, x, w, bias, y, stream);
+  const int rc1 = Abi<T>::conv_forward(shape, x, w, bias, y, nullptr, 0, stream);
   if (rc1 != MMS_OK) return rc1;
-  return stage_bn_pool_forward(g, 1, T(0), y, scale, shift, const_cast<T*>(mean), const_cast<T*>(var), top, sp, save_mean,
-                               save_std, nullptr, 0, stream);
+  // phase 1 (TEST) reads running_mean / running_var, writes neither and needs no workspace
+  const auto bn_pool_tanh = g.max ? Abi<T>::bn_maxpool_tanh_forward : Abi<T>::bn_pool_tanh_forward;
+  return bn_pool_tanh(1, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, T(0), y, scale, shift, const_cast<T*>(mean),
+                      const_cast<T*>(var), top, sp, save_mean, save_std, nullptr, 0, stream);
 }
 
 }  // namespace

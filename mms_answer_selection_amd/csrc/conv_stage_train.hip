@@ -153,13 +153,7 @@ __global__ __launch_bounds__(kBnThreads) void train_finish_kernel(
 
 template <typename T>
 size_t bn_bytes(const StageDims& g) {
-  return std::is_same<T, float>::value
-             ? mms_bn_pool_tanh_workspace_bytes(g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw)
-             : mms_bn_pool_tanh_workspace_bytes_f64(g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw);
-}
-template <typename T>
-size_t conv_bytes(const mms_conv_shape* s) {
-  return std::is_same<T, float>::value ? mms_conv_workspace_bytes(s) : mms_conv_workspace_bytes_f64(s);
+  return Abi<T>::bn_pool_tanh_workspace_bytes(g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw);
 }
 
 // The backward's workspace with every output: [dy][the BN call's][the convolution's], the first two rounded to 16 bytes.
@@ -171,7 +165,7 @@ struct BackwardCarve {
 template <typename T>
 BackwardCarve<T> backward_carve(const mms_conv_shape* shape, const StageDims& g) {
   const size_t map = (size_t)g.d.N * g.d.K * g.d.OH * g.d.OW;
-  return {round16(map * sizeof(T)), round16(bn_bytes<T>(g)), conv_bytes<T>(shape)};
+  return {round_up(map * sizeof(T), 16), round_up(bn_bytes<T>(g), 16), Abi<T>::conv_workspace_bytes(shape)};
 }
 
 enum { kAuto = -1, kSequence = MMS_CONV_STAGE_TRAIN_ROUTE_SEQUENCE, kFused = MMS_CONV_STAGE_TRAIN_ROUTE_FUSED };
@@ -196,30 +190,14 @@ size_t train_workspace_bytes(const mms_conv_shape* shape, int ph, int pw, int po
   return f > b ? f : b;
 }
 
-inline int conv_bwd(const mms_conv_shape* s, const float* x, const float* w, const float* dy, float* dx, float* dw,
-                    float* db, void* ws, size_t wsb, void* st) {
-  return mms_conv_backward_f32(s, x, w, dy, dx, dw, db, ws, wsb, st);
-}
-inline int conv_bwd(const mms_conv_shape* s, const double* x, const double* w, const double* dy, double* dx, double* dw,
-                    double* db, void* ws, size_t wsb, void* st) {
-  return mms_conv_backward_f64(s, x, w, dy, dx, dw, db, ws, wsb, st);
-}
-inline int bn_bwd(const StageDims& g, const float* y, const float* top, const float* td, const float* sp,
-                  const float* sc, const float* sh, const float* sm, const float* ss, float* dy, float* dsc, float* dsh,
-                  void* ws, size_t wsb, void* st) {
+// the BN -> pool -> TanH backward of g's method; shift is an input of the MAX form only
+template <typename T>
+int bn_bwd(const StageDims& g, const T* y, const T* top, const T* td, const T* sp, const T* sc, const T* sh, const T* sm,
+           const T* ss, T* dy, T* dsc, T* dsh, void* ws, size_t wsb, void* st) {
   const int N = g.d.N, K = g.d.K, OH = g.d.OH, OW = g.d.OW;
-  return g.max ? mms_bn_maxpool_tanh_backward_f32(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sh, sm, ss, dy, dsc, dsh,
+  return g.max ? Abi<T>::bn_maxpool_tanh_backward(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sh, sm, ss, dy, dsc, dsh,
                                                   ws, wsb, st)
-               : mms_bn_pool_tanh_backward_f32(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sm, ss, dy, dsc, dsh, ws,
-                                               wsb, st);
-}
-inline int bn_bwd(const StageDims& g, const double* y, const double* top, const double* td, const double* sp,
-                  const double* sc, const double* sh, const double* sm, const double* ss, double* dy, double* dsc,
-                  double* dsh, void* ws, size_t wsb, void* st) {
-  const int N = g.d.N, K = g.d.K, OH = g.d.OH, OW = g.d.OW;
-  return g.max ? mms_bn_maxpool_tanh_backward_f64(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sh, sm, ss, dy, dsc, dsh,
-                                                  ws, wsb, st)
-               : mms_bn_pool_tanh_backward_f64(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sm, ss, dy, dsc, dsh, ws,
+               : Abi<T>::bn_pool_tanh_backward(N, K, OH, OW, g.ph, g.pw, y, top, td, sp, sc, sm, ss, dy, dsc, dsh, ws,
                                                wsb, st);
 }
 
@@ -237,7 +215,7 @@ int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_me
     return MMS_ERR_INVALID_ARG;
   const void* const inputs[] = {x, w, bias, scale, shift};
   const void* const outputs[] = {y, top, save_pool, save_mean, save_std, running_mean, running_var};
-  if (stage_outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
+  if (outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (force == kFused && !train_plan(g).p.ok) return MMS_ERR_UNSUPPORTED;
     if (force == kFused || (force == kAuto && train_route(g) == MMS_CONV_STAGE_TRAIN_ROUTE_FUSED)) {
@@ -270,10 +248,11 @@ int train_forward(const mms_conv_shape* shape, int ph, int pw, int pool, T bn_me
   const size_t need = bn_bytes<T>(g);
   if (need && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
-  const int rc1 = stage_conv_forward(shape, x, w, bias, y, stream);
+  const int rc1 = Abi<T>::conv_forward(shape, x, w, bias, y, nullptr, 0, stream);
   if (rc1 != MMS_OK) return rc1;
-  return stage_bn_pool_forward(g, 0, bn_memory, y, scale, shift, running_mean, running_var, top, save_pool, save_mean,
-                               save_std, workspace, workspace_bytes, stream);
+  const auto bn_pool_tanh = g.max ? Abi<T>::bn_maxpool_tanh_forward : Abi<T>::bn_pool_tanh_forward;
+  return bn_pool_tanh(0, g.d.N, g.d.K, g.d.OH, g.d.OW, g.ph, g.pw, bn_memory, y, scale, shift, running_mean, running_var,
+                      top, save_pool, save_mean, save_std, workspace, workspace_bytes, stream);
 }
 
 template <typename T>
@@ -290,7 +269,7 @@ int train_backward(const mms_conv_shape* shape, int ph, int pw, int pool, const 
     return MMS_ERR_INVALID_ARG;
   const void* const inputs[] = {x, w, y, top, top_diff, save_pool, scale, shift, save_mean, save_std};
   const void* const outputs[] = {dx, dw, db, dscale, dshift};
-  if (stage_outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
+  if (outputs_alias(outputs, inputs)) return MMS_ERR_INVALID_ARG;
   const bool conv = dx || dw || db;
   const BackwardCarve<T> carve = backward_carve<T>(shape, g);
   const size_t need = conv ? carve.all() : bn_bytes<T>(g);
@@ -302,7 +281,7 @@ int train_backward(const mms_conv_shape* shape, int ph, int pw, int pool, const 
   const int rc1 = bn_bwd(g, y, top, top_diff, save_pool, scale, shift, save_mean, save_std, dy, dscale, dshift, bn_ws,
                          bn_bytes<T>(g), stream);
   if (rc1 != MMS_OK || !conv) return rc1;
-  return conv_bwd(shape, x, w, dy, dx, dw, db, base + carve.dy + carve.bn, carve.conv, stream);
+  return Abi<T>::conv_backward(shape, x, w, dy, dx, dw, db, base + carve.dy + carve.bn, carve.conv, stream);
 }
 
 }  // namespace

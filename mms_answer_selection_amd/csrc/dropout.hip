@@ -223,11 +223,10 @@ int dropout_apply(const T* x, T* y, long long count, T ratio, int phase, unsigne
   if ((rc = dropout_check(count, seed, sequence, offset, &key, &ngroups)) != MMS_OK) return rc;
   if (count == 0) return MMS_OK;
   if (!x || !y) return MMS_ERR_INVALID_ARG;
-  const uintptr_t xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
-  const uintptr_t bytes = (uintptr_t)count * sizeof(T);
-  if (xa != ya && xa < ya + bytes && ya < xa + bytes) return MMS_ERR_INVALID_ARG;
+  const size_t bytes = (size_t)count * sizeof(T);
+  if (x != y && spans_meet(byte_span(x, bytes), byte_span(y, bytes))) return MMS_ERR_INVALID_ARG;     // in place, or apart
   if (phase == MMS_DROPOUT_TEST) {
-    if (xa == ya) return MMS_OK;
+    if (x == y) return MMS_OK;
     return hipMemcpyAsync(y, x, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess ? MMS_OK : MMS_ERR_LAUNCH;
   }
   const dim3 grid = dropout_grid(ngroups), block(kDropThreads);

@@ -455,9 +455,7 @@ static int embed_backward_src(int M, int N, int K, const EmbedSrc<T, S>& src,
     const dim3 grid((unsigned)std::min(M, K), (unsigned)((N + 63) / 64));   // at most min(M, K) distinct ids
     constexpr int CH = kSegChunk<T>;
     constexpr size_t kLongLds = 2 * CH * (64 * sizeof(T) + sizeof(unsigned));   // 130 KB of the CU's 160 KB
-    static const hipError_t once = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&embed_bwd_seg_kernel<CH, 8, T, S>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongLds);
+    static const hipError_t once = allow_dynamic_lds(&embed_bwd_seg_kernel<CH, 8, T, S>, (int)kLongLds);
     (void)once;
     const unsigned seg_blocks = (grid.x + 3) / 4, fin_blocks = bias_rides ? (unsigned)((N + 255) / 256) : 0u;
     hipLaunchKernelGGL((embed_bwd_short_kernel<T, S>), dim3(seg_blocks + fin_blocks, grid.y), dim3(256), 0, s, M, N, k1, v1,

@@ -377,25 +377,7 @@ __global__ __launch_bounds__(kFcThreads) void fc_concat_kernel(ConcatArgs a, voi
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-struct FcSpan {
-  uintptr_t lo, hi;
-};
-inline FcSpan fc_span(const void* p, size_t bytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const FcSpan s = {a, p ? a + bytes : a};
-  return s;
-}
-inline bool fc_meet(const FcSpan& a, const FcSpan& b) {
-  return a.lo != a.hi && b.lo != b.hi && a.lo < b.hi && b.lo < a.hi;
-}
-// whether one of the `nout` outputs (the first spans of the list) shares a byte with any other array of the list
-inline bool fc_outputs_overlap(const FcSpan* s, int n, int nout) {
-  for (int i = 0; i < nout; ++i)
-    for (int j = i + 1; j < n; ++j)
-      if (fc_meet(s[i], s[j])) return true;
-  return false;
-}
-
+// The overlap refusals are csrc/host_args.h's: outputs_overlap over a list whose first spans are the call's outputs.
 template <typename T>
 int ip_forward(const mms_inner_product_shape* shape, const T* x, const T* w, const T* b, T* top, bool generic,
                hipStream_t s) {
@@ -403,9 +385,10 @@ int ip_forward(const mms_inner_product_shape* shape, const T* x, const T* w, con
   const int rc = fc_ip_check(shape, &d);
   if (rc != MMS_OK || d.M == 0) return rc;
   if (!x || !w || !top || (d.bias && !b)) return MMS_ERR_INVALID_ARG;
-  const FcSpan spans[] = {fc_span(top, (size_t)d.M * d.N * sizeof(T)), fc_span(x, (size_t)d.M * d.K * sizeof(T)),
-                          fc_span(w, (size_t)d.K * d.N * sizeof(T)), fc_span(d.bias ? b : nullptr, d.N * sizeof(T))};
-  if (fc_outputs_overlap(spans, 4, 1)) return MMS_ERR_INVALID_ARG;
+  const ByteSpan spans[] = {byte_span(top, (size_t)d.M * d.N * sizeof(T)), byte_span(x, (size_t)d.M * d.K * sizeof(T)),
+                            byte_span(w, (size_t)d.K * d.N * sizeof(T)),
+                            byte_span(d.bias ? b : nullptr, d.N * sizeof(T))};
+  if (outputs_overlap(spans, 4, 1)) return MMS_ERR_INVALID_ARG;
   if (!d.bias) b = nullptr;
   if constexpr (sizeof(T) == 4) {
     if (!generic && fc_ip_route(d, MMS_FC_PASS_FORWARD) == MMS_FC_ROUTE_FAST) {
@@ -429,12 +412,12 @@ int ip_backward(const mms_inner_product_shape* shape, const T* x, const T* w, co
   if (!top_diff || (w_diff && !x) || (bottom_diff && !w) || (b_diff && !d.bias) || (!w_diff && !b_diff && !bottom_diff))
     return MMS_ERR_INVALID_ARG;
   const size_t nx = (size_t)d.M * d.K * sizeof(T), nw = (size_t)d.K * d.N * sizeof(T);
-  const size_t need = (size_t)fc_ip_workspace_elems(d) * sizeof(T);
+  const size_t need = (size_t)fc_ip_workspace_elems(d) * sizeof(T), nt = (size_t)d.M * d.N * sizeof(T);
   const bool sums = w_diff || b_diff;
-  const FcSpan spans[] = {fc_span(w_diff, nw), fc_span(b_diff, d.N * sizeof(T)), fc_span(bottom_diff, nx),
-                          fc_span(sums ? workspace : nullptr, need), fc_span(top_diff, (size_t)d.M * d.N * sizeof(T)),
-                          fc_span(w_diff ? x : nullptr, nx), fc_span(bottom_diff ? w : nullptr, nw)};
-  if (fc_outputs_overlap(spans, 7, 4)) return MMS_ERR_INVALID_ARG;
+  const ByteSpan spans[] = {byte_span(w_diff, nw), byte_span(b_diff, d.N * sizeof(T)), byte_span(bottom_diff, nx),
+                            byte_span(sums ? workspace : nullptr, need), byte_span(top_diff, nt),
+                            byte_span(w_diff ? x : nullptr, nx), byte_span(bottom_diff ? w : nullptr, nw)};
+  if (outputs_overlap(spans, 7, 4)) return MMS_ERR_INVALID_ARG;
   if (sums && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;
   bool fast = false;
   if constexpr (sizeof(T) == 4) fast = !generic && fc_ip_route(d, MMS_FC_PASS_BACKWARD) == MMS_FC_ROUTE_FAST;
@@ -507,9 +490,9 @@ int softmax_call(const mms_softmax_shape* shape, const T* a, const T* b, T* out,
   if (rc != MMS_OK || d.outer == 0) return rc;
   if (!a || !out || (BWD && !b)) return MMS_ERR_INVALID_ARG;
   const size_t bytes = (size_t)d.outer * d.channels * d.inner * sizeof(T);
-  const FcSpan so = fc_span(out, bytes), sa = fc_span(a, bytes), sb = fc_span(b, bytes);
-  if (fc_meet(so, sa) || (BWD && fc_meet(sa, sb))) return MMS_ERR_INVALID_ARG;
-  if (BWD && out != b && fc_meet(so, sb)) return MMS_ERR_INVALID_ARG;     // bottom_diff may BE top_diff
+  const ByteSpan so = byte_span(out, bytes), sa = byte_span(a, bytes), sb = byte_span(b, bytes);
+  if (spans_meet(so, sa) || (BWD && spans_meet(sa, sb))) return MMS_ERR_INVALID_ARG;
+  if (BWD && out != b && spans_meet(so, sb)) return MMS_ERR_INVALID_ARG;     // bottom_diff may BE top_diff
   softmax_launch<T, BWD>(d, a, b, out, s);
   return launch_status();
 }
@@ -543,9 +526,9 @@ int loss_forward(const mms_softmax_loss_shape* shape, const T* bottom, const T* 
   if (!bottom || !label || !prob || !loss) return MMS_ERR_INVALID_ARG;
   const long long P = (long long)d.outer * d.inner;
   const size_t bytes = (size_t)P * d.channels * sizeof(T), need = fc_loss_workspace_bytes(P, sizeof(T));
-  const FcSpan spans[] = {fc_span(prob, bytes), fc_span(loss, sizeof(T)), fc_span(workspace, need),
-                          fc_span(bottom, bytes), fc_span(label, (size_t)P * sizeof(T))};
-  if (fc_outputs_overlap(spans, 5, 3)) return MMS_ERR_INVALID_ARG;
+  const ByteSpan spans[] = {byte_span(prob, bytes), byte_span(loss, sizeof(T)), byte_span(workspace, need),
+                            byte_span(bottom, bytes), byte_span(label, (size_t)P * sizeof(T))};
+  if (outputs_overlap(spans, 5, 3)) return MMS_ERR_INVALID_ARG;
   if (!workspace || workspace_bytes < need) return MMS_ERR_WORKSPACE;
   const int slabs = fc_loss_slabs(P);
   const LossWs<T> w(workspace, slabs);
@@ -565,9 +548,9 @@ int loss_backward(const mms_softmax_loss_shape* shape, const T* prob, const T* l
   if (!prob || !label || !bottom_diff) return MMS_ERR_INVALID_ARG;
   const long long P = (long long)d.outer * d.inner;
   const size_t bytes = (size_t)P * d.channels * sizeof(T), need = fc_loss_workspace_bytes(P, sizeof(T));
-  const FcSpan spans[] = {fc_span(bottom_diff, bytes), fc_span(workspace, need), fc_span(prob, bytes),
-                          fc_span(label, (size_t)P * sizeof(T))};
-  if (fc_outputs_overlap(spans, 4, 2)) return MMS_ERR_INVALID_ARG;
+  const ByteSpan spans[] = {byte_span(bottom_diff, bytes), byte_span(workspace, need), byte_span(prob, bytes),
+                            byte_span(label, (size_t)P * sizeof(T))};
+  if (outputs_overlap(spans, 4, 2)) return MMS_ERR_INVALID_ARG;
   if (!workspace || workspace_bytes < need) return MMS_ERR_WORKSPACE;
   const int slabs = fc_loss_slabs(P);
   const LossWs<T> w(workspace, slabs);
@@ -596,19 +579,19 @@ int concat_call(const mms_concat_shape* shape, const T* const* ptrs, const T* wh
   a.num_concats = d.num_concats;
   a.top_run = d.top_axis * d.inner;
   const size_t top_bytes = (size_t)d.num_concats * a.top_run * sizeof(T);
-  const FcSpan top_span = fc_span(whole, top_bytes);
-  FcSpan bs[MMS_CONCAT_MAX_BOTTOMS];
+  const ByteSpan top_span = byte_span(whole, top_bytes);
+  ByteSpan bs[MMS_CONCAT_MAX_BOTTOMS];
   bool any = false;
   for (int b = 0; b < d.nb; ++b) {
     a.run[b] = d.extent[b] * d.inner;
     a.offset[b] = d.offset[b] * d.inner;
     a.bottom[b] = a.run[b] ? ptrs[b] : nullptr;
     if (TO_TOP && a.run[b] && !ptrs[b]) return MMS_ERR_INVALID_ARG;
-    bs[b] = fc_span(a.bottom[b], (size_t)d.num_concats * a.run[b] * sizeof(T));
-    if (fc_meet(bs[b], top_span)) return MMS_ERR_INVALID_ARG;
+    bs[b] = byte_span(a.bottom[b], (size_t)d.num_concats * a.run[b] * sizeof(T));
+    if (spans_meet(bs[b], top_span)) return MMS_ERR_INVALID_ARG;
     if (!TO_TOP)
       for (int c = 0; c < b; ++c)
-        if (fc_meet(bs[b], bs[c])) return MMS_ERR_INVALID_ARG;
+        if (spans_meet(bs[b], bs[c])) return MMS_ERR_INVALID_ARG;
     any = any || a.bottom[b];
     const size_t run_bytes = (size_t)a.run[b] * sizeof(T);
     a.vec[b] = a.bottom[b] && run_bytes % 16 == 0 && ((size_t)a.top_run * sizeof(T)) % 16 == 0 &&

@@ -40,6 +40,9 @@
 //
 // z1, d, z2 and dz1 never go to memory on the fast route.  Nothing is read 16 bytes at a time, so alignment cannot
 // change an order; every workspace word that is read has been written by this call.
+//
+// head_loss_from_terms (declared in csrc/mms_internal.h) is for the fused tails, csrc/score_tail.hip and
+// csrc/train_tail.hip, whose kernels run csrc/head_tile.h's steps themselves: the loss from each sample's term.
 #include "head_tile.h"
 #include "mms_head.h"
 #include "mms_internal.h"
@@ -207,6 +210,18 @@ __global__ void head_loss_finish_kernel(HeadArgs<T> a) {
     c += a.counts[k];
   }
   *a.loss = s / head_normalizer<T>(a.d, c);
+}
+
+// the fused tails (head_loss_from_terms): loss = (term 0 + term 1 + ...) / max(1, normalizer), n ascending
+__global__ void head_loss_from_terms_kernel(const float* terms, const int* valid, HeadDims d, float* loss) {
+  if (threadIdx.x || blockIdx.x) return;
+  float sum = terms[0];
+  int c = valid[0];
+  for (int n = 1; n < d.N; ++n) {
+    sum += terms[n];
+    c += valid[n];
+  }
+  *loss = sum / head_normalizer<float>(d, c);
 }
 
 template <typename T>
@@ -568,23 +583,6 @@ T head_scale(const mms_head_shape* s) {
   return T(1. / (1. - s->dropout_ratio));   // dropout_layer.cpp:14-18: threshold_ is a float, the quotient a double
 }
 
-bool head_aliased(const void* const* outs, int nout, const void* const* ins, int nin) {
-  for (int i = 0; i < nout; ++i) {
-    if (!outs[i]) continue;
-    for (int j = 0; j < nin; ++j)
-      if (outs[i] == ins[j]) return true;
-    for (int j = i + 1; j < nout; ++j)
-      if (outs[i] == outs[j]) return true;
-  }
-  return false;
-}
-
-template <class K>
-hipError_t head_allow_lds(K kernel) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             kHeadMaxLdsBytes);
-}
-
 template <typename T>
 int head_forward(const mms_head_shape* shape, const T* x0, const T* x1, const T* w1, const T* b1, const unsigned* mask,
                  const T* w2, const T* b2, const T* label, T* h, T* prob, T* loss, void* workspace,
@@ -595,9 +593,9 @@ int head_forward(const mms_head_shape* shape, const T* x0, const T* x1, const T*
   if (d.N == 0) return MMS_OK;
   if (!x0 || !w1 || !w2 || !h || !prob || (d.F1 > 0 && !x1) || (d.train && !mask) || (loss && !label))
     return MMS_ERR_INVALID_ARG;
-  const void* outs[] = {h, prob, loss};
-  const void* ins[] = {x0, x1, w1, b1, mask, w2, b2, label};
-  if (head_aliased(outs, 3, ins, 8)) return MMS_ERR_INVALID_ARG;
+  const void* const outs[] = {h, prob, loss};
+  const void* const ins[] = {x0, x1, w1, b1, mask, w2, b2, label};
+  if (outputs_alias(outs, ins)) return MMS_ERR_INVALID_ARG;
   if (loss && (!workspace || workspace_bytes < head_workspace_bytes<T>(shape))) return MMS_ERR_WORKSPACE;
   HeadArgs<T> a = {};
   a.d = d;
@@ -609,7 +607,7 @@ int head_forward(const mms_head_shape* shape, const T* x0, const T* x1, const T*
   if constexpr (std::is_same<T, float>::value) {
     if (!generic && head_route(d, MMS_HEAD_PASS_FORWARD) == MMS_HEAD_ROUTE_FAST) {
       const HeadFastPlan p = head_fast_plan(d);
-      static const hipError_t once = head_allow_lds(&head_fast_forward_kernel);
+      static const hipError_t once = allow_dynamic_lds(&head_fast_forward_kernel, kHeadMaxLdsBytes);
       if (once != hipSuccess) return MMS_ERR_LAUNCH;
       hipLaunchKernelGGL(head_fast_forward_kernel, dim3(a.slabs), dim3(kHeadThreads), p.fwd_lds, s, a, p);
       if ((rc = launch_status()) != MMS_OK || !loss || a.slabs == 1) return rc;
@@ -639,9 +637,9 @@ int head_backward(const mms_head_shape* shape, const T* x0, const T* x1, const T
     return MMS_ERR_INVALID_ARG;
   if (d.F1 == 0) x1d = nullptr;             // an array of no elements
   if (!x0d && !x1d && !w1d && !b1d && !w2d && !b2d) return MMS_ERR_INVALID_ARG;
-  const void* outs[] = {x0d, x1d, w1d, b1d, w2d, b2d};
-  const void* ins[] = {x0, x1, w1, w2, mask, h, prob, label};
-  if (head_aliased(outs, 6, ins, 8)) return MMS_ERR_INVALID_ARG;
+  const void* const outs[] = {x0d, x1d, w1d, b1d, w2d, b2d};
+  const void* const ins[] = {x0, x1, w1, w2, mask, h, prob, label};
+  if (outputs_alias(outs, ins)) return MMS_ERR_INVALID_ARG;
   if (!workspace || workspace_bytes < head_workspace_bytes<T>(shape)) return MMS_ERR_WORKSPACE;
   HeadArgs<T> a = {};
   a.d = d;
@@ -657,7 +655,7 @@ int head_backward(const mms_head_shape* shape, const T* x0, const T* x1, const T
   if constexpr (std::is_same<T, float>::value) {
     if (!generic && head_route(d, MMS_HEAD_PASS_BACKWARD) == MMS_HEAD_ROUTE_FAST) {
       const HeadFastPlan p = head_fast_plan(d);
-      static const hipError_t once = head_allow_lds(&head_fast_backward_kernel);
+      static const hipError_t once = allow_dynamic_lds(&head_fast_backward_kernel, kHeadMaxLdsBytes);
       if (once != hipSuccess) return MMS_ERR_LAUNCH;
       hipLaunchKernelGGL(head_fast_backward_kernel, dim3(a.slabs), dim3(kHeadThreads), p.bwd_lds, s, a, p);
       if ((rc = launch_status()) != MMS_OK || !want_p || a.slabs == 1) return rc;
@@ -681,6 +679,12 @@ int head_backward(const mms_head_shape* shape, const T* x0, const T* x1, const T
 }
 
 }  // namespace
+
+int head_loss_from_terms(const float* terms, const int* valid, const HeadDims& d, float* loss, hipStream_t s) {
+  hipLaunchKernelGGL(head_loss_from_terms_kernel, dim3(1), dim3(64), 0, s, terms, valid, d, loss);
+  return launch_status();
+}
+
 }  // namespace mms
 
 using namespace mms;

@@ -28,6 +28,13 @@ inline bool vec4_ok(int D, const void* p0, const void* p1, const void* p2, const
 
 inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
+// A kernel's opt-in to more than 64 KB of dynamic LDS, up to `bytes`.  Once per kernel at the call site:
+// `static const hipError_t once = allow_dynamic_lds(&K<...>, limit)`.
+template <class K>
+inline hipError_t allow_dynamic_lds(K kernel, int bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
 // A runtime bool as a template argument: with_bool(flag, [&](auto B) { launch K<..., decltype(B)::value> }).
 // Both instantiations of the lambda exist, as with `if (flag) K<true> else K<false>` written out.
 template <class F>

@@ -3,6 +3,7 @@
 #ifndef MMS_INTERNAL_H_
 #define MMS_INTERNAL_H_
 
+#include "host_args.h"
 #include "mms_common.h"
 
 namespace mms {
@@ -156,6 +157,10 @@ int null_launch(int workgroups, hipStream_t s);
 template <class T>
 int dot(int n, const T* x, const T* y, T* out, hipStream_t s);
 int split_sum(int count, int ntop, const float* const* top_diffs, float* bottom_diff, hipStream_t s);
+// head.hip: what the fused tails (score_tail.hip, train_tail.hip) end a loss with, from each sample's term and whether
+// it counts: one launch of one thread, the terms added in ascending n.  d: the head's dims (csrc/head_tile.h)
+struct HeadDims;
+int head_loss_from_terms(const float* terms, const int* valid, const HeadDims& d, float* loss, hipStream_t s);
 // f64_paths.hip
 size_t simcross_workspace_bytes_f64(int mode, int N, int W1, int W2, int D, int M);
 int simcross_forward_f64(int mode, int N, int W1, int W2, int D, int M, const double* q, const double* a, const double* W,

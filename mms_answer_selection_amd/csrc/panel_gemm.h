@@ -745,7 +745,7 @@ inline void panel_launch_t(const PanelArgs& p, hipStream_t s) {
   const size_t lds = PanelGeom<NT, A_KC>::kLdsBytes;
   auto kern = panel_gemm_kernel<NT, A_KC>;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)allow_dynamic_lds(kern, (int)lds);
     attr_set = true;
   }
   const unsigned gx = p.ksplit > 1 ? 8u * ((p.ksplit + 7) / 8) * p.row_blocks : (unsigned)p.row_blocks;

@@ -223,25 +223,7 @@ __global__ __launch_bounds__(kPoolThreads) void pool_tanh_kernel(long long count
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-struct PoolSpan {
-  uintptr_t lo, hi;
-};
-inline PoolSpan pool_span(const void* p, size_t bytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const PoolSpan s = {a, p ? a + bytes : a};
-  return s;
-}
-// whether two of the arrays (a NULL one is none) share a byte; with `in_place`, spans 0 and n - 1 may be one array
-template <int NS>
-bool pool_overlap(const PoolSpan (&s)[NS], bool in_place) {
-  for (int i = 0; i < NS; ++i)
-    for (int j = i + 1; j < NS; ++j) {
-      if (s[i].lo == s[i].hi || s[j].lo == s[j].hi) continue;
-      if (in_place && i == 0 && j == NS - 1 && s[i].lo == s[j].lo) continue;
-      if (s[i].lo < s[j].hi && s[j].lo < s[i].hi) return true;
-    }
-  return false;
-}
+// The overlap refusals are csrc/host_args.h's: arrays_overlap, no two arrays of a call share a byte.
 
 // what forward and backward judge alike; *done: MMS_OK with nothing to launch
 int pool_check(const mms_pool_shape* shape, PoolGeom* g, long long* nbottom, long long* ntop, bool* done) {
@@ -263,9 +245,9 @@ int pool_forward(const mms_pool_shape* shape, const T* bottom, T* top, int* mask
   const int rc = pool_check(shape, &g, &nb, &nt, &done);
   if (rc != MMS_OK || done) return rc;
   if (!bottom || !top) return MMS_ERR_INVALID_ARG;
-  const PoolSpan spans[] = {pool_span(bottom, (size_t)nb * sizeof(T)), pool_span(top, (size_t)nt * sizeof(T)),
-                            pool_span(mask, (size_t)nt * sizeof(int)), pool_span(top_mask, (size_t)nt * sizeof(T))};
-  if (pool_overlap(spans, false)) return MMS_ERR_INVALID_ARG;
+  const ByteSpan spans[] = {byte_span(bottom, (size_t)nb * sizeof(T)), byte_span(top, (size_t)nt * sizeof(T)),
+                            byte_span(mask, (size_t)nt * sizeof(int)), byte_span(top_mask, (size_t)nt * sizeof(T))};
+  if (arrays_overlap(spans, 4, false)) return MMS_ERR_INVALID_ARG;
   if (g.method == MMS_POOL_AVE) mask = nullptr, top_mask = nullptr;          // ignored
   const PoolPlan p = pool_forward_plan(g, (int)sizeof(T));
   const dim3 grid((unsigned)p.blocks), block(kPoolThreads);
@@ -297,9 +279,9 @@ int pool_backward(const mms_pool_shape* shape, const T* top_diff, const int* mas
   if (rc != MMS_OK || done) return rc;
   if (!top_diff || !bottom_diff) return MMS_ERR_INVALID_ARG;
   if (g.method == MMS_POOL_MAX && !mask && !top_mask) return MMS_ERR_INVALID_ARG;
-  const PoolSpan spans[] = {pool_span(top_diff, (size_t)nt * sizeof(T)), pool_span(mask, (size_t)nt * sizeof(int)),
-                            pool_span(top_mask, (size_t)nt * sizeof(T)), pool_span(bottom_diff, (size_t)nb * sizeof(T))};
-  if (pool_overlap(spans, false)) return MMS_ERR_INVALID_ARG;
+  const ByteSpan spans[] = {byte_span(top_diff, (size_t)nt * sizeof(T)), byte_span(mask, (size_t)nt * sizeof(int)),
+                            byte_span(top_mask, (size_t)nt * sizeof(T)), byte_span(bottom_diff, (size_t)nb * sizeof(T))};
+  if (arrays_overlap(spans, 4, false)) return MMS_ERR_INVALID_ARG;
   const bool vec = aligned16(bottom_diff);
   const int VW = vec ? 16 / (int)sizeof(T) : 1;
   const dim3 grid((unsigned)pool_sweep_blocks((nb + VW - 1) / VW)), block(kPoolThreads);
@@ -324,9 +306,9 @@ int pool_tanh_call(long long count, const T* a, const T* b, T* out, hipStream_t 
   if ((unsigned long long)count > (unsigned long long)(SIZE_MAX / sizeof(T))) return MMS_ERR_INVALID_ARG;
   const size_t bytes = (size_t)count * sizeof(T);
   // the in-place pair is (b, out) in the backward and (a, out) in the forward: first and last of the list
-  const PoolSpan fwd[] = {pool_span(a, bytes), pool_span(out, bytes)};
-  const PoolSpan bwd[] = {pool_span(b, bytes), pool_span(a, bytes), pool_span(out, bytes)};
-  if (BWD ? pool_overlap(bwd, true) : pool_overlap(fwd, true)) return MMS_ERR_INVALID_ARG;
+  const ByteSpan fwd[] = {byte_span(a, bytes), byte_span(out, bytes)};
+  const ByteSpan bwd[] = {byte_span(b, bytes), byte_span(a, bytes), byte_span(out, bytes)};
+  if (BWD ? arrays_overlap(bwd, 3, true) : arrays_overlap(fwd, 2, true)) return MMS_ERR_INVALID_ARG;
   const bool vec = aligned16(a) && aligned16(out) && (!BWD || aligned16(b));
   const int VW = vec ? 16 / (int)sizeof(T) : 1;
   const dim3 grid((unsigned)pool_sweep_blocks((count + VW - 1) / VW)), block(kPoolThreads);

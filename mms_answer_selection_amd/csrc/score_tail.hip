@@ -21,7 +21,7 @@
 //             flt where asked).  Then csrc/head_tile.h's steps on those rows: fc1
 //             blocks of 16 samples x 16 hidden units dealt to the four waves, fc2 one thread per (sample, class),
 //             softmax one thread per sample.  With a loss each sample's term and whether it counts go to the workspace
-//             and tail_loss_finish_kernel, one thread, adds them in ascending n: a second launch.
+//             and head_loss_from_terms (csrc/head.hip), one thread, adds them in ascending n: a second launch.
 //
 // A value of flt, h or prob is the same chain of operations on both routes: the convolution's chunks are the
 // convolution's own (tail_plan refuses a plan that would cut them differently) and every later step is per sample.
@@ -212,37 +212,19 @@ __global__ __launch_bounds__(kConvThreads) void score_tail_kernel(TailArgs s) {
   conv_tile_product<MT>(s.p, conv_lds, epi);
 }
 
-// loss = (term 0 + term 1 + ...) / max(1, normalizer), n ascending
-__global__ void tail_loss_finish_kernel(const float* terms, const int* valid, HeadDims d, float* loss) {
-  if (threadIdx.x || blockIdx.x) return;
-  float sum = terms[0];
-  int c = valid[0];
-  for (int n = 1; n < d.N; ++n) {
-    sum += terms[n];
-    c += valid[n];
-  }
-  *loss = sum / head_normalizer<float>(d, c);
-}
-
 struct TailSequenceWorkspace {
-  size_t stage, flt, h, head, total;       // bytes of each part; flt and h start at round16 offsets
+  size_t stage, flt, h, head, total;       // bytes of each part; flt and h start at offsets rounded up to 16
 };
 
 template <typename T>
 TailSequenceWorkspace tail_sequence_workspace(const mms_score_tail_shape* s, const TailDims& g) {
   TailSequenceWorkspace w;
-  if (std::is_same<T, float>::value) {
-    w.stage = g.max ? mms_conv_maxpool_stage_workspace_bytes(&s->conv, g.ph, g.pw)
-                    : mms_conv_stage_workspace_bytes(&s->conv, g.ph, g.pw);
-    w.head = mms_head_workspace_bytes(&g.hs);
-  } else {
-    w.stage = g.max ? mms_conv_maxpool_stage_workspace_bytes_f64(&s->conv, g.ph, g.pw)
-                    : mms_conv_stage_workspace_bytes_f64(&s->conv, g.ph, g.pw);
-    w.head = mms_head_workspace_bytes_f64(&g.hs);
-  }
+  const auto stage_bytes = g.max ? Abi<T>::conv_maxpool_stage_workspace_bytes : Abi<T>::conv_stage_workspace_bytes;
+  w.stage = stage_bytes(&s->conv, g.ph, g.pw);
+  w.head = Abi<T>::head_workspace_bytes(&g.hs);
   w.flt = (size_t)g.hd.N * g.hd.F0 * sizeof(T);
   w.h = (size_t)g.hd.N * g.hd.H * sizeof(T);
-  w.total = round16(w.stage) + round16(w.flt) + round16(w.h) + round16(w.head);
+  w.total = round_up(w.stage, 16) + round_up(w.flt, 16) + round_up(w.h, 16) + round_up(w.head, 16);
   return w;
 }
 
@@ -257,38 +239,9 @@ size_t tail_workspace_bytes(const mms_score_tail_shape* shape, bool sequence) { 
   return tail_sequence_workspace<T>(shape, g).total;
 }
 
-inline int stage_public(bool max, const mms_conv_shape* s, int ph, int pw, const float* x, const float* w,
-                        const float* b, const float* mean, const float* var, const float* scale, const float* shift,
-                        float* top, void* ws, size_t wsb, void* st) {
-  const auto call = max ? mms_conv_maxpool_stage_forward_f32 : mms_conv_stage_forward_f32;
-  return call(s, ph, pw, x, w, b, mean, var, scale, shift, top, nullptr, ws, wsb, st);
-}
-inline int stage_public(bool max, const mms_conv_shape* s, int ph, int pw, const double* x, const double* w,
-                        const double* b, const double* mean, const double* var, const double* scale,
-                        const double* shift, double* top, void* ws, size_t wsb, void* st) {
-  const auto call = max ? mms_conv_maxpool_stage_forward_f64 : mms_conv_stage_forward_f64;
-  return call(s, ph, pw, x, w, b, mean, var, scale, shift, top, nullptr, ws, wsb, st);
-}
-inline int head_public(const mms_head_shape* s, const float* x0, const float* x1, const float* w1, const float* b1,
-                       const float* w2, const float* b2, const float* label, float* h, float* prob, float* loss,
-                       void* ws, size_t wsb, void* st) {
-  return mms_head_forward_f32(s, x0, x1, w1, b1, nullptr, w2, b2, label, h, prob, loss, ws, wsb, st);
-}
-inline int head_public(const mms_head_shape* s, const double* x0, const double* x1, const double* w1, const double* b1,
-                       const double* w2, const double* b2, const double* label, double* h, double* prob, double* loss,
-                       void* ws, size_t wsb, void* st) {
-  return mms_head_forward_f64(s, x0, x1, w1, b1, nullptr, w2, b2, label, h, prob, loss, ws, wsb, st);
-}
-
-template <class K>
-hipError_t tail_allow_lds(K kernel) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             kTailMaxLdsBytes);
-}
-
 template <int MT, bool MAX>
 int tail_launch(const TailArgs& a, void* stream) {
-  static const hipError_t once = tail_allow_lds(&score_tail_kernel<MT, MAX>);
+  static const hipError_t once = allow_dynamic_lds(&score_tail_kernel<MT, MAX>, kTailMaxLdsBytes);
   if (once != hipSuccess) return MMS_ERR_LAUNCH;
   hipLaunchKernelGGL((score_tail_kernel<MT, MAX>), dim3((unsigned)stage_groups(a.p)), dim3(kConvThreads), a.lds_bytes,
                      as_stream(stream), a);
@@ -310,7 +263,7 @@ int tail_forward(const mms_score_tail_shape* shape, const T* x, const T* w, cons
   if (!w1 || !w2 || !prob || (g.hd.F1 > 0 && !overlap) || (loss && !label)) return MMS_ERR_INVALID_ARG;
   const void* const outs[] = {flt, h, prob, loss};
   const void* const ins[] = {x, w, bias, mean, var, scale, shift, overlap, w1, b1, w2, b2, label};
-  if (stage_outputs_alias(outs, ins)) return MMS_ERR_INVALID_ARG;
+  if (outputs_alias(outs, ins)) return MMS_ERR_INVALID_ARG;
   if constexpr (std::is_same<T, float>::value) {
     if (force == MMS_SCORE_TAIL_ROUTE_FUSED && !tail_plan(g, kTailImages).ok) return MMS_ERR_UNSUPPORTED;
     if (force == MMS_SCORE_TAIL_ROUTE_FUSED ||
@@ -329,22 +282,23 @@ int tail_forward(const mms_score_tail_shape* shape, const T* x, const T* w, cons
         rc = g.max ? tail_launch<decltype(M)::value, true>(a, stream) : tail_launch<decltype(M)::value, false>(a, stream);
       });
       if (rc != MMS_OK || !loss) return rc;
-      hipLaunchKernelGGL(tail_loss_finish_kernel, dim3(1), dim3(64), 0, as_stream(stream), a.terms, a.valid, g.hd, loss);
-      return launch_status();
+      return head_loss_from_terms(a.terms, a.valid, g.hd, loss, as_stream(stream));
     }
   }
   const TailSequenceWorkspace ws = tail_sequence_workspace<T>(shape, g);
   if (!workspace || workspace_bytes < ws.total) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(workspace);
   void* stage_ws = base;
-  T* flt_ws = reinterpret_cast<T*>(base + round16(ws.stage));
-  T* h_ws = reinterpret_cast<T*>(base + round16(ws.stage) + round16(ws.flt));
-  void* head_ws = base + round16(ws.stage) + round16(ws.flt) + round16(ws.h);
+  T* flt_ws = reinterpret_cast<T*>(base + round_up(ws.stage, 16));
+  T* h_ws = reinterpret_cast<T*>(base + round_up(ws.stage, 16) + round_up(ws.flt, 16));
+  void* head_ws = base + round_up(ws.stage, 16) + round_up(ws.flt, 16) + round_up(ws.h, 16);
   T* f = flt ? flt : flt_ws;
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
-  rc = stage_public(g.max, &shape->conv, g.ph, g.pw, x, w, bias, mean, var, scale, shift, f, stage_ws, ws.stage, stream);
+  const auto stage_forward = g.max ? Abi<T>::conv_maxpool_stage_forward : Abi<T>::conv_stage_forward;
+  rc = stage_forward(&shape->conv, g.ph, g.pw, x, w, bias, mean, var, scale, shift, f, nullptr, stage_ws, ws.stage, stream);
   if (rc != MMS_OK) return rc;
-  return head_public(&g.hs, f, overlap, w1, b1, w2, b2, label, h ? h : h_ws, prob, loss, head_ws, ws.head, stream);
+  return Abi<T>::head_forward(&g.hs, f, overlap, w1, b1, nullptr, w2, b2, label, h ? h : h_ws, prob, loss, head_ws,
+                              ws.head, stream);
 }
 
 }  // namespace

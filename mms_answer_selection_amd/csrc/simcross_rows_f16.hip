@@ -347,8 +347,7 @@ int simcross_euclid_rows_f16(int N, int D, const void* q, const void* a, const f
     static const bool once = [] {
       for (const auto& row : kernels)
         for (const Kernel f : row)
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024);
+          (void)allow_dynamic_lds(f, 160 * 1024);
       return true;
     }();
     (void)once;

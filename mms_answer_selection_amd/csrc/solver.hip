@@ -28,7 +28,6 @@
 
 #include <algorithm>
 #include <exception>
-#include <utility>
 #include <vector>
 
 #include "mms_internal.h"
@@ -318,13 +317,6 @@ size_t solver_workspace_bytes(const mms_solver_param* p, const mms_solver_blob* 
   return (kSolverHeaderWords + (size_t)items) * sizeof(T);
 }
 
-typedef std::pair<uintptr_t, uintptr_t> SolverSpan;   // [first, second) in bytes
-
-inline SolverSpan solver_span(const void* p, size_t bytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  return SolverSpan(a, a + bytes);
-}
-
 // The next table: up to kSolverBlobs blobs of count > 0 from blobs[*next ...], in blob order; *next moves past them.
 template <typename T>
 void solver_next_table(const mms_solver_blob* blobs, int nblobs, int* next, bool ada, T rate, T wd, SolverTable<T>* tab) {
@@ -365,12 +357,14 @@ int solver_step(const mms_solver_param* p, const mms_solver_blob* blobs, int nbl
   }
   if (nonempty == 0) return MMS_OK;
 
-  // no two arrays overlap: the address ranges, sorted.  One launch's worth of them fits the stack; a longer list
-  // takes host memory, and a call that cannot have it is refused like any other (nothing crosses the C boundary).
+  // no two arrays overlap: the address ranges (csrc/host_args.h), none of them NULL or empty, sorted by (lo, hi), so
+  // that two that meet are neighbours -- O(n log n) for O(blobs) spans.  One launch's worth of them fits the stack; a
+  // longer list takes host memory, and a call that cannot have it is refused like any other (nothing crosses the C
+  // boundary).
   const size_t nspans_max = 4 * (size_t)nonempty + 2;
-  SolverSpan on_stack[4 * kSolverBlobs + 2];
-  std::vector<SolverSpan> on_heap;
-  SolverSpan* spans = on_stack;
+  ByteSpan on_stack[4 * kSolverBlobs + 2];
+  std::vector<ByteSpan> on_heap;
+  ByteSpan* spans = on_stack;
   if (nspans_max > sizeof(on_stack) / sizeof(on_stack[0])) {
     try {
       on_heap.resize(nspans_max);
@@ -384,16 +378,16 @@ int solver_step(const mms_solver_param* p, const mms_solver_blob* blobs, int nbl
     const mms_solver_blob& bl = blobs[i];
     if (bl.count == 0) continue;
     const size_t bytes = (size_t)bl.count * sizeof(T);
-    spans[nspans++] = solver_span(bl.data, bytes);
-    spans[nspans++] = solver_span(bl.diff, bytes);
-    spans[nspans++] = solver_span(bl.hist_grad, bytes);
-    if (ada) spans[nspans++] = solver_span(bl.hist_update, bytes);
+    spans[nspans++] = byte_span(bl.data, bytes);
+    spans[nspans++] = byte_span(bl.diff, bytes);
+    spans[nspans++] = byte_span(bl.hist_grad, bytes);
+    if (ada) spans[nspans++] = byte_span(bl.hist_update, bytes);
   }
-  if (clip_info) spans[nspans++] = solver_span(clip_info, 2 * sizeof(T));
-  if (clips && workspace) spans[nspans++] = solver_span(workspace, need);
+  if (clip_info) spans[nspans++] = byte_span(clip_info, 2 * sizeof(T));
+  if (clips && workspace) spans[nspans++] = byte_span(workspace, need);
   std::sort(spans, spans + nspans);
   for (size_t i = 1; i < nspans; ++i)
-    if (spans[i - 1].second > spans[i].first) return MMS_ERR_INVALID_ARG;
+    if (spans_meet(spans[i - 1], spans[i])) return MMS_ERR_INVALID_ARG;
   if (clips && (!workspace || workspace_bytes < need)) return MMS_ERR_WORKSPACE;
 
   const T wd = T(p->weight_decay);

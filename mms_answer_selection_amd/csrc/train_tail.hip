@@ -29,7 +29,7 @@
 //             bn_pool_train_finish into save_pool, flt and the samples' feat rows in LDS, next to their overlap rows,
 //             and runs csrc/head_tile.h's steps on those rows.  The loss: one workgroup adds its terms itself, thread 0
 //             in ascending n; several leave each sample's term and whether it counts in the workspace for
-//             train_tail_loss_kernel, one thread, the same chain.
+//             head_loss_from_terms (csrc/head.hip), one thread, the same chain.
 #include "conv_pool_tile.h"
 #include "head_tile.h"
 #include "mms_conv_stage_train.h"
@@ -293,41 +293,24 @@ __global__ __launch_bounds__(kHeadThreads) void train_tail_finish_kernel(TrainTa
   }
 }
 
-// loss = (term 0 + term 1 + ...) / max(1, normalizer), n ascending
-__global__ void train_tail_loss_kernel(const float* terms, const int* valid, HeadDims d, float* loss) {
-  if (threadIdx.x || blockIdx.x) return;
-  float sum = terms[0];
-  int c = valid[0];
-  for (int n = 1; n < d.N; ++n) {
-    sum += terms[n];
-    c += valid[n];
-  }
-  *loss = sum / head_normalizer<float>(d, c);
-}
-
 // ---- host -----------------------------------------------------------------------------------------------------------
 struct TrainTailCarve {
   size_t stage, x0d, head;   // bytes of each part of the sequence layout, before rounding
-  size_t total() const { return round16(stage) + round16(x0d) + round16(head); }
+  size_t total() const { return round_up(stage, 16) + round_up(x0d, 16) + round_up(head, 16); }
 };
 
 template <typename T>
 TrainTailCarve train_tail_carve(const mms_score_tail_shape* s, const TrainTailDims& g) {
   TrainTailCarve w;
-  if (std::is_same<T, float>::value) {
-    w.stage = mms_conv_stage_train_workspace_bytes(&s->conv, g.ph, g.pw, g.pool);
-    w.head = mms_head_workspace_bytes(&g.hs);
-  } else {
-    w.stage = mms_conv_stage_train_workspace_bytes_f64(&s->conv, g.ph, g.pw, g.pool);
-    w.head = mms_head_workspace_bytes_f64(&g.hs);
-  }
+  w.stage = Abi<T>::conv_stage_train_workspace_bytes(&s->conv, g.ph, g.pw, g.pool);
+  w.head = Abi<T>::head_workspace_bytes(&g.hs);
   w.x0d = (size_t)g.hd.N * g.hd.F0 * sizeof(T);
   return w;
 }
 
 inline size_t train_tail_part_bytes(const TrainTailArgs& a) { return (size_t)2 * a.p.Cout * a.groups * sizeof(float); }
 inline size_t train_tail_fused_bytes(const TrainTailArgs& a, const TrainTailDims& g) {
-  return round16(train_tail_part_bytes(a)) + round16((size_t)g.hd.N * (sizeof(float) + sizeof(int)));
+  return round_up(train_tail_part_bytes(a), 16) + round_up((size_t)g.hd.N * (sizeof(float) + sizeof(int)), 16);
 }
 
 enum { kAuto = -1, kSequence = MMS_TRAIN_TAIL_ROUTE_SEQUENCE, kFused = MMS_TRAIN_TAIL_ROUTE_FUSED };
@@ -351,58 +334,6 @@ size_t train_tail_workspace_bytes(const mms_score_tail_shape* shape, int force) 
   return train_tail_bytes<T>(shape, g, force);
 }
 
-inline int stage_fwd(const mms_conv_shape* s, int ph, int pw, int pool, float mem, const float* x, const float* w,
-                     const float* b, const float* sc, const float* sh, float* rm, float* rv, float* y, float* top,
-                     float* sp, float* sm, float* ss, void* ws, size_t wsb, void* st) {
-  return mms_conv_stage_train_forward_f32(s, ph, pw, pool, mem, x, w, b, sc, sh, rm, rv, y, top, sp, sm, ss, ws, wsb, st);
-}
-inline int stage_fwd(const mms_conv_shape* s, int ph, int pw, int pool, double mem, const double* x, const double* w,
-                     const double* b, const double* sc, const double* sh, double* rm, double* rv, double* y, double* top,
-                     double* sp, double* sm, double* ss, void* ws, size_t wsb, void* st) {
-  return mms_conv_stage_train_forward_f64(s, ph, pw, pool, mem, x, w, b, sc, sh, rm, rv, y, top, sp, sm, ss, ws, wsb, st);
-}
-inline int stage_bwd(const mms_conv_shape* s, int ph, int pw, int pool, const float* x, const float* w, const float* y,
-                     const float* top, const float* td, const float* sp, const float* sc, const float* sh,
-                     const float* sm, const float* ss, float* dx, float* dw, float* db, float* dsc, float* dsh, void* ws,
-                     size_t wsb, void* st) {
-  return mms_conv_stage_train_backward_f32(s, ph, pw, pool, x, w, y, top, td, sp, sc, sh, sm, ss, dx, dw, db, dsc, dsh,
-                                           ws, wsb, st);
-}
-inline int stage_bwd(const mms_conv_shape* s, int ph, int pw, int pool, const double* x, const double* w,
-                     const double* y, const double* top, const double* td, const double* sp, const double* sc,
-                     const double* sh, const double* sm, const double* ss, double* dx, double* dw, double* db,
-                     double* dsc, double* dsh, void* ws, size_t wsb, void* st) {
-  return mms_conv_stage_train_backward_f64(s, ph, pw, pool, x, w, y, top, td, sp, sc, sh, sm, ss, dx, dw, db, dsc, dsh,
-                                           ws, wsb, st);
-}
-inline int head_fwd(const mms_head_shape* s, const float* x0, const float* x1, const float* w1, const float* b1,
-                    const unsigned* mask, const float* w2, const float* b2, const float* label, float* h, float* prob,
-                    float* loss, void* ws, size_t wsb, void* st) {
-  return mms_head_forward_f32(s, x0, x1, w1, b1, mask, w2, b2, label, h, prob, loss, ws, wsb, st);
-}
-inline int head_fwd(const mms_head_shape* s, const double* x0, const double* x1, const double* w1, const double* b1,
-                    const unsigned* mask, const double* w2, const double* b2, const double* label, double* h,
-                    double* prob, double* loss, void* ws, size_t wsb, void* st) {
-  return mms_head_forward_f64(s, x0, x1, w1, b1, mask, w2, b2, label, h, prob, loss, ws, wsb, st);
-}
-inline int head_bwd(const mms_head_shape* s, const float* x0, const float* x1, const float* w1, const float* w2,
-                    const unsigned* mask, const float* h, const float* prob, const float* label, float lw, float* x0d,
-                    float* x1d, float* w1d, float* b1d, float* w2d, float* b2d, void* ws, size_t wsb, void* st) {
-  return mms_head_backward_f32(s, x0, x1, w1, w2, mask, h, prob, label, lw, x0d, x1d, w1d, b1d, w2d, b2d, ws, wsb, st);
-}
-inline int head_bwd(const mms_head_shape* s, const double* x0, const double* x1, const double* w1, const double* w2,
-                    const unsigned* mask, const double* h, const double* prob, const double* label, double lw,
-                    double* x0d, double* x1d, double* w1d, double* b1d, double* w2d, double* b2d, void* ws, size_t wsb,
-                    void* st) {
-  return mms_head_backward_f64(s, x0, x1, w1, w2, mask, h, prob, label, lw, x0d, x1d, w1d, b1d, w2d, b2d, ws, wsb, st);
-}
-
-template <class K>
-hipError_t train_tail_allow_lds(K kernel) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             kTrainTailMaxLdsBytes - (int)kTrainTailFinishStatic);
-}
-
 // force: kAuto (train_tail_route decides), kSequence or kFused (float; MMS_ERR_UNSUPPORTED where the plan refuses)
 template <typename T>
 int train_tail_forward(const mms_score_tail_shape* shape, int phase, T bn_memory, float dropout_ratio, const T* x,
@@ -420,7 +351,7 @@ int train_tail_forward(const mms_score_tail_shape* shape, int phase, T bn_memory
   const void* const arrays[] = {x,  w,  bias,  scale, shift, running_mean, running_var, overlap,  w1, b1,   mask,
                                 w2, b2, label, y,     flt,   save_pool,    save_mean,   save_std, h,  prob, loss};
   const void* const ws_only[] = {workspace};
-  if (stage_outputs_alias(arrays, ws_only)) return MMS_ERR_INVALID_ARG;     // any two arrays, the workspace included
+  if (outputs_alias(arrays, ws_only)) return MMS_ERR_INVALID_ARG;     // any two arrays, the workspace included
   const TrainTailCarve carve = train_tail_carve<T>(shape, g);
   char* base = static_cast<char*>(workspace);
   if constexpr (std::is_same<T, float>::value) {
@@ -430,7 +361,8 @@ int train_tail_forward(const mms_score_tail_shape* shape, int phase, T bn_memory
       TrainTailArgs a = train_tail_plan(g, kTrainTailImages);
       a.p.in = x; a.p.w = w; a.p.bias = bias; a.p.out = y;
       a.scale = scale; a.save_pool = save_pool; a.part = reinterpret_cast<float*>(base);
-      static const hipError_t once = train_tail_allow_lds(&train_tail_finish_kernel);
+      static const hipError_t once =
+          allow_dynamic_lds(&train_tail_finish_kernel, kTrainTailMaxLdsBytes - (int)kTrainTailFinishStatic);
       if (once != hipSuccess) return MMS_ERR_LAUNCH;
       conv_with_mt(a.p.MT, [&](auto M) {
         with_bool(g.max, [&](auto MAX) {
@@ -447,7 +379,7 @@ int train_tail_forward(const mms_score_tail_shape* shape, int phase, T bn_memory
       f.save_std = save_std; f.flt = flt; f.h = h; f.prob = prob; f.loss = loss;
       const unsigned finish_groups = (unsigned)((g.hd.N + kHeadFastSamples - 1) / kHeadFastSamples);
       if (loss && finish_groups > 1) {
-        f.terms = reinterpret_cast<float*>(base + round16(train_tail_part_bytes(a)));
+        f.terms = reinterpret_cast<float*>(base + round_up(train_tail_part_bytes(a), 16));
         f.valid = reinterpret_cast<int*>(f.terms + g.hd.N);
       }
       f.bn_memory = bn_memory;
@@ -457,18 +389,18 @@ int train_tail_forward(const mms_score_tail_shape* shape, int phase, T bn_memory
       hipLaunchKernelGGL(train_tail_finish_kernel, dim3(finish_groups), dim3(kHeadThreads), a.finish_lds_bytes,
                          as_stream(stream), f);
       if ((rc = launch_status()) != MMS_OK || !f.terms) return rc;
-      hipLaunchKernelGGL(train_tail_loss_kernel, dim3(1), dim3(64), 0, as_stream(stream), (const float*)f.terms,
-                         (const int*)f.valid, g.hd, loss);
-      return launch_status();
+      return head_loss_from_terms(f.terms, f.valid, g.hd, loss, as_stream(stream));
     }
   }
   if (!workspace || workspace_bytes < carve.total()) return MMS_ERR_WORKSPACE;
-  void* head_ws = base + round16(carve.stage) + round16(carve.x0d);
+  void* head_ws = base + round_up(carve.stage, 16) + round_up(carve.x0d, 16);
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
-  rc = stage_fwd(&shape->conv, g.ph, g.pw, g.pool, bn_memory, x, w, bias, scale, shift, running_mean, running_var, y, flt,
-                 save_pool, save_mean, save_std, base, carve.stage, stream);
+  rc = Abi<T>::conv_stage_train_forward(&shape->conv, g.ph, g.pw, g.pool, bn_memory, x, w, bias, scale, shift,
+                                        running_mean, running_var, y, flt, save_pool, save_mean, save_std, base,
+                                        carve.stage, stream);
   if (rc != MMS_OK) return rc;
-  return head_fwd(&g.hs, flt, overlap, w1, b1, mask, w2, b2, label, h, prob, loss, head_ws, carve.head, stream);
+  return Abi<T>::head_forward(&g.hs, flt, overlap, w1, b1, mask, w2, b2, label, h, prob, loss, head_ws, carve.head,
+                              stream);
 }
 
 template <typename T>
@@ -489,14 +421,14 @@ int train_tail_backward(const mms_score_tail_shape* shape, int phase, float drop
   const TrainTailCarve carve = train_tail_carve<T>(shape, g);
   if (!workspace || workspace_bytes < carve.total()) return MMS_ERR_WORKSPACE;
   char* base = static_cast<char*>(workspace);
-  T* x0d = stage ? reinterpret_cast<T*>(base + round16(carve.stage)) : nullptr;
-  void* head_ws = base + round16(carve.stage) + round16(carve.x0d);
+  T* x0d = stage ? reinterpret_cast<T*>(base + round_up(carve.stage, 16)) : nullptr;
+  void* head_ws = base + round_up(carve.stage, 16) + round_up(carve.x0d, 16);
   // Both calls' own refusals have been answered above: neither can refuse after the other has enqueued.
-  rc = head_bwd(&g.hs, flt, overlap, w1, w2, mask, h, prob, label, loss_weight, x0d, doverlap, w1d, b1d, w2d, b2d,
-                head_ws, carve.head, stream);
+  rc = Abi<T>::head_backward(&g.hs, flt, overlap, w1, w2, mask, h, prob, label, loss_weight, x0d, doverlap, w1d, b1d, w2d,
+                             b2d, head_ws, carve.head, stream);
   if (rc != MMS_OK || !stage) return rc;
-  return stage_bwd(&shape->conv, g.ph, g.pw, g.pool, x, w, y, flt, x0d, save_pool, scale, shift, save_mean, save_std, dx,
-                   dw, db, dscale, dshift, base, carve.stage, stream);
+  return Abi<T>::conv_stage_train_backward(&shape->conv, g.ph, g.pw, g.pool, x, w, y, flt, x0d, save_pool, scale, shift,
+                                           save_mean, save_std, dx, dw, db, dscale, dshift, base, carve.stage, stream);
 }
 
 }  // namespace

@@ -30,8 +30,6 @@ struct TrainTailBackwardPlan {
   bool ok;                   // false: the fused launches do not reach this shape
 };
 
-inline size_t train_tail_backward_round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // head_bytes: mms_head_workspace_bytes of the tail's head.
 inline TrainTailBackwardPlan train_tail_backward_plan(const TrainTailDims& g, int images, size_t head_bytes) {
   TrainTailBackwardPlan p = {};
@@ -62,10 +60,10 @@ inline TrainTailBackwardPlan train_tail_backward_plan(const TrainTailDims& g, in
   const size_t NK = (size_t)d.N * d.K, nW = (size_t)d.K * d.C * d.kh * d.kw;
   p.coef_floats = 2 * (size_t)d.K + NK;
   p.off_x0d = 0;
-  p.off_head = p.off_x0d + train_tail_backward_round16(NK * sizeof(float));
-  p.off_coef = p.off_head + train_tail_backward_round16(head_bytes);
-  p.off_part = p.off_coef + train_tail_backward_round16(p.coef_floats * sizeof(float) + NK * sizeof(int));
-  p.bytes = p.off_part + train_tail_backward_round16((size_t)w.slabs * (nW + d.K) * sizeof(float));
+  p.off_head = p.off_x0d + round_up(NK * sizeof(float), 16);
+  p.off_coef = p.off_head + round_up(head_bytes, 16);
+  p.off_part = p.off_coef + round_up(p.coef_floats * sizeof(float) + NK * sizeof(int), 16);
+  p.bytes = p.off_part + round_up((size_t)w.slabs * (nW + d.K) * sizeof(float), 16);
   p.ok = p.bottom_lds <= (size_t)kTrainTailBackwardMaxLdsBytes && p.wdiff_lds <= (size_t)kTrainTailBackwardMaxLdsBytes &&
          p.head_lds <= (size_t)kTrainTailBackwardMaxLdsBytes;
   return p;

@@ -50,7 +50,7 @@ int train_tail_backward_args(const TrainTailDims& g, const T* x, const T* w, con
   const void* const arrays[] = {x,    w,    y,     flt, save_pool, scale,  shift,  save_mean, save_std,  overlap, w1,  w2,  mask,
                                 h,    prob, label, dx,  dw,        db,     dscale, dshift,    *doverlap, w1d,     b1d, w2d, b2d};
   const void* const ws_only[] = {workspace};
-  if (stage_outputs_alias(arrays, ws_only)) return MMS_ERR_INVALID_ARG;     // any two arrays, the workspace included
+  if (outputs_alias(arrays, ws_only)) return MMS_ERR_INVALID_ARG;     // any two arrays, the workspace included
   return MMS_OK;
 }
 
